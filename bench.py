@@ -21,6 +21,10 @@ Extra objects in that line:
                   the same for the fp32 parity mode of the HIP path.
   cpu_baseline    the CPU oracle (oracle/unet_oracle.py, kind "port") timed on the host on a bounded sample of the
                   same workload (rank 0, N == 1 only): 1 warm-up + 2 timed train steps at bs=1.
+
+--dump-outputs DIR: what the last timed step handed to its caller, as float32 DIR/<name>.npy (dump_outputs below).  Model,
+batch and Dropout3d masks come from fixed seeds, so the same arguments give the same inputs in every run and two builds
+can be compared file by file.
 """
 import argparse
 import gc
@@ -38,6 +42,8 @@ for p in (ROOT, PKG):
 
 HBM_PEAK = 8.0e12        # B/s, MI355X spec (MI355X_MICROARCH.md)
 MFMA_BF16_PEAK = 2.5e15  # FLOP/s dense
+# --dump-outputs: float32 elements kept per file; 62 MB for the three together, under the 64 MB the directory may hold
+DUMP_CAPS = {"logits": 13_000_000, "params": 1_250_000, "grads": 1_250_000}
 
 
 def parse():
@@ -64,7 +70,13 @@ def parse():
                     help="graph: replay the step from a hipGraph captured after the warm-up (1 GPU, bf16/fp32, fused "
                          "Adam); eager: issue every launch from Python")
     ap.add_argument("--eval-mode", action="store_true", help="dropout off")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (rank 0's loss, logits, parameters, "
+                         "gradients) to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (it is the number of timed steps)")
+    return args
 
 
 def spawn_ranks(args):
@@ -198,6 +210,29 @@ def parity_report(args, model, dims, dev, dtype):
     return out
 
 
+def dump_outputs(path, loss, logits, model):
+    """What a caller of the training step holds once it has run, one float32 file each: the loss and the network output
+    it returned, the parameters as its Adam update left them and the gradients of its backward pass (parameters without
+    one are left out).  The 2 x 3 x 128^3 logits of the default workload are written whole; the parameters and gradients
+    are flattened in model.parameters() order, and an array beyond its share of DUMP_CAPS is cut down to the elements at
+    sorted positions drawn with a fixed seed, the same positions in every run.  Every tensor crosses to the host as it
+    is and is flattened and cut there: nothing is allocated on the device, whose allocator the eager steps that follow
+    find as the warm-up left it."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    params = list(model.parameters())
+    arrays = {"loss": loss.detach().cpu().reshape(1), "logits": logits.detach().cpu(),
+              "params": torch.cat([p.detach().cpu().reshape(-1) for p in params]),
+              "grads": torch.cat([p.grad.cpu().reshape(-1) for p in params if p.grad is not None])}
+    for name, t in arrays.items():
+        cap = DUMP_CAPS.get(name)
+        if cap is not None and t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(20241)).sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), t.float().contiguous().numpy())
+
+
 class _StdoutToStderr:
     """gloo and RCCL announce themselves on STDOUT (C++ side); bench.py's stdout is one JSON line."""
 
@@ -300,9 +335,13 @@ def main():
     x = torch.randn(shape, generator=g, device=dev).clamp_(-2.34, 2.64)
     y = torch.randint(0, args.classes, (args.batch,) + dims, generator=g, device=dev)
 
+    kept = {}      # --dump-outputs: the network output of the latest eager step (a graphed step keeps its own)
+
     def make_step(optimizer):
         def step():
             logits = model(x)
+            if args.dump_outputs:
+                kept["logits"] = logits.detach()
             loss = criterion(logits, y)
             optimizer.zero_grad()
             if sync is not None:
@@ -371,6 +410,8 @@ def main():
     loss_value = float(loss.item())
     # a replay allocates nothing: the step's peak is the one seen while it was captured
     peak_mem = peak_mem_capture if use_graph else torch.cuda.max_memory_allocated(dev)
+    if args.dump_outputs and rank == 0:      # here: the steps below train the same model further
+        dump_outputs(args.dump_outputs, loss, gstep.logits if use_graph else kept["logits"], model)
     eager_ms = eager_host_ms = None
     if use_graph:
         # the same steps issued launch by launch, right behind the timed replays: the eager figure for comparison, and

@@ -324,6 +324,45 @@ def test_bench_algorithmic_work_matches_survey_table():
         assert abs(f - flops) / flops < 2e-3 and abs(b - nbytes) / nbytes < 3e-3, (cfg, f, b)
 
 
+def test_bench_dump_outputs_writes_bounded_float32_files(tmp_path, monkeypatch):
+    """bench.dump_outputs: loss / logits / params / grads as float32 .npy; whole while they fit their share of
+    bench.DUMP_CAPS, otherwise the elements at the same seeded positions in every run; parameters without a gradient
+    are left out of grads."""
+    import bench
+    torch.manual_seed(5)
+    model = torch.nn.Sequential(torch.nn.Conv3d(1, 4, 3, padding=1), torch.nn.Conv3d(4, 2, 1))
+    unused = torch.nn.Parameter(torch.ones(7))
+    model.register_parameter("unused", unused)
+    logits = model(torch.randn(2, 1, 6, 6, 6)).to(torch.bfloat16)
+    loss = logits.float().square().mean()
+    loss.backward()
+    flat_p = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    flat_g = torch.cat([p.grad.reshape(-1) for p in model.parameters() if p.grad is not None])
+    assert flat_g.numel() == flat_p.numel() - 7
+
+    bench.dump_outputs(str(tmp_path / "a"), loss, logits, model)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("loss", "logits", "params", "grads")}
+    assert sorted(os.listdir(str(tmp_path / "a"))) == ["grads.npy", "logits.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss"].shape == (1,) and got["loss"][0] == np.float32(loss.item())
+    assert got["logits"].shape == (2, 2, 6, 6, 6) and np.array_equal(got["logits"], logits.detach().float().numpy())
+    assert np.array_equal(got["params"], flat_p.numpy()) and np.array_equal(got["grads"], flat_g.numpy())
+
+    monkeypatch.setattr(bench, "DUMP_CAPS", {"logits": 100, "params": 50, "grads": 50})
+    for run in "bc":
+        bench.dump_outputs(str(tmp_path / run), loss, logits, model)
+    for n, whole in (("logits", logits.detach().float().reshape(-1)), ("params", flat_p), ("grads", flat_g)):
+        b, c = (np.load(str(tmp_path / run / (n + ".npy"))) for run in "bc")
+        assert b.shape == (bench.DUMP_CAPS[n],) and np.array_equal(b, c)
+        # a sample in flat order: b is a subsequence of the whole array
+        pos, whole = 0, whole.numpy()
+        for v in b:
+            while whole[pos] != v:
+                pos += 1
+    monkeypatch.undo()
+    assert 4 * (sum(bench.DUMP_CAPS.values()) + 1) + 4 * 1024 <= 64 * 10 ** 6      # four files with their headers
+
+
 def test_stream_follows_the_operands_device(monkeypatch):
     """the stream handed to the C ABI is the current stream of the operands' device, not of the
     thread's current device."""
