@@ -120,6 +120,13 @@ SIGNATURES = {
     "ru3d_tversky": (_i, [_vp, _vp, _i64, _f, _f, _f, _vp, _vp, _sz, _vp]),
     "ru3d_predict_accumulate": (_i, [_P, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ru3d_predict_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ru3d_components_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_label_components": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_component_stats": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ru3d_filter_components_workspace_bytes": (_sz, [_i]),
+    "ru3d_filter_components": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_region_accumulate": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "ru3d_cascade_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ru3d_adam_multi": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "ru3d_adam_multi_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ru3d_adam_multi_amp": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

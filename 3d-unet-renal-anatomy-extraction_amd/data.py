@@ -225,7 +225,11 @@ def resample_normalize_case(case, target_spacing, normalize_stats):
 
 
 def regions_crop_case(case, threshold=0, padding=20, based_on='label'):
-    """Connected foreground regions of the label (or prediction), each cropped with `padding` millimetres around it."""
+    """Connected foreground regions of the label (or prediction), each cropped with `padding` millimetres around it.
+    When `case[based_on]` is a HIP tensor the boxes come from the device labelling (only the components' sizes and boxes
+    cross to the host), and whatever of 'image' / 'label' is a HIP tensor is cropped and padded on the device."""
+    if torch.is_tensor(case[based_on]) and case[based_on].is_cuda:
+        return _regions_crop_case_device(case, threshold, padding, based_on)
     based = remove_small_region(np.array(case[based_on] > 0), threshold)
     labels, _ = ndi.label(based)
     spacing = np.array(get_spacing(case['affine']))
@@ -240,5 +244,29 @@ def regions_crop_case(case, threshold=0, padding=20, based_on='label'):
                   'image': crop_pad_to_bbox(case['image'], bbox_c)}
         if 'label' in case:
             region['label'] = crop_pad_to_bbox(case['label'], bbox)
+        regions.append(region)
+    return regions
+
+
+def _regions_crop_case_device(case, threshold, padding, based_on):
+    import components
+    spacing = np.array(get_spacing(case['affine']))
+    pad_vox = np.round(padding / spacing).astype(int)
+
+    def crop(volume, bbox):
+        if torch.is_tensor(volume) and volume.is_cuda:
+            return components.crop_pad_to_bbox(volume, bbox)
+        return crop_pad_to_bbox(volume, bbox)
+
+    regions = []
+    for i, box in enumerate(components.region_boxes(case[based_on] > 0, threshold)):
+        bbox = np.array([[int(box[d][0]) - pad_vox[d], int(box[d][1]) + pad_vox[d]] for d in range(3)])
+        bbox_c = np.concatenate([bbox, [[0, case['image'].shape[-1]]]])
+        region = {'case_id': '%s_%03d' % (case['case_id'], i),
+                  'affine': apply_translate(case['affine'], bbox[:, 0] * spacing),
+                  'bbox': bbox,
+                  'image': crop(case['image'], bbox_c)}
+        if 'label' in case:
+            region['label'] = crop(case['label'], bbox)
         regions.append(region)
     return regions

@@ -156,14 +156,16 @@ def _zoomed_shape(shape, scale):
 
 
 def predict_case(case, model, target_spacing, normalize_stats, num_classes=3, patch_size=(96, 96, 96),
-                 step_per_patch=4, verbose=True, one_hot=False, patch_batch=1):
+                 step_per_patch=4, verbose=True, one_hot=False, patch_batch=1, return_device=False):
     """reference trainer.py:101-133: resample the case to `target_spacing` and normalise it (data.py:222-283), run the
     sliding-window prediction, resize the prediction back to the case's shape.  Everything between the upload of the
     image and the download of the prediction runs on the device: the two resamplings are the order-1 zoom kernel of
-    the augmentation path (label rule included), the sliding window is predict_per_patch."""
+    the augmentation path (label rule included), the sliding window is predict_per_patch.  `case['image']` may already
+    be a HIP tensor (no upload), and `return_device` leaves `case['pred']` in HBM (no download): the cascade chains its
+    stages that way."""
     import augment
     device = next(model.parameters()).device
-    image = np.asarray(case['image'])
+    image = case['image'] if torch.is_tensor(case['image']) else np.asarray(case['image'])
     if image.ndim == 3:
         image = image[..., None]
     orig_shape = tuple(int(s) for s in image.shape[:-1])
@@ -173,7 +175,10 @@ def predict_case(case, model, target_spacing, normalize_stats, num_classes=3, pa
         print('Resampling the case for prediction...')
     spacing = np.array([np.linalg.norm(affine[i, :3]) for i in range(3)])
     scale = spacing / np.array(target_spacing, dtype=np.float64)
-    vol = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(device)
+    if torch.is_tensor(image):
+        vol = image.to(device=device, dtype=torch.float32).contiguous()
+    else:
+        vol = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(device)
     vol = augment.resample_image(vol, _zoomed_shape(orig_shape, scale))
     for c, s in enumerate(stats):                 # clip to the percentiles, then (x - mean) / (std + 1e-8)
         vol[..., c].clamp_(float(s['pct_00_5']), float(s['pct_99_5'])).sub_(float(s['mean'])).div_(float(s['std']) + 1e-8)
@@ -185,10 +190,10 @@ def predict_case(case, model, target_spacing, normalize_stats, num_classes=3, pa
     if verbose:
         print('Resizing the case to origial shape...')
     if one_hot:
-        out = augment.resample_image(pred, orig_shape).cpu().numpy()
+        out = augment.resample_image(pred, orig_shape)
     else:
-        out = augment.resample_label(pred, orig_shape).to(torch.uint8).cpu().numpy()
-    case['pred'] = out
+        out = augment.resample_label(pred, orig_shape).to(torch.uint8)
+    case['pred'] = out if return_device else out.cpu().numpy()
     case['affine'] = affine
     if verbose:
         print('All done!')

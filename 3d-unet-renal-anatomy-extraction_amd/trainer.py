@@ -540,10 +540,24 @@ def batch_predict_case(load_dir, save_dir, model, target_spacing, normalize_stat
 
 def cascade_predict_case(case, coarse_model, coarse_target_spacing, coarse_normalize_stats, coarse_patch_size,
                          detail_model, detail_target_spacing, detail_normalize_stats, detail_patch_size,
-                         num_classes=3, step_per_patch=4, region_threshold=10000, crop_padding=20, verbose=True):
+                         num_classes=3, step_per_patch=4, region_threshold=10000, crop_padding=20, verbose=True,
+                         on_device=None):
     """trainer.py:164-245: a single-class coarse pass finds the regions of interest, the detail model predicts class
-    probabilities inside each (padded) region, the regions' maps are averaged where they overlap and arg-maxed."""
+    probabilities inside each (padded) region, the regions' maps are averaged where they overlap and arg-maxed.
+
+    on_device: keep the case in HBM between the stages - the image is uploaded once, the coarse mask is labelled and its
+    regions are cropped on the device, every region's probability map is added into device `total` / `hits` volumes
+    (float64, like the host arithmetic) and only the final uint8 mask is downloaded.  None: yes when both models live on
+    a HIP device, unless RU3D_CASCADE_DEVICE=0.  False: the reference's host glue (scipy labelling, numpy merge).  Both
+    routes return the same dict."""
     from data import regions_crop_case
+    if on_device is None:
+        on_device = _models_on_hip(coarse_model, detail_model) and os.environ.get("RU3D_CASCADE_DEVICE", "1") != "0"
+    if on_device:
+        return _cascade_predict_case_device(case, coarse_model, coarse_target_spacing, coarse_normalize_stats,
+                                            coarse_patch_size, detail_model, detail_target_spacing,
+                                            detail_normalize_stats, detail_patch_size, step_per_patch, region_threshold,
+                                            crop_padding, verbose)
     if verbose:
         print('Predicting the rough shape for further prediction...')
     case = predict_case(case, coarse_model, coarse_target_spacing, coarse_normalize_stats, 1, coarse_patch_size,
@@ -580,9 +594,63 @@ def cascade_predict_case(case, coarse_model, coarse_target_spacing, coarse_norma
     return case
 
 
+def _models_on_hip(*models):
+    for m in models:
+        p = next(m.parameters(), None)
+        if p is None or not p.is_cuda:
+            return False
+    return True
+
+
+def _cascade_predict_case_device(case, coarse_model, coarse_target_spacing, coarse_normalize_stats, coarse_patch_size,
+                                 detail_model, detail_target_spacing, detail_normalize_stats, detail_patch_size,
+                                 step_per_patch, region_threshold, crop_padding, verbose):
+    """cascade_predict_case with every intermediate in HBM (components.py, csrc/components.hip)."""
+    import components
+    from data import regions_crop_case
+    device = next(coarse_model.parameters()).device
+    if next(detail_model.parameters()).device != device:
+        raise ValueError("cascade_predict_case(on_device=True): the two models live on %s and %s"
+                         % (device, next(detail_model.parameters()).device))
+    image = case['image'] if torch.is_tensor(case['image']) else np.asarray(case['image'])
+    if image.ndim == 3:
+        image = image[..., None]
+    if torch.is_tensor(image):
+        dev_image = image.to(device=device, dtype=torch.float32)
+    else:
+        dev_image = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(device)
+    if verbose:
+        print('Predicting the rough shape for further prediction...')
+    work = dict(case)
+    work['image'] = dev_image
+    work = predict_case(work, coarse_model, coarse_target_spacing, coarse_normalize_stats, 1, coarse_patch_size,
+                        step_per_patch, verbose=verbose, return_device=True)
+    regions = regions_crop_case(work, region_threshold, crop_padding, 'pred')
+    num_classes = detail_model.out_channels
+    orig_shape = tuple(int(v) for v in dev_image.shape[:-1])
+    acc = components.CascadeAccumulator(orig_shape, num_classes, device)
+    if verbose:
+        print('Cropping regions (%d)...' % len(regions))
+    for idx, region in enumerate(regions):
+        bbox = region['bbox']
+        if verbose:
+            print('Region {} {} predicting...'.format(idx, tuple(region['image'].shape[:-1])))
+        region = predict_case(region, detail_model, detail_target_spacing, detail_normalize_stats, num_classes,
+                              detail_patch_size, step_per_patch, verbose=verbose, one_hot=True, return_device=True)
+        acc.add(region['pred'], bbox[:, 0])
+    if verbose:
+        print('Merging all regions...')
+    case['pred'] = acc.merge().cpu().numpy()
+    case['affine'] = work['affine']
+    if verbose:
+        print('All done!')
+    return case
+
+
 def cascade_predict(image_file, coarse_model, coarse_target_spacing, coarse_normalize_stats, coarse_patch_size,
                     detail_model, detail_target_spacing, detail_normalize_stats, detail_patch_size, air=-200, num_classes=3,
-                    step_per_patch=4, region_threshold=10000, crop_padding=20, label_file=None, verbose=True):
+                    step_per_patch=4, region_threshold=10000, crop_padding=20, label_file=None, verbose=True,
+                    on_device=None):
     """trainer.py:248-302: load a NIfTI image, reorient + crop it to its non-air box, run the cascade on the crop, and
     put the mask back into a volume of the original file's grid.  As in the reference the final step applies the
     forward orientation once more (`apply_orientation(orig_pred, orient)`), which undoes the first one for the
@@ -592,7 +660,7 @@ def cascade_predict(image_file, coarse_model, coarse_target_spacing, coarse_norm
     case = orient_crop_case(orig_case, air)
     case = cascade_predict_case(case, coarse_model, coarse_target_spacing, coarse_normalize_stats, coarse_patch_size,
                                 detail_model, detail_target_spacing, detail_normalize_stats, detail_patch_size,
-                                num_classes, step_per_patch, region_threshold, crop_padding, verbose)
+                                num_classes, step_per_patch, region_threshold, crop_padding, verbose, on_device)
     ornt = io_orientation(orig_case['affine'])
     order = ornt[:, 0].astype(int)
     orig_shape = np.take(np.array(orig_case['image'].shape[:3]), order)
@@ -609,7 +677,7 @@ def cascade_predict(image_file, coarse_model, coarse_target_spacing, coarse_norm
 def batch_cascade_predict(image_dir, save_dir, coarse_model, coarse_target_spacing, coarse_normalize_stats,
                           coarse_patch_size, detail_model, detail_target_spacing, detail_normalize_stats,
                           detail_patch_size, air=-200, num_classes=3, step_per_patch=4, region_threshold=10000,
-                          crop_padding=20, data_range=None):
+                          crop_padding=20, data_range=None, on_device=None):
     """trainer.py:305-345: every file of `image_dir` through cascade_predict, masks written with save_pred."""
     from pathlib import Path
     from data import save_pred
@@ -618,7 +686,7 @@ def batch_cascade_predict(image_dir, save_dir, coarse_model, coarse_target_spaci
         case = cascade_predict(image_files[i], coarse_model, coarse_target_spacing, coarse_normalize_stats,
                                coarse_patch_size, detail_model, detail_target_spacing, detail_normalize_stats,
                                detail_patch_size, air, num_classes, step_per_patch, region_threshold, crop_padding,
-                               None, False)
+                               None, False, on_device)
         save_pred(case, save_dir)
 
 

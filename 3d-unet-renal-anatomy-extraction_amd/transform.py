@@ -11,6 +11,7 @@ seed reproduces the reference's patches (checked against tests/golden/g7_augment
 """
 import numpy as np
 import scipy.ndimage as ndi
+import torch
 
 from augment import DeviceAugment, DeviceCase  # noqa: F401  (the on-device replacement of the Random* chain)
 
@@ -130,7 +131,23 @@ def pad(input, pad_size, pad_mode='constant', pad_cval=0):
 
 
 # ------------------------------------------------------------------ labels (transform.py:5-20, 323-384)
+def label_components(mask):
+    """Connected components (6-connectivity) of the non-zero voxels: (labels int32, K), the components numbered in the
+    order of their first voxel.  numpy in -> scipy.ndimage.label; HIP tensor in -> the kernels of csrc/components.hip,
+    an int32 HIP tensor out, with the same numbering."""
+    if torch.is_tensor(mask):
+        import components
+        return components.label(mask)
+    labels, count = ndi.label(mask)
+    return labels, int(count)
+
+
 def remove_small_region(input, threshold):
+    """numpy: as the reference.  A HIP tensor is labelled, measured and filtered on the device; like the numpy route it
+    is modified in place and returned."""
+    if torch.is_tensor(input):
+        import components
+        return components.remove_small_region(input, threshold)
     labels, _ = ndi.label(input)
     areas = np.bincount(labels.ravel())
     input[(areas < threshold)[labels]] = 0

@@ -318,6 +318,38 @@ int ru3d_predict_accumulate(const ru3d_tensor* logits, int dtype, int sample, fl
 int ru3d_predict_merge(const float* acc, const float* cnt, int X, int Y, int Z, int num_classes, int cx, int cy,
                        int cz, int sx, int sy, int sz, int one_hot, void* out, void* stream);
 
+/* ------------------------------------------------------------------ connected components + cascade merge */
+/* 3D connected-component labelling with 6-connectivity, scipy.ndimage.label's default structure (transform.py:5-11,
+ * data.py:464-492).  mask: uint8 [X, Y, Z], Z contiguous, any non-zero byte is foreground.  labels: int32 [X, Y, Z],
+ * 0 on background and 1..K on foreground, the components numbered by the linear index of their first voxel - scipy's
+ * numbering, element for element.  K is written to *count_dev (device int32).  Integer atomics only: the result is a
+ * pure function of the mask.  X*Y*Z must stay below 2^31.  `ws`: device scratch of the size the query returns. */
+size_t ru3d_components_workspace_bytes(int X, int Y, int Z);
+int ru3d_label_components(const uint8_t* mask, int X, int Y, int Z, int32_t* labels, int32_t* count_dev, void* ws,
+                          size_t ws_bytes, void* stream);
+/* sizes[k] (int32) = voxels of component k + 1, boxes[k] (int32[6]) = {x0, x1, y0, y1, z0, z1} with x1 = last x + 1
+ * (np.bincount(labels)[1:] and scipy.ndimage.find_objects).  `count` = K, read back by the caller. */
+int ru3d_component_stats(const int32_t* labels, int X, int Y, int Z, int count, int32_t* sizes, int32_t* boxes,
+                         void* stream);
+/* remove_small_region (transform.py:5-11): components with sizes[k] < threshold are zeroed in mask_inout (uint8, may
+ * be NULL) and the survivors renumbered 1..kept in their old order into labels_out (int32, may be NULL, may be
+ * `labels` itself) - what a second labelling of the filtered mask would return.  *kept_dev (device int32) = kept. */
+size_t ru3d_filter_components_workspace_bytes(int count);
+int ru3d_filter_components(const int32_t* labels, int X, int Y, int Z, int count, const int32_t* sizes, int threshold,
+                           uint8_t* mask_inout, int32_t* labels_out, int32_t* kept_dev, void* ws, size_t ws_bytes,
+                           void* stream);
+/* cascade_predict_case (trainer.py:203-240).  total: zero-initialised float64 [X, Y, Z, C], hits: zero-initialised
+ * int32 [X, Y, Z] (the reference's C copies of `hits` are equal).  accumulate: prob is one region's float32
+ * [rx, ry, rz, C] map whose box starts at (bx, by, bz) in volume coordinates (negative where the padded box leaves the
+ * volume); the part inside the volume is added to `total` and counted in `hits`.  Regions that overlap must be
+ * accumulated on one stream; the sum order is then the launch order, as in the reference's region loop.
+ * merge: out (uint8 [X, Y, Z]) = total / hits where hits > 0, then round half to even for C == 1, argmax_c softmax_c
+ * with the first maximum winning for C > 1; a row holding a NaN gives 0.  All arithmetic in float64. */
+int ru3d_region_accumulate(const float* prob, int rx, int ry, int rz, int num_classes, int bx, int by, int bz,
+                           double* total, int32_t* hits, int X, int Y, int Z, void* stream);
+int ru3d_cascade_merge(const double* total, const int32_t* hits, int X, int Y, int Z, int num_classes, uint8_t* out,
+                       void* stream);
+
 /* ------------------------------------------------------------------ patch sampling + augmentation */
 /* The reference's training transform chain on the device: RandomRescaleCrop -> RandomMirror ->
  * RandomContrast -> RandomBrightness -> RandomGamma -> ToTensor (transform.py:573-652, 279-301, 176-259, 156-163;
