@@ -71,42 +71,53 @@ class GraphedTrainStep:
     def _capture(self, x, y):
         dev = x.device
         groups = len(self.optimizer.param_groups)
-        self.x = torch.empty_like(x)
-        self.y = torch.empty_like(y)
-        self.x.copy_(x)
-        self.y.copy_(y)
-        # device block rewritten before each replay: [0] dropout counter base (int64) | Adam scalars float32 [groups, 8]
-        self.block = torch.zeros(8 + groups * 32, dtype=torch.uint8, device=dev)
-        self.drop_base = self.block[:8].view(torch.int64)
-        self.hyper = self.block[8:].view(torch.float32).view(groups, 8)
-        self.host = [torch.zeros(8 + groups * 32, dtype=torch.uint8).pin_memory() for _ in range(_RING)]
-        self.host_ev = [None] * _RING
         self.stream = torch.cuda.Stream(dev)
-        self.optimizer.begin_capture(self.hyper)
-        if self.scaler is not None:
-            self.scaler.begin_capture(self.optimizer, dev)
-        self.optimizer.zero_grad(set_to_none=True)
-        g = torch.cuda.CUDAGraph()
         drop0 = _ops._drop_counter[0]
-        _ops.DROP_OFFSET_BASE[0] = self.drop_base
         import loss as _loss_mod
-        _loss_mod.CAPTURE_SINK[0] = self.label_states = []
-        self.stream.wait_stream(torch.cuda.current_stream(dev))
         try:
-            with torch.cuda.graph(g, stream=self.stream, capture_error_mode="thread_local"):
-                logits = self.model(self.x)
-                loss = self.criterion(logits, self.y)
-                if self.scaler is None:
-                    loss.backward()
-                    self.optimizer.step()
-                else:
-                    self.scaler.scale(loss).backward()
-                    self.scaler.step(self.optimizer)
-                self.loss = loss.detach()
-                self._static_logits = logits.detach()
-        finally:
-            _ops.DROP_OFFSET_BASE[0] = None
-            _loss_mod.CAPTURE_SINK[0] = None
+            self.x = torch.empty_like(x)
+            self.y = torch.empty_like(y)
+            self.x.copy_(x)
+            self.y.copy_(y)
+            # device block rewritten before each replay: [0] dropout counter base (int64) | Adam scalars float32 [groups, 8]
+            self.block = torch.zeros(8 + groups * 32, dtype=torch.uint8, device=dev)
+            self.drop_base = self.block[:8].view(torch.int64)
+            self.hyper = self.block[8:].view(torch.float32).view(groups, 8)
+            self.host = [torch.zeros(8 + groups * 32, dtype=torch.uint8).pin_memory() for _ in range(_RING)]
+            self.host_ev = [None] * _RING
+            self.optimizer.begin_capture(self.hyper)
+            if self.scaler is not None:
+                self.scaler.begin_capture(self.optimizer, dev)
+            self.optimizer.zero_grad(set_to_none=True)
+            g = torch.cuda.CUDAGraph()
+            _ops.DROP_OFFSET_BASE[0] = self.drop_base
+            _loss_mod.CAPTURE_SINK[0] = self.label_states = []
+            self.stream.wait_stream(torch.cuda.current_stream(dev))
+            try:
+                with torch.cuda.graph(g, stream=self.stream, capture_error_mode="thread_local"):
+                    logits = self.model(self.x)
+                    loss = self.criterion(logits, self.y)
+                    if self.scaler is None:
+                        loss.backward()
+                        self.optimizer.step()
+                    else:
+                        self.scaler.scale(loss).backward()
+                        self.scaler.step(self.optimizer)
+                    self.loss = loss.detach()
+                    self._static_logits = logits.detach()
+            finally:
+                _ops.DROP_OFFSET_BASE[0] = None
+                _loss_mod.CAPTURE_SINK[0] = None
+        except BaseException:
+            # nothing of the failed capture stays behind: optimizer and scaler leave captured mode (an eager loop can go
+            # on with them), the step a captured optimizer.step() counted is taken back (no replay will ever run it), no
+            # Dropout3d mask has been drawn, and the half-built static buffers and the capture's pool are dropped
+            _ops._drop_counter[0] = drop0
+            cap = self.optimizer._captured
+            if cap is not None and cap["steps"]:
+                cap["dirty"] = True
+            self.release()
+            raise
         self.draws = _ops._drop_counter[0] - drop0      # Dropout3d draws of one step
         _ops._drop_counter[0] = drop0                   # nothing has been drawn yet: the first replay is this step
         self.drop_origin = drop0
@@ -159,7 +170,7 @@ class GraphedTrainStep:
         self.optimizer._captured = None
         for key in [k for k in self.optimizer._plans if k[1]]:       # (group, captured=True)
             del self.optimizer._plans[key]
-        if self.graph is not None:
+        if self.graph is not None or hasattr(self, "stream"):        # captured, or a capture that failed half-way
             self.optimizer.zero_grad(set_to_none=True)
             sid = self.stream.cuda_stream
             # the side stream of the small levels' weight gradients (ops._OnSide) joined the capture: its workspace sits

@@ -314,6 +314,12 @@ class LossScaler:
         dev = self._dev
         self.sync()
         optimizer.sync_captured_steps()
+        # _upload() below restarts the device's count of steps taken at 0, whether or not this step is skipped: the base
+        # it is added to moves up to the count reached now (amp_base + device steps == updates applied, always)
+        cap = optimizer._captured
+        if cap is not None:
+            for gi in cap["steps"]:
+                cap["amp_base"][gi] = cap["steps"][gi]
         self._dev = None
         self._scale_t = self._found = None
         try:

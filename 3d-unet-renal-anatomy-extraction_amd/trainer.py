@@ -252,8 +252,9 @@ class Trainer():
                     if self.capture_step or graphed.graph is not None:
                         raise
                     # auto mode and the capture itself failed (an op that cannot be captured): eager from here on
+                    # (release(): optimizer and loss scaler must not stay in captured mode - the eager step below uses them)
                     self._capture_failed = True
-                    self._graphed = None
+                    self._release_graph()
                     graphed = None
             if graphed is not None:
                 y_pred = graphed.logits
