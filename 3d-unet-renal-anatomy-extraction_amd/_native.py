@@ -43,6 +43,15 @@ class PatchParams(ctypes.Structure):
                 ("gamma_eps", ctypes.c_float)]
 
 
+class MorphRow(ctypes.Structure):
+    """struct ru3d_morph_row"""
+    _fields_ = [("dx", ctypes.c_int8), ("dy", ctypes.c_int8), ("zmask", ctypes.c_uint16)]
+
+
+MASK_NE, MASK_EQ, MASK_GT, MASK_GE = 0, 1, 2, 3
+MORPH_ERODE, MORPH_DILATE = 0, 1
+MORPH_MAX_EXTENT, MORPH_MAX_ROWS = 15, 225
+CONFUSION_MAX_CLASSES = 32
 PACK_MAX = 40
 _P = ctypes.POINTER(Tensor)
 _vp, _i, _i64, _f, _sz, _u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t,
@@ -127,6 +136,11 @@ SIGNATURES = {
     "ru3d_filter_components": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_region_accumulate": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     "ru3d_cascade_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ru3d_mask_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_mask_pack": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ru3d_mask_unpack": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ru3d_binary_morph": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.POINTER(MorphRow), _i, _i, _vp]),
+    "ru3d_confusion_counts": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "ru3d_adam_multi": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "ru3d_adam_multi_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ru3d_adam_multi_amp": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

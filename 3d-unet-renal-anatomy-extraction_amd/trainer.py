@@ -542,7 +542,7 @@ def batch_predict_case(load_dir, save_dir, model, target_spacing, normalize_stat
 def cascade_predict_case(case, coarse_model, coarse_target_spacing, coarse_normalize_stats, coarse_patch_size,
                          detail_model, detail_target_spacing, detail_normalize_stats, detail_patch_size,
                          num_classes=3, step_per_patch=4, region_threshold=10000, crop_padding=20, verbose=True,
-                         on_device=None):
+                         *, return_device=False, post_transform=None, on_device=None):
     """trainer.py:164-245: a single-class coarse pass finds the regions of interest, the detail model predicts class
     probabilities inside each (padded) region, the regions' maps are averaged where they overlap and arg-maxed.
 
@@ -550,15 +550,24 @@ def cascade_predict_case(case, coarse_model, coarse_target_spacing, coarse_norma
     regions are cropped on the device, every region's probability map is added into device `total` / `hits` volumes
     (float64, like the host arithmetic) and only the final uint8 mask is downloaded.  None: yes when both models live on
     a HIP device, unless RU3D_CASCADE_DEVICE=0.  False: the reference's host glue (scipy labelling, numpy merge).  Both
-    routes return the same dict."""
+    routes return the same dict.  The arguments up to `verbose` are the reference's, in its order; what this code base
+    added behind them is passed by keyword.
+
+    post_transform: any callable volume -> volume (e.g. `functools.partial(transform.post_transform, threshold=t)`),
+    applied to the merged mask - on the device route while it is still in HBM (a uint8 HIP tensor in), on the host route
+    to the numpy mask.  return_device: leave case['pred'] on the device as a uint8 HIP tensor (device route only; the
+    host route has no device copy to return and raises)."""
     from data import regions_crop_case
     if on_device is None:
         on_device = _models_on_hip(coarse_model, detail_model) and os.environ.get("RU3D_CASCADE_DEVICE", "1") != "0"
+    if return_device and not on_device:
+        raise ValueError("cascade_predict_case: return_device=True needs the device route (on_device); the host route "
+                         "keeps nothing in HBM")
     if on_device:
         return _cascade_predict_case_device(case, coarse_model, coarse_target_spacing, coarse_normalize_stats,
                                             coarse_patch_size, detail_model, detail_target_spacing,
                                             detail_normalize_stats, detail_patch_size, step_per_patch, region_threshold,
-                                            crop_padding, verbose)
+                                            crop_padding, verbose, return_device, post_transform)
     if verbose:
         print('Predicting the rough shape for further prediction...')
     case = predict_case(case, coarse_model, coarse_target_spacing, coarse_normalize_stats, 1, coarse_patch_size,
@@ -590,6 +599,8 @@ def cascade_predict_case(case, coarse_model, coarse_target_spacing, coarse_norma
         e = np.exp(total - total.max(axis=-1, keepdims=True))      # scipy.special.softmax, then argmax
         merged = np.argmax(e / e.sum(axis=-1, keepdims=True), axis=-1)
     case['pred'] = merged.astype(np.uint8)
+    if post_transform is not None:
+        case['pred'] = post_transform(case['pred'])
     if verbose:
         print('All done!')
     return case
@@ -605,7 +616,8 @@ def _models_on_hip(*models):
 
 def _cascade_predict_case_device(case, coarse_model, coarse_target_spacing, coarse_normalize_stats, coarse_patch_size,
                                  detail_model, detail_target_spacing, detail_normalize_stats, detail_patch_size,
-                                 step_per_patch, region_threshold, crop_padding, verbose):
+                                 step_per_patch, region_threshold, crop_padding, verbose, return_device=False,
+                                 post_transform=None):
     """cascade_predict_case with every intermediate in HBM (components.py, csrc/components.hip)."""
     import components
     from data import regions_crop_case
@@ -641,7 +653,10 @@ def _cascade_predict_case_device(case, coarse_model, coarse_target_spacing, coar
         acc.add(region['pred'], bbox[:, 0])
     if verbose:
         print('Merging all regions...')
-    case['pred'] = acc.merge().cpu().numpy()
+    pred = acc.merge()
+    if post_transform is not None:
+        pred = post_transform(pred)
+    case['pred'] = pred if return_device or not torch.is_tensor(pred) else pred.cpu().numpy()
     case['affine'] = work['affine']
     if verbose:
         print('All done!')
@@ -651,17 +666,22 @@ def _cascade_predict_case_device(case, coarse_model, coarse_target_spacing, coar
 def cascade_predict(image_file, coarse_model, coarse_target_spacing, coarse_normalize_stats, coarse_patch_size,
                     detail_model, detail_target_spacing, detail_normalize_stats, detail_patch_size, air=-200, num_classes=3,
                     step_per_patch=4, region_threshold=10000, crop_padding=20, label_file=None, verbose=True,
-                    on_device=None):
+                    on_device=None, post_transform=None):
     """trainer.py:248-302: load a NIfTI image, reorient + crop it to its non-air box, run the cascade on the crop, and
     put the mask back into a volume of the original file's grid.  As in the reference the final step applies the
     forward orientation once more (`apply_orientation(orig_pred, orient)`), which undoes the first one for the
-    orientations that are their own inverse - every pure flip, and the usual axis swaps."""
+    orientations that are their own inverse - every pure flip, and the usual axis swaps.
+
+    post_transform (a callable volume -> volume) is applied by cascade_predict_case to the mask of the cropped,
+    re-oriented case - before that mask is pasted into the file's grid, so a size threshold or a structure is in the
+    crop's voxels and the volume's faces (the border rule of a closing) are the crop's faces."""
     from data import apply_orientation, io_orientation, load_case, orient_crop_case
     orig_case = load_case(image_file, label_file)
     case = orient_crop_case(orig_case, air)
     case = cascade_predict_case(case, coarse_model, coarse_target_spacing, coarse_normalize_stats, coarse_patch_size,
                                 detail_model, detail_target_spacing, detail_normalize_stats, detail_patch_size,
-                                num_classes, step_per_patch, region_threshold, crop_padding, verbose, on_device)
+                                num_classes, step_per_patch, region_threshold, crop_padding, verbose,
+                                on_device=on_device, post_transform=post_transform)
     ornt = io_orientation(orig_case['affine'])
     order = ornt[:, 0].astype(int)
     orig_shape = np.take(np.array(orig_case['image'].shape[:3]), order)
@@ -678,8 +698,9 @@ def cascade_predict(image_file, coarse_model, coarse_target_spacing, coarse_norm
 def batch_cascade_predict(image_dir, save_dir, coarse_model, coarse_target_spacing, coarse_normalize_stats,
                           coarse_patch_size, detail_model, detail_target_spacing, detail_normalize_stats,
                           detail_patch_size, air=-200, num_classes=3, step_per_patch=4, region_threshold=10000,
-                          crop_padding=20, data_range=None, on_device=None):
-    """trainer.py:305-345: every file of `image_dir` through cascade_predict, masks written with save_pred."""
+                          crop_padding=20, data_range=None, on_device=None, post_transform=None):
+    """trainer.py:305-345: every file of `image_dir` through cascade_predict, masks written with save_pred.
+    post_transform: see cascade_predict (applied to the cropped, re-oriented mask of every file)."""
     from pathlib import Path
     from data import save_pred
     image_files = [path for path in sorted(Path(image_dir).iterdir()) if path.is_file()]
@@ -687,17 +708,89 @@ def batch_cascade_predict(image_dir, save_dir, coarse_model, coarse_target_spaci
         case = cascade_predict(image_files[i], coarse_model, coarse_target_spacing, coarse_normalize_stats,
                                coarse_patch_size, detail_model, detail_target_spacing, detail_normalize_stats,
                                detail_patch_size, air, num_classes, step_per_patch, region_threshold, crop_padding,
-                               None, False, on_device)
+                               None, False, on_device, post_transform)
         save_pred(case, save_dir)
 
 
+_EVAL_CLASSES = 32          # the device table tells classes 0 .. 31 apart; row / column 32 collects everything above
+
+
+def _is_hip(v):
+    return torch.is_tensor(v) and v.is_cuda
+
+
+def _device_bytes(v, device):
+    """uint8 HIP tensor of a label volume (numpy or tensor, any integer type; values above 255 stay above 31)."""
+    if torch.is_tensor(v):
+        return v.to(device) if v.dtype == torch.uint8 else v.to(device).clamp(0, 255).to(torch.uint8)
+    v = np.asarray(v)
+    if v.dtype != np.uint8:
+        v = np.clip(v, 0, 255).astype(np.uint8)
+    return torch.from_numpy(np.ascontiguousarray(v)).to(device)
+
+
+def _confusion_table(case):
+    """(int64 numpy table [K, K] with entry [l][p] = voxels of label l predicted as p, highest label present).
+    HIP operands: one launch of the confusion kernel (the other operand is uploaded if needed) and one download of the
+    33 x 33 table; numpy operands: one np.bincount."""
+    pred, label = case['pred'], case['label']
+    if _is_hip(pred) or _is_hip(label):
+        import morphology
+        device = pred.device if _is_hip(pred) else label.device
+        table = morphology.confusion(_device_bytes(pred, device), _device_bytes(label, device), _EVAL_CLASSES)
+        table = table.cpu().numpy()
+        present = np.flatnonzero(table.sum(axis=1))
+        top = int(present.max()) if present.size else 0
+        if top >= _EVAL_CLASSES:
+            raise ValueError("evaluate: case['label'] holds a class above %d; the device table tells classes 0 .. %d apart"
+                             % (_EVAL_CLASSES - 1, _EVAL_CLASSES - 1))
+        return table, top
+    pred = np.asarray(pred.cpu() if torch.is_tensor(pred) else pred).astype(np.int64).ravel()
+    label = np.asarray(label.cpu() if torch.is_tensor(label) else label).astype(np.int64).ravel()
+    top = int(label.max())
+    k = max(top, int(pred.max())) + 1
+    return np.bincount(label * k + pred, minlength=k * k).reshape(k, k), top
+
+
+def _class_counts(table, c):
+    """true positives, false negatives, false positives, true negatives of class c as Python ints."""
+    tp = int(table[c, c])
+    fn = int(table[c].sum()) - tp
+    fp = int(table[:, c].sum()) - tp
+    return tp, fn, fp, int(table.sum()) - tp - fn - fp
+
+
 def evaluate_case(case):
-    """trainer.py:348-356: Dice (loss.dice, alpha = beta = 0.5) of every foreground class of label vs pred."""
+    """trainer.py:348-356: Dice (loss.dice, alpha = beta = 0.5) of every foreground class of label vs pred.  When the
+    prediction or the label is a HIP tensor the Dice values come from the integer confusion table of the two volumes
+    (one kernel launch, csrc/morphology.hip) in Python floats."""
+    if _is_hip(case['pred']) or _is_hip(case['label']):
+        table, top = _confusion_table(case)
+        out = []
+        for c in range(1, top + 1):
+            tp, fn, fp, _ = _class_counts(table, c)
+            out.append((tp + 1e-7) / (tp + 0.5 * fn + 0.5 * fp + 1e-7))
+        return out
     out = []
     for c in range(int(case['label'].max())):
         p = np.array(case['pred'] == c + 1).astype(np.float32)
         g = np.array(case['label'] == c + 1).astype(np.float32)
         out.append(dice(torch.tensor(p), torch.tensor(g)).item())
+    return out
+
+
+def evaluate_metrics(case, smooth=1e-7):
+    """Dice, sensitivity, specificity and accuracy (the formulas of the reference's nb.py:11-25) of every foreground
+    class 1 .. label.max(): a list of dicts with the keys dsc / sen / spe / acc.  All four are functions of one table
+    of integer counts - np.bincount on numpy volumes, the confusion kernel when either volume is a HIP tensor."""
+    table, top = _confusion_table(case)
+    out = []
+    for c in range(1, top + 1):
+        tp, fn, fp, tn = _class_counts(table, c)
+        out.append({'dsc': (tp + smooth) / (tp + 0.5 * (fn + fp) + smooth),
+                    'sen': (tp + smooth) / (tp + fn + smooth),
+                    'spe': (tn + smooth) / (tn + fp + smooth),
+                    'acc': (tp + tn + smooth) / (tp + tn + fn + fp + smooth)})
     return out
 
 

@@ -154,6 +154,69 @@ def remove_small_region(input, threshold):
     return input
 
 
+# ------------------------------------------------------------------ binary morphology + clean-up (nb_post.py:88-112)
+def _binary_morphology(name, input, structure, iterations, border_value):
+    """numpy in -> scipy.ndimage.<name>, boolean numpy out; HIP tensor in -> pack (!= 0), the kernels of
+    csrc/morphology.hip, unpack: a torch.bool HIP tensor of the input's shape with the same voxels set."""
+    if torch.is_tensor(input):
+        import components
+        import morphology
+        fn = {'binary_erosion': morphology.erode, 'binary_dilation': morphology.dilate,
+              'binary_opening': morphology.open, 'binary_closing': morphology.close}[name]
+        result = fn(morphology.pack(components.as_mask(input)), structure, iterations, border_value)
+        return morphology.unpack(result, 1, out=torch.empty(input.shape, dtype=torch.bool, device=input.device))
+    return getattr(ndi, name)(input, structure=structure, iterations=iterations, border_value=border_value)
+
+
+def binary_erosion(input, structure=None, iterations=1, border_value=0):
+    """scipy.ndimage.binary_erosion (structure None = the centre and its 6 neighbours) for numpy arrays and HIP tensors."""
+    return _binary_morphology('binary_erosion', input, structure, iterations, border_value)
+
+
+def binary_dilation(input, structure=None, iterations=1, border_value=0):
+    """scipy.ndimage.binary_dilation for numpy arrays and HIP tensors."""
+    return _binary_morphology('binary_dilation', input, structure, iterations, border_value)
+
+
+def binary_opening(input, structure=None, iterations=1, border_value=0):
+    """scipy.ndimage.binary_opening (erosions, then dilations) for numpy arrays and HIP tensors."""
+    return _binary_morphology('binary_opening', input, structure, iterations, border_value)
+
+
+def binary_closing(input, structure=None, iterations=1, border_value=0):
+    """scipy.ndimage.binary_closing (dilations, then erosions) for numpy arrays and HIP tensors.  With border_value 0
+    the erosion clears what lies within the structure's reach of the volume's faces - scipy's rule, kept."""
+    return _binary_morphology('binary_closing', input, structure, iterations, border_value)
+
+
+def create_sphere(shape, center, r):
+    """nb_post.py:81-85: integer array of `shape`, 1 where the distance to `center` is at most r."""
+    x, y, z = np.ogrid[:shape[0], :shape[1], :shape[2]]
+    return 1 * (np.sqrt((x - center[0]) ** 2 + (y - center[1]) ** 2 + (z - center[2]) ** 2) <= r)
+
+
+def post_transform(input, threshold=10000, label=2, structure=None):
+    """The clean-up of a predicted label volume (nb_post.py:88-112): 1 on the components of `input > 0` that have at
+    least `threshold` voxels, and `label` where `input == label` survives a closing by `structure` (None: the 251-voxel
+    ball create_sphere((7, 7, 7), (3, 3, 3), 4)) and an opening by the 6-neighbour cross.  numpy in -> scipy; a uint8
+    HIP tensor in -> packed masks on the device (morphology.py), a uint8 HIP tensor out.  `input` is left as it is."""
+    if structure is None:
+        structure = create_sphere((7, 7, 7), (3, 3, 3), 4)
+    if torch.is_tensor(input):
+        import components
+        import morphology
+        if input.dtype != torch.uint8:
+            raise ValueError("post_transform: expected a uint8 label volume on the device, got %s" % input.dtype)
+        output = morphology.unpack(morphology.pack(input, 'gt', 0), 1)
+        components.remove_small_region(output, threshold)
+        kept = morphology.open(morphology.close(morphology.pack(input, 'eq', label), structure))
+        return morphology.unpack(kept, label, out=output, paint=True)
+    output = np.zeros_like(input)
+    output[remove_small_region(input > 0, threshold)] = 1
+    output[ndi.binary_opening(ndi.binary_closing(input == label, structure))] = label
+    return output
+
+
 def combination_labels(input, combinations, num_classes):
     """transform.py:323-363: merge label classes.  `combinations` is one group or a list of groups of class indices.
     The new class order follows the old classes 0, 1, ...: a class that belongs to a group puts that whole group at
@@ -269,6 +332,17 @@ class RemoveSmallRegion(object):
 
     def __call__(self, case):
         case['label'] = remove_small_region(case['label'], self.threshold)
+        return case
+
+
+class PostTransform(object):
+    """post_transform on case[key] (the prediction by default), for numpy cases and cases that live on the device."""
+
+    def __init__(self, threshold=10000, label=2, structure=None, key='pred'):
+        self.threshold, self.label, self.structure, self.key = threshold, label, structure, key
+
+    def __call__(self, case):
+        case[self.key] = post_transform(case[self.key], self.threshold, self.label, self.structure)
         return case
 
 

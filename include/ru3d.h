@@ -350,6 +350,41 @@ int ru3d_region_accumulate(const float* prob, int rx, int ry, int rz, int num_cl
 int ru3d_cascade_merge(const double* total, const int32_t* hits, int X, int Y, int Z, int num_classes, uint8_t* out,
                        void* stream);
 
+/* ------------------------------------------------------------------ binary morphology on packed masks + confusion table */
+/* The clean-up and the evaluation of a prediction (nb_post.py:88-112, nb.py:11-37) on volumes that stay in HBM.
+ * A packed mask holds 64 voxels of the contiguous Z axis per 64-bit word: bit b of word w of row (x, y) is voxel
+ * z = 64 w + b; a row has ceil(Z / 64) words and the rows follow each other in the volume's [X, Y] order
+ * (ru3d_mask_bytes = X * Y * ceil(Z / 64) * 8).  Every packed volume these calls write has zeros in the bits at
+ * z >= Z of a row's last word.  X*Y*Z must stay below 2^31.  Nothing here needs a workspace. */
+enum { RU3D_MASK_NE = 0, RU3D_MASK_EQ = 1, RU3D_MASK_GT = 2, RU3D_MASK_GE = 3 };
+enum { RU3D_MORPH_ERODE = 0, RU3D_MORPH_DILATE = 1 };
+#define RU3D_MORPH_MAX_EXTENT 15 /* odd extents up to 15 per axis: offsets -7 .. 7 */
+#define RU3D_MORPH_MAX_ROWS 225
+/* one (dx, dy) row of a structuring element: bit k of zmask stands for the offset (dx, dy, k - 7) */
+typedef struct ru3d_morph_row {
+    int8_t dx, dy;
+    uint16_t zmask;
+} ru3d_morph_row;
+size_t ru3d_mask_bytes(int X, int Y, int Z);
+/* bits = (src != 0), (src == value), (src > value) or (src >= value) of a uint8 [X, Y, Z] volume (`value` is ignored
+ * by RU3D_MASK_NE): `pred == 2` or `pred > 0` without a byte mask in between. */
+int ru3d_mask_pack(const uint8_t* src, int X, int Y, int Z, int op, int value, uint64_t* bits, void* stream);
+/* paint == 0: dst = bit ? value : 0 over the whole uint8 [X, Y, Z] volume; paint == 1: dst = value where the bit is
+ * set, untouched elsewhere (`output[mask] = value`). */
+int ru3d_mask_unpack(const uint64_t* bits, int X, int Y, int Z, int value, int paint, uint8_t* dst, void* stream);
+/* One erosion (dst[p] = AND over the offsets o of src[p + o]) or dilation (OR) of a packed volume, not in place;
+ * voxels outside the volume read as border_value (0 or 1).  `rows` is a HOST array of num_rows (1 .. 225) rows with
+ * |dx|, |dy| <= 7 and a non-empty zmask; it travels in the kernel arguments, nothing is uploaded.  The offsets are
+ * gathered as given: scipy.ndimage.binary_erosion by a centred structure S is the offsets {s - centre}, and
+ * binary_dilation is the reflected set {centre - s}. */
+int ru3d_binary_morph(const uint64_t* src, uint64_t* dst, int X, int Y, int Z, int op, const ru3d_morph_row* rows,
+                      int num_rows, int border_value, void* stream);
+/* table (device int64 [(C + 1)][(C + 1)], C = num_classes <= 32; zeroed by the call, on `stream`):
+ * table[min(label[i], C)][min(pred[i], C)] += 1 over n < 2^31 voxels of two uint8 volumes of any alignment.  Integer
+ * atomics only: exact, and the same in every run.  The grid is sized by ru3d_get_cu_budget(). */
+int ru3d_confusion_counts(const uint8_t* pred, const uint8_t* label, int64_t n, int num_classes, int64_t* table,
+                          void* stream);
+
 /* ------------------------------------------------------------------ patch sampling + augmentation */
 /* The reference's training transform chain on the device: RandomRescaleCrop -> RandomMirror ->
  * RandomContrast -> RandomBrightness -> RandomGamma -> ToTensor (transform.py:573-652, 279-301, 176-259, 156-163;
