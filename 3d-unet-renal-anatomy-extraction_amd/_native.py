@@ -43,6 +43,12 @@ class PatchParams(ctypes.Structure):
                 ("gamma_eps", ctypes.c_float)]
 
 
+class SpatialParams(ctypes.Structure):
+    """struct ru3d_spatial_params"""
+    _fields_ = [("centre", ctypes.c_double * 3), ("matrix", ctypes.c_double * 9), ("lattice", ctypes.c_int32 * 3),
+                ("spacing", ctypes.c_int32 * 3)]
+
+
 class MorphRow(ctypes.Structure):
     """struct ru3d_morph_row"""
     _fields_ = [("dx", ctypes.c_int8), ("dy", ctypes.c_int8), ("zmask", ctypes.c_uint16)]
@@ -52,6 +58,7 @@ MASK_NE, MASK_EQ, MASK_GT, MASK_GE = 0, 1, 2, 3
 MORPH_ERODE, MORPH_DILATE = 0, 1
 MORPH_MAX_EXTENT, MORPH_MAX_ROWS = 15, 225
 CONFUSION_MAX_CLASSES = 32
+SPATIAL_MAX_YZ = 2560           # RU3D_SPATIAL_MAX_YZ: (ny + 4) * nz of an elastic lattice
 PACK_MAX = 40
 _P = ctypes.POINTER(Tensor)
 _vp, _i, _i64, _f, _sz, _u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t,
@@ -151,6 +158,8 @@ SIGNATURES = {
                                         ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp]),
     "ru3d_augment_patch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(PatchParams), _vp, _vp, _vp, _vp, _sz,
                                _vp]),
+    "ru3d_augment_patch_spatial": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(PatchParams),
+                                       ctypes.POINTER(SpatialParams), _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_grad_scale_check": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
     "ru3d_comm_unique_id": (_i, [_vp]),
     "ru3d_comm_init": (_i, [ctypes.POINTER(_vp), _vp, _i, _i, _i]),

@@ -12,6 +12,11 @@ a patch costs three small kernels (csrc/augment.hip) and never leaves the GPU.
 The random numbers are drawn on the HOST from numpy's global generator in exactly the reference's order (one uniform for
 the scale, one randint per axis with room for the crop corner - again for every retry of enforce_label_indices -, one
 uniform per mirror axis, one uniform per intensity op), so `np.random.seed(s)` reproduces the CPU pipeline's patch.
+
+`rotation`, `elastic_spacing` and `elastic_magnitude` switch the resampling to a free-form spatial transform (rotation
+about the crop box's centre, the same per-axis zoom, cubic B-spline elastic deformation; geometry and draw order: module
+`spatial`, kernel: spatial_kernel in csrc/augment.hip).  `transform.RandomSpatialCrop` is its numpy twin.  Left at None
+they change nothing: the same draws, the same C calls, the same bits.
 """
 import ctypes
 
@@ -19,6 +24,7 @@ import numpy as np
 import torch
 
 import _native as N
+import spatial
 from _native import check, ptr, stream
 
 
@@ -55,9 +61,16 @@ class DeviceCase:
 class DeviceAugment:
     def __init__(self, scale=0.1, crop_size=128, crop_mode="random", crop_margin=0, enforce_label_indices=(),
                  image_pad_cval=0, label_pad_cval=0, mirror_p=(0.5, 0.5, 0.5), contrast=0.1, brightness=0.1,
-                 gamma=0.1, rng=None):
+                 gamma=0.1, rng=None, rotation=None, elastic_spacing=None, elastic_magnitude=None):
         """Arguments as the reference classes take them; contrast / brightness / gamma = None switches the op off,
-        mirror_p = None the mirror.  rng: an object with numpy's `uniform` / `randint` (default: numpy's global one)."""
+        mirror_p = None the mirror.  rng: an object with numpy's `uniform` / `randint` (default: numpy's global one).
+
+        rotation: None | r (each axis uniform in [-r, r] radians) | three (lo, hi) pairs, about x, y, z.
+        elastic_spacing: control spacing of the deformation lattice in patch voxels (an int or three, >= 4) and
+        elastic_magnitude: (lo, hi) in voxels - every control vector's components are uniform in [-m, m], m uniform in
+        [lo, hi]; both or neither.  With any of the three set, the patch is cut *around* the drawn crop box, not equal
+        to it: the box gives the centre and the zoom, enforce_label_indices and the label rule's class count test the
+        axis-aligned box, and what the rotated or deformed patch reaches outside the volume reads the pad constants."""
         assert crop_mode in ("center", "random"), "crop mode must be either center or random"
         self.scale = _range(scale)
         self.crop_size = crop_size
@@ -70,6 +83,13 @@ class DeviceAugment:
         self.brightness = None if brightness is None else _range(brightness)
         self.gamma = None if gamma is None else _range(gamma)
         self.rng = rng if rng is not None else np.random
+        self.rotation = spatial.check_rotation(rotation)
+        self.elastic = spatial.check_elastic(elastic_spacing, elastic_magnitude, self._patch())
+        self.spatial = self.rotation is not None or self.elastic is not None
+
+    def _patch(self):
+        return [self.crop_size] * 3 if not isinstance(self.crop_size, (list, tuple, np.ndarray)) \
+            else [int(v) for v in self.crop_size]
 
     # ------------------------------------------------------------------ host side: the draws
     def _bbox(self, before, shape, margin):
@@ -95,9 +115,15 @@ class DeviceAugment:
     def sample(self, case, out_image=None, out_label=None):
         """One augmented patch of `case` (a DeviceCase): (image fp32 [C, px, py, pz], label int64 [px, py, pz] or None),
         written into out_image / out_label when given (slices of a batch buffer)."""
+        drawn = self._draw(case)
+        lattice = _upload([drawn[2][1]], case.image.device)[0] if self.elastic is not None else None
+        return self._launch(case, drawn, lattice, out_image, out_label)
+
+    def _draw(self, case):
+        """Every host draw of one patch, in order (the presence kernel runs here: the enforce loop needs its answer) ->
+        (PatchParams, presence mask, None | (SpatialParams, phi))."""
         shape = case.shape
-        patch = [self.crop_size] * 3 if not isinstance(self.crop_size, (list, tuple, np.ndarray)) \
-            else [int(v) for v in self.crop_size]
+        patch = self._patch()
         margin = [self.crop_margin] * 3 if not isinstance(self.crop_margin, (list, tuple, np.ndarray)) \
             else [int(v) for v in self.crop_margin]
         dev = case.image.device
@@ -114,6 +140,15 @@ class DeviceAugment:
             bits = int(mask.item()) & 0xffffffff          # only the enforce_label_indices loop reads back
             if all((bits >> min(int(i), 31)) & 1 for i in self.enforce):
                 break
+        geometry = None
+        if self.spatial:
+            angles, phi = spatial.draw_spatial(self.rng, self.rotation, self.elastic, patch)
+            centre, matrix = spatial.patch_geometry(lo, before, patch, angles)
+            sp = N.SpatialParams()
+            sp.centre[:], sp.matrix[:] = centre.tolist(), matrix.reshape(-1).tolist()
+            if phi is not None:
+                sp.lattice[:], sp.spacing[:] = phi.shape[1:], self.elastic[0]
+            geometry = (sp, phi)
         flips = [0, 0, 0]
         if self.mirror_p is not None:
             ps = self.mirror_p if isinstance(self.mirror_p, (list, tuple, np.ndarray)) else [self.mirror_p] * 3
@@ -129,6 +164,11 @@ class DeviceAugment:
             if rng_ is not None:
                 setattr(pr, "do_" + name, 1)
                 setattr(pr, name, float(self.rng.uniform(rng_[0], rng_[1])))
+        return pr, mask, geometry
+
+    def _launch(self, case, drawn, lattice, out_image, out_label):
+        pr, mask, geometry = drawn
+        shape, patch, dev = case.shape, list(pr.patch), case.image.device
         c = shape[3]
         if out_image is None:
             out_image = torch.empty((c,) + tuple(patch), dtype=torch.float32, device=dev)
@@ -140,6 +180,13 @@ class DeviceAugment:
         lab = case.label
         code = N.LABEL_I64 if (lab is None or lab.dtype == torch.int64) else N.LABEL_U8
         N.note_device(dev)
+        if geometry is not None:
+            check(N.lib.ru3d_augment_patch_spatial(ptr(case.image), ptr(lab), code, shape[0], shape[1], shape[2], c,
+                                                   ctypes.byref(pr), ctypes.byref(geometry[0]), ptr(lattice),
+                                                   ptr(mask) if lab is not None else None, ptr(out_image),
+                                                   ptr(out_label), ptr(ws), ws.numel(), stream()),
+                  "augment_patch_spatial")
+            return out_image, out_label
         check(N.lib.ru3d_augment_patch(ptr(case.image), ptr(lab), code, shape[0], shape[1], shape[2], c,
                                        ctypes.byref(pr), ptr(mask) if lab is not None else None, ptr(out_image),
                                        ptr(out_label), ptr(ws), ws.numel(), stream()), "augment_patch")
@@ -157,16 +204,34 @@ class DeviceAugment:
     def batch(self, cases, batch_size):
         """`batch_size` patches drawn from `cases` (list of DeviceCase) with replacement, like the reference's
         RandomSampler(replacement=True) (trainer.py:549-551): {'image': [N, C, ...] fp32, 'label': [N, ...] int64}."""
-        patch = [self.crop_size] * 3 if not isinstance(self.crop_size, (list, tuple, np.ndarray)) \
-            else [int(v) for v in self.crop_size]
+        patch = self._patch()
         dev = cases[0].image.device
         c = cases[0].shape[3]
         x = torch.empty((batch_size, c) + tuple(patch), dtype=torch.float32, device=dev)
         y = torch.empty((batch_size,) + tuple(patch), dtype=torch.int64, device=dev)
+        if self.elastic is None:
+            for b in range(batch_size):
+                case = cases[int(self.rng.randint(0, len(cases)))]
+                self.sample(case, x[b], y[b])
+            return {"image": x, "label": y}
+        # elastic: all draws first (same order), then the lattices of the whole batch in one upload, then the patches
+        picked, drawn = [], []
         for b in range(batch_size):
-            case = cases[int(self.rng.randint(0, len(cases)))]
-            self.sample(case, x[b], y[b])
+            picked.append(cases[int(self.rng.randint(0, len(cases)))])
+            drawn.append(self._draw(picked[-1]))
+        lattices = _upload([d[2][1] for d in drawn], dev)
+        for b in range(batch_size):
+            self._launch(picked[b], drawn[b], lattices[b], x[b], y[b])
         return {"image": x, "label": y}
+
+
+def _upload(phis, device):
+    """Control lattices (equal shapes) -> one device tensor [len, 3, nx, ny, nz], through pinned memory and a copy queued
+    on the current stream: the host does not wait for the device."""
+    staged = torch.empty((len(phis),) + phis[0].shape, dtype=torch.float32, pin_memory=True)
+    for i, phi in enumerate(phis):
+        staged[i].copy_(torch.from_numpy(phi))
+    return staged.to(device, non_blocking=True)
 
 
 # --------------------------------------------------------------------------- plain resampling (inference: predict_case)

@@ -14,6 +14,8 @@ import scipy.ndimage as ndi
 import torch
 
 from augment import DeviceAugment, DeviceCase  # noqa: F401  (the on-device replacement of the Random* chain)
+import spatial
+from spatial import bspline_displacement, resample_at, rotation_matrix, spatial_coordinates  # noqa: F401
 
 
 class Compose(object):
@@ -432,4 +434,41 @@ class RandomRescaleCrop(Crop):
         cropped_image = crop_pad_to_bbox(case['image'], bbox, self.image_pad_mode, self.image_pad_cval)
         case['image'] = resize(cropped_image, self.crop_size)
         case['label'] = resize(cropped_label, self.crop_size, is_label=True)
+        return case
+
+
+class RandomSpatialCrop(Crop):
+    """RandomRescaleCrop with a rotation about the crop box's centre and a cubic B-spline elastic deformation (module
+    spatial: geometry and draw order): the numpy twin of DeviceAugment(rotation=..., elastic_spacing=...,
+    elastic_magnitude=...).  Scale and crop box are drawn as RandomRescaleCrop draws them, enforce_label_indices and the
+    label rule's class count look at that axis-aligned box; the patch is cut *around* it (a rotated or deformed patch
+    reaches outside it, and outside the volume it reads the pad constants).  With zero angles and a zero lattice the
+    patch is RandomRescaleCrop's."""
+
+    def __init__(self, scale, crop_size=128, rotation=None, elastic_spacing=None, elastic_magnitude=None,
+                 crop_mode='center', crop_margin=0, enforce_label_indices=[], image_pad_cval=0, label_pad_cval=0,
+                 label_margin=False):
+        super().__init__(crop_size, crop_mode=crop_mode, crop_margin=crop_margin,
+                         enforce_label_indices=enforce_label_indices, image_pad_cval=image_pad_cval,
+                         label_pad_cval=label_pad_cval)
+        self.scale = _as_range(scale)
+        self.rotation = spatial.check_rotation(rotation)
+        self.elastic = spatial.check_elastic(elastic_spacing, elastic_magnitude)
+        self.label_margin = label_margin       # also store case['label_margin'] (resample_at's return_margin)
+
+    def __call__(self, case):
+        self.crop_size = _per_axis(self.crop_size, 3)
+        self.crop_margin = _per_axis(self.crop_margin, 3)
+        s = np.random.uniform(self.scale[0], self.scale[1])
+        before = np.round(np.array(self.crop_size) / s).astype(int)
+        bbox, cropped_label = self._box(case['image'], case['label'], before)
+        angles, phi = spatial.draw_spatial(np.random, self.rotation, self.elastic, self.crop_size)
+        centre, matrix = spatial.patch_geometry([b[0] for b in bbox[:3]], before, self.crop_size, angles)
+        coords = spatial_coordinates(self.crop_size, centre, matrix, phi, self.elastic and self.elastic[0])
+        case['image'] = resample_at(case['image'], coords, self.image_pad_cval).astype(case['image'].dtype)
+        label = resample_at(case['label'], coords, self.label_pad_cval, is_label=True,
+                            num_classes=int(np.unique(cropped_label).max()) + 1, return_margin=self.label_margin)
+        if self.label_margin:
+            label, case['label_margin'] = label
+        case['label'] = label
         return case

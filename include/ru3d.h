@@ -413,6 +413,44 @@ int ru3d_augment_patch(const float* image, const void* label, int label_dtype, i
                        const ru3d_patch_params* p, const uint32_t* presence_mask, float* out_image, int64_t* out_label,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* The same patch through a free-form spatial transform: rotation, the per-axis zoom above and a cubic B-spline elastic
+ * displacement.  All of the geometry is float64.  Patch P = p->patch, output voxel o, mirrored index
+ * o'_d = p->flip[d] ? P_d - 1 - o_d : o_d, centred u = o' - (P - 1) / 2:
+ *
+ *     s(o) = centre + matrix . (u + D(o'))          source coordinate in voxels of the volume
+ *
+ * The host folds the crop box into the two: centre = lo + (before - 1) / 2, matrix = R . diag(step) with
+ * step_d = (before_d - 1) / (P_d - 1) (0 when P_d == 1) and R = Rz(az) . Ry(ay) . Rx(ax), right-handed
+ * (Rx(a) = [[1,0,0],[0,cos a,-sin a],[0,sin a,cos a]]).  R = I and D = 0 give lo + o' * step, the coordinate of
+ * ru3d_augment_patch.  D, in patch voxels, comes from control vectors phi = lattice[3][nx][ny][nz] (float32, device) with
+ * n_d = ceil((P_d - 1) / g_d) + 3 for a control spacing of g_d = spacing[d] patch voxels: with t_d = o'_d / g_d,
+ * i_d = floor(t_d), f_d = t_d - i_d
+ *
+ *     D(o') = sum over a, b, c in 0..3 of B_a(fx) B_b(fy) B_c(fz) * phi[:][ix + a][iy + b][iz + c]
+ *     B_0 = (1-f)^3 / 6,  B_1 = (3f^3 - 6f^2 + 4) / 6,  B_2 = (-3f^3 + 3f^2 + 3f + 1) / 6,  B_3 = f^3 / 6
+ *
+ * (the uniform cubic B-spline; a constant lattice is a pure shift; where (P_d - 1) / g_d is whole the last voxel of the
+ * axis has i_d + 3 == n_d with weight B_3(0) = 0; that tap reads the last control point).  Sampling at s, clamped to [-2, extent + 1] per axis:
+ * i0 = floor(s), w = s - i0, the 8 neighbours i0 + {0, 1}; a neighbour outside the volume contributes image_cval /
+ * label_cval (the volume continued by the constant); float64 lerps along axis 0, then 1, then 2, float32 result; labels by
+ * the rule of ru3d_augment_patch with the presence mask of the drawn (axis-aligned) crop box.  p->lo / p->before are not
+ * read.  Workspace, per-block partials and the intensity chain are those of ru3d_augment_patch.
+ * A workgroup keeps the lattice collapsed along x - [3][ny][nz] float64 - and one [3][nz] row per wave in LDS (60 KB at
+ * most): a lattice with (ny + 4) * nz > RU3D_SPATIAL_MAX_YZ is refused.  128^3 at g = 16 is 15 * 11, 256^3 at g = 16
+ * 23 * 19, 128^3 at g = 4 39 * 35 (all accepted); 192^3 at g = 4 is 55 * 51 (refused). */
+#define RU3D_SPATIAL_MAX_YZ 2560
+typedef struct ru3d_spatial_params {
+    double centre[3];   /* c                                                                                        */
+    double matrix[9];   /* M, row-major                                                                             */
+    int32_t lattice[3]; /* control points per axis; all 0 = no displacement                                         */
+    int32_t spacing[3]; /* g: patch voxels per lattice cell (>= 4); read when there is a lattice                    */
+} ru3d_spatial_params;
+int ru3d_augment_patch_spatial(const float* image, const void* label, int label_dtype, int X, int Y, int Z, int C,
+                               const ru3d_patch_params* p, const ru3d_spatial_params* sp,
+                               const float* lattice /* device, [3][nx][ny][nz]; NULL without a lattice */,
+                               const uint32_t* presence_mask, float* out_image, int64_t* out_label, void* ws,
+                               size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ optimizer --------------- */
 /* torch.optim.Adam step (nb_train_iia.py:18 defaults), fused over one flat fp32 parameter run.
  * grad may be bf16/f32 (grad_dtype); bias corrections are passed in by the host. */

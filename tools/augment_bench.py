@@ -1,4 +1,5 @@
-"""Throughput of the on-device patch sampling / augmentation (GPU box): python tools/augment_bench.py"""
+"""Throughput of the on-device patch sampling / augmentation (GPU box): python tools/augment_bench.py [--spatial]
+(--spatial adds a row for the same batch with rotation and elastic deformation switched on)."""
 import os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -8,14 +9,31 @@ dev = torch.device("cuda:0")
 rng = np.random.RandomState(0)
 cases = [augment.DeviceCase(rng.randn(256, 256, 160, 1).astype(np.float32), (rng.rand(256, 256, 160) * 4).astype(np.uint8), dev)
          for _ in range(2)]
-aug = augment.DeviceAugment(scale=0.1, crop_size=128, crop_mode="random")
-for _ in range(3):
-    aug.batch(cases, 2)
-torch.cuda.synchronize()
-t0 = time.perf_counter(); n = 50
-for _ in range(n):
-    aug.batch(cases, 2)
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / n
-print("batch of 2 x 128^3 patches (rescale-crop + mirror + contrast + brightness + gamma): %.3f ms = %.0f M voxels/s"
-      % (1e3 * dt, 2 * 128 ** 3 / dt / 1e6))
+
+
+def measure(aug, what, n=50, repeats=5):
+    """Warm-up, then the median over `repeats` timed windows of `n` batches, each window closed by a device synchronise."""
+    for _ in range(3):
+        aug.batch(cases, 2)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        for _ in range(n):
+            aug.batch(cases, 2)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) / n)
+    dt = float(np.median(times))
+    print("batch of 2 x 128^3 patches (%s): %.3f ms = %.0f M voxels/s  [min %.3f, max %.3f ms over %d windows of %d]"
+          % (what, 1e3 * dt, 2 * 128 ** 3 / dt / 1e6, 1e3 * min(times), 1e3 * max(times), repeats, n))
+
+
+np.random.seed(0)
+measure(augment.DeviceAugment(scale=0.1, crop_size=128, crop_mode="random"),
+        "rescale-crop + mirror + contrast + brightness + gamma")
+if "--spatial" in sys.argv[1:]:
+    # the same batch through the free-form transform: the training script's rotation about x, elastic deformation on
+    measure(augment.DeviceAugment(scale=0.1, crop_size=128, crop_mode="random",
+                                  rotation=((-0.1 * np.pi, 0.1 * np.pi), (0, 0), (0, 0)), elastic_spacing=16,
+                                  elastic_magnitude=(0, 8)),
+            "rotation + rescale + elastic g=16 + mirror + contrast + brightness + gamma")
