@@ -58,6 +58,7 @@ MASK_NE, MASK_EQ, MASK_GT, MASK_GE = 0, 1, 2, 3
 MORPH_ERODE, MORPH_DILATE = 0, 1
 MORPH_MAX_EXTENT, MORPH_MAX_ROWS = 15, 225
 CONFUSION_MAX_CLASSES = 32
+ORDER_STATS_MAX_RANKS = 8
 SPATIAL_MAX_YZ = 2560           # RU3D_SPATIAL_MAX_YZ: (ny + 4) * nz of an elastic lattice
 PACK_MAX = 40
 _P = ctypes.POINTER(Tensor)
@@ -148,6 +149,13 @@ SIGNATURES = {
     "ru3d_mask_unpack": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ru3d_binary_morph": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.POINTER(MorphRow), _i, _i, _vp]),
     "ru3d_confusion_counts": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "ru3d_threshold_bbox": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "ru3d_masked_sample_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_masked_sample": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ru3d_order_stats_workspace_bytes": (_sz, []),
+    "ru3d_order_stats": (_i, [_vp, _i64, ctypes.POINTER(ctypes.c_int64), _i, _vp, _vp, _sz, _vp]),
+    "ru3d_moments_workspace_bytes": (_sz, []),
+    "ru3d_moments": (_i, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "ru3d_adam_multi": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "ru3d_adam_multi_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ru3d_adam_multi_amp": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -155,6 +155,17 @@ def _zoomed_shape(shape, scale):
     return tuple(int(round(s * z)) for s, z in zip(shape, scale))
 
 
+def resample_normalize_image(vol, out_shape, stats):
+    """fp32 HIP volume [X, Y, Z, C] -> [x, y, z, len(stats)]: the order-1 zoom kernel, then per channel the clip to
+    [pct_00_5, pct_99_5] and (x - mean) / (std + 1e-8) (reference data.py:222-283).  Shared by predict_case and
+    data.resample_normalize_case."""
+    import augment
+    vol = augment.resample_image(vol, out_shape)
+    for c, s in enumerate(stats):
+        vol[..., c].clamp_(float(s['pct_00_5']), float(s['pct_99_5'])).sub_(float(s['mean'])).div_(float(s['std']) + 1e-8)
+    return vol[..., :len(stats)]
+
+
 def predict_case(case, model, target_spacing, normalize_stats, num_classes=3, patch_size=(96, 96, 96),
                  step_per_patch=4, verbose=True, one_hot=False, patch_batch=1, return_device=False):
     """reference trainer.py:101-133: resample the case to `target_spacing` and normalise it (data.py:222-283), run the
@@ -179,10 +190,7 @@ def predict_case(case, model, target_spacing, normalize_stats, num_classes=3, pa
         vol = image.to(device=device, dtype=torch.float32).contiguous()
     else:
         vol = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(device)
-    vol = augment.resample_image(vol, _zoomed_shape(orig_shape, scale))
-    for c, s in enumerate(stats):                 # clip to the percentiles, then (x - mean) / (std + 1e-8)
-        vol[..., c].clamp_(float(s['pct_00_5']), float(s['pct_99_5'])).sub_(float(s['mean'])).div_(float(s['std']) + 1e-8)
-    vol = vol[..., :len(stats)]
+    vol = resample_normalize_image(vol, _zoomed_shape(orig_shape, scale), stats)
     if verbose:
         print('Predicting the case...')
     pred = predict_per_patch(vol, model, num_classes, patch_size, step_per_patch, verbose, one_hot,

@@ -385,6 +385,37 @@ int ru3d_binary_morph(const uint64_t* src, uint64_t* dst, int X, int Y, int Z, i
 int ru3d_confusion_counts(const uint8_t* pred, const uint8_t* label, int64_t n, int num_classes, int64_t* table,
                           void* stream);
 
+/* ------------------------------------------------------------------ dataset preparation */
+/* What orient_crop_case / analyze_cases (reference data.py:117-172, 322-461) need beyond data movement, for a case that
+ * lives in HBM.  `image` is the case layout, fp32 [X, Y, Z, C] dense with the channel last; fewer than 2^31 voxels.
+ * Every result is exact and the same in every run: integer atomics and fixed-order sums only.
+ *
+ * ru3d_threshold_bbox: box (device int32 [6]) = per axis the smallest and the LARGEST index (x0, x1, y0, y1, z0, z1) of a
+ * voxel with any channel > threshold, count (device int64) = the number of such voxels.  count == 0 leaves the box at
+ * (INT_MAX, -1) per axis.  One read of the volume. */
+int ru3d_threshold_bbox(const float* image, int X, int Y, int Z, int C, float threshold, int32_t* box, int64_t* count,
+                        void* stream);
+/* ru3d_masked_sample: out = image[..., channel][label > 0][::stride] in numpy's element order (x outermost, z fastest):
+ * the foreground voxel of rank r goes to out[r / stride] when r % stride == 0.  `label` is uint8 or int64 [X, Y, Z]
+ * (RU3D_LABEL_U8 / RU3D_LABEL_I64).  count (device int64) receives the number of samples, ceil(foreground / stride),
+ * whatever the capacity; nothing is written at or beyond out[capacity], so a count above the capacity means the buffer
+ * was too small.  out == NULL counts only (image may then be NULL as well).  Workspace: one int per 2048 voxels. */
+size_t ru3d_masked_sample_workspace_bytes(int X, int Y, int Z);
+int ru3d_masked_sample(const float* image, int X, int Y, int Z, int C, int channel, const void* label, int label_dtype,
+                       int stride, float* out, int64_t capacity, int64_t* count, void* ws, size_t ws_bytes, void* stream);
+/* ru3d_order_stats: out[i] (device fp32) = the ranks[i]-th smallest of n finite device values, zero-based - the value
+ * np.sort(values)[ranks[i]] (the two zeros are one value: compare with ==).  `ranks` is a HOST array of 1 ..
+ * RU3D_ORDER_STATS_MAX_RANKS entries, each < n.  Radix select, 8 bits per pass: the values are read four times, never
+ * moved. */
+#define RU3D_ORDER_STATS_MAX_RANKS 8
+size_t ru3d_order_stats_workspace_bytes(void);
+int ru3d_order_stats(const float* values, int64_t n, const int64_t* ranks, int num_ranks, float* out, void* ws,
+                     size_t ws_bytes, void* stream);
+/* ru3d_moments: out (device float64 [5]) = (n, min, max, mean, population standard deviation) of n finite device
+ * values, accumulated in float64 in two passes (sum; squared deviations from the mean). */
+size_t ru3d_moments_workspace_bytes(void);
+int ru3d_moments(const float* values, int64_t n, double* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ patch sampling + augmentation */
 /* The reference's training transform chain on the device: RandomRescaleCrop -> RandomMirror ->
  * RandomContrast -> RandomBrightness -> RandomGamma -> ToTensor (transform.py:573-652, 279-301, 176-259, 156-163;
