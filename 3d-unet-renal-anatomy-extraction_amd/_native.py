@@ -59,6 +59,7 @@ MORPH_ERODE, MORPH_DILATE = 0, 1
 MORPH_MAX_EXTENT, MORPH_MAX_ROWS = 15, 225
 CONFUSION_MAX_CLASSES = 32
 ORDER_STATS_MAX_RANKS = 8
+EDT_MAX_AXIS = 4096             # RU3D_EDT_MAX_AXIS: x and y extents of the distance transform
 SPATIAL_MAX_YZ = 2560           # RU3D_SPATIAL_MAX_YZ: (ny + 4) * nz of an elastic lattice
 PACK_MAX = 40
 _P = ctypes.POINTER(Tensor)
@@ -156,6 +157,13 @@ SIGNATURES = {
     "ru3d_order_stats": (_i, [_vp, _i64, ctypes.POINTER(ctypes.c_int64), _i, _vp, _vp, _sz, _vp]),
     "ru3d_moments_workspace_bytes": (_sz, []),
     "ru3d_moments": (_i, [_vp, _i64, _vp, _vp, _sz, _vp]),
+    "ru3d_edt_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_edt_squared": (_i, [_vp, _i, _i, _i, ctypes.POINTER(_dbl), _vp, _vp, _sz, _vp]),
+    "ru3d_mask_surface": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ru3d_edt_gather_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_edt_gather": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ru3d_edt_reduce_workspace_bytes": (_sz, [_i64]),
+    "ru3d_edt_reduce": (_i, [_vp, _vp, _i64, _dbl, _vp, _vp, _sz, _vp]),
     "ru3d_adam_multi": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "ru3d_adam_multi_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ru3d_adam_multi_amp": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

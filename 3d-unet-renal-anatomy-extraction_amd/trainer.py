@@ -813,3 +813,147 @@ def batch_evaluate(label_dir, pred_dir, data_range=None):
     for i, m in enumerate(np.array(results).mean(axis=0)):
         print("label_%d: %f" % (i + 1, m))
     return results
+
+
+# ------------------------------------------------------------------ surface-distance metrics
+def _spacing3(spacing, ndim):
+    """`spacing` (None = 1 per axis) as three floats for a volume of 1 to 3 axes, leading axes of length 1 first."""
+    if not 1 <= ndim <= 3:
+        raise ValueError("evaluate_surface_case: a volume of %d axes (1 to 3)" % ndim)
+    s = (1.0,) * ndim if spacing is None else tuple(float(v) for v in spacing)
+    if len(s) != ndim or not all(math.isfinite(v) and v > 0 for v in s):
+        raise ValueError("evaluate_surface_case: spacing=%r for a volume of %d axes (one finite value > 0 per axis)"
+                         % (spacing, ndim))
+    return (1.0,) * (3 - ndim) + s
+
+
+def _nearest_feature_numpy(features, spacing):
+    """scipy's feature transform: int32 [3, X, Y, Z], the index of the nearest set voxel of `features` (not empty)."""
+    import scipy.ndimage as ndi
+    return ndi.distance_transform_edt(~features, sampling=spacing, return_distances=False, return_indices=True)
+
+
+def _contract_sq_numpy(src, nearest, spacing):
+    """Squared distances from the set voxels of `src` (element order) to the voxels `nearest` names for them, through
+    the expression the device transform is held to: fl(A + fl(B + C)) with A = fl(fl(sx (px - fx))^2), in float64 - not
+    the square of scipy's rooted output."""
+    at = np.nonzero(src)
+    a, b, c = ((spacing[k] * (at[k] - nearest[k][at]).astype(np.float64)) ** 2 for k in range(3))
+    return a + (b + c)
+
+
+def _surface_reduce_numpy(d_ab, d_ba, tolerance):
+    """The reductions of distance.surface_stats over two non-empty vectors of squared distances."""
+    tol_sq = float(tolerance) * float(tolerance)
+    lo, hi = _percentile_ranks(d_ab.size + d_ba.size)
+    both = np.partition(np.concatenate((d_ab, d_ba)), (lo, hi))
+    return dict(n_ab=int(d_ab.size), n_ba=int(d_ba.size),
+                max_ab=float(d_ab.max()), within_ab=int((d_ab <= tol_sq).sum()), sum_ab=float(np.sqrt(d_ab).sum()),
+                max_ba=float(d_ba.max()), within_ba=int((d_ba <= tol_sq).sum()), sum_ba=float(np.sqrt(d_ba).sum()),
+                lo=float(both[lo]), hi=float(both[hi]))
+
+
+def _surface_numpy(mask):
+    import scipy.ndimage as ndi
+    return mask & ~ndi.binary_erosion(mask)
+
+
+def _surface_stats_numpy(a, b, spacing, tolerance):
+    """distance.surface_stats on the host: the same dict from two boolean volumes [X, Y, Z]."""
+    sa, sb = _surface_numpy(a), _surface_numpy(b)
+    if not sa.any() or not sb.any():
+        return {'n_ab': int(sa.sum()), 'n_ba': int(sb.sum())}
+    return _surface_reduce_numpy(_contract_sq_numpy(sa, _nearest_feature_numpy(sb, spacing), spacing),
+                                 _contract_sq_numpy(sb, _nearest_feature_numpy(sa, spacing), spacing), tolerance)
+
+
+def _percentile_ranks(n, q=95.0):
+    """The two zero-based order statistics np.percentile(., q) interpolates between for n values (its default, linear)."""
+    lo = int(math.floor(q / 100.0 * (n - 1)))
+    return lo, min(lo + 1, n - 1)
+
+
+def _surface_metrics(stats, q=95.0):
+    """hd / hd95 / assd / nsd from the dict of distance.surface_stats (or its host twin).  The square root is taken
+    here, on a handful of numbers; the percentile is np.percentile's linear interpolation written out."""
+    n_ab, n_ba = stats['n_ab'], stats['n_ba']
+    if n_ab == 0 and n_ba == 0:
+        return {'hd': 0.0, 'hd95': 0.0, 'assd': 0.0, 'nsd': 1.0}
+    if n_ab == 0 or n_ba == 0:
+        return {'hd': math.inf, 'hd95': math.inf, 'assd': math.inf, 'nsd': 0.0}
+    n = n_ab + n_ba
+    lo, hi = math.sqrt(stats['lo']), math.sqrt(stats['hi'])
+    gamma = q / 100.0 * (n - 1) - _percentile_ranks(n, q)[0]
+    hd95 = hi - (hi - lo) * (1 - gamma) if gamma >= 0.5 else lo + (hi - lo) * gamma
+    return {'hd': math.sqrt(max(stats['max_ab'], stats['max_ba'])),
+            'hd95': hd95,
+            'assd': (stats['sum_ab'] / n_ab + stats['sum_ba'] / n_ba) / 2,
+            'nsd': (stats['within_ab'] + stats['within_ba']) / n}
+
+
+def _surface_stats_case(case, spacing, tolerance):
+    """One dict of surface statistics (distance.surface_stats) per foreground class 1 .. label.max()."""
+    pred, label = case['pred'], case['label']
+    if tuple(pred.shape) != tuple(label.shape):
+        raise ValueError("evaluate_surface_case: pred has shape %s, label %s" % (tuple(pred.shape), tuple(label.shape)))
+    spacing = _spacing3(spacing, len(label.shape))
+    if float(tolerance) < 0 or math.isnan(float(tolerance)):
+        raise ValueError("evaluate_surface_case: tolerance=%r (>= 0)" % (tolerance,))
+    if _is_hip(pred) or _is_hip(label):
+        import distance
+        import morphology
+        device = pred.device if _is_hip(pred) else label.device
+        pred, label = _device_bytes(pred, device), _device_bytes(label, device)
+        top = int(label.max().item()) if label.numel() else 0
+        sampling = spacing[3 - label.dim():]
+        return [distance.surface_stats(morphology.pack(pred, 'eq', c), morphology.pack(label, 'eq', c), sampling, tolerance)
+                for c in range(1, top + 1)]
+    pred = np.asarray(pred.cpu() if torch.is_tensor(pred) else pred)
+    label = np.asarray(label.cpu() if torch.is_tensor(label) else label)
+    shape3 = (1,) * (3 - label.ndim) + label.shape
+    pred, label = pred.reshape(shape3), label.reshape(shape3)
+    top = int(label.max()) if label.size else 0
+    return [_surface_stats_numpy(pred == c, label == c, spacing, tolerance) for c in range(1, top + 1)]
+
+
+def evaluate_surface_case(case, spacing=None, tolerance=1.0):
+    """Boundary metrics of every foreground class 1 .. label.max(): a list of dicts with the keys
+      hd    Hausdorff distance: the largest distance from a surface voxel of one mask to the other mask's surface,
+      hd95  np.percentile(., 95) of all those distances (both directions concatenated),
+      assd  average symmetric surface distance: the mean of the two directions' mean distances,
+      nsd   surface Dice at `tolerance`: the share of surface voxels (of both masks) within the tolerance of the other
+            surface, decided on the squared distances in float64.
+    A mask's surface is `mask & ~binary_erosion(mask)` (6-neighbour cross, the volume's faces count as outside) and
+    distances are Euclidean between voxel centres in `spacing` units (None: 1 per axis).  Both masks empty gives
+    0, 0, 0, 1; exactly one empty gives inf, inf, inf, 0.  numpy operands run on the host (scipy); when `pred` or
+    `label` is a HIP tensor the other operand is uploaded and surfaces, distance transforms (csrc/distance.hip),
+    gathers and reductions stay on the device: per class one download of ten numbers."""
+    return [_surface_metrics(s) for s in _surface_stats_case(case, spacing, tolerance)]
+
+
+def evaluate_surface(label_file, pred_file, tolerance=1.0, device=None):
+    """evaluate_surface_case of two NIfTI files, with the spacing of the label's affine.  device: a HIP device uploads
+    both volumes (as bytes) and evaluates there."""
+    import nifti
+    from data import get_spacing
+    label, affine, _ = nifti.load(label_file)
+    pred, _, _ = nifti.load(pred_file)
+    case = {'label': label.astype(np.uint8), 'pred': pred.astype(np.uint8)}
+    if device is not None:
+        case = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in case.items()}
+    return evaluate_surface_case(case, spacing=get_spacing(affine), tolerance=tolerance)
+
+
+def batch_evaluate_surface(label_dir, pred_dir, data_range=None, tolerance=1.0, device=None):
+    """evaluate_surface over the sorted *.nii.gz files of two directories; prints the mean of each metric per class
+    (over the cases that have the class) and returns the per-case lists."""
+    from pathlib import Path
+    label_files = sorted(Path(label_dir).glob('*.nii.gz'))
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    results = [evaluate_surface(label_files[i], pred_files[i], tolerance, device)
+               for i in (data_range if data_range is not None else range(len(label_files)))]
+    for key in ('hd', 'hd95', 'assd', 'nsd'):
+        print('\nThe mean %s of each label:' % key)
+        for c in range(max((len(r) for r in results), default=0)):
+            print("label_%d: %f" % (c + 1, np.mean([r[c][key] for r in results if len(r) > c])))
+    return results

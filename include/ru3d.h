@@ -416,6 +416,40 @@ int ru3d_order_stats(const float* values, int64_t n, const int64_t* ranks, int n
 size_t ru3d_moments_workspace_bytes(void);
 int ru3d_moments(const float* values, int64_t n, double* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ distance transform + surface-distance reductions */
+/* Boundary metrics of a prediction that stays in HBM (Hausdorff distance, its percentile, average symmetric surface
+ * distance, surface Dice).  Masks are the packed masks of the morphology section; X*Y*Z < 2^31.
+ *
+ * ru3d_edt_squared: the exact squared Euclidean distance transform.  The set bits of `bits` are the FEATURE voxels,
+ * `spacing` is a HOST array of three finite values > 0, out is float64 [X, Y, Z]:
+ *     out[p] = min over the feature voxels f of  fl(A + fl(B + C)),
+ *     A = fl(fl(sx (px - fx))^2),  B = fl(fl(sy (py - fy))^2),  C = fl(fl(sz (pz - fz))^2)
+ * in float64, fl = round to nearest.  That expression is the contract: the result does not depend on the order the
+ * candidates are visited in and can be compared with ==.  No feature voxel at all: +inf everywhere.  X and Y may not
+ * exceed RU3D_EDT_MAX_AXIS (a column of the scanned axis is held in LDS); Z is bounded by the voxel count alone. */
+#define RU3D_EDT_MAX_AXIS 4096
+size_t ru3d_edt_workspace_bytes(int X, int Y, int Z);
+int ru3d_edt_squared(const uint64_t* bits, int X, int Y, int Z, const double* spacing, double* out, void* ws,
+                     size_t ws_bytes, void* stream);
+/* dst = src & ~erode(src) with the 6-neighbour cross and border_value 0, not in place: the voxels of the mask that have
+ * a face neighbour outside it, the volume's faces counting as outside. */
+int ru3d_mask_surface(const uint64_t* src, uint64_t* dst, int X, int Y, int Z, void* stream);
+/* values[r] = sq[p_r] for the set bits p_r of `query` in numpy's element order (x outermost, z fastest): numpy's
+ * sq[query].  count (device int64) receives the number of set bits whatever the capacity; nothing is written at or
+ * beyond values[capacity].  values == NULL counts only (sq may then be NULL as well).  Workspace: one int per 256
+ * words of the mask. */
+size_t ru3d_edt_gather_workspace_bytes(int X, int Y, int Z);
+int ru3d_edt_gather(const double* sq, const uint64_t* query, int X, int Y, int Z, double* values, int64_t capacity,
+                    int64_t* count, void* ws, size_t ws_bytes, void* stream);
+/* out (device float64 [4]) = (n, max v, #{v <= tau_sq}, sum of sqrt(v)) over the first n = min(*count, capacity)
+ * device values v >= 0; `count` is a DEVICE int64, so a gather and its reductions are enqueued without a host read in
+ * between.  n == 0 gives four zeros.  The sum runs in float64 over a fixed partition in a fixed order: the same bits
+ * in every run and under every CU budget.  The square root is monotone, so maximum and count are taken on the squared
+ * distances and are exact. */
+size_t ru3d_edt_reduce_workspace_bytes(int64_t capacity);
+int ru3d_edt_reduce(const double* values, const int64_t* count, int64_t capacity, double tau_sq, double* out, void* ws,
+                    size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ patch sampling + augmentation */
 /* The reference's training transform chain on the device: RandomRescaleCrop -> RandomMirror ->
  * RandomContrast -> RandomBrightness -> RandomGamma -> ToTensor (transform.py:573-652, 279-301, 176-259, 156-163;

@@ -25,7 +25,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "3d-unet-renal-anatomy-extraction_amd", "csrc")
 SRCS = ["conv_slide32.hip", "conv_slide64.hip", "conv_s2.hip", "conv_ws.hip", "fused_skip.hip", "wgrad_slide.hip", "wgrad_s2.hip", "conv_mfma.hip", "small_convs.hip", "conv_generic.hip",
-        "norm.hip", "norm_small.hip", "loss.hip", "predict.hip", "comm.hip", "components.hip", "morphology.hip", "augment.hip", "prepare.hip"]
+        "norm.hip", "norm_small.hip", "loss.hip", "predict.hip", "comm.hip", "components.hip", "morphology.hip", "augment.hip", "prepare.hip", "distance.hip"]
 TWICE = {"conv_slide32.hip", "conv_slide64.hip", "conv_s2.hip", "conv_ws.hip", "fused_skip.hip", "wgrad_slide.hip", "wgrad_s2.hip", "conv_mfma.hip", "small_convs.hip", "conv_generic.hip",
          "norm.hip", "norm_small.hip"}
 # spilled VGPRs tolerated per kernel-name pattern (everything else: 0)
@@ -122,11 +122,11 @@ def parse(path):
         kernels[name] = {"mfma": len(mf), "scratch_in_mfma_span": inside,
                          "copies_into_operands": copies_into_mfma_operands(lines, mf) if mf else 0,
                          "scratch_total": sum(1 for l in lines if re.search(r"\bscratch_(load|store)", l))}
-    for m in re.finditer(r"- \.agpr_count:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?"
+    for m in re.finditer(r"- \.agpr_count:\s+(\d+).*?\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?"
                          r"\.sgpr_count:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", text, re.S):
-        agpr, name, scratch, sgpr, vgpr, spill = m.groups()
+        agpr, lds, name, scratch, sgpr, vgpr, spill = m.groups()
         if name in kernels:
-            kernels[name].update(agpr=int(agpr), scratch_bytes=int(scratch), sgpr=int(sgpr), vgpr=int(vgpr),
+            kernels[name].update(agpr=int(agpr), lds=int(lds), scratch_bytes=int(scratch), sgpr=int(sgpr), vgpr=int(vgpr),
                                  spill=int(spill))
     return kernels
 
@@ -149,8 +149,8 @@ def main():
                 nice = re.sub(r"\(.*$", "", nice)
                 allow = max([a for pat, a in ALLOW if re.search(pat, nice)] or [0])
                 rows.append((src + (" [f16]" if f16 else ""), nice, k.get("vgpr", -1), k.get("agpr", -1),
-                             k.get("sgpr", -1), k.get("spill", -1), k.get("scratch_bytes", -1), k["mfma"],
-                             k["scratch_in_mfma_span"]))
+                             k.get("sgpr", -1), k.get("spill", -1), k.get("scratch_bytes", -1), k.get("lds", -1),
+                             k["mfma"], k["scratch_in_mfma_span"]))
                 if k.get("spill", 0) > allow:
                     failures.append("%s: %s spills %d VGPRs (allowance %d)" % (src, nice, k["spill"], allow))
                 if any(re.search(p, nice) for p in NO_SCRATCH_IN_MFMA_SPAN) and k["scratch_in_mfma_span"]:
@@ -159,10 +159,11 @@ def main():
                 if any(re.search(p, nice) for p in NO_COPY_INTO_MFMA_OPERANDS) and k["copies_into_operands"]:
                     failures.append("%s: %s copies into an MFMA operand register next to / between its MFMAs "
                                     "(%d times)" % (src, nice, k["copies_into_operands"]))
-    lines = ["%-24s %-62s %5s %5s %5s %6s %8s %6s %s" % ("source", "kernel", "vgpr", "agpr", "sgpr", "spill", "scratchB",
-                                                          "mfma", "scratch-in-mfma-span")]
+    # ldsB: the static LDS of the code object; a tile a launch sizes (extern __shared__) comes on top of it
+    lines = ["%-24s %-62s %5s %5s %5s %6s %8s %6s %6s %s" % ("source", "kernel", "vgpr", "agpr", "sgpr", "spill", "scratchB",
+                                                              "ldsB", "mfma", "scratch-in-mfma-span")]
     for r in rows:
-        lines.append("%-24s %-62s %5d %5d %5d %6d %8d %6d %d" % (r[0], r[1][:62], *r[2:]))
+        lines.append("%-24s %-62s %5d %5d %5d %6d %8d %6d %6d %d" % (r[0], r[1][:62], *r[2:]))
     lines.append("")
     lines.append("FAILURES: %d" % len(failures))
     lines += failures
