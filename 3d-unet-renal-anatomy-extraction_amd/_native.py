@@ -164,6 +164,12 @@ SIGNATURES = {
     "ru3d_edt_gather": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ru3d_edt_reduce_workspace_bytes": (_sz, [_i64]),
     "ru3d_edt_reduce": (_i, [_vp, _vp, _i64, _dbl, _vp, _vp, _sz, _vp]),
+    "ru3d_mesh_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_mesh_count": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ru3d_mesh_emit": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ru3d_mesh_smooth": (_i, [_vp, _vp, _vp, _i64, _dbl, _vp]),
+    "ru3d_mesh_measure_workspace_bytes": (_sz, [_i64]),
+    "ru3d_mesh_measure": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ru3d_adam_multi": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "ru3d_adam_multi_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ru3d_adam_multi_amp": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

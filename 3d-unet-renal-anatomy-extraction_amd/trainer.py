@@ -957,3 +957,107 @@ def batch_evaluate_surface(label_dir, pred_dir, data_range=None, tolerance=1.0, 
         for c in range(max((len(r) for r in results), default=0)):
             print("label_%d: %f" % (c + 1, np.mean([r[c][key] for r in results if len(r) > c])))
     return results
+
+
+# ------------------------------------------------------------------ surface meshes of the predicted structures
+def _mesh_labels(labels, top):
+    """[(name, (values ...)), ...]: None = every value 1 .. top; an entry may be a tuple, meaning the union of its
+    values (kidney and tumour = (1, 2))."""
+    if labels is None:
+        labels = range(1, top + 1)
+    out = []
+    for entry in labels:
+        values = tuple(int(v) for v in entry) if isinstance(entry, (tuple, list)) else (int(entry),)
+        if not values or any(v < 1 or v > 255 for v in values):
+            raise ValueError("extract_mesh_case: label %r (values 1 .. 255, or a tuple of them)" % (entry,))
+        out.append((tuple(entry) if isinstance(entry, (tuple, list)) else int(entry), values))
+    return out
+
+
+def extract_mesh_case(case, labels=None, key='pred', smooth_iterations=10, lam=0.5, mu=-0.53, return_device=False):
+    """One closed triangle mesh per structure of the label volume `case[key]`: a list of dicts
+      label     the value (or the tuple of values whose union was meshed),
+      vertices  float64 [V, 3] in the world coordinates of `case['affine']` (millimetres; voxel coordinates without one),
+      faces     int32 [F, 3], counter-clockwise seen from outside (also under an affine that mirrors),
+      area, volume   of the mesh in those units (mm^2, mm^3).
+    The surface is the voxels' own faces (transform.extract_mesh), Taubin-smoothed in index space; the affine is applied
+    afterwards and the measures are taken on the world positions.  labels=None means every value 1 .. max.  A numpy
+    volume takes the numpy route.  A HIP volume - for instance `cascade_predict_case(..., return_device=True)['pred']` -
+    is packed, meshed, smoothed, mapped and measured on the device (csrc/mesh.hip); what is downloaded is the finished
+    vertices and faces, or with return_device=True only the two measures."""
+    import transform
+    volume = case[key]
+    affine = np.asarray(case['affine'], dtype=np.float64) if case.get('affine') is not None else np.eye(4)
+    results = []
+    if _is_hip(volume):
+        import mesh
+        import morphology
+        if volume.dim() < 1 or volume.dim() > 3:
+            raise ValueError("extract_mesh_case: case[%r] has shape %s (1 to 3 axes)" % (key, tuple(volume.shape)))
+        volume = _device_bytes(volume, volume.device)
+        top = int(volume.max().item()) if labels is None else 0
+        for name, values in _mesh_labels(labels, top):
+            packed = morphology.pack(volume, 'eq', values[0])
+            for v in values[1:]:
+                packed.bits |= morphology.pack(volume, 'eq', v).bits
+            m = mesh.smooth(mesh.extract(packed), smooth_iterations, lam, mu)
+            vertices, faces = mesh.to_world(m.vertices, affine, m.faces)
+            area, vol = mesh.measure(vertices, faces).tolist()
+            if not return_device:
+                vertices, faces = vertices.cpu().numpy(), faces.cpu().numpy()
+            results.append({'label': name, 'vertices': vertices, 'faces': faces, 'area': area, 'volume': vol})
+        return results
+    volume = np.asarray(volume.cpu() if torch.is_tensor(volume) else volume)
+    if volume.ndim < 1 or volume.ndim > 3:
+        raise ValueError("extract_mesh_case: case[%r] has shape %s (1 to 3 axes)" % (key, volume.shape))
+    top = int(volume.max()) if labels is None and volume.size else 0
+    for name, values in _mesh_labels(labels, top):
+        m = transform.extract_mesh(np.isin(volume, values), smooth_iterations, lam, mu)
+        vertices, faces = transform._to_world_numpy(m.vertices, m.faces, affine)
+        area, vol = transform._measure_mesh_numpy(vertices, faces)
+        results.append({'label': name, 'vertices': vertices, 'faces': faces, 'area': area, 'volume': vol})
+    return results
+
+
+def _label_name(label):
+    return '_'.join(str(v) for v in label) if isinstance(label, tuple) else str(label)
+
+
+def extract_mesh(pred_file, save_dir=None, fmt='stl', device=None, labels=None, smooth_iterations=10, lam=0.5, mu=-0.53):
+    """extract_mesh_case of a NIfTI label volume (a `*.pred.nii.gz` of save_pred, or a ground-truth segmentation) with
+    the file's affine.  save_dir: every non-empty structure is written as `<case_id>.label_<n>.<fmt>` (fmt 'stl' or
+    'ply'; a union (1, 2) is named label_1_2) and its dict gains 'file'.  device: a HIP device uploads the volume (as
+    bytes) and meshes there.  Prints volume (ml) and area (mm^2) per structure; returns the list of dicts."""
+    import nifti
+    import meshfile
+    from pathlib import Path
+    if fmt not in meshfile.WRITERS:
+        raise ValueError("extract_mesh: fmt=%r ('stl' or 'ply')" % (fmt,))
+    pred_file = Path(pred_file)
+    case_id = pred_file.name
+    for suffix in ('.gz', '.nii', '.pred'):
+        if case_id.endswith(suffix):
+            case_id = case_id[:-len(suffix)]
+    pred, affine, _ = nifti.load(pred_file)
+    pred = np.ascontiguousarray(np.clip(pred, 0, 255).astype(np.uint8))
+    case = {'case_id': case_id, 'affine': affine, 'pred': pred if device is None else torch.from_numpy(pred).to(device)}
+    results = extract_mesh_case(case, labels, 'pred', smooth_iterations, lam, mu)
+    if save_dir is not None:
+        save_dir = Path(save_dir)
+        save_dir.mkdir(parents=True, exist_ok=True)
+    for r in results:
+        print("%s label_%s: volume %.3f ml, area %.1f mm^2, %d vertices, %d triangles"
+              % (case_id, _label_name(r['label']), r['volume'] / 1000.0, r['area'], len(r['vertices']), len(r['faces'])))
+        if save_dir is not None and len(r['faces']):
+            r['file'] = save_dir / ('%s.label_%s.%s' % (case_id, _label_name(r['label']), fmt))
+            meshfile.WRITERS[fmt](r['file'], r['vertices'], r['faces'])
+    return results
+
+
+def batch_extract_mesh(pred_dir, save_dir, data_range=None, fmt='stl', device=None, labels=None, smooth_iterations=10,
+                       lam=0.5, mu=-0.53):
+    """extract_mesh over the sorted *.nii.gz files of `pred_dir`; returns the per-file lists."""
+    from pathlib import Path
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    return [extract_mesh(pred_files[i], save_dir, fmt, device, labels, smooth_iterations, lam, mu)
+            for i in (data_range if data_range is not None else range(len(pred_files)))]

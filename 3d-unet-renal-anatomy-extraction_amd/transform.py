@@ -206,6 +206,134 @@ def distance_transform_edt(input, sampling=None, squared=False):
     return out * out if squared else out
 
 
+# ------------------------------------------------------------------ surface meshes (contract: include/ru3d.h)
+# corners q0 .. q3 of the quad of direction d (-x, +x, -y, +y, -z, +z) as offsets from the voxel's own corner: for +u,
+# (u, v, w) cyclic, the far-u corners with (v, w) offsets 00 10 11 01; for -u the near-u corners with 00 01 11 10
+def _quad_offsets():
+    table = np.zeros((6, 4, 3), dtype=np.int64)
+    for u in range(3):
+        v, w = (u + 1) % 3, (u + 2) % 3
+        for far, steps in ((0, ((0, 0), (0, 1), (1, 1), (1, 0))), (1, ((0, 0), (1, 0), (1, 1), (0, 1)))):
+            for c, (dv, dw) in enumerate(steps):
+                table[2 * u + far, c, u] = far
+                table[2 * u + far, c, v] = dv
+                table[2 * u + far, c, w] = dw
+    return table
+
+
+_QUAD_OFFSETS = _quad_offsets()
+
+
+def _mixed(blocks):
+    """neither all set nor all unset, over a list of boolean arrays of one shape"""
+    some, every = blocks[0].copy(), blocks[0].copy()
+    for b in blocks[1:]:
+        some |= b
+        every &= b
+    return some & ~every
+
+
+def _extract_mesh_numpy(mask):
+    """(corners int32 [V, 3], faces int32 [2 Q, 3], neighbours int32 [V, 6]) of a boolean volume [X, Y, Z] from the
+    plain definition.  The work is done on the mask's bounding box: corner order and quad order are lexicographic, so
+    cropping changes no number."""
+    if not mask.any():
+        return np.zeros((0, 3), np.int32), np.zeros((0, 3), np.int32), np.zeros((0, 6), np.int32)
+    lo = [int(np.flatnonzero(mask.any(axis=tuple(a for a in range(3) if a != ax)))[0]) for ax in range(3)]
+    hi = [int(np.flatnonzero(mask.any(axis=tuple(a for a in range(3) if a != ax)))[-1]) + 1 for ax in range(3)]
+    m = mask[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+    X, Y, Z = m.shape
+    p = np.zeros((X + 2, Y + 2, Z + 2), dtype=bool)                         # voxel (x, y, z) at p[x + 1, y + 1, z + 1]
+    p[1:-1, 1:-1, 1:-1] = m
+    cshape = (X + 1, Y + 1, Z + 1)
+
+    def around(a, b, c):                                                   # voxels (i - 1 + a, j - 1 + b, k - 1 + c)
+        return p[a:a + X + 1, b:b + Y + 1, c:c + Z + 1]
+
+    vertex = _mixed([around(a, b, c) for a in (0, 1) for b in (0, 1) for c in (0, 1)])
+    linear = np.flatnonzero(vertex)                                         # sorted: a corner's number is its rank here
+    corners = np.stack(np.unravel_index(linear, cshape), axis=1)
+
+    def number(ijk):
+        return np.searchsorted(linear, np.ravel_multi_index((ijk[..., 0], ijk[..., 1], ijk[..., 2]), cshape))
+
+    inner = p[1:-1, 1:-1, 1:-1]
+    beside = (p[:-2, 1:-1, 1:-1], p[2:, 1:-1, 1:-1], p[1:-1, :-2, 1:-1], p[1:-1, 2:, 1:-1], p[1:-1, 1:-1, :-2],
+              p[1:-1, 1:-1, 2:])
+    quads = np.argwhere(np.stack([inner & ~b for b in beside], axis=-1))    # [Q, 4]: x, y, z, d
+    q = number(quads[:, None, :3] + _QUAD_OFFSETS[quads[:, 3]])            # [Q, 4]
+    faces = np.stack((q[:, [0, 1, 2]], q[:, [0, 2, 3]]), axis=1).reshape(-1, 3)
+
+    # the lattice edge leaving corner (i, j, k) in direction -u / +u is surrounded by the voxels with u = i_u - 1 / i_u
+    neighbours = np.full((len(corners), 6), -1, dtype=np.int64)
+    at = (corners[:, 0], corners[:, 1], corners[:, 2])
+    for u in range(3):
+        for far in (0, 1):
+            pick = [(0, 1)] * 3
+            pick[u] = (far,)
+            edge = _mixed([around(a, b, c) for a in pick[0] for b in pick[1] for c in pick[2]])[at]
+            step = corners[edge].copy()
+            step[:, u] += 2 * far - 1
+            neighbours[edge, 2 * u + far] = number(step)
+    corners = corners + np.array(lo)
+    return corners.astype(np.int32), faces.astype(np.int32), neighbours.astype(np.int32)
+
+
+def _umbrella_numpy(p, neighbours, factor):
+    """One umbrella step of the contract: s = 0 plus the present neighbours in direction order, q = p + f (s / m - p)."""
+    present = neighbours >= 0
+    s = np.zeros_like(p)
+    for d in range(6):
+        s = s + np.where(present[:, d:d + 1], p[np.maximum(neighbours[:, d], 0)], 0.0)
+    m = present.sum(axis=1, keepdims=True).astype(np.float64)
+    moved = p + np.float64(factor) * (s / np.maximum(m, 1.0) - p)
+    return np.where(m > 0, moved, p)
+
+
+def _measure_mesh_numpy(vertices, faces):
+    """(area, enclosed volume) of a triangle list: half the sum of |(p1 - p0) x (p2 - p0)|, a sixth of the sum of
+    p0 . (p1 x p2)."""
+    if not len(faces):
+        return 0.0, 0.0
+    a, b, c = (vertices[faces[:, k]] for k in range(3))
+    area = 0.5 * np.sqrt((np.cross(b - a, c - a) ** 2).sum(axis=1)).sum()
+    return float(area), float((a * np.cross(b, c)).sum() / 6.0)
+
+
+def _to_world_numpy(vertices, faces, affine):
+    """The numpy twin of mesh.to_world: same expression, same order."""
+    import mesh
+    r, t, flipped = mesh.world_terms(affine)
+    out = vertices[:, 0:1] * r[:, 0] + vertices[:, 1:2] * r[:, 1] + vertices[:, 2:3] * r[:, 2] + t
+    return out, (np.ascontiguousarray(faces[:, [0, 2, 1]]) if flipped else faces)
+
+
+def extract_mesh(input, smooth_iterations=10, lam=0.5, mu=-0.53):
+    """The closed triangle mesh around the non-zero voxels of a volume of 1 to 3 axes, Taubin-smoothed on the lattice's
+    edge graph: a `mesh.Mesh` with `corners`, `vertices` (float64, voxel coordinates: voxel centres on integers),
+    `faces` (counter-clockwise seen from outside), `neighbours` and `shape`.  numpy in -> the definition of
+    include/ru3d.h in vectorised numpy, numpy arrays out; HIP tensor in -> the kernels of csrc/mesh.hip, HIP tensors
+    out, the same numbers either way.  Unsmoothed (`smooth_iterations=0`) the mesh is the voxels' own faces: its volume
+    is the voxel count and its area the number of exposed faces."""
+    import mesh
+    if int(smooth_iterations) != smooth_iterations or smooth_iterations < 0:
+        raise ValueError("extract_mesh: smooth_iterations=%r (a count >= 0)" % (smooth_iterations,))
+    if torch.is_tensor(input):
+        import components
+        import morphology
+        if input.dim() < 1 or input.dim() > 3:
+            raise ValueError("extract_mesh: expected a volume of 1 to 3 axes, got shape %s" % (tuple(input.shape),))
+        return mesh.smooth(mesh.extract(morphology.pack(components.as_mask(input))), smooth_iterations, lam, mu)
+    volume = np.asarray(input) != 0
+    if volume.ndim < 1 or volume.ndim > 3:
+        raise ValueError("extract_mesh: expected a volume of 1 to 3 axes, got shape %s" % (volume.shape,))
+    corners, faces, neighbours = _extract_mesh_numpy(volume.reshape((1,) * (3 - volume.ndim) + volume.shape))
+    vertices = corners.astype(np.float64) - 0.5
+    for _ in range(int(smooth_iterations)):
+        vertices = _umbrella_numpy(_umbrella_numpy(vertices, neighbours, lam), neighbours, mu)
+    return mesh.Mesh(corners, vertices, faces, neighbours, volume.shape)
+
+
 def create_sphere(shape, center, r):
     """nb_post.py:81-85: integer array of `shape`, 1 where the distance to `center` is at most r."""
     x, y, z = np.ogrid[:shape[0], :shape[1], :shape[2]]

@@ -450,6 +450,58 @@ size_t ru3d_edt_reduce_workspace_bytes(int64_t capacity);
 int ru3d_edt_reduce(const double* values, const int64_t* count, int64_t capacity, double tau_sq, double* out, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ surface meshes */
+/* The anatomy as closed triangle meshes: the faces between a set voxel and an unset one of a packed mask (the
+ * "cuberille"), Taubin smoothing on the lattice's own edge graph, area and enclosed volume.  Masks are the packed masks
+ * of the morphology section; everything outside the volume reads as unset.  X*Y*Z < 2^31, V < 2^31, 2Q < 2^31.
+ *
+ * Lattice corner (i, j, k), 0 <= i <= X, 0 <= j <= Y, 0 <= k <= Z, is the point (i - 0.5, j - 0.5, k - 0.5) in voxel
+ * coordinates (voxel centres sit on integers, as in NIfTI).
+ *   Vertices.   A corner is a vertex iff the eight voxels around it, M[i-1..i][j-1..j][k-1..k], are neither all set nor
+ *               all unset.  Vertices are numbered in corner order, i outermost, k fastest.  corners: int32 [V][3].
+ *   Quads.      exposed[x][y][z][d], d in the order -x, +x, -y, +y, -z, +z, is true iff the voxel is set and its
+ *               neighbour in direction d is unset or outside.  Quads are numbered in element order of that array (x
+ *               outermost, d fastest).  For direction +u, with (u, v, w) a cyclic permutation of (x, y, z), the quad's
+ *               corners q0 .. q3 are the voxel's far-u corners with (v, w) offsets (0,0), (1,0), (1,1), (0,1); for -u
+ *               the near-u corners with (0,0), (0,1), (1,1), (1,0).
+ *   Triangles.  Quad q gives triangles 2q = (q0, q1, q2) and 2q + 1 = (q0, q2, q3): counter-clockwise seen from
+ *               outside in index space.  faces: int32 [2Q][3] of vertex numbers.  The surface is closed and consistently
+ *               oriented: every undirected edge is used equally often in both directions.
+ *   Edge graph. neighbours: int32 [V][6], same direction order: the vertex number of the corner one lattice step away
+ *               if the four voxels around that lattice edge are neither all set nor all unset, else -1.  Quad diagonals
+ *               are not edges of this graph.  The table is symmetric and every vertex has at least three neighbours.
+ *   Smoothing.  Positions are float64 [V][3], initially corners - 0.5.  One umbrella step with factor f: s = 0, then
+ *               the present neighbours' positions added to it in direction order, m = their number,
+ *                   q[v] = fl(p[v] + fl(f * fl(fl(s / m) - p[v])))      per component, no fused multiply-add
+ *               (m = 0: q[v] = p[v]).  Taubin smoothing of n iterations is n times (step with lam, then step with mu).
+ *               Expression and order are fixed, so the result can be compared with == against a restatement in numpy.
+ *               Smoothing runs in index space with uniform weights whatever the voxel spacing; an affine is applied
+ *               to the smoothed positions afterwards.
+ *   Measures.   Over float64 positions and a face list: area = fl(0.5 * S), S = the sum over the faces of
+ *               |(p1 - p0) x (p2 - p0)|; volume = fl(T / 6), T = the sum of p0 . (p1 x p2).  Both sums run in float64
+ *               over a fixed partition in a fixed order: the same bits in every run and under every CU budget.  On the
+ *               unsmoothed mesh in voxel coordinates volume == popcount(M) and area == Q exactly.
+ *
+ * ru3d_mesh_count: counts (device int64 [2]) = (V, Q).  ru3d_mesh_emit: the same counts again, whatever the capacities,
+ * and the first vcap vertices (corners, neighbours) and the first qcap quads (faces: 2 * qcap triangles); nothing is
+ * written at or beyond a capacity, so counts above them mean the buffers were too small.  A capacity of 0 skips that
+ * output (its pointers may then be NULL).  When V or 2Q is not below 2^31 the counts are still exact and the buffers'
+ * contents are not defined.  The two calls are independent: emit needs nothing of count's but the caller's sizes.
+ * Workspace (ru3d_mesh_workspace_bytes): the corner flags as packed words of Z + 1 bits per (i, j) row, an int32
+ * count of the vertices in front of each such word, and one int per 256 words of flags and of the mask. */
+size_t ru3d_mesh_workspace_bytes(int X, int Y, int Z);
+int ru3d_mesh_count(const uint64_t* bits, int X, int Y, int Z, int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+int ru3d_mesh_emit(const uint64_t* bits, int X, int Y, int Z, int32_t* corners, int32_t* neighbours, int64_t vcap,
+                   int32_t* faces, int64_t qcap, int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+/* One umbrella step dst = step(src) over V vertices, not in place.  An entry of `neighbours` outside 0 .. V - 1 counts
+ * as absent. */
+int ru3d_mesh_smooth(const double* src, double* dst, const int32_t* neighbours, int64_t V, double factor, void* stream);
+/* out (device float64 [2]) = (area, volume) of F triangles over V positions; a face that names a vertex outside
+ * 0 .. V - 1 adds nothing.  Workspace: two doubles per 2048 faces. */
+size_t ru3d_mesh_measure_workspace_bytes(int64_t F);
+int ru3d_mesh_measure(const double* vertices, int64_t V, const int32_t* faces, int64_t F, double* out, void* ws,
+                      size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ patch sampling + augmentation */
 /* The reference's training transform chain on the device: RandomRescaleCrop -> RandomMirror ->
  * RandomContrast -> RandomBrightness -> RandomGamma -> ToTensor (transform.py:573-652, 279-301, 176-259, 156-163;
