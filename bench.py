@@ -12,10 +12,17 @@ One step = forward (train mode, Dropout3d on) + HybirdLoss + backward + gradient
 + Adam(lr=1e-4), on `ResUnet3D(4, 32, 1, 3)`, bf16 storage / fp32 accumulate, 2 x 128^3 synthetic CT patches per GPU
 resident in HBM.  Rank 0 prints ONE JSON line.
 
-Extra objects in that line:
+A plain run does what the headline figure needs and no more: set-up, the warm-up, the timed steps, the line.  That line
+carries `roofline_step`, the whole step against SURVEY 8(d)'s ALG_FLOPS / ALG_BYTES for the configuration (arithmetic on
+the measured step time).  --full adds the legs that take runs of their own, behind the timed steps, each of which
+--no-torch-adam / --no-parity / --no-cpu-baseline / --no-probe leaves out again:
+  ms_per_step_eager, host_enqueue_ms_per_step_eager
+                  the same steps issued launch by launch (when the timed ones were hipGraph replays).
   roofline        the 3x3x3 conv 32->32 on the 2x128^3 grid (forward and stride-1 dgrad launches of the same kernel),
-                  timed live with HIP events recorded on the launch stream around each launch inside the timed steps.
-  roofline_step   the whole step against SURVEY 8(d)'s ALG_FLOPS / ALG_BYTES for the configuration.
+                  timed live with HIP events recorded on the launch stream around each launch of those eager steps.  An
+                  eager timed loop (--launch eager, N > 1) carries the events itself and reports it without --full.
+  ms_per_step_torch_adam
+                  the same model stepped by a caller-owned torch.optim.Adam.
   parity          N == 1: the bf16 model's eval-mode argmax mask against the CPU oracle's (same weights, same input):
                   per-class Dice (reference `dice`, loss.py:32-48), flipped voxels, flips outside the margin band;
                   the same for the fp32 parity mode of the HIP path.
@@ -62,10 +69,14 @@ def parse():
     ap.add_argument("--checkpoint", action="store_true", help="recompute ResBlock interiors in backward")
     ap.add_argument("--grad-transport", default=os.environ.get("RU3D_GRAD_TRANSPORT", "fp32"),
                     choices=["fp32", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-torch-adam", action="store_true")
-    ap.add_argument("--no-probe", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed steps, also run what the headline figure does not need (1 GPU): the eager twin "
+                         "of the replayed steps with the roofline kernel's HIP events, torch.optim.Adam on the same "
+                         "model, the parity of the argmax mask with the CPU oracle, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the parity report")
+    ap.add_argument("--no-torch-adam", action="store_true", help="--full without the torch.optim.Adam steps")
+    ap.add_argument("--no-probe", action="store_true", help="no HIP events around the roofline kernel's launches")
     ap.add_argument("--launch", default="auto", choices=["auto", "graph", "eager"],
                     help="graph: replay the step from a hipGraph captured after the warm-up (1 GPU, bf16/fp32, fused "
                          "Adam); eager: issue every launch from Python")
@@ -393,7 +404,8 @@ def main():
     gc.collect()
     gc.freeze()
     probe = None
-    if not args.no_probe and dtype != torch.float32:
+    # a replayed step cannot carry the probe's events: its roofline figure needs the eager twin, a run of its own (--full)
+    if not args.no_probe and dtype != torch.float32 and (args.full or not use_graph):
         probe = ops.Probe(n=args.batch, cin=args.features, cout=args.features, extent=dims)
         if not use_graph:
             ops.set_probe(probe)
@@ -413,7 +425,7 @@ def main():
     if args.dump_outputs and rank == 0:      # here: the steps below train the same model further
         dump_outputs(args.dump_outputs, loss, gstep.logits if use_graph else kept["logits"], model)
     eager_ms = eager_host_ms = None
-    if use_graph:
+    if use_graph and args.full:
         # the same steps issued launch by launch, right behind the timed replays: the eager figure for comparison, and
         # the HIP-event timing of the roofline kernel (events recorded inside a captured graph cannot be read back)
         if scaler is not None:
@@ -456,7 +468,7 @@ def main():
                    "global_batch": args.batch * world, "parallelism": "dp%d" % world,
                    "optimizer": "optim.Adam (fused multi-tensor)" if args.optimizer == "fused" else "torch.optim.Adam"},
     }
-    if use_graph:
+    if use_graph and args.full:
         out["ms_per_step_eager"] = eager_ms
         out["host_enqueue_ms_per_step_eager"] = eager_host_ms
     if rehearse:
@@ -517,7 +529,7 @@ def main():
                                "frac": mf / MFMA_BF16_PEAK, "traffic": traffic, "launches": n_launch,
                                "avg_ms": mean_ms, "alg_bytes": alg_bytes, "alg_flops": alg_flops,
                                "hbm_gbps": hbm / 1e9, "hbm_frac": hbm / HBM_PEAK}
-    if world == 1 and args.optimizer == "fused" and not args.no_torch_adam:
+    if args.full and world == 1 and args.optimizer == "fused" and not args.no_torch_adam:
         # the caller-owned optimizer of the reference scripts (nb_train_iia.py:18) on the same model
         topt = torch.optim.Adam(model.parameters(), lr=1e-4)
         if gstep is not None:
@@ -532,12 +544,12 @@ def main():
         fence()
         out["ms_per_step_torch_adam"] = 1e3 * (time.perf_counter() - t1) / args.steps
         del topt
-    if rank == 0 and world == 1 and not args.no_parity:
+    if args.full and rank == 0 and world == 1 and not args.no_parity:
         try:
             out["parity"] = parity_report(args, model, dims, dev, dtype)
         except Exception as e:  # pragma: no cover
             out["parity"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args, dims)
         except Exception as e:  # pragma: no cover

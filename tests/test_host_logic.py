@@ -313,6 +313,18 @@ def test_bench_refuses_gpus_that_disagree_with_the_launcher():
     assert p.returncode == 2 and b"WORLD_SIZE=3" in p.stderr
 
 
+def test_bench_full_is_an_option_that_is_off_by_default(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs the headline figure alone; --full asks for the other legs."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    args = bench.parse()
+    assert args.full is False and (args.steps, args.warmup, args.launch) == (4, 2, "auto")
+    monkeypatch.setattr(sys, "argv", sys.argv + ["--full", "--no-cpu-baseline"])
+    args = bench.parse()
+    assert args.full is True and args.no_cpu_baseline and not args.no_parity
+
+
 def test_bench_algorithmic_work_matches_survey_table():
     """ALG_FLOPS / ALG_BYTES per step for the four configurations."""
     import bench
