@@ -54,7 +54,29 @@ class MorphRow(ctypes.Structure):
     _fields_ = [("dx", ctypes.c_int8), ("dy", ctypes.c_int8), ("zmask", ctypes.c_uint16)]
 
 
+class RenderTile(ctypes.Structure):
+    """struct ru3d_render_tile"""
+    _fields_ = [("volume", ctypes.c_void_p), ("table", ctypes.c_void_p), ("overlay", ctypes.c_void_p * 2),
+                ("overlay_table", ctypes.c_void_p * 2), ("vmin", ctypes.c_double), ("vmax", ctypes.c_double),
+                ("origin", ctypes.c_double * 2), ("step", ctypes.c_double * 2), ("x0", ctypes.c_int32),
+                ("y0", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("X", ctypes.c_int32),
+                ("Y", ctypes.c_int32), ("Z", ctypes.c_int32), ("C", ctypes.c_int32), ("channel", ctypes.c_int32),
+                ("kind", ctypes.c_int32), ("axis", ctypes.c_int32), ("index", ctypes.c_int32),
+                ("overlay_mode", ctypes.c_int32 * 2)]
+
+
+class RenderView(ctypes.Structure):
+    """struct ru3d_render_view"""
+    _fields_ = [("o", ctypes.c_double * 3), ("du", ctypes.c_double * 3), ("dv", ctypes.c_double * 3),
+                ("dw", ctypes.c_double * 3), ("spacing", ctypes.c_double * 3), ("light", ctypes.c_double * 3),
+                ("ambient", ctypes.c_double), ("diffuse", ctypes.c_double), ("background", ctypes.c_double * 3),
+                ("num_steps", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 MASK_NE, MASK_EQ, MASK_GT, MASK_GE = 0, 1, 2, 3
+TILE_F32, TILE_U8 = 0, 1
+OVERLAY_FILL, OVERLAY_OUTLINE = 0, 1
+RENDER_MAX_TILES = 256
 MORPH_ERODE, MORPH_DILATE = 0, 1
 MORPH_MAX_EXTENT, MORPH_MAX_ROWS = 15, 225
 CONFUSION_MAX_CLASSES = 32
@@ -170,6 +192,10 @@ SIGNATURES = {
     "ru3d_mesh_smooth": (_i, [_vp, _vp, _vp, _i64, _dbl, _vp]),
     "ru3d_mesh_measure_workspace_bytes": (_sz, [_i64]),
     "ru3d_mesh_measure": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ru3d_render_tiles": (_i, [_vp, _i, _vp, _i, _i, _vp]),
+    "ru3d_render_surface_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_render_surface_prepare": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ru3d_render_surface": (_i, [_vp, _i, _i, _i, _vp, ctypes.POINTER(RenderView), _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "ru3d_adam_multi": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "ru3d_adam_multi_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ru3d_adam_multi_amp": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

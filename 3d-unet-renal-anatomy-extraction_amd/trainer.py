@@ -1061,3 +1061,75 @@ def batch_extract_mesh(pred_dir, save_dir, data_range=None, fmt='stl', device=No
     pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
     return [extract_mesh(pred_files[i], save_dir, fmt, device, labels, smooth_iterations, lam, mu)
             for i in (data_range if data_range is not None else range(len(pred_files)))]
+
+
+def preview_case(case, key='pred', axes=(0, 1, 2), num_slices=8, views=((30, 20), (120, 20), (210, -20)), size=256,
+                 alpha=None, labels=None, colours=None, window=None, pixel_mm=None):
+    """One picture of a case to leaf through, uint8 [H, W, 3]: `visualize.case_sheet` (slices of the image under the
+    filled label and the outlined prediction; without an image the mask alone) and below it the shaded views of
+    `visualize.render_case` of case[key], side by side.  alpha=None makes label 1 translucent (0.35) when the volume may
+    hold more than one label, so that what lies inside the kidney shows.  numpy volumes take the numpy route, HIP
+    tensors - for instance what `cascade_predict_case(..., return_device=True)` returns - are rendered on the device
+    (csrc/render.hip) and only the pictures are downloaded."""
+    import visualize
+    overlays = tuple(k for k in ('label', 'pred') if case.get(k) is not None)
+    if key not in case or case[key] is None:
+        raise ValueError("preview_case: the case has no %r" % (key,))
+    sheet = visualize.case_sheet(case, axes, num_slices, window, overlays, pixel_mm, colours)
+    if alpha is None:
+        alpha = {1: 0.35} if labels is None or len(tuple(labels)) > 1 else 1.0
+    shots = visualize.render_case(case, key, labels, views, size, alpha, colours) if len(views) else ()
+    gap = 2
+    width = max(sheet.shape[1], len(shots) * (size + gap) - gap)
+    out = np.zeros((sheet.shape[0] + ((gap + size) if len(shots) else 0), width, 3), dtype=np.uint8)
+    out[:sheet.shape[0], :sheet.shape[1]] = sheet
+    for i, shot in enumerate(shots):
+        out[sheet.shape[0] + gap:, i * (size + gap):i * (size + gap) + size] = shot
+    return out
+
+
+def preview(pred_file, image_file=None, label_file=None, save_dir=None, device=None, **options):
+    """preview_case of a NIfTI label volume (a `*.pred.nii.gz` of save_pred) with the file's affine, over the image and
+    beside the ground truth when their files are given.  save_dir: the picture is written as `<case_id>.preview.png`
+    (pngfile.write_png).  device: a HIP device uploads the volumes once and renders there.  `options` go to
+    preview_case.  Returns the picture."""
+    import nifti
+    import pngfile
+    from pathlib import Path
+    pred_file = Path(pred_file)
+    case_id = pred_file.name
+    for suffix in ('.gz', '.nii', '.pred'):
+        if case_id.endswith(suffix):
+            case_id = case_id[:-len(suffix)]
+    pred, affine, _ = nifti.load(pred_file)
+    case = {'case_id': case_id, 'affine': affine, 'pred': np.ascontiguousarray(np.clip(pred, 0, 255).astype(np.uint8))}
+    if label_file is not None:
+        case['label'] = np.ascontiguousarray(np.clip(nifti.load(label_file)[0], 0, 255).astype(np.uint8))
+    if image_file is not None:
+        image = np.asarray(nifti.load(image_file)[0], dtype=np.float32)
+        case['image'] = np.ascontiguousarray(image[..., None] if image.ndim == 3 else image)
+    if device is not None:
+        for k in ('pred', 'label', 'image'):
+            if k in case:
+                case[k] = torch.from_numpy(case[k]).to(device)
+    picture = preview_case(case, **options)
+    if save_dir is not None:
+        save_dir = Path(save_dir)
+        save_dir.mkdir(parents=True, exist_ok=True)
+        pngfile.write_png(save_dir / ('%s.preview.png' % case_id), picture)
+    return picture
+
+
+def batch_preview(pred_dir, save_dir, image_dir=None, label_dir=None, data_range=None, device=None, **options):
+    """preview over the sorted *.nii.gz files of `pred_dir`, one PNG per case in `save_dir`; the i-th sorted file of
+    `image_dir` / `label_dir` belongs to the i-th prediction, as in batch_evaluate.  Returns the pictures."""
+    from pathlib import Path
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    image_files = sorted(Path(image_dir).glob('*.nii.gz')) if image_dir is not None else None
+    label_files = sorted(Path(label_dir).glob('*.nii.gz')) if label_dir is not None else None
+    for name, files in (('image_dir', image_files), ('label_dir', label_files)):
+        if files is not None and len(files) != len(pred_files):
+            raise ValueError("batch_preview: %d files in %s for %d predictions" % (len(files), name, len(pred_files)))
+    return [preview(pred_files[i], image_files[i] if image_files else None, label_files[i] if label_files else None,
+                    save_dir, device, **options)
+            for i in (data_range if data_range is not None else range(len(pred_files)))]

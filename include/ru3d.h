@@ -502,6 +502,87 @@ size_t ru3d_mesh_measure_workspace_bytes(int64_t F);
 int ru3d_mesh_measure(const double* vertices, int64_t V, const int32_t* faces, int64_t F, double* out, void* ws,
                       size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ rendering: slice tiles and shaded surface views */
+/* Pictures of a case that lives in HBM (csrc/render.hip): RGB8 canvases [H, W, 3], row-major, written by the device
+ * and downloaded as they are.  The arithmetic below is the contract; visualize.py restates it in numpy and the two
+ * routes are compared with ==.  Integers wherever possible; every float64 expression is evaluated as written, one
+ * rounding per operation (fl), no fused multiply-add, no transcendental function.  Volumes have fewer than 2^31
+ * elements.  Colour tables are device arrays of 256 RGBA rows (uint8 [256][4]).
+ *
+ * ru3d_render_tiles: one launch paints a DEVICE table of num_tiles (1 .. RU3D_RENDER_MAX_TILES) records into the canvas.
+ *   A record shows slice `index` of axis `axis` of its volume; the two other axes in ascending order are the tile's
+ *   row axis and column axis (matplotlib's imshow of volume[index, :, :]).  Tile pixel (r, c), 0 <= r < h, 0 <= c < w,
+ *   is canvas pixel (y0 + r, x0 + c); pixels outside the canvas are not stored.  It shows the voxel whose in-plane
+ *   indices are floor(fl(origin[0] + fl(r * step[0]))) and floor(fl(origin[1] + fl(c * step[1]))) - nearest voxel on a
+ *   grid whose step is pixel size / voxel size, which is how anisotropic spacing becomes square pixels; an index
+ *   outside the volume gives a black pixel.
+ *   Base colour.  RU3D_TILE_F32: volume is the fp32 case layout [X][Y][Z][C], value v of channel `channel` as float64,
+ *   t = fl(fl(v - vmin) / fl(vmax - vmin)), then t = 0 unless t > 0, t = 1 if t > 1 (NaN and 0/0 become 0),
+ *   g = floor(fl(fl(255 * t) + 0.5)) on all three channels.  RU3D_TILE_U8: volume is uint8 [X][Y][Z], colour = the
+ *   RGB of table[value] (alpha ignored).
+ *   Overlays, 0 then 1, each a uint8 [X][Y][Z] volume of the same shape or NULL: l = its value at the voxel,
+ *   (R, G, B, A) = overlay_table[l].  Nothing is drawn when A == 0, nor in mode RU3D_OVERLAY_OUTLINE unless l differs
+ *   from the overlay's value at one of the voxel's four in-plane neighbours (a neighbour outside the volume reads 0).
+ *   Otherwise every channel becomes (A * colour + (255 - A) * channel + 127) / 255 in integers.
+ *   A record with a bad axis, index, channel, kind or extent, or a RU3D_TILE_F32 volume that is not 4-byte aligned,
+ *   paints nothing.  The rectangles of one table must not overlap inside the canvas: tiles are painted by different
+ *   workgroups in no order, and where two rectangles share a pixel its colour is that of either tile.
+ * ru3d_render_surface: orthographic ray cast of a uint8 label volume [X][Y][Z] into rgb [H][W][3] and depth int32
+ *   [H][W].  Coordinates are VOXEL units: voxel (i, j, k) is the box [i, i+1) x [j, j+1) x [k, k+1); the host divides
+ *   its millimetre vectors by the spacing per component.  Sample n = 0 .. num_steps - 1 of pixel (row v, column u)
+ *   sits at q_c = fl(fl(fl(o_c + fl(u * du_c)) + fl(v * dv_c)) + fl(n * dw_c)) per component c and reads the label of
+ *   voxel floor(q); outside the volume the label is 0.  Label L is drawn iff L != 0 and table[L].A != 0.
+ *   A surface event is a sample whose label L is drawn and differs from the previous sample's label (0 in front of
+ *   sample 0).  At an event in voxel p: g_c = the sum over the offsets d in {-1, 0, 1}^3 of d_c * [label(p + d) == L]
+ *   (three integers in -9 .. 9), m_c = fl(-g_c / spacing_c), dot = fl(fl(fl(m_0 l_0) + fl(m_1 l_1)) + fl(m_2 l_2)) with
+ *   the light vector l, len2 the same expression with m in place of l;
+ *       shade = fl(ambient + fl(fl(diffuse * max(dot, 0)) / sqrt(len2))),   len2 == 0: shade = fl(ambient + diffuse).
+ *   Front to back, starting from T = 1 and C = (0, 0, 0), with a = fl(A / 255):
+ *       C_c = fl(C_c + fl(fl(fl(T * a) * shade) * colour_c)),  then  T = fl(T * fl(1 - a));
+ *   the ray ends when T < 1/256 or after the last sample.  Finally C_c = fl(C_c + fl(T * background_c)) and the pixel
+ *   is floor(fl(min(max(C_c, 0), 255) + 0.5)).  depth = n of the first event, -1 without one.
+ *   ru3d_render_surface_prepare fills the workspace for one (volume, table) pair - the drawn voxels as a packed mask
+ *   in the layout of the morphology section, and one byte per 8 x 8 x 8 brick that holds a drawn voxel - and any
+ *   number of views may follow.  The kernel does not visit every sample.  What it leaves out, and why that cannot
+ *   change the picture: (1) samples outside n_lo <= n < n_hi of a slab test against the volume in real arithmetic from
+ *   fl(fl(o + fl(u du)) + fl(v dv)), widened by two samples - rounding is monotone and 0 and the extents are
+ *   representable, so a sample the contract places inside the volume lies within 2^-32 samples of that interval;
+ *   (2) samples n + 1 .. n + j - 1 behind a sample n that lies in a brick without a drawn voxel, where j comes from an
+ *   estimate of the brick's exit and is used only if the contract's own position of sample n + j - 1 lies in the same
+ *   brick - every component of q is monotone in n, so all samples between lie in it too and read an undrawn label
+ *   (without that check the estimate is wrong by many samples where |dw_c| is below an ulp of q_c, as for the
+ *   cos(270 deg) of a lateral view); (3) the label byte of a sample whose mask bit is clear: it is not drawn, and a drawn
+ *   label always differs from an undrawn one.  Every visited sample is placed by the expression above from its n.
+ *   The view travels in the kernel arguments.  `ws` is 8-byte aligned in both calls. */
+#define RU3D_RENDER_MAX_TILES 256
+enum { RU3D_TILE_F32 = 0, RU3D_TILE_U8 = 1 };
+enum { RU3D_OVERLAY_FILL = 0, RU3D_OVERLAY_OUTLINE = 1 };
+typedef struct ru3d_render_tile {
+    const void* volume;
+    const uint8_t* table;            /* RU3D_TILE_U8 only */
+    const uint8_t* overlay[2];       /* NULL: none */
+    const uint8_t* overlay_table[2];
+    double vmin, vmax;               /* RU3D_TILE_F32 only */
+    double origin[2], step[2];       /* row axis, column axis */
+    int32_t x0, y0, w, h;
+    int32_t X, Y, Z, C, channel, kind, axis, index;
+    int32_t overlay_mode[2];
+} ru3d_render_tile;
+typedef struct ru3d_render_view {
+    double o[3], du[3], dv[3], dw[3]; /* voxel units; all finite */
+    double spacing[3];                /* positive */
+    double light[3];
+    double ambient, diffuse;
+    double background[3];
+    int32_t num_steps, reserved;
+} ru3d_render_view;
+int ru3d_render_tiles(const ru3d_render_tile* tiles, int num_tiles, uint8_t* canvas, int H, int W, void* stream);
+size_t ru3d_render_surface_workspace_bytes(int X, int Y, int Z);
+int ru3d_render_surface_prepare(const uint8_t* labels, int X, int Y, int Z, const uint8_t* table, void* ws, size_t ws_bytes,
+                                void* stream);
+int ru3d_render_surface(const uint8_t* labels, int X, int Y, int Z, const uint8_t* table, const ru3d_render_view* view,
+                        uint8_t* rgb, int32_t* depth, int H, int W, const void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ patch sampling + augmentation */
 /* The reference's training transform chain on the device: RandomRescaleCrop -> RandomMirror ->
  * RandomContrast -> RandomBrightness -> RandomGamma -> ToTensor (transform.py:573-652, 279-301, 176-259, 156-163;
