@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RU3D_LIB", os.path.join(_HERE, "libru3d.so"))
 
 F32, BF16, F16 = 0, 1, 2
+PREDICT_MAX_BATCH = 16      # RU3D_PREDICT_MAX_BATCH: windows per ru3d_predict_gather launch
 LABEL_I64, LABEL_U8 = 0, 1
 ROLE_CONV_FWD, ROLE_CONV_DGRAD, ROLE_CONVT_FWD, ROLE_CONVT_DGRAD, ROLE_BIAS = 0, 1, 2, 3, 4
 LOSS_HYBIRD, LOSS_DICELOSS, LOSS_FOCAL, LOSS_DICE = 0, 1, 2, 3
@@ -160,6 +161,8 @@ SIGNATURES = {
     "ru3d_tversky": (_i, [_vp, _vp, _i64, _f, _f, _f, _vp, _vp, _sz, _vp]),
     "ru3d_predict_accumulate": (_i, [_P, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ru3d_predict_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ru3d_predict_gather": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _P, _vp]),
+    "ru3d_predict_accumulate_weighted": (_i, [_P, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ru3d_components_workspace_bytes": (_sz, [_i, _i, _i]),
     "ru3d_label_components": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_component_stats": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),

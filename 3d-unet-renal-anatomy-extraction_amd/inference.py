@@ -16,8 +16,26 @@ accumulate and the divide + softmax + argmax + crop are two streaming HIP kernel
 [X, Y, Z, C] / [X, Y, Z] fp32 for the whole case and only the final mask crosses PCIe.
 `patch_batch` windows are pushed through the network per forward (InstanceNorm is per sample, so the
 result does not depend on it); the sums are still accumulated in the reference's window order.
+
+Beyond the reference (keyword-only options of `predict_per_patch`; at their defaults the code above runs unchanged):
+  * `placement='cover'`: per axis of padded length L and patch P, n = ceil((L - P) * s / P) + 1 windows with lower
+    corners (i * (L - P)) // (n - 1) (`cover_origins`) - the first at 0, the last at L - P, steps of at most
+    ceil(P / s) - so every voxel is predicted and nothing comes back NaN; the final crop uses `pad_offset`, so the
+    result sits on the input's own grid (no one-voxel shift for an odd pad);
+  * `weighting='gaussian'`: a window's probabilities are weighted by (g_x[a] * g_y[j]) * g_z[k], g from
+    `gaussian_profile` (float64 on the host, rounded to fp32, uploaded once); `cnt` sums the same weights;
+  * `mirror_axes`: every window is predicted once per subset of the axes (`mirror_subsets`: by size, then
+    lexicographic, the empty set first), the input mirrored on the way into the model and the probabilities
+    mirrored back on the way into `acc`, both by index arithmetic inside `ru3d_predict_gather` /
+    `ru3d_predict_accumulate_weighted` - no flipped copies of inputs or logits exist;
+  * `model` may be a list: all members add into the same `acc` / `cnt`.
+Summation order (fixed): models in list order, outermost; inside a model the windows in loop order (x outer, z inner);
+inside a window the mirror subsets in `mirror_subsets` order.  Every term is one accumulate launch on one stream and a
+launch owns each voxel of its window once, so there are no atomics and no races; `patch_batch` only decides how many
+consecutive terms share a forward, never the order of the sums: the result is bit-identical for every `patch_batch`.
 """
 import ctypes
+import itertools
 import math
 
 import numpy as np
@@ -72,14 +90,183 @@ def window_origins(shape, patch_size, step_per_patch):
             for x in axes[0] for y in axes[1] for z in axes[2]], [len(a) for a in axes]
 
 
+PLACEMENTS = ('reference', 'cover')
+WEIGHTINGS = ('uniform', 'gaussian')
+
+
+def cover_origins(length, patch, step_per_patch):
+    """Lower corners of the windows along one axis of padded length `length` >= `patch` under placement='cover':
+    n = ceil((length - patch) * step_per_patch / patch) + 1 windows at (i * (length - patch)) // (n - 1), integers
+    throughout.  First corner 0, last corner length - patch, steps of at most ceil(patch / step_per_patch)."""
+    length, patch, s = int(length), int(patch), int(step_per_patch)
+    if patch < 1 or s < 1 or length < patch:
+        raise ValueError("cover_origins: need length >= patch >= 1 and step_per_patch >= 1, got (%d, %d, %d)"
+                         % (length, patch, s))
+    span = length - patch
+    n = -((-span * s) // patch) + 1
+    if n == 1:
+        return [0]
+    return [(i * span) // (n - 1) for i in range(n)]
+
+
+def cover_window_origins(shape, patch_size, step_per_patch):
+    """`window_origins` for placement='cover': same loop order (x outer, z inner)."""
+    axes = [cover_origins(shape[i], patch_size[i], step_per_patch) for i in range(3)]
+    return [(x, y, z) for x in axes[0] for y in axes[1] for z in axes[2]], [len(a) for a in axes]
+
+
+def gaussian_profile(P, sigma_scale=0.125):
+    """Per-axis blending weights of a window of `P` voxels: g[i] = exp(-0.5 * ((i - (P - 1) / 2) / (sigma_scale * P))**2),
+    computed in float64 and rounded to float32.  The smallest product of three (a window corner) stays a normal fp32
+    number for sigma_scale = 1/8 and is neither clamped nor flushed."""
+    P = int(P)
+    sigma_scale = float(sigma_scale)
+    if P < 1 or not sigma_scale > 0:
+        raise ValueError("gaussian_profile: need P >= 1 and sigma_scale > 0, got (%d, %r)" % (P, sigma_scale))
+    i = np.arange(P, dtype=np.float64)
+    return np.exp(-0.5 * ((i - (P - 1) / 2.0) / (sigma_scale * P)) ** 2).astype(np.float32)
+
+
+def mirror_subsets(axes):
+    """The mirror variants of a window for `mirror_axes`: every subset of the axes as a sorted tuple, ordered by size,
+    then lexicographically; the empty set (the plain window) first."""
+    axes = sorted(int(a) for a in axes)
+    return [c for r in range(len(axes) + 1) for c in itertools.combinations(axes, r)]
+
+
+_DEFAULTS = dict(placement='reference', weighting='uniform', mirror_axes=(), sigma_scale=0.125)
+
+
+class Blended:
+    """A model, or a list of models, together with blending options: accepted wherever a driver takes a model.  The
+    drivers whose parameter lists are fixed (cascade_predict_case, cascade_predict, batch_cascade_predict) receive the
+    options this way, per stage; for the others it is the same as passing the keywords.  `parameters()` and
+    `out_channels` are the first member's, which is what the drivers ask a model for."""
+
+    def __init__(self, model, *, placement='reference', weighting='uniform', mirror_axes=(), sigma_scale=0.125):
+        if isinstance(model, Blended):
+            raise ValueError("Blended: model is already a Blended")
+        self.options = dict(placement=placement, weighting=weighting, mirror_axes=tuple(mirror_axes),
+                            sigma_scale=sigma_scale)
+        self.models, _ = check_options(model, who="Blended", **self.options)
+
+    def parameters(self):
+        return self.models[0].parameters()
+
+    @property
+    def out_channels(self):
+        return self.models[0].out_channels
+
+
+def _model_list(model, who="predict_per_patch"):
+    models = list(model) if isinstance(model, (list, tuple)) else [model]
+    if not models:
+        raise ValueError("%s: model is an empty list" % who)
+    return models
+
+
+def check_options(model, placement='reference', weighting='uniform', mirror_axes=(), sigma_scale=0.125,
+                  who="predict_per_patch"):
+    """Validate the blending options on the host, before anything touches the device.  Returns (models, mirror axes)."""
+    if isinstance(model, Blended):
+        raise ValueError("%s: model is a Blended; unwrap it with resolve_options" % who)
+    if placement not in PLACEMENTS:
+        raise ValueError("%s: placement must be one of %s, got %r" % (who, PLACEMENTS, placement))
+    if weighting not in WEIGHTINGS:
+        raise ValueError("%s: weighting must be one of %s, got %r" % (who, WEIGHTINGS, weighting))
+    try:
+        axes = tuple(mirror_axes)
+    except TypeError:
+        raise ValueError("%s: mirror_axes must be a sequence of axes out of (0, 1, 2), got %r" % (who, mirror_axes))
+    for a in axes:
+        if isinstance(a, bool) or not isinstance(a, (int, np.integer)) or not 0 <= int(a) <= 2:
+            raise ValueError("%s: mirror_axes holds %r; the axes are 0, 1, 2 (X, Y, Z)" % (who, a))
+    axes = tuple(int(a) for a in axes)
+    if len(set(axes)) != len(axes):
+        raise ValueError("%s: mirror_axes names an axis twice: %s" % (who, axes))
+    if isinstance(sigma_scale, bool) or not isinstance(sigma_scale, (int, float, np.floating, np.integer)) \
+            or not float(sigma_scale) > 0 or not math.isfinite(float(sigma_scale)):
+        raise ValueError("%s: sigma_scale must be a finite number > 0, got %r" % (who, sigma_scale))
+    models = _model_list(model, who)
+    devices = [p.device for p in (next(m.parameters(), None) for m in models) if p is not None]
+    if any(d != devices[0] for d in devices):
+        raise ValueError("%s: the models of the ensemble live on different devices: %s"
+                         % (who, ", ".join(str(d) for d in devices)))
+    return models, axes
+
+
+def resolve_options(model, placement='reference', weighting='uniform', mirror_axes=(), sigma_scale=0.125,
+                    who="predict_per_patch"):
+    """(models, options dict) of a driver call: the keywords, or - when `model` is a Blended - its options, which a
+    keyword may repeat but not contradict."""
+    given = dict(placement=placement, weighting=weighting, mirror_axes=mirror_axes, sigma_scale=sigma_scale)
+    if isinstance(model, Blended):
+        for k, v in given.items():
+            if k == 'mirror_axes' and isinstance(v, (list, tuple)):
+                v = tuple(v)
+            if v != _DEFAULTS[k] and v != model.options[k]:
+                raise ValueError("%s: %s=%r contradicts the Blended model's %s=%r" % (who, k, v, k, model.options[k]))
+        given = dict(model.options)
+        model = model.models
+    models, axes = check_options(model, who=who, **given)
+    given['mirror_axes'] = axes
+    return models, given
+
+
+def _blend_windows(vol, models, num_classes, patch_size, origins, flips, tables, acc, cnt, patch_batch, bar):
+    """The mirrored / weighted / ensemble window loop.  vol: dense fp32 [X, Y, Z, Cin] on the device.  Terms are
+    issued in the fixed order (model, window, mirror subset); `patch_batch` consecutive terms share one forward."""
+    device = vol.device
+    X, Y, Z, cin = (int(v) for v in vol.shape)
+    px, py, pz = patch_size
+    terms = [(o, f) for o in origins for f in flips]
+    gx, gy, gz = (ptr(t) for t in tables) if tables is not None else (None, None, None)
+    for model in models:
+        model.eval()
+        for b0 in range(0, len(terms), patch_batch):
+            group = terms[b0:b0 + patch_batch]
+            x = N.new_act(len(group), cin, px, py, pz, torch.float32, device)
+            for g0 in range(0, len(group), N.PREDICT_MAX_BATCH):
+                part = group[g0:g0 + N.PREDICT_MAX_BATCH]
+                flat = (ctypes.c_int32 * (4 * len(part)))(*[v for (o, f) in part for v in (o[0], o[1], o[2], f)])
+                d = N.desc(x[g0:g0 + len(part)])
+                check(N.lib.ru3d_predict_gather(ptr(vol), X, Y, Z, cin, flat, len(part), ctypes.byref(d), stream()),
+                      "predict_gather")
+            logits = model(x)
+            if logits.shape[1] != num_classes:
+                raise ValueError("predict_per_patch: model returns %d classes, num_classes is %d"
+                                 % (logits.shape[1], num_classes))
+            logits = N.to_ndhwc(logits)
+            d = N.desc(logits)
+            for i, ((ox, oy, oz), f) in enumerate(group):
+                check(N.lib.ru3d_predict_accumulate_weighted(ctypes.byref(d), N.dtype_code(logits.dtype), i, f, gx, gy,
+                                                             gz, ptr(acc), ptr(cnt), X, Y, Z, ox, oy, oz, stream()),
+                      "predict_accumulate_weighted")
+            if bar is not None:
+                bar.update(len(group))
+
+
 def predict_per_patch(input, model, num_classes=3, patch_size=(96, 96, 96), step_per_patch=4, verbose=True,
-                      one_hot=False, patch_batch=1, return_device=False):
+                      one_hot=False, patch_batch=1, return_device=False, *,
+                      placement='reference', weighting='uniform', mirror_axes=(), sigma_scale=0.125):
     """input: numpy (or torch, host or device) [X, Y, Z, C_in] (the reference's W,H,D,C case layout).  Returns the
     uint8 mask [X, Y, Z] (or the float32 [X, Y, Z, num_classes] probability map when one_hot) at the input's own shape,
     as a numpy array like the reference - or as the device tensor when return_device (predict_case keeps going on
-    the GPU)."""
+    the GPU).
+
+    model: one model or a list / tuple of models on one HIP device (an ensemble; architectures and compute dtypes may
+    differ).  placement: 'reference' (the reference's windows and crop, uncovered NaN border included) or 'cover'
+    (every voxel inside a window, result on the input's own grid).  weighting: 'uniform' or 'gaussian' (centre-weighted,
+    width sigma_scale * patch per axis).  mirror_axes: subset of (0, 1, 2); every window is also predicted mirrored
+    along every non-empty subset of these axes.  The module docstring has the rules and the summation order."""
+    models, opt = resolve_options(model, placement, weighting, mirror_axes, sigma_scale)
+    placement, weighting, mirror_axes, sigma_scale = (opt[k] for k in ('placement', 'weighting', 'mirror_axes',
+                                                                        'sigma_scale'))
+    blended = placement != 'reference' or weighting != 'uniform' or len(mirror_axes) > 0 or len(models) > 1
+    model = models[0]
     device = next(model.parameters()).device
-    N.require_device(next(model.parameters()), "model")
+    for m in models:
+        N.require_device(next(m.parameters()), "model")
     patch_size = tuple(int(p) for p in patch_size)
     if any(p % 2 for p in patch_size):
         # the reference slices [c - p//2, c + p//2): an odd patch would feed the model p-1 voxels
@@ -99,9 +286,14 @@ def predict_per_patch(input, model, num_classes=3, patch_size=(96, 96, 96), step
     vol[0, lo[0]:lo[0] + original_shape[0], lo[1]:lo[1] + original_shape[1], lo[2]:lo[2] + original_shape[2]] = \
         (input.to(device=device, dtype=torch.float32) if torch.is_tensor(input)
          else torch.from_numpy(np.ascontiguousarray(input, dtype=np.float32)).to(device))
+    dense = vol[0]                                                     # [X, Y, Z, C], what the gather kernel reads
     vol = vol.permute(0, 4, 1, 2, 3)                                   # [1, C, X, Y, Z] view
 
-    origins, counts = window_origins(full, patch_size, step_per_patch)
+    if placement == 'cover':
+        origins, counts = cover_window_origins(full, patch_size, step_per_patch)
+        co = lo                                                        # crop where pad put the case: no shift
+    else:
+        origins, counts = window_origins(full, patch_size, step_per_patch)
     for (ox, oy, oz) in origins:
         if ox < 0 or oy < 0 or oz < 0 or ox + patch_size[0] > full[0] or oy + patch_size[1] > full[1] \
                 or oz + patch_size[2] > full[2]:
@@ -114,10 +306,17 @@ def predict_per_patch(input, model, num_classes=3, patch_size=(96, 96, 96), step
     cnt = torch.zeros(full, dtype=torch.float32, device=device)
     px, py, pz = patch_size
     patch_batch = max(1, int(patch_batch))
-    bar = tqdm(total=len(origins)) if (verbose and tqdm is not None) else None
+    flips = [sum(1 << a for a in sub) for sub in mirror_subsets(mirror_axes)]
+    total = len(origins) * len(flips) * len(models) if blended else len(origins)
+    bar = tqdm(total=total) if (verbose and tqdm is not None) else None
     model.eval()
     with torch.no_grad():
-        for b0 in range(0, len(origins), patch_batch):
+        if blended:
+            tables = None
+            if weighting == 'gaussian':
+                tables = [torch.from_numpy(gaussian_profile(p, sigma_scale)).to(device) for p in patch_size]
+            _blend_windows(dense, models, num_classes, patch_size, origins, flips, tables, acc, cnt, patch_batch, bar)
+        for b0 in (() if blended else range(0, len(origins), patch_batch)):
             group = origins[b0:b0 + patch_batch]
             x = N.new_act(len(group), cin, px, py, pz, torch.float32, device)
             for i, (ox, oy, oz) in enumerate(group):
@@ -167,15 +366,17 @@ def resample_normalize_image(vol, out_shape, stats):
 
 
 def predict_case(case, model, target_spacing, normalize_stats, num_classes=3, patch_size=(96, 96, 96),
-                 step_per_patch=4, verbose=True, one_hot=False, patch_batch=1, return_device=False):
+                 step_per_patch=4, verbose=True, one_hot=False, patch_batch=1, return_device=False, *,
+                 placement='reference', weighting='uniform', mirror_axes=(), sigma_scale=0.125):
     """reference trainer.py:101-133: resample the case to `target_spacing` and normalise it (data.py:222-283), run the
     sliding-window prediction, resize the prediction back to the case's shape.  Everything between the upload of the
     image and the download of the prediction runs on the device: the two resamplings are the order-1 zoom kernel of
     the augmentation path (label rule included), the sliding window is predict_per_patch.  `case['image']` may already
     be a HIP tensor (no upload), and `return_device` leaves `case['pred']` in HBM (no download): the cascade chains its
-    stages that way."""
+    stages that way.  `model` may be a list; placement / weighting / mirror_axes / sigma_scale go to predict_per_patch."""
     import augment
-    device = next(model.parameters()).device
+    models, opt = resolve_options(model, placement, weighting, mirror_axes, sigma_scale, "predict_case")
+    device = next(models[0].parameters()).device
     image = case['image'] if torch.is_tensor(case['image']) else np.asarray(case['image'])
     if image.ndim == 3:
         image = image[..., None]
@@ -193,8 +394,8 @@ def predict_case(case, model, target_spacing, normalize_stats, num_classes=3, pa
     vol = resample_normalize_image(vol, _zoomed_shape(orig_shape, scale), stats)
     if verbose:
         print('Predicting the case...')
-    pred = predict_per_patch(vol, model, num_classes, patch_size, step_per_patch, verbose, one_hot,
-                             patch_batch=patch_batch, return_device=True)
+    pred = predict_per_patch(vol, models, num_classes, patch_size, step_per_patch, verbose, one_hot,
+                             patch_batch=patch_batch, return_device=True, **opt)
     if verbose:
         print('Resizing the case to origial shape...')
     if one_hot:

@@ -529,13 +529,15 @@ class Trainer():
 # ---------------------------------------------------------------------------------------------------------------------
 # Case-level drivers around predict_case (reference trainer.py:136-400): host glue, the arithmetic is in inference.py.
 def batch_predict_case(load_dir, save_dir, model, target_spacing, normalize_stats, num_classes=3,
-                       patch_size=(240, 240, 80), step_per_patch=4, data_range=None):
-    """trainer.py:136-161"""
+                       patch_size=(240, 240, 80), step_per_patch=4, data_range=None, *,
+                       placement='reference', weighting='uniform', mirror_axes=(), sigma_scale=0.125):
+    """trainer.py:136-161.  `model` may be a list (an ensemble); the keyword-only options are predict_per_patch's."""
     from data import CaseDataset, save_pred
     cases = CaseDataset(load_dir)
     for i in (data_range if data_range is not None else range(len(cases))):
         case = predict_case(cases[i], model, target_spacing, normalize_stats, num_classes, patch_size,
-                            step_per_patch, False)
+                            step_per_patch, False, placement=placement, weighting=weighting,
+                            mirror_axes=mirror_axes, sigma_scale=sigma_scale)
         save_pred(case, save_dir)
 
 
@@ -556,8 +558,18 @@ def cascade_predict_case(case, coarse_model, coarse_target_spacing, coarse_norma
     post_transform: any callable volume -> volume (e.g. `functools.partial(transform.post_transform, threshold=t)`),
     applied to the merged mask - on the device route while it is still in HBM (a uint8 HIP tensor in), on the host route
     to the numpy mask.  return_device: leave case['pred'] on the device as a uint8 HIP tensor (device route only; the
-    host route has no device copy to return and raises)."""
+    host route has no device copy to return and raises).
+
+    Blending options (placement / weighting / mirror_axes / sigma_scale of predict_per_patch) and ensembles: this
+    function's parameter list is the reference's plus the three keywords above and stays that way, so the options ride
+    on the model arguments - `inference.Blended(model_or_list, placement='cover', weighting='gaussian', ...)` for
+    either stage (usually both).  A plain list or tuple of models is an ensemble with the default options."""
     from data import regions_crop_case
+    from inference import Blended
+    if isinstance(coarse_model, (list, tuple)):
+        coarse_model = Blended(coarse_model)
+    if isinstance(detail_model, (list, tuple)):
+        detail_model = Blended(detail_model)
     if on_device is None:
         on_device = _models_on_hip(coarse_model, detail_model) and os.environ.get("RU3D_CASCADE_DEVICE", "1") != "0"
     if return_device and not on_device:

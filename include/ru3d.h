@@ -317,6 +317,25 @@ int ru3d_predict_accumulate(const ru3d_tensor* logits, int dtype, int sample, fl
  * (the reference's second softmax); uncovered voxels -> 0. */
 int ru3d_predict_merge(const float* acc, const float* cnt, int X, int Y, int Z, int num_classes, int cx, int cy,
                        int cz, int sx, int sy, int sz, int one_hot, void* out, void* stream);
+/* Mirrored / weighted / ensemble sliding windows (inference.py: placement, weighting, mirror_axes, model lists).
+ * A mirror mask has bit 0 for the volume's X axis, bit 1 for Y, bit 2 for Z.
+ * gather: one launch fills the whole model input.  vol is the padded volume, fp32 [X, Y, Z, cin]; dst the dense NDHWC
+ * fp32 activation [count, px, py, pz, cin]; `windows` is a HOST array of 4 * count int32 (ox, oy, oz, mirror mask) per
+ * batch entry, copied into the launch arguments (count <= RU3D_PREDICT_MAX_BATCH; more is refused):
+ *     dst[b][a][j][k][c] = vol[ox_b + a'][oy_b + j'][oz_b + k'][c],  a' = px-1-a where bit 0 of the mask is set, else a
+ * (likewise j', k'), i.e. torch.flip of the window along the masked axes. */
+#define RU3D_PREDICT_MAX_BATCH 16
+int ru3d_predict_gather(const float* vol, int X, int Y, int Z, int cin, const int32_t* windows, int count,
+                        const ru3d_tensor* dst, void* stream);
+/* accumulate_weighted: as accumulate, for logits the model computed on a window mirrored by `flip`: the probabilities
+ * are mirrored back (read at the mirrored index), multiplied by (gx[a] * gy[j]) * gz[k] in fp32 - three DEVICE tables
+ * of d, h and w floats indexed by the voxel's place in the window, all three NULL for weight 1 - and added into acc;
+ * the weight is added into cnt, so merge stays acc / cnt.  No atomics: one thread owns a voxel of the window, launches
+ * on one stream sum in launch order, and the result does not depend on how windows were batched.  With flip 0 and
+ * NULL tables the sums are bit-identical to accumulate's.  Same argument checks, refused before launch. */
+int ru3d_predict_accumulate_weighted(const ru3d_tensor* logits, int dtype, int sample, int flip, const float* gx,
+                                     const float* gy, const float* gz, float* acc, float* cnt, int X, int Y, int Z,
+                                     int ox, int oy, int oz, void* stream);
 
 /* ------------------------------------------------------------------ connected components + cascade merge */
 /* 3D connected-component labelling with 6-connectivity, scipy.ndimage.label's default structure (transform.py:5-11,

@@ -1,4 +1,6 @@
-"""Throughput of trainer.predict_per_patch on the GPU box: config-2 model, bf16, one 256x256x160 case, 128^3 windows."""
+"""Throughput of trainer.predict_per_patch on the GPU box: config-2 model, bf16, one 256x256x160 case, 128^3 windows.
+The first three rows are the reference placement; the rows after them the blended modes (covering windows, Gaussian
+weights, 2 and 8 mirror variants), where a forward is one (window, mirror variant) term."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "3d-unet-renal-anatomy-extraction_amd"))
@@ -16,3 +18,17 @@ for spp, pb in ((2, 1), (2, 2), (4, 2)):
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
     print("step_per_patch %d patch_batch %d: %d windows %s, %.1f ms total, %.2f ms/window, %.1f M window-voxels/s" % (
         spp, pb, len(origins), counts, 1e3 * dt, 1e3 * dt / len(origins), len(origins) * 128 ** 3 / dt / 1e6))
+for name, kw in (("cover uniform", dict(placement="cover")),
+                 ("cover gaussian", dict(placement="cover", weighting="gaussian")),
+                 ("cover gaussian mirror (2,)", dict(placement="cover", weighting="gaussian", mirror_axes=(2,))),
+                 ("cover gaussian mirror (0, 1, 2)", dict(placement="cover", weighting="gaussian", mirror_axes=(0, 1, 2)))):
+    spp, pb = 2, 2
+    origins, counts = I.cover_window_origins(I.padded_shape(vol.shape[:3], (128,) * 3), (128,) * 3, spp)
+    terms = len(origins) * 2 ** len(kw.get("mirror_axes", ()))
+    T.predict_per_patch(vol, model, 3, (128, 128, 128), spp, False, False, patch_batch=pb, **kw)
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    mask = T.predict_per_patch(vol, model, 3, (128, 128, 128), spp, False, False, patch_batch=pb, **kw)
+    torch.cuda.synchronize(); dt = time.perf_counter() - t0
+    print("%s, step_per_patch %d patch_batch %d: %d windows %s, %d forwards, %.1f ms total, %.2f ms/forward, "
+          "%.1f M window-voxels/s" % (name, spp, pb, len(origins), counts, terms, 1e3 * dt, 1e3 * dt / terms,
+                                      terms * 128 ** 3 / dt / 1e6))
