@@ -189,6 +189,12 @@ SIGNATURES = {
     "ru3d_edt_gather": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ru3d_edt_reduce_workspace_bytes": (_sz, [_i64]),
     "ru3d_edt_reduce": (_i, [_vp, _vp, _i64, _dbl, _vp, _vp, _sz, _vp]),
+    "ru3d_skeleton_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_skeleton_thin": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "ru3d_skeleton_classify": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ru3d_skeleton_length": (_i, [_vp, _i, _i, _i, ctypes.POINTER(_dbl), _vp, _vp, _sz, _vp]),
+    "ru3d_skeleton_overlap": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "ru3d_skeleton_radius_stats": (_i, [_vp, _i64, _vp, _vp]),
     "ru3d_mesh_workspace_bytes": (_sz, [_i, _i, _i]),
     "ru3d_mesh_count": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ru3d_mesh_emit": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),

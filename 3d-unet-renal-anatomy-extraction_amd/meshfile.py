@@ -2,7 +2,8 @@
 
 STL holds float32 triangles with a normal each and no shared vertices; PLY holds the float64 positions and the int32
 face rows as they are, so a PLY round trip is exact and an STL round trip is exact up to float32.  The readers exist for
-the round-trip tests and for users; they read what the writers write (plus any binary STL).
+the round-trip tests and for users; they read what the writers write (plus any binary STL).  A centreline is a PLY of
+vertices alone with a radius each (write_points_ply / read_points_ply).
 """
 import struct
 
@@ -99,6 +100,44 @@ def read_ply(path):
     if nf and not (records['count'] == 3).all():
         raise ValueError("%s: a face that is not a triangle" % path)
     return vertices, records['index'].astype(np.int32)
+
+
+_POINT_HEADER = ['property double x', 'property double y', 'property double z', 'property double radius', 'end_header']
+
+
+def write_points_ply(path, points, radius, comment=None):
+    """Binary little-endian PLY of vertices alone, `double` x, y, z and radius each: a centreline with the radius of the
+    structure at every point."""
+    p = np.asarray(points, dtype=np.float64)
+    r = np.asarray(radius, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 3 or r.shape != (len(p),):
+        raise ValueError("write_points_ply: points [V, 3] and radius [V], got %s and %s" % (p.shape, r.shape))
+    lines = ['ply', 'format binary_little_endian 1.0']
+    if comment:
+        lines += ['comment %s' % line for line in str(comment).splitlines()]
+    lines += ['element vertex %d' % len(p)] + _POINT_HEADER
+    with open(str(path), 'wb') as out:
+        out.write(('\n'.join(lines) + '\n').encode('ascii'))
+        out.write(np.column_stack((p, r)).astype('<f8').tobytes())
+
+
+def read_points_ply(path):
+    """-> (points float64 [V, 3], radius float64 [V]) of a file write_points_ply wrote."""
+    with open(str(path), 'rb') as src:
+        raw = src.read()
+    end = raw.find(b'end_header\n')
+    if not raw.startswith(b'ply\n') or end < 0:
+        raise ValueError("%s: not a PLY file" % path)
+    header = [line for line in raw[:end + len(b'end_header')].decode('ascii').splitlines() if not line.startswith('comment')]
+    if (len(header) != 3 + len(_POINT_HEADER) or header[:2] != ['ply', 'format binary_little_endian 1.0']
+            or header[2].split()[:2] != ['element', 'vertex'] or header[3:] != _POINT_HEADER):
+        raise ValueError("%s: only binary little-endian PLY files of double x, y, z, radius vertices are read" % path)
+    nv = int(header[2].split()[2])
+    body = end + len(b'end_header\n')
+    if len(raw) != body + nv * 32:
+        raise ValueError("%s: %d bytes do not hold %d vertices" % (path, len(raw), nv))
+    table = np.frombuffer(raw, dtype='<f8', count=4 * nv, offset=body).reshape(nv, 4).astype(np.float64)
+    return np.ascontiguousarray(table[:, :3]), np.ascontiguousarray(table[:, 3])
 
 
 WRITERS = {'stl': write_stl, 'ply': write_ply}

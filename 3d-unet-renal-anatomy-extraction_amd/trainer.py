@@ -1075,6 +1075,217 @@ def batch_extract_mesh(pred_dir, save_dir, data_range=None, fmt='stl', device=No
             for i in (data_range if data_range is not None else range(len(pred_files)))]
 
 
+# ------------------------------------------------------------------ centrelines of the tubular structures
+def _ratio(num, den):
+    return num / den if den else math.nan
+
+
+def _radius_stats_numpy(sq):
+    """skeleton.radius_stats on the host: (n, min, mean, max) of the radii whose squares are `sq`, the mean's sum in the
+    order of include/ru3d.h (256 strided partial sums, then seven halving steps)."""
+    n = int(sq.size)
+    if not n:
+        return 0, math.nan, math.nan, math.nan
+    rows = np.zeros((n + 255) // 256 * 256, dtype=np.float64)
+    rows[:n] = np.sqrt(sq)
+    part = np.zeros(256, dtype=np.float64)
+    for row in rows.reshape(-1, 256):
+        part = part + row
+    h = 128
+    while h:
+        part = part[:h] + part[h:2 * h]
+        h //= 2
+    return n, math.sqrt(float(sq.min())), float(part[0]) / n, math.sqrt(float(sq.max()))
+
+
+def _radii_squared_numpy(skel, mask, spacing):
+    """skeleton.radii_squared on the host: the squared distance from every voxel of `skel` (element order) to the nearest
+    voxel outside `mask`, through scipy's feature transform and the expression the device transform is held to."""
+    if mask.all():
+        return np.full(int(skel.sum()), np.inf)
+    return _contract_sq_numpy(skel, _nearest_feature_numpy(~mask, spacing), spacing)
+
+
+def _centerline_operands(case, keys, what):
+    """The volumes case[k] for k in keys on one route: uint8 HIP tensors when any of them is one, else numpy arrays
+    reshaped to three axes; and the number of axes they came with."""
+    volumes = [case[k] for k in keys]
+    shape = tuple(volumes[0].shape)
+    if any(tuple(v.shape) != shape for v in volumes):
+        raise ValueError("%s: volumes of shapes %s" % (what, [tuple(v.shape) for v in volumes]))
+    if not 1 <= len(shape) <= 3:
+        raise ValueError("%s: a volume of shape %s (1 to 3 axes)" % (what, shape))
+    hip = [v for v in volumes if _is_hip(v)]
+    if hip:
+        return [_device_bytes(v, hip[0].device) for v in volumes], len(shape), True
+    shape3 = (1,) * (3 - len(shape)) + shape
+    return [np.asarray(v.cpu() if torch.is_tensor(v) else v).reshape(shape3) for v in volumes], len(shape), False
+
+
+def _packed_union(volume, values):
+    import morphology
+    packed = morphology.pack(volume, 'eq', values[0])
+    for v in values[1:]:
+        packed.bits |= morphology.pack(volume, 'eq', v).bits
+    return packed
+
+
+def evaluate_centerline_case(case, labels=None):
+    """Centreline Dice (clDice) of every foreground class 1 .. label.max() of case['label'] vs case['pred'] (labels: a
+    list of values, a tuple standing for the union of its values): a list of dicts.  With S the curve skeleton
+    (transform.skeletonize) and V the mask of the class,
+      tprec   |S_pred & V_label| / |S_pred|      how much of the predicted centreline lies inside the true structure,
+      tsens   |S_label & V_pred| / |S_label|     how much of the true centreline the prediction covers,
+      cldice  2 tprec tsens / (tprec + tsens),
+    and the four integers as n_pred_skeleton, n_pred_skeleton_in_label, n_label_skeleton, n_label_skeleton_in_pred.  A
+    zero denominator gives nan for that ratio.  numpy operands run on the host (the numpy twin of the thinning); when
+    `pred` or `label` is a HIP tensor the other operand is uploaded and masks, skeletons (csrc/skeleton.hip) and
+    counts stay on the device: per class one download of six integers beside the thinning's own iteration counter."""
+    (pred, label), _, hip = _centerline_operands(case, ('pred', 'label'), "evaluate_centerline_case")
+    top = 0
+    if labels is None:
+        top = (int(label.max().item()) if label.numel() else 0) if hip else (int(label.max()) if label.size else 0)
+    results = []
+    for name, values in _mesh_labels(labels, top):
+        if hip:
+            import skeleton
+            vp, vl = _packed_union(pred, values), _packed_union(label, values)
+            counts = torch.cat((skeleton.overlap_device(skeleton.thin(vp), vl),
+                                skeleton.overlap_device(skeleton.thin(vl), vp))).tolist()
+            sp, sp_in, sl, sl_in = int(counts[0]), int(counts[2]), int(counts[3]), int(counts[5])
+        else:
+            import transform
+            vp, vl = np.isin(pred, values), np.isin(label, values)
+            s_pred, s_label = transform._skeleton_numpy(vp)[0], transform._skeleton_numpy(vl)[0]
+            sp, sp_in, sl, sl_in = int(s_pred.sum()), int((s_pred & vl).sum()), int(s_label.sum()), int((s_label & vp).sum())
+        tprec, tsens = _ratio(sp_in, sp), _ratio(sl_in, sl)
+        both = tprec + tsens
+        results.append({'label': name, 'tprec': tprec, 'tsens': tsens,
+                        'cldice': 2 * tprec * tsens / both if both > 0 else math.nan,
+                        'n_pred_skeleton': sp, 'n_pred_skeleton_in_label': sp_in,
+                        'n_label_skeleton': sl, 'n_label_skeleton_in_pred': sl_in})
+    return results
+
+
+def evaluate_centerline(label_file, pred_file, device=None):
+    """evaluate_centerline_case of two NIfTI files.  device: a HIP device uploads both volumes (as bytes) and evaluates
+    there."""
+    import nifti
+    label, _, _ = nifti.load(label_file)
+    pred, _, _ = nifti.load(pred_file)
+    case = {'label': label.astype(np.uint8), 'pred': pred.astype(np.uint8)}
+    if device is not None:
+        case = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in case.items()}
+    return evaluate_centerline_case(case)
+
+
+def batch_evaluate_centerline(label_dir, pred_dir, data_range=None, device=None):
+    """evaluate_centerline over the sorted *.nii.gz files of two directories; prints the mean of each ratio per class
+    (over the cases that have the class and a defined ratio) and returns the per-case lists."""
+    from pathlib import Path
+    label_files = sorted(Path(label_dir).glob('*.nii.gz'))
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    results = [evaluate_centerline(label_files[i], pred_files[i], device)
+               for i in (data_range if data_range is not None else range(len(label_files)))]
+    for key in ('cldice', 'tprec', 'tsens'):
+        print('\nThe mean %s of each label:' % key)
+        for c in range(max((len(r) for r in results), default=0)):
+            values = [r[c][key] for r in results if len(r) > c and not math.isnan(r[c][key])]
+            print("label_%d: %f" % (c + 1, np.mean(values) if values else math.nan))
+    return results
+
+
+def centerline_case(case, labels=None, key='pred', return_device=False):
+    """The centreline of every structure of the label volume `case[key]`: a list of dicts
+      label       the value (or the tuple of values whose union was thinned),
+      voxels, ends, junctions   the skeleton's voxel count, its end voxels (one neighbour among the 26) and its
+                  junction voxels (three or more),
+      length      of the skeleton's voxel graph in millimetres (skeleton.length: every pair of 26-adjacent voxels counts),
+      radius_min, radius_mean, radius_max   distance from the skeleton voxels to the nearest voxel outside the structure,
+      points, radii   float64 [n, 3] world coordinates (`case['affine']`; voxel coordinates without one) of the skeleton
+                  voxels in element order and float64 [n] radii - left out with return_device=True.
+    The voxel spacing is that of the affine.  A numpy volume takes the numpy route; a HIP volume is packed, thinned,
+    classified and measured on the device (csrc/skeleton.hip, csrc/distance.hip) and only the numbers above, or with
+    return_device=False the points and radii too, are downloaded."""
+    from data import get_spacing
+    import transform
+    (volume,), ndim, hip = _centerline_operands(case, (key,), "centerline_case")
+    affine = np.asarray(case['affine'], dtype=np.float64) if case.get('affine') is not None else np.eye(4)
+    spacing = get_spacing(affine)
+    top = 0
+    if labels is None:
+        top = (int(volume.max().item()) if volume.numel() else 0) if hip else (int(volume.max()) if volume.size else 0)
+    results = []
+    for name, values in _mesh_labels(labels, top):
+        if hip:
+            import mesh
+            import morphology
+            import skeleton
+            mask = _packed_union(volume, values)
+            skel = skeleton.thin(mask)
+            _, _, n, n_ends, n_junctions = skeleton.classify(skel)
+            total = skeleton.length(skel, spacing[3 - ndim:])
+            sq = skeleton.radii_squared(skel, mask, spacing[3 - ndim:])
+            _, lo, mean, hi = skeleton.radius_stats(sq)
+            if not return_device:
+                index = torch.nonzero(morphology.unpack(skel).reshape(skel.shape3)).to(torch.float64)
+                points = mesh.to_world(index, affine).cpu().numpy()
+                radii = np.sqrt(sq.cpu().numpy())
+        else:
+            mask = np.isin(volume, values)
+            skel = transform._skeleton_numpy(mask)[0]
+            _, _, n, n_ends, n_junctions = transform._skeleton_classify_numpy(skel)
+            total = transform._skeleton_length_numpy(skel, spacing)
+            sq = _radii_squared_numpy(skel, mask, spacing)
+            _, lo, mean, hi = _radius_stats_numpy(sq)
+            points = transform._to_world_numpy(np.argwhere(skel).astype(np.float64), np.zeros((0, 3), np.int32), affine)[0]
+            radii = np.sqrt(sq)
+        result = {'label': name, 'voxels': n, 'ends': n_ends, 'junctions': n_junctions, 'length': total,
+                  'radius_min': lo, 'radius_mean': mean, 'radius_max': hi}
+        if not return_device:
+            result.update(points=points, radii=radii)
+        results.append(result)
+    return results
+
+
+def extract_centerline(pred_file, save_dir=None, device=None, labels=None):
+    """centerline_case of a NIfTI label volume with the file's affine.  save_dir: every non-empty centreline is written as
+    `<case_id>.label_<n>.centerline.ply`, a vertex-only binary PLY with x, y, z and radius per skeleton voxel
+    (meshfile.write_points_ply), and its dict gains 'file'.  device: a HIP device uploads the volume (as bytes) and works
+    there.  Prints one line per structure; returns the list of dicts."""
+    import nifti
+    import meshfile
+    from pathlib import Path
+    pred_file = Path(pred_file)
+    case_id = pred_file.name
+    for suffix in ('.gz', '.nii', '.pred'):
+        if case_id.endswith(suffix):
+            case_id = case_id[:-len(suffix)]
+    pred, affine, _ = nifti.load(pred_file)
+    pred = np.ascontiguousarray(np.clip(pred, 0, 255).astype(np.uint8))
+    case = {'case_id': case_id, 'affine': affine, 'pred': pred if device is None else torch.from_numpy(pred).to(device)}
+    results = centerline_case(case, labels, 'pred')
+    if save_dir is not None:
+        save_dir = Path(save_dir)
+        save_dir.mkdir(parents=True, exist_ok=True)
+    for r in results:
+        print("%s label_%s: %d centreline voxels, %d ends, %d junctions, length %.1f mm, radius %.2f / %.2f / %.2f mm"
+              % (case_id, _label_name(r['label']), r['voxels'], r['ends'], r['junctions'], r['length'], r['radius_min'],
+                 r['radius_mean'], r['radius_max']))
+        if save_dir is not None and r['voxels']:
+            r['file'] = save_dir / ('%s.label_%s.centerline.ply' % (case_id, _label_name(r['label'])))
+            meshfile.write_points_ply(r['file'], r['points'], r['radii'])
+    return results
+
+
+def batch_extract_centerline(pred_dir, save_dir, data_range=None, device=None, labels=None):
+    """extract_centerline over the sorted *.nii.gz files of `pred_dir`; returns the per-file lists."""
+    from pathlib import Path
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    return [extract_centerline(pred_files[i], save_dir, device, labels)
+            for i in (data_range if data_range is not None else range(len(pred_files)))]
+
+
 def preview_case(case, key='pred', axes=(0, 1, 2), num_slices=8, views=((30, 20), (120, 20), (210, -20)), size=256,
                  alpha=None, labels=None, colours=None, window=None, pixel_mm=None):
     """One picture of a case to leaf through, uint8 [H, W, 3]: `visualize.case_sheet` (slices of the image under the

@@ -9,6 +9,8 @@ To* classes; `Compose` stands in for torchvision's (absent here).  Cases are dic
 reference (third-party there too).  The random draws come from numpy's global generator in the reference's order, so a
 seed reproduces the reference's patches (checked against tests/golden/g7_augment.npz).
 """
+import math
+
 import numpy as np
 import scipy.ndimage as ndi
 import torch
@@ -334,6 +336,155 @@ def extract_mesh(input, smooth_iterations=10, lam=0.5, mu=-0.53):
     return mesh.Mesh(corners, vertices, faces, neighbours, volume.shape)
 
 
+# ------------------------------------------------------------------ curve skeletons (contract: include/ru3d.h)
+# The 3 x 3 x 3 neighbourhood of a voxel as a 27-bit code: bit 9 (dx + 1) + 3 (dy + 1) + (dz + 1), the voxel itself bit 13.
+_SK_ALL, _SK_N26, _SK_N18, _SK_N6 = 0x7ffffff, 0x7ffdfff, 0x2ebdeba, 0x415410
+# cells a step along +z, -z, +y, -y may land on (the cells whose z is not 0, not 2, whose y is not 0, not 2)
+_SK_NZ0, _SK_NZ2, _SK_NY0, _SK_NY2 = 0x6db6db6, 0x36db6db, 0x7e3f1f8, 0xfc7e3f
+_SK_DIRECTIONS = ((-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1))
+# the 13 offsets that name every unordered pair of 26-adjacent voxels once: cells 14 .. 26 of the code, in that order
+_SK_HALF = tuple((i // 9 - 1, (i // 3) % 3 - 1, i % 3 - 1) for i in range(14, 27))
+
+
+def _sk_grow26(r):
+    """The cells of a code and everything 26-adjacent to them inside the cube: three 1-D dilations, one per axis."""
+    r = r | ((r << 1) & _SK_NZ0) | ((r >> 1) & _SK_NZ2)
+    r = r | ((r << 3) & _SK_NY0) | ((r >> 3) & _SK_NY2)
+    return (r | (r << 9) | (r >> 9)) & _SK_ALL
+
+
+def _sk_grow6(r):
+    """The cells of a code and their face neighbours inside the cube."""
+    return (r | ((r << 1) & _SK_NZ0) | ((r >> 1) & _SK_NZ2) | ((r << 3) & _SK_NY0) | ((r >> 3) & _SK_NY2)
+            | (r << 9) | (r >> 9)) & _SK_ALL
+
+
+def _sk_fill(seed, allowed, grow):
+    """Flood fill of `seed` inside `allowed` (uint32 arrays of codes) until nothing grows any more."""
+    reach = seed
+    while True:
+        grown = grow(reach) & allowed
+        if np.array_equal(grown, reach):
+            return reach
+        reach = grown
+
+
+def _sk_simple(code):
+    """Simple voxels (T26 = 1 and T6bar = 1) among the object voxels whose neighbourhood codes are `code` (uint32)."""
+    code = np.asarray(code, dtype=np.uint32)
+    obj = code & np.uint32(_SK_N26)
+    seed = obj ^ (obj & (obj - np.uint32(1)))                              # the lowest set bit (0 stays 0)
+    t26 = (obj != 0) & (_sk_fill(seed, obj, _sk_grow26) == obj)
+    back = ~code & np.uint32(_SK_N18)
+    faces = back & np.uint32(_SK_N6)
+    seed = faces ^ (faces & (faces - np.uint32(1)))
+    t6 = (faces != 0) & ((faces & ~_sk_fill(seed, back, _sk_grow6)) == 0)
+    return t26 & t6
+
+
+def _sk_end(code):
+    """End voxels: exactly one object voxel among the 26 neighbours."""
+    return np.bitwise_count(np.asarray(code, dtype=np.uint32) & np.uint32(_SK_N26)) == 1
+
+
+def _sk_codes(padded, x, y, z):
+    """Neighbourhood codes of the voxels (x, y, z) of the volume whose zero-padded copy (one voxel a side) is `padded`."""
+    code = np.zeros(len(x), dtype=np.uint32)
+    for i in range(27):
+        code |= padded[x + i // 9, y + (i // 3) % 3, z + i % 3].astype(np.uint32) << np.uint32(i)
+    return code
+
+
+def _skeleton_numpy(volume, max_iterations=None):
+    """(curve skeleton, iterations run) of a boolean volume [X, Y, Z]: the thinning include/ru3d.h defines, in vectorised
+    numpy.  The iteration that deletes nothing and ends the run is counted."""
+    X, Y, Z = volume.shape
+    padded = np.zeros((X + 2, Y + 2, Z + 2), dtype=bool)
+    core = padded[1:-1, 1:-1, 1:-1]
+    core[...] = volume
+    iterations = 0
+    while max_iterations is None or iterations < max_iterations:
+        deleted = 0
+        for dx, dy, dz in _SK_DIRECTIONS:
+            cx, cy, cz = np.nonzero(core & ~padded[1 + dx:X + 1 + dx, 1 + dy:Y + 1 + dy, 1 + dz:Z + 1 + dz])
+            subfield = 4 * (cx & 1) + 2 * (cy & 1) + (cz & 1)
+            for s in range(8):
+                pick = subfield == s
+                if not pick.any():
+                    continue
+                x, y, z = cx[pick], cy[pick], cz[pick]
+                code = _sk_codes(padded, x, y, z)
+                kill = _sk_simple(code) & ~_sk_end(code)
+                core[x[kill], y[kill], z[kill]] = False
+                deleted += int(kill.sum())
+        iterations += 1
+        if not deleted:
+            break
+    return core.copy(), iterations
+
+
+def _skeleton_neighbours_numpy(skel):
+    """int [X, Y, Z]: the number of set voxels among the 26 neighbours of every voxel."""
+    X, Y, Z = skel.shape
+    padded = np.zeros((X + 2, Y + 2, Z + 2), dtype=np.int32)
+    padded[1:-1, 1:-1, 1:-1] = skel
+    count = -padded[1:-1, 1:-1, 1:-1]
+    for i in range(27):
+        count = count + padded[i // 9:X + i // 9, (i // 3) % 3:Y + (i // 3) % 3, i % 3:Z + i % 3]
+    return count
+
+
+def _skeleton_classify_numpy(skel):
+    """skeleton.classify on the host: (ends, junctions, n_voxels, n_ends, n_junctions) of a boolean volume [X, Y, Z]."""
+    count = _skeleton_neighbours_numpy(skel)
+    ends, junctions = skel & (count == 1), skel & (count >= 3)
+    return ends, junctions, int(skel.sum()), int(ends.sum()), int(junctions.sum())
+
+
+def _skeleton_step_lengths(spacing):
+    """The 13 step lengths of _SK_HALF in `spacing` units: sqrt(fl(A + fl(B + C))), A = fl(fl(sx dx)^2), in float64."""
+    sx, sy, sz = (float(s) for s in spacing)
+    return [math.sqrt((sx * dx) * (sx * dx) + ((sy * dy) * (sy * dy) + (sz * dz) * (sz * dz))) for dx, dy, dz in _SK_HALF]
+
+
+def _skeleton_length_numpy(skel, spacing):
+    """skeleton.length on the host: the pairs of 26-adjacent set voxels counted per offset of _SK_HALF, then
+    total = fl(total + fl(count * step)) in that order."""
+    X, Y, Z = skel.shape
+    padded = np.zeros((X + 2, Y + 2, Z + 2), dtype=bool)
+    padded[1:-1, 1:-1, 1:-1] = skel
+    total = 0.0
+    for (dx, dy, dz), step in zip(_SK_HALF, _skeleton_step_lengths(spacing)):
+        pairs = int((skel & padded[1 + dx:X + 1 + dx, 1 + dy:Y + 1 + dy, 1 + dz:Z + 1 + dz]).sum())
+        total = total + float(pairs) * step
+    return total
+
+
+def skeletonize(input, max_iterations=None):
+    """The curve skeleton of the non-zero voxels of a bool / uint8 volume of 1 to 3 axes: a topology-preserving thinning
+    (objects 26-connected, background 6-connected, outside the volume is background) that deletes simple voxels
+    direction by direction and subfield by subfield and keeps end voxels - the contract of include/ru3d.h, "skeleton".
+    The result has the input's kind and dtype, the skeleton voxels 1 / True.  numpy in -> the vectorised numpy twin; a
+    HIP tensor in -> the kernels of csrc/skeleton.hip, voxel for voxel the same.  max_iterations stops the thinning
+    early; `input` is left as it is."""
+    if max_iterations is not None and (int(max_iterations) != max_iterations or max_iterations < 0):
+        raise ValueError("skeletonize: max_iterations=%r (None or a count >= 0)" % (max_iterations,))
+    if torch.is_tensor(input):
+        import morphology
+        import skeleton
+        if input.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("skeletonize: expected a bool or uint8 volume, got %s" % input.dtype)
+        thin = skeleton.thin(morphology.pack(input), max_iterations)
+        return morphology.unpack(thin, 1, out=torch.empty(input.shape, dtype=input.dtype, device=input.device))
+    volume = np.asarray(input)
+    if volume.dtype not in (np.bool_, np.uint8):
+        raise ValueError("skeletonize: expected a bool or uint8 volume, got %s" % volume.dtype)
+    if volume.ndim < 1 or volume.ndim > 3:
+        raise ValueError("skeletonize: expected a volume of 1 to 3 axes, got shape %s" % (volume.shape,))
+    skel, _ = _skeleton_numpy((volume != 0).reshape((1,) * (3 - volume.ndim) + volume.shape), max_iterations)
+    return skel.reshape(volume.shape).astype(volume.dtype)
+
+
 def create_sphere(shape, center, r):
     """nb_post.py:81-85: integer array of `shape`, 1 where the distance to `center` is at most r."""
     x, y, z = np.ogrid[:shape[0], :shape[1], :shape[2]]
@@ -488,6 +639,22 @@ class PostTransform(object):
 
     def __call__(self, case):
         case[self.key] = post_transform(case[self.key], self.threshold, self.label, self.structure)
+        return case
+
+
+class Skeletonize(object):
+    """skeletonize on case[key] (the prediction by default), for numpy cases and cases that live on the device.
+    label=None thins the non-zero voxels; label=k thins `case[key] == k`.  The result replaces case[key] as a uint8
+    volume of the same kind with 1 on the skeleton."""
+
+    def __init__(self, key='pred', label=None):
+        self.key, self.label = key, label
+
+    def __call__(self, case):
+        volume = case[self.key]
+        picked = (volume != 0) if self.label is None else (volume == self.label)
+        as_bytes = picked.to(torch.uint8) if torch.is_tensor(picked) else np.asarray(picked).astype(np.uint8)
+        case[self.key] = skeletonize(as_bytes)
         return case
 
 

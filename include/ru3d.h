@@ -469,6 +469,51 @@ size_t ru3d_edt_reduce_workspace_bytes(int64_t capacity);
 int ru3d_edt_reduce(const double* values, const int64_t* count, int64_t capacity, double tau_sq, double* out, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ skeleton */
+/* Curve skeletons of tubular structures (vessels) and what is measured on them: centreline Dice, end and branch
+ * voxels, centreline length, radii.  Masks are the packed masks of the morphology section; X*Y*Z < 2^31.
+ *
+ * The thinning.  Objects are 26-connected, the background is 6-connected, voxels outside the volume are background.
+ * N26*(p) is the 26 neighbours of p without p.
+ *   Simple voxel.  An object voxel p such that (T26 = 1) the object voxels of N26*(p) are not empty and form exactly one
+ *                  26-connected component, and (T6bar = 1) the background voxels of the 18-neighbourhood of p include a
+ *                  6-neighbour of p and all background 6-neighbours of p lie in one 6-connected component of that
+ *                  18-neighbourhood background.  An interior voxel and an isolated voxel are not simple.
+ *   End voxel.     An object voxel with exactly one object voxel in N26*(p).  End voxels are kept: a curve skeleton.
+ *   Iteration.     For each direction d in the order -x, +x, -y, +y, -z, +z: (1) the candidates are the object voxels
+ *                  whose neighbour at p + d is background, on the mask as it is when the direction begins; (2) for each
+ *                  subfield s = 4 (x & 1) + 2 (y & 1) + (z & 1) in the order 0 .. 7, every candidate of subfield s
+ *                  that is simple and not an end voxel is deleted, both predicates evaluated on the mask as it is when
+ *                  that sub-pass begins.  No two voxels of a subfield are 26-adjacent, so the deletions of a sub-pass
+ *                  cannot influence one another: the result does not depend on thread order or launch geometry.
+ *   Iterations repeat until one whole iteration deletes nothing (that last iteration is counted), or max_iterations.
+ *
+ * ru3d_skeleton_thin thins `mask` in place on `stream`, reads the deletion counter back once per iteration and
+ * returns the number of iterations run (>= 0), or a negative status.  max_iterations < 0: until nothing changes.
+ * Workspace: the candidate mask and the counters. */
+size_t ru3d_skeleton_workspace_bytes(int X, int Y, int Z);
+int ru3d_skeleton_thin(uint64_t* mask, int X, int Y, int Z, int max_iterations, void* ws, size_t ws_bytes, void* stream);
+/* ends / junctions (packed, distinct from skel and from each other) = the set voxels with exactly 1 / with 3 or more
+ * set voxels among their 26 neighbours; counts (device int64 [3]) = (set voxels, end voxels, junction voxels). */
+int ru3d_skeleton_classify(const uint64_t* skel, int X, int Y, int Z, uint64_t* ends, uint64_t* junctions, int64_t* counts,
+                           void* stream);
+/* out (device float64 [1]) = the length of the voxel graph: over the 13 offsets o = (dx, dy, dz) of cells 14 .. 26 of
+ * the 3 x 3 x 3 cube (index 9 (dx + 1) + 3 (dy + 1) + (dz + 1); each unordered pair of 26-adjacent voxels once), in
+ * that order, total = fl(total + fl(pairs(o) * step(o))) with pairs(o) the number of set voxels p with p + o set and
+ * step(o) = sqrt(fl(A + fl(B + C))), A = fl(fl(sx dx)^2), in float64.  `spacing` is a HOST array of three finite
+ * values > 0.  Every edge of the graph counts, so the short diagonals inside the clique of voxels at a junction are
+ * included: on a curve without junctions this is the curve's length, at each branch point it adds a few voxel steps.
+ * Workspace: 256 bytes. */
+int ru3d_skeleton_length(const uint64_t* skel, int X, int Y, int Z, const double* spacing, double* out, void* ws,
+                         size_t ws_bytes, void* stream);
+/* counts (device int64 [3]) = (|a|, |b|, |a & b|) of two packed masks of one shape: with a skeleton and a mask, the
+ * integers centreline Dice is made of. */
+int ru3d_skeleton_overlap(const uint64_t* a, const uint64_t* b, int X, int Y, int Z, int64_t* counts, void* stream);
+/* out (device float64 [4]) = (n, min v, max v, sum of sqrt(v)) over n device values v >= 0 (squared radii gathered at
+ * the skeleton voxels); n == 0 gives (0, +inf, 0, 0).  The sum has a fixed order: 256 partial sums, partial t over the
+ * elements t, t + 256, .. in order starting from 0, then seven halving steps s[t] = fl(s[t] + s[t + h]), h = 128 .. 1. */
+int ru3d_skeleton_radius_stats(const double* sq, int64_t n, double* out, void* stream);
+
 /* ------------------------------------------------------------------ surface meshes */
 /* The anatomy as closed triangle meshes: the faces between a set voxel and an unset one of a packed mask (the
  * "cuberille"), Taubin smoothing on the lattice's own edge graph, area and enclosed volume.  Masks are the packed masks
