@@ -145,50 +145,61 @@ def _flat_strides(x):
     return x.stride(0), x.stride(1), sv
 
 
+def _loss_operands(input, target, check_labels):
+    """What every fused loss does to its operands before it launches: float32 logits with a single spatial stride,
+    contiguous int64 / uint8 labels, and the blocking label check where one is asked for."""
+    N.require_device(input, "loss input")
+    if target.device != input.device:
+        raise N.Ru3dError("loss: target is on %s but input on %s" % (target.device, input.device))
+    if input.dim() < 2:
+        raise N.Ru3dError("loss: input must be (N, C, d1, ..., dn)")
+    n, c = input.shape[0], input.shape[1]
+    if c > N.MAX_CLASSES:
+        raise N.Ru3dError("loss: %d classes (max %d)" % (c, N.MAX_CLASSES))
+    if tuple(target.shape) != (n,) + tuple(input.shape[2:]):
+        raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape),
+                                                                             tuple(input.shape)))
+    x = input.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    st = _flat_strides(x)
+    if st is None:
+        x = x.contiguous()
+        st = _flat_strides(x)
+    v = 1
+    for s in x.shape[2:]:
+        v *= s
+    if target.dtype == torch.int64:
+        lab, lab_code = target.contiguous(), N.LABEL_I64
+    elif target.dtype == torch.uint8:
+        lab, lab_code = target.contiguous(), N.LABEL_U8
+    else:
+        lab, lab_code = target.long().contiguous(), N.LABEL_I64
+    if check_labels or c == 1:
+        # reference: F.one_hot(target, C) raises for labels >= C (always hit by C == 1 with labels {0,1})
+        if lab.numel() and (int(lab.max()) >= c or int(lab.min()) < 0):
+            raise RuntimeError(_BAD_LABELS)
+    return x, st, lab, lab_code, n, c, v
+
+
+def _weight_array(weight_v, c):
+    if weight_v is None:
+        return None
+    if len(weight_v) != c:
+        raise RuntimeError("weight_v has %d entries for %d classes" % (len(weight_v), c))
+    return (N.ctypes.c_float * c)(*[float(w) for w in weight_v])
+
+
 class _FusedLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, target, kind, gamma, weight_v, alpha, beta, smooth, check_labels):
-        N.require_device(input, "loss input")
-        if target.device != input.device:
-            raise N.Ru3dError("loss: target is on %s but input on %s" % (target.device, input.device))
-        if input.dim() < 2:
-            raise N.Ru3dError("loss: input must be (N, C, d1, ..., dn)")
-        n, c = input.shape[0], input.shape[1]
-        if c > N.MAX_CLASSES:
-            raise N.Ru3dError("loss: %d classes (max %d)" % (c, N.MAX_CLASSES))
-        if tuple(target.shape) != (n,) + tuple(input.shape[2:]):
-            raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape),
-                                                                                 tuple(input.shape)))
-        x = input.detach()
-        if x.dtype != torch.float32:
-            x = x.float()
-        st = _flat_strides(x)
-        if st is None:
-            x = x.contiguous()
-            st = _flat_strides(x)
-        v = 1
-        for s in x.shape[2:]:
-            v *= s
-        if target.dtype == torch.int64:
-            lab, lab_code = target.contiguous(), N.LABEL_I64
-        elif target.dtype == torch.uint8:
-            lab, lab_code = target.contiguous(), N.LABEL_U8
-        else:
-            lab, lab_code = target.long().contiguous(), N.LABEL_I64
-        if check_labels or c == 1:
-            # reference: F.one_hot(target, C) raises for labels >= C (always hit by C == 1 with labels {0,1})
-            if lab.numel() and (int(lab.max()) >= c or int(lab.min()) < 0):
-                raise RuntimeError(_BAD_LABELS)
+        x, st, lab, lab_code, n, c, v = _loss_operands(input, target, check_labels)
         raise_on_bad_labels()          # an earlier call's verdict, if it has landed (no wait)
         dev = x.device
         state = torch.empty(N.lib.ru3d_loss_state_bytes(c), dtype=torch.uint8, device=dev)
         out = torch.empty((), dtype=torch.float32, device=dev)
         ws = N.workspace(N.lib.ru3d_loss_workspace_bytes(n, v, c), dev)
-        wv = None
-        if weight_v is not None:
-            if len(weight_v) != c:
-                raise RuntimeError("weight_v has %d entries for %d classes" % (len(weight_v), c))
-            wv = (N.ctypes.c_float * c)(*[float(w) for w in weight_v])
+        wv = _weight_array(weight_v, c)
         check(N.lib.ru3d_loss_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, kind, float(gamma),
                                   N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None, float(alpha),
                                   float(beta), float(smooth), ptr(state), ptr(out), ptr(ws), ws.numel(), stream()),
@@ -309,3 +320,264 @@ class FocalDiceCoefLoss(HybirdLoss):
 
     def __init__(self, d_weight=None, gamma=2, alpha=0.5, beta=0.5, smooth=1e-7):
         super().__init__(gamma=gamma, weight_v=d_weight, alpha=alpha, beta=beta, smooth=smooth)
+
+
+# --------------------------------------------------------------------------- soft skeletons, soft-clDice
+# The soft skeleton of Shit et al. (clDice, CVPR 2021) on (N, K, A, B, Z) volumes, Z fastest; nothing outside a volume takes
+# part, nothing crosses between samples or classes:
+#   E(x)[v] = min over v and its face neighbours, D(x)[v] = max over the 3x3x3 block, both clipped at the faces;
+#   x_0 = x, x_{j+1} = E(x_j), d_j = relu(x_j - D(x_{j+1})), s_0 = d_0, s_j = s_{j-1} + relu(d_j - s_{j-1} d_j), S_k = s_k.
+# (The paper's opening of x_j is D(E(x_j)) = D(x_{j+1}): one erosion and one dilation per iteration.)  A minimum or
+# maximum hands its gradient to ONE voxel of its window, among equal candidates the one with the lowest linear index -
+# every x_j with j >= 1 is made of plateaus of copied minima, so ties are the rule and the rule is part of the contract.
+MAX_SKELETON_ITERATIONS = 64
+_E_OFFSETS = ((-1, 0, 0), (0, -1, 0), (0, 0, -1), (0, 0, 0), (0, 0, 1), (0, 1, 0), (1, 0, 0))
+_D_OFFSETS = tuple((da, db, dz) for da in (-1, 0, 1) for db in (-1, 0, 1) for dz in (-1, 0, 1))
+
+
+def _window_extremum(x, offsets, fill, pick):
+    """Host twin of E / D: the shifted copies stacked in ascending linear index, gathered at argmin / argmax (which
+    return the first of equal extrema), so autograd follows the tie rule."""
+    a, b, z = x.shape[-3:]
+    xp = F.pad(x, (1, 1, 1, 1, 1, 1), value=fill)
+    stack = torch.stack([xp[..., 1 + da:1 + da + a, 1 + db:1 + db + b, 1 + dz:1 + dz + z] for da, db, dz in offsets])
+    return stack.gather(0, pick(stack.detach(), dim=0, keepdim=True))[0]
+
+
+def soft_erode(x):
+    """E on a host tensor (..., A, B, Z), in its own dtype."""
+    return _window_extremum(x, _E_OFFSETS, float("inf"), torch.argmin)
+
+
+def soft_dilate(x):
+    """D on a host tensor (..., A, B, Z), in its own dtype."""
+    return _window_extremum(x, _D_OFFSETS, float("-inf"), torch.argmax)
+
+
+def _check_iterations(iterations):
+    k = int(iterations)
+    if k < 0 or k > MAX_SKELETON_ITERATIONS:
+        raise N.Ru3dError("soft skeleton: iterations = %d (0 .. %d)" % (k, MAX_SKELETON_ITERATIONS))
+    return k
+
+
+def _soft_skeleton_host(x, k):
+    xj, s = x, None
+    for _ in range(k + 1):
+        xn = soft_erode(xj)
+        d = torch.relu(xj - soft_dilate(xn))
+        s = d if s is None else s + torch.relu(d - s * d)
+        xj = xn
+    return s
+
+
+def _skeleton_buffers(k, plane, dev):
+    return (torch.empty((k + 1, plane), dtype=torch.float32, device=dev),
+            torch.empty((k + 1, plane), dtype=torch.float32, device=dev),
+            torch.empty((k + 1, plane), dtype=torch.uint8, device=dev),
+            torch.empty((k + 1, plane), dtype=torch.uint8, device=dev))
+
+
+class _SoftSkeletonFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prob, k):
+        N.require_device(prob, "soft_skeleton input")
+        x = prob.detach().float().contiguous()
+        n, kk, a, b, z = x.shape
+        dev = x.device
+        delta, s, emin, dmax = _skeleton_buffers(k, x.numel(), dev)
+        ws = N.workspace(N.lib.ru3d_cldice_workspace_bytes(n * kk, a, b, z, k), dev)
+        check(N.lib.ru3d_soft_skeleton_fwd(ptr(x), n * kk, a, b, z, k, ptr(delta), ptr(s), ptr(emin), ptr(dmax), ptr(ws),
+                                           ws.numel(), stream()), "soft_skeleton_fwd")
+        ctx.save_for_backward(delta, s, emin, dmax)
+        ctx.meta = (tuple(x.shape), k, prob.dtype)
+        return s[k].clone().view(x.shape)   # a copy: the caller may edit it in place, the saved planes stay intact
+
+    @staticmethod
+    def backward(ctx, gout):
+        delta, s, emin, dmax = ctx.saved_tensors
+        (n, kk, a, b, z), k, in_dtype = ctx.meta
+        dev = delta.device
+        g = gout.detach().to(device=dev, dtype=torch.float32).contiguous()
+        N.note_device(dev)
+        gx = torch.empty((n, kk, a, b, z), dtype=torch.float32, device=dev)
+        ws = N.workspace(N.lib.ru3d_cldice_workspace_bytes(n * kk, a, b, z, k), dev)
+        check(N.lib.ru3d_soft_skeleton_bwd(ptr(g), n * kk, a, b, z, k, ptr(delta), ptr(s), ptr(emin), ptr(dmax), ptr(gx),
+                                           ptr(ws), ws.numel(), stream()), "soft_skeleton_bwd")
+        return (gx if in_dtype == torch.float32 else gx.to(in_dtype)), None
+
+
+def soft_skeleton(prob, iterations=3):
+    """S_k of (N, K, A, B, Z) probabilities, differentiable.  HIP tensors go through the kernels and come back in
+    float32; host tensors go through the torch twin above - the definition written down - in the dtype they have."""
+    if prob.dim() != 5:
+        raise N.Ru3dError("soft_skeleton: input must be (N, K, A, B, Z) - three spatial dimensions - not %s"
+                          % (tuple(prob.shape),))
+    k = _check_iterations(iterations)
+    if prob.is_cuda:
+        return _SoftSkeletonFn.apply(prob, k)
+    return _soft_skeleton_host(prob, k)
+
+
+def _cldice_classes(classes, c):
+    cls = tuple(range(1, c)) if classes is None else tuple(int(q) for q in classes)
+    if not cls or len(set(cls)) != len(cls) or min(cls) < 0 or max(cls) >= c:
+        raise N.Ru3dError("clDice: classes %s must be distinct class numbers of 0 .. %d" % (cls, c - 1))
+    return cls
+
+
+def _cldice_shape_check(input):
+    if input.dim() != 5:
+        raise N.Ru3dError("clDice: input must be (N, C, A, B, Z) - three spatial dimensions - not %s"
+                          % (tuple(input.shape),))
+    if input.shape[1] < 2:
+        raise N.Ru3dError("clDice: C == 1 is not supported (softmax over at least two classes)")
+
+
+def _soft_cldice_host(input, target, k, classes, weight_v, smooth):
+    """The definition on host tensors, in the logits' dtype (what the device path is tested against)."""
+    c = input.shape[1]
+    cls = _cldice_classes(classes, c)
+    if weight_v is not None and len(weight_v) != c:
+        raise RuntimeError("weight_v has %d entries for %d classes" % (len(weight_v), c))
+    w = torch.tensor([1.0 if weight_v is None else float(weight_v[q]) for q in cls], dtype=input.dtype)
+    w = w / w.abs().sum().clamp_min(1e-12)
+    p = torch.softmax(input, dim=1)[:, list(cls)]
+    g = F.one_hot(target.long(), num_classes=c).movedim(-1, 1)[:, list(cls)].to(input.dtype)
+    sp, sg = _soft_skeleton_host(p, k), _soft_skeleton_host(g, k)
+    dims = (0, 2, 3, 4)
+    tprec = ((sp * g).sum(dims) + smooth) / (sp.sum(dims) + smooth)
+    tsens = ((sg * p).sum(dims) + smooth) / (sg.sum(dims) + smooth)
+    return (w * (1 - 2 * tprec * tsens / (tprec + tsens))).sum()
+
+
+class _ClDiceFn(torch.autograd.Function):
+    """(1 - cl_weight) Hybird + cl_weight clDice in one node (hyb = (gamma, weight_v, alpha, beta, smooth)), or the
+    clDice term alone (hyb None): the clDice backward adds into the gradient the Hybird backward wrote."""
+
+    @staticmethod
+    def forward(ctx, input, target, hyb, cl_weight, k, classes, weight_v, smooth, check_labels):
+        _cldice_shape_check(input)
+        x, st, lab, lab_code, n, c, v = _loss_operands(input, target, check_labels)
+        cls = _cldice_classes(classes, c)
+        raise_on_bad_labels()
+        dev = x.device
+        a, b, z = x.shape[2:]
+        nsel = len(cls)
+        lam = float(cl_weight)
+        state_h = None
+        if hyb is not None:
+            gamma, hyb_weight, alpha, beta, hyb_smooth = hyb
+            state_h = torch.empty(N.lib.ru3d_loss_state_bytes(c), dtype=torch.uint8, device=dev)
+            out_h = torch.empty((), dtype=torch.float32, device=dev)
+            ws = N.workspace(N.lib.ru3d_loss_workspace_bytes(n, v, c), dev)
+            wh = _weight_array(hyb_weight, c)
+            check(N.lib.ru3d_loss_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, N.LOSS_HYBIRD,
+                                      float(gamma), N.ctypes.cast(wh, N.ctypes.c_void_p) if wh is not None else None,
+                                      float(alpha), float(beta), float(hyb_smooth), ptr(state_h), ptr(out_h), ptr(ws),
+                                      ws.numel(), stream()), "loss_fwd")
+        delta, s, emin, dmax = _skeleton_buffers(k, n * nsel * v, dev)
+        skel_g = torch.empty(n * nsel * v, dtype=torch.float32, device=dev)
+        state_c = torch.empty(N.lib.ru3d_cldice_state_bytes(), dtype=torch.uint8, device=dev)
+        out_c = torch.empty((), dtype=torch.float32, device=dev)
+        ws = N.workspace(N.lib.ru3d_cldice_workspace_bytes(n * nsel, a, b, z, k), dev)
+        carr = (N.ctypes.c_int * nsel)(*cls)
+        wv = _weight_array(weight_v, c)
+        check(N.lib.ru3d_cldice_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, a, b, z, c,
+                                    N.ctypes.cast(carr, N.ctypes.c_void_p), nsel, k,
+                                    N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None, float(smooth),
+                                    ptr(delta), ptr(s), ptr(emin), ptr(dmax), ptr(skel_g), ptr(state_c), ptr(out_c),
+                                    ptr(ws), ws.numel(), stream()), "cldice_fwd")
+        if not check_labels:
+            _note_label_flag(state_c if state_h is None else state_h)
+        saved = [x, lab, delta, s, emin, dmax, skel_g, state_c]
+        if state_h is not None:
+            saved.append(state_h)
+        ctx.save_for_backward(*saved)
+        ctx.meta = (st, lab_code, n, v, c, cls, k, lam, None if hyb is None else float(hyb[0]), input.dtype)
+        if state_h is None:
+            return out_c
+        return out_h * (1.0 - lam) + out_c * lam
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, lab, delta, s, emin, dmax, skel_g, state_c = ctx.saved_tensors[:8]
+        st, lab_code, n, v, c, cls, k, lam, gamma, in_dtype = ctx.meta
+        g = gout.detach()
+        if g.dtype != torch.float32 or g.device != x.device:
+            g = g.to(device=x.device, dtype=torch.float32)
+        g = g.reshape(1).contiguous()
+        dev = x.device
+        N.note_device(dev)
+        a, b, z = x.shape[2:]
+        dz = torch.empty_like(x)
+        if dz.stride() != x.stride():
+            dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=dev)
+        scale, accumulate = 1.0, 0
+        if gamma is not None:
+            state_h = ctx.saved_tensors[8]
+            gh = g * (1.0 - lam)
+            check(N.lib.ru3d_loss_bwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, gamma, ptr(state_h),
+                                      ptr(gh), ptr(dz), N.F32, stream()), "loss_bwd")
+            scale, accumulate = lam, 1
+        nsel = len(cls)
+        ws = N.workspace(N.lib.ru3d_cldice_workspace_bytes(n * nsel, a, b, z, k), dev)
+        carr = (N.ctypes.c_int * nsel)(*cls)
+        check(N.lib.ru3d_cldice_bwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, a, b, z, c,
+                                    N.ctypes.cast(carr, N.ctypes.c_void_p), nsel, k, ptr(delta), ptr(s), ptr(emin),
+                                    ptr(dmax), ptr(skel_g), ptr(state_c), ptr(g), scale, accumulate, ptr(dz), ptr(ws),
+                                    ws.numel(), stream()), "cldice_bwd")
+        if in_dtype != torch.float32:
+            dz = dz.to(in_dtype)
+        return dz, None, None, None, None, None, None, None, None
+
+
+class SoftClDiceLoss(_FusedLoss):
+    """sum_{c in classes} w_c (1 - clDice_c), clDice_c the harmonic mean of
+    Tprec_c = (sum S_k(P_c) G_c + smooth) / (sum S_k(P_c) + smooth) and
+    Tsens_c = (sum S_k(G_c) P_c + smooth) / (sum S_k(G_c) + smooth), P = softmax(logits), G = one-hot(labels), sums over
+    the batch's samples and voxels jointly; w = weight_v restricted to `classes` (default 1 .. C-1) over the sum of
+    its absolute values.  Host tensors take the torch twin of the definition."""
+
+    def __init__(self, iterations=3, weight_v=None, classes=None, smooth=1.0):
+        super().__init__()
+        self.iterations = _check_iterations(iterations)
+        self.weight_v = weight_v
+        self.classes = classes
+        self.smooth = smooth
+
+    def forward(self, input, target):
+        if not input.is_cuda:
+            _cldice_shape_check(input)
+            return _soft_cldice_host(input, target, self.iterations, self.classes, self.weight_v, self.smooth)
+        return _ClDiceFn.apply(input, target, None, 1.0, self.iterations, self.classes, self.weight_v, self.smooth,
+                               getattr(self, "check_labels", _CHECK_LABELS))
+
+
+class HybirdClDiceLoss(_FusedLoss):
+    """(1 - cl_weight) HybirdLoss(gamma, weight_c, weight_v, alpha, beta, smooth)
+    + cl_weight SoftClDiceLoss(iterations, weight_v, classes, cl_smooth).  cl_weight == 0 is HybirdLoss itself: no
+    clDice kernel is launched; cl_weight == 1 is the clDice term alone: no Hybird kernel is launched.  Device tensors
+    only (host tensors raise, as with the other fused losses; SoftClDiceLoss has the host twin)."""
+    _kind = N.LOSS_HYBIRD
+
+    def __init__(self, cl_weight=0.5, iterations=3, classes=None, cl_smooth=1.0, gamma=2, weight_c=None, weight_v=None,
+                 alpha=0.5, beta=0.5, smooth=1e-7):
+        super().__init__()
+        self.cl_weight = float(cl_weight)
+        self.iterations = _check_iterations(iterations)
+        self.classes = classes
+        self.cl_smooth = cl_smooth
+        self.gamma = gamma
+        self.weight_c = weight_c      # accepted, no effect (reference behaviour)
+        self.weight_v = weight_v
+        self.alpha = alpha
+        self.beta = beta
+        self.smooth = smooth
+
+    def forward(self, input, target):
+        if self.cl_weight == 0.0:
+            return self._call(input, target, self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)
+        hyb = None if self.cl_weight == 1.0 else (self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)
+        return _ClDiceFn.apply(input, target, hyb, self.cl_weight, self.iterations, self.classes, self.weight_v, self.cl_smooth,
+                               getattr(self, "check_labels", _CHECK_LABELS))

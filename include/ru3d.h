@@ -514,6 +514,48 @@ int ru3d_skeleton_overlap(const uint64_t* a, const uint64_t* b, int X, int Y, in
  * elements t, t + 256, .. in order starting from 0, then seven halving steps s[t] = fl(s[t] + s[t + h]), h = 128 .. 1. */
 int ru3d_skeleton_radius_stats(const double* sq, int64_t n, double* out, void* stream);
 
+/* ------------------------------------------------------------------ soft skeletons, soft-clDice loss */
+/* The soft skeleton of Shit et al. (clDice, CVPR 2021) on float32 volumes x[A][B][Z] (Z fastest), `nvol` of them behind
+ * one another; nothing outside a volume takes part and nothing crosses from one volume into the next.
+ *   E(x)[v] = min over v and its face neighbours inside the volume; D(x)[v] = max over the 3x3x3 block inside the volume;
+ *   x_0 = x, x_{j+1} = E(x_j), d_j = relu(x_j - D(x_{j+1})), s_0 = d_0, s_j = s_{j-1} + relu(d_j - s_{j-1} d_j), j <= k.
+ *   relu' is 0 at 0.  A minimum / maximum hands its gradient to ONE voxel of its window: among equal candidates the one
+ *   with the lowest linear index (a B + b) Z + z.  Candidate order of E: (a-1), (b-1), (z-1), centre, (z+1), (b+1), (a+1);
+ *   of D: the 27 offsets in ascending (da, db, dz).
+ * A "plane" is nvol * A * B * Z elements.  The forward fills, for j = 0 .. k (k = iterations, 0 .. 64), plane j of
+ *   delta (float32: d_j), s (float32: s_j; the result is plane k), emin (uint8: which candidate of E gave x_{j+1}) and
+ *   dmax (uint8: which candidate of D was taken for d_j); the backward reads exactly these, never x.
+ * Everything is stream-ordered, allocates nothing, takes no atomics (two runs give the same bits) and may be captured.
+ * Workspace for both directions and for the loss: ru3d_cldice_workspace_bytes(nvol, ...), nvol = N * selected classes. */
+size_t ru3d_cldice_workspace_bytes(int nvol, int A, int B, int Z, int iterations);
+int ru3d_soft_skeleton_fwd(const float* x, int nvol, int A, int B, int Z, int iterations, float* delta, float* s,
+                           uint8_t* emin, uint8_t* dmax, void* ws, size_t ws_bytes, void* stream);
+/* grad_x (one plane, distinct from the workspace) = d<grad_out, s_k>/dx. */
+int ru3d_soft_skeleton_bwd(const float* grad_out, int nvol, int A, int B, int Z, int iterations, const float* delta,
+                           const float* s, const uint8_t* emin, const uint8_t* dmax, float* grad_x, void* ws,
+                           size_t ws_bytes, void* stream);
+/* Soft-clDice loss.  P = softmax(logits) in float32 (logits addressed as in ru3d_loss_fwd, C = num_classes >= 2),
+ * G = one-hot(labels); `classes` (HOST array of num_selected distinct class numbers) selects the volumes (n, class);
+ *   Tprec_c = (sum S_k(P_c) G_c + eps) / (sum S_k(P_c) + eps), Tsens_c = (sum S_k(G_c) P_c + eps) / (sum S_k(G_c) + eps),
+ *   loss = sum_c w_c (1 - 2 Tprec_c Tsens_c / (Tprec_c + Tsens_c)), sums over the batch's samples and voxels jointly,
+ *   w = weight_v (HOST array of C floats, NULL: ones) restricted to `classes` over the sum of its absolute values.
+ * delta, s, emin, dmax: as above for nvol = n * num_selected, volume (n, slot) at index n * num_selected + slot;
+ * skel_g: one float32 plane, receives S_k(G) (no gradient flows through it).  state: ru3d_cldice_state_bytes() bytes;
+ * the count of labels outside [0, C) sits at ru3d_loss_state_bad_labels_offset() as in the fused losses' state (the
+ * loss is NaN then).  loss_out: 1 float32 on the device. */
+size_t ru3d_cldice_state_bytes(void);
+int ru3d_cldice_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
+                    int label_dtype, int n, int A, int B, int Z, int num_classes, const int* classes, int num_selected,
+                    int iterations, const float* weight_v, float smooth, float* delta, float* s, uint8_t* emin,
+                    uint8_t* dmax, float* skel_g, void* state, float* loss_out, void* ws, size_t ws_bytes, void* stream);
+/* dlogits (float32, the logits' strides) = or, with accumulate != 0, += grad_out[0] * scale * dloss/dlogits
+ * (grad_out: device float32 or NULL for 1). */
+int ru3d_cldice_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
+                    int label_dtype, int n, int A, int B, int Z, int num_classes, const int* classes, int num_selected,
+                    int iterations, const float* delta, const float* s, const uint8_t* emin, const uint8_t* dmax,
+                    const float* skel_g, const void* state, const float* grad_out, float scale, int accumulate,
+                    float* dlogits, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ surface meshes */
 /* The anatomy as closed triangle meshes: the faces between a set voxel and an unset one of a packed mask (the
  * "cuberille"), Taubin smoothing on the lattice's own edge graph, area and enclosed volume.  Masks are the packed masks
