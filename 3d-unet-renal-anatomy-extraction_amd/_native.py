@@ -50,6 +50,13 @@ class SpatialParams(ctypes.Structure):
                 ("spacing", ctypes.c_int32 * 3)]
 
 
+class DegradeParams(ctypes.Structure):
+    """struct ru3d_degrade_params"""
+    _fields_ = [("do_noise", ctypes.c_int32), ("do_blur", ctypes.c_int32), ("do_low_res", ctypes.c_int32),
+                ("noise_key", ctypes.c_uint32 * 2), ("reserved", ctypes.c_int32), ("noise_variance", ctypes.c_double),
+                ("blur_sigma", ctypes.c_double), ("low_res_zoom", ctypes.c_double)]
+
+
 class MorphRow(ctypes.Structure):
     """struct ru3d_morph_row"""
     _fields_ = [("dx", ctypes.c_int8), ("dy", ctypes.c_int8), ("zmask", ctypes.c_uint16)]
@@ -84,6 +91,7 @@ CONFUSION_MAX_CLASSES = 32
 ORDER_STATS_MAX_RANKS = 8
 EDT_MAX_AXIS = 4096             # RU3D_EDT_MAX_AXIS: x and y extents of the distance transform
 SPATIAL_MAX_YZ = 2560           # RU3D_SPATIAL_MAX_YZ: (ny + 4) * nz of an elastic lattice
+DEGRADE_MAX_RADIUS = 16         # RU3D_DEGRADE_MAX_RADIUS: taps to either side of the Gaussian blur
 PACK_MAX = 40
 _P = ctypes.POINTER(Tensor)
 _vp, _i, _i64, _f, _sz, _u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t,
@@ -225,6 +233,9 @@ SIGNATURES = {
                                _vp]),
     "ru3d_augment_patch_spatial": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(PatchParams),
                                        ctypes.POINTER(SpatialParams), _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_augment_degrade_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ru3d_augment_degrade": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(DegradeParams), _vp, _sz, _vp, _vp]),
+    "ru3d_augment_intensity": (_i, [_vp, _i64, _vp, _i, ctypes.POINTER(PatchParams), _vp]),
     "ru3d_grad_scale_check": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
     "ru3d_comm_unique_id": (_i, [_vp]),
     "ru3d_comm_init": (_i, [ctypes.POINTER(_vp), _vp, _i, _i, _i]),

@@ -17,6 +17,12 @@ uniform per mirror axis, one uniform per intensity op), so `np.random.seed(s)` r
 about the crop box's centre, the same per-axis zoom, cubic B-spline elastic deformation; geometry and draw order: module
 `spatial`, kernel: spatial_kernel in csrc/augment.hip).  `transform.RandomSpatialCrop` is its numpy twin.  Left at None
 they change nothing: the same draws, the same C calls, the same bits.
+
+`noise`, `blur` and `low_res` add Gaussian noise, Gaussian blur and simulated low resolution between the resampling and
+the intensity chain (semantics, draw order and numpy twins: module `degrade`; kernels: csrc/degrade.hip).  A patch on
+which one of them applies takes three C calls - the resampling with the intensity flags cleared, ru3d_augment_degrade,
+ru3d_augment_intensity on the statistics of the degraded image; a patch on which none applies, and every patch when the
+three keywords are None, takes the one call it always took.
 """
 import ctypes
 
@@ -24,6 +30,7 @@ import numpy as np
 import torch
 
 import _native as N
+import degrade
 import spatial
 from _native import check, ptr, stream
 
@@ -61,7 +68,8 @@ class DeviceCase:
 class DeviceAugment:
     def __init__(self, scale=0.1, crop_size=128, crop_mode="random", crop_margin=0, enforce_label_indices=(),
                  image_pad_cval=0, label_pad_cval=0, mirror_p=(0.5, 0.5, 0.5), contrast=0.1, brightness=0.1,
-                 gamma=0.1, rng=None, rotation=None, elastic_spacing=None, elastic_magnitude=None):
+                 gamma=0.1, rng=None, rotation=None, elastic_spacing=None, elastic_magnitude=None, noise=None, blur=None,
+                 low_res=None):
         """Arguments as the reference classes take them; contrast / brightness / gamma = None switches the op off,
         mirror_p = None the mirror.  rng: an object with numpy's `uniform` / `randint` (default: numpy's global one).
 
@@ -70,7 +78,13 @@ class DeviceAugment:
         elastic_magnitude: (lo, hi) in voxels - every control vector's components are uniform in [-m, m], m uniform in
         [lo, hi]; both or neither.  With any of the three set, the patch is cut *around* the drawn crop box, not equal
         to it: the box gives the centre and the zoom, enforce_label_indices and the label rule's class count test the
-        axis-aligned box, and what the rotated or deformed patch reaches outside the volume reads the pad constants."""
+        axis-aligned box, and what the rotated or deformed patch reaches outside the volume reads the pad constants.
+
+        noise, blur, low_res: None | (p, (lo, hi)) - with probability p per patch, Gaussian noise of a variance uniform
+        in [lo, hi], a Gaussian blur of a sigma (voxels, one for the three axes) uniform in [lo, hi], a round trip through
+        a grid of zoom uniform in [lo, hi] (0 < lo <= hi <= 1) voxels per voxel.  The usual recipe is noise
+        (0.1, (0, 0.1)), blur (0.2, (0.5, 1.0)), low_res (0.25, (0.5, 1.0)).  The blur reaches int(4 sigma + 0.5) voxels
+        to either side: at most 16 and at most the smallest patch extent."""
         assert crop_mode in ("center", "random"), "crop mode must be either center or random"
         self.scale = _range(scale)
         self.crop_size = crop_size
@@ -86,6 +100,10 @@ class DeviceAugment:
         self.rotation = spatial.check_rotation(rotation)
         self.elastic = spatial.check_elastic(elastic_spacing, elastic_magnitude, self._patch())
         self.spatial = self.rotation is not None or self.elastic is not None
+        self.noise = degrade.check_noise(noise)
+        self.blur = degrade.check_blur(blur, self._patch())
+        self.low_res = degrade.check_low_res(low_res, self._patch())
+        self.degrade = self.noise is not None or self.blur is not None or self.low_res is not None
 
     def _patch(self):
         return [self.crop_size] * 3 if not isinstance(self.crop_size, (list, tuple, np.ndarray)) \
@@ -121,7 +139,8 @@ class DeviceAugment:
 
     def _draw(self, case):
         """Every host draw of one patch, in order (the presence kernel runs here: the enforce loop needs its answer) ->
-        (PatchParams, presence mask, None | (SpatialParams, phi))."""
+        (PatchParams, presence mask, None | (SpatialParams, phi)), and with noise / blur / low_res configured a fourth
+        entry: None | DegradeParams of the ops that apply to this patch."""
         shape = case.shape
         patch = self._patch()
         margin = [self.crop_margin] * 3 if not isinstance(self.crop_margin, (list, tuple, np.ndarray)) \
@@ -160,14 +179,18 @@ class DeviceAugment:
             pr.lo[i], pr.before[i], pr.patch[i], pr.flip[i] = lo[i], before[i], patch[i], flips[i]
         pr.image_cval, pr.label_cval = self.image_pad_cval, self.label_pad_cval
         pr.gamma_eps = 1e-7
+        ops = degrade.draw(self.rng, self.noise, self.blur, self.low_res) if self.degrade else {}
         for name, rng_ in (("contrast", self.contrast), ("brightness", self.brightness), ("gamma", self.gamma)):
             if rng_ is not None:
                 setattr(pr, "do_" + name, 1)
                 setattr(pr, name, float(self.rng.uniform(rng_[0], rng_[1])))
+        if self.degrade:
+            return pr, mask, geometry, degrade.params(ops) if ops else None
         return pr, mask, geometry
 
     def _launch(self, case, drawn, lattice, out_image, out_label):
-        pr, mask, geometry = drawn
+        pr, mask, geometry = drawn[:3]
+        dg = drawn[3] if len(drawn) > 3 else None
         shape, patch, dev = case.shape, list(pr.patch), case.image.device
         c = shape[3]
         if out_image is None:
@@ -176,7 +199,14 @@ class DeviceAugment:
             out_label = torch.empty(tuple(patch), dtype=torch.int64, device=dev)
         if not out_image.is_contiguous() or (out_label is not None and not out_label.is_contiguous()):
             raise N.Ru3dError("DeviceAugment: output slices must be contiguous")
-        ws = N.workspace(N.lib.ru3d_augment_workspace_bytes(*patch), dev)
+        full = pr
+        if dg is not None:
+            # the resampling without its intensity chain; the chain follows the degrade call on fresh statistics
+            ws, tail = degrade.workspace(c, patch, dev)
+            pr = N.PatchParams.from_buffer_copy(full)
+            pr.do_contrast = pr.do_brightness = pr.do_gamma = 0
+        else:
+            ws = N.workspace(N.lib.ru3d_augment_workspace_bytes(*patch), dev)
         lab = case.label
         code = N.LABEL_I64 if (lab is None or lab.dtype == torch.int64) else N.LABEL_U8
         N.note_device(dev)
@@ -186,10 +216,16 @@ class DeviceAugment:
                                                    ptr(mask) if lab is not None else None, ptr(out_image),
                                                    ptr(out_label), ptr(ws), ws.numel(), stream()),
                   "augment_patch_spatial")
-            return out_image, out_label
-        check(N.lib.ru3d_augment_patch(ptr(case.image), ptr(lab), code, shape[0], shape[1], shape[2], c,
-                                       ctypes.byref(pr), ptr(mask) if lab is not None else None, ptr(out_image),
-                                       ptr(out_label), ptr(ws), ws.numel(), stream()), "augment_patch")
+        else:
+            check(N.lib.ru3d_augment_patch(ptr(case.image), ptr(lab), code, shape[0], shape[1], shape[2], c,
+                                           ctypes.byref(pr), ptr(mask) if lab is not None else None, ptr(out_image),
+                                           ptr(out_label), ptr(ws), ws.numel(), stream()), "augment_patch")
+        if dg is not None:
+            total = patch[0] * patch[1] * patch[2]
+            degrade.launch(out_image, dg, ws, tail)
+            if full.do_contrast or full.do_brightness or full.do_gamma:
+                check(N.lib.ru3d_augment_intensity(ptr(out_image), c * total, ptr(ws), (total + 255) // 256,
+                                                   ctypes.byref(full), stream()), "augment_intensity")
         return out_image, out_label
 
     def __call__(self, case):

@@ -574,3 +574,11 @@ extern "C" int ru3d_augment_patch_spatial(const float* image, const void* label,
     if (rc) return rc;
     return launch_intensity(image != nullptr, p, out_image, total * C, part, (int)blocks, stream);
 }
+
+extern "C" int ru3d_augment_intensity(float* image, int64_t count, const double* part, int nparts,
+                                      const ru3d_patch_params* p, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(image && part && p, "augment_intensity: bad argument");
+    RU3D_REQUIRE(count > 0 && nparts > 0, "augment_intensity: empty image or no partials");
+    return launch_intensity(true, p, image, count, part, nparts, stream);
+}

@@ -16,6 +16,7 @@ import scipy.ndimage as ndi
 import torch
 
 from augment import DeviceAugment, DeviceCase  # noqa: F401  (the on-device replacement of the Random* chain)
+import degrade
 import spatial
 from spatial import bspline_displacement, resample_at, rotation_matrix, spatial_coordinates  # noqa: F401
 
@@ -549,6 +550,42 @@ def adjust_gamma(input, gamma, epsilon=1e-7):
     return (np.power((input - low) / span, gamma) * span + low).astype(input.dtype)
 
 
+# ------------------------------------------------------------------ noise, blur, low resolution (module degrade)
+def _degrade(image, ops):
+    """channels-last image [X, Y, Z, C] (or one volume [X, Y, Z]): numpy in -> the numpy twins of module degrade, float32
+    numpy out; HIP tensor in -> the kernels of csrc/degrade.hip, a new fp32 HIP tensor out."""
+    if torch.is_tensor(image):
+        return degrade.apply_device(image, ops)
+    image = np.asarray(image)
+    if image.ndim == 3:
+        return degrade.apply_numpy(image[None], ops)[0]
+    return np.ascontiguousarray(to_numpy(degrade.apply_numpy(np.ascontiguousarray(to_tensor(image)), ops)))
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 of 32-bit counter words [..., 4] under key (k0, k1) -> uint32 [..., 4]."""
+    return degrade.philox4x32(counter, key)
+
+
+def gaussian_noise(image, variance, key):
+    """image + sqrt(variance) * n, n standard normals from Philox4x32-10 under key (k0, k1) and Box-Muller in float64:
+    the voxel with linear index i over [C][x][y][z] takes normal i & 3 of the call with counter (i >> 2, 0, 0, 0)."""
+    return _degrade(image, {"noise": (float(variance), (int(key[0]), int(key[1])))})
+
+
+def gaussian_blur(image, sigma):
+    """scipy.ndimage.gaussian_filter(channel, sigma) with scipy's defaults (mode='reflect', truncate=4) on every channel:
+    passes along x, y, z accumulated in float64 and stored as float32.  The radius int(4 sigma + 0.5) may be at most 16
+    and at most the smallest extent."""
+    return _degrade(image, {"blur": float(sigma)})
+
+
+def simulate_low_resolution(image, zoom):
+    """Every channel nearest-neighbour down to the grid max(round(P * zoom), 2) and order 1 back up to P:
+    resize(resize(x, n, order=0), P, order=1), as one gather in float64 rounded to float32 once.  0 < zoom <= 1."""
+    return _degrade(image, {"low_res": float(zoom)})
+
+
 # ------------------------------------------------------------------ transform classes
 class _ImageFactor(object):
     """One uniform draw from a range, applied to case['image'] (RandomContrast / Brightness / Gamma: :196-259)."""
@@ -577,6 +614,35 @@ class RandomGamma(_ImageFactor):
     def __init__(self, gamma_range):
         super().__init__(gamma_range)
         self.gamma_range = self.factor_range
+
+
+class _RandomDegrade(object):
+    """With probability p, one of the three ops of module degrade on case['image'] with a parameter drawn from `range`:
+    the draws of DeviceAugment(noise= / blur= / low_res=(p, range)), from numpy's global generator."""
+    name = None
+
+    def __init__(self, p, range):
+        check = {"noise": degrade.check_noise, "blur": degrade.check_blur, "low_res": degrade.check_low_res}[self.name]
+        self.p, self.range = check((p, range))
+
+    def __call__(self, case):
+        ops = degrade.draw(np.random, **{k: (self.p, self.range) if k == self.name else None
+                                         for k in ("noise", "blur", "low_res")})
+        if ops:
+            case['image'] = _degrade(case['image'], ops)
+        return case
+
+
+class RandomGaussianNoise(_RandomDegrade):
+    name = "noise"
+
+
+class RandomGaussianBlur(_RandomDegrade):
+    name = "blur"
+
+
+class RandomLowResolution(_RandomDegrade):
+    name = "low_res"
 
 
 class RandomMirror(object):

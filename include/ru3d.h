@@ -755,6 +755,52 @@ int ru3d_augment_patch_spatial(const float* image, const void* label, int label_
                                const uint32_t* presence_mask, float* out_image, int64_t* out_label, void* ws,
                                size_t ws_bytes, void* stream);
 
+/* Image-quality augmentation of a sampled patch, between the resampling above and the intensity chain: Gaussian noise,
+ * Gaussian blur, simulated low resolution, in that order, each on the image only and on all C channels of the patch
+ * image[C][px][py][pz] (fp32, in place) with one parameter set.  The HOST draws the parameters; the kernels are
+ * deterministic and restate the numpy twins of degrade.py.
+ *
+ *   noise    Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) with key
+ *            noise_key and counter (j, 0, 0, 0) gives x0..x3; in float64 u_a = (x0 + 0.5) * 2^-32, u_b = (x1 + 0.5) * 2^-32,
+ *            n0 = sqrt(-2 ln u_a) cos(2 pi u_b), n1 = sqrt(-2 ln u_a) sin(2 pi u_b), n2 / n3 from x2 / x3 alike.  The voxel
+ *            with linear index i over [C][px][py][pz] takes normal i & 3 of call j = i >> 2:
+ *            out = float32(float64(x) + sqrt(noise_variance) * n), one rounding.
+ *   blur     scipy.ndimage.gaussian_filter(x, blur_sigma) with its defaults (mode 'reflect': ... b a | a b ..., truncate 4),
+ *            one sigma for the three axes: radius r = int(4 sigma + 0.5), weights exp(-t^2 / 2 sigma^2) normalised in
+ *            float64, passes along x, then y, then z, each accumulated in float64 (the centre, then the pairs of taps from
+ *            the outermost inwards) and stored as float32.  r > RU3D_DEGRADE_MAX_RADIUS and r > min(px, py, pz) (a
+ *            single reflection would not suffice) are refused.
+ *   low-res  nearest-neighbour down to the grid n_d = max(round-half-even(P_d * low_res_zoom), 2), order 1 back up to P,
+ *            scipy.ndimage.zoom's corner-aligned coordinates: output voxel o reads low-grid coordinate
+ *            t = o * ((n - 1) / (P - 1)) (the ratio formed once in float64), low-grid voxel l is source voxel
+ *            floor(l * ((P - 1) / (n - 1)) + 0.5); the 8 sources are weighted in float64 (value times the x, y and z
+ *            weight in turn, summed with the last axis fastest) and rounded to float32 once.  0 < zoom <= 1, P_d >= 2;
+ *            zoom 1 returns the input bits.  One fused gather: no low-resolution volume is materialised.
+ *
+ * The call ends by writing the per-block {sum, min, max} partials of the FINAL image to `part`
+ * ((px * py * pz + 255) / 256 triples of doubles, block b = voxels 256 b .. 256 b + 255 of every channel, summed in a
+ * fixed order): the layout ru3d_augment_patch leaves in its workspace, so that ru3d_augment_intensity describes the
+ * degraded image.  With no op switched on only the partials are written.  `ws` (device,
+ * ru3d_augment_degrade_workspace_bytes) holds the ping-pong image and the low-res tables and must not overlap `part`. */
+#define RU3D_DEGRADE_MAX_RADIUS 16
+typedef struct ru3d_degrade_params {
+    int32_t do_noise, do_blur, do_low_res;
+    uint32_t noise_key[2]; /* Philox key (k0, k1)                                                                   */
+    int32_t reserved;
+    double noise_variance; /* >= 0                                                                                   */
+    double blur_sigma;     /* > 0, in voxels                                                                         */
+    double low_res_zoom;   /* in (0, 1]                                                                              */
+} ru3d_degrade_params;
+size_t ru3d_augment_degrade_workspace_bytes(int C, int px, int py, int pz);
+int ru3d_augment_degrade(float* image /* [C][px][py][pz], in place */, int C, int px, int py, int pz,
+                         const ru3d_degrade_params* p, void* ws, size_t ws_bytes, double* part, void* stream);
+/* The intensity chain of ru3d_augment_patch on its own: contrast about the mean, brightness about the minimum, gamma on
+ * the [min, max] range of image[count] (fp32, in place), the statistics taken from `nparts` {sum, min, max} triples (what
+ * ru3d_augment_patch / _spatial leave at the start of their workspace, or ru3d_augment_degrade in `part`).  Reads the
+ * do_* flags, factors and gamma_eps of p; nothing is launched when no flag is set. */
+int ru3d_augment_intensity(float* image, int64_t count, const double* part, int nparts, const ru3d_patch_params* p,
+                           void* stream);
+
 /* ------------------------------------------------------------------ optimizer --------------- */
 /* torch.optim.Adam step (nb_train_iia.py:18 defaults), fused over one flat fp32 parameter run.
  * grad may be bf16/f32 (grad_dtype); bias corrections are passed in by the host. */

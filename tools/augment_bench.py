@@ -1,5 +1,6 @@
-"""Throughput of the on-device patch sampling / augmentation (GPU box): python tools/augment_bench.py [--spatial]
-(--spatial adds a row for the same batch with rotation and elastic deformation switched on)."""
+"""Throughput of the on-device patch sampling / augmentation (GPU box): python tools/augment_bench.py [--spatial] [--degrade]
+(--spatial adds a row for the same batch with rotation and elastic deformation switched on, --degrade one with Gaussian
+noise, Gaussian blur and simulated low resolution forced on for every patch)."""
 import os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,3 +38,8 @@ if "--spatial" in sys.argv[1:]:
                                   rotation=((-0.1 * np.pi, 0.1 * np.pi), (0, 0), (0, 0)), elastic_spacing=16,
                                   elastic_magnitude=(0, 8)),
             "rotation + rescale + elastic g=16 + mirror + contrast + brightness + gamma")
+if "--degrade" in sys.argv[1:]:
+    # the same batch with the three image-quality ops on every patch (p = 1), at the usual recipe's parameter ranges
+    measure(augment.DeviceAugment(scale=0.1, crop_size=128, crop_mode="random", noise=(1.0, (0, 0.1)),
+                                  blur=(1.0, (0.5, 1.0)), low_res=(1.0, (0.5, 1.0))),
+            "rescale-crop + mirror + noise + blur + low-res + contrast + brightness + gamma")
