@@ -91,6 +91,7 @@ CONFUSION_MAX_CLASSES = 32
 ORDER_STATS_MAX_RANKS = 8
 EDT_MAX_AXIS = 4096             # RU3D_EDT_MAX_AXIS: x and y extents of the distance transform
 SPATIAL_MAX_YZ = 2560           # RU3D_SPATIAL_MAX_YZ: (ny + 4) * nz of an elastic lattice
+BOUNDARY_MAX_AXIS = 2048        # RU3D_BOUNDARY_MAX_AXIS: every extent of a patch of the signed distance maps
 DEGRADE_MAX_RADIUS = 16         # RU3D_DEGRADE_MAX_RADIUS: taps to either side of the Gaussian blur
 PACK_MAX = 40
 _P = ctypes.POINTER(Tensor)
@@ -211,6 +212,12 @@ SIGNATURES = {
                              _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_cldice_bwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _f, _i, _vp, _vp, _sz, _vp]),
+    "ru3d_boundary_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ru3d_boundary_state_bytes": (_sz, []),
+    "ru3d_signed_distance": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_boundary_fwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                               _sz, _vp]),
+    "ru3d_boundary_bwd": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "ru3d_mesh_workspace_bytes": (_sz, [_i, _i, _i]),
     "ru3d_mesh_count": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ru3d_mesh_emit": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),

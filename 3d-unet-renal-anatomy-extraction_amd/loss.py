@@ -581,3 +581,253 @@ class HybirdClDiceLoss(_FusedLoss):
         hyb = None if self.cl_weight == 1.0 else (self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)
         return _ClDiceFn.apply(input, target, hyb, self.cl_weight, self.iterations, self.classes, self.weight_v, self.cl_smooth,
                                getattr(self, "check_labels", _CHECK_LABELS))
+
+
+# --------------------------------------------------------------------------- signed distance maps, boundary loss
+# The boundary loss of Kervadec et al. (MIDL 2019): the mean of softmax probability x signed distance to the boundary of the
+# ground truth.  The maps are made from the label patch as it is - after DeviceAugment cut, zoomed, warped and mirrored
+# it - on the device, every step.  For sample n, class q, G = {label == q}:
+#   v outside G: d2 = min over u in G of |v - u|^2, phi = +sqrt(d2);  v inside G: d2 = min over u outside G, phi = -(sqrt(d2) - 1)
+#   (a foreground voxel on the boundary has phi = 0);  G empty or the whole volume of that sample: phi = 0, d2 = 0 there -
+#   an absent class gives no loss and no gradient.  Distances are in voxels (unit spacing: there is no `sampling`
+#   argument), nothing outside the patch exists, the patch faces are no boundary, a label outside [0, C) matches no class.
+def _boundary_classes(classes, c):
+    cls = tuple(range(1, c)) if classes is None else tuple(int(q) for q in classes)
+    if not cls or len(set(cls)) != len(cls) or min(cls) < 0 or max(cls) >= c:
+        raise N.Ru3dError("boundary: classes %s must be distinct class numbers of 0 .. %d" % (cls, c - 1))
+    return cls
+
+
+def _boundary_shape_check(input):
+    if input.dim() != 5:
+        raise N.Ru3dError("boundary: input must be (N, C, A, B, Z) - three spatial dimensions - not %s"
+                          % (tuple(input.shape),))
+    if input.shape[1] < 2:
+        raise N.Ru3dError("boundary: C == 1 is not supported (softmax over at least two classes)")
+
+
+def _signed_squares_host(target, cls):
+    """The written definition on a host tensor: int32 (N, K, A, B, Z), +d2 outside, -d2 inside, 0 where degenerate."""
+    import numpy as np
+    import scipy.ndimage as ndi
+    lab = target.detach().cpu().numpy()
+    out = np.zeros((lab.shape[0], len(cls)) + lab.shape[1:], dtype=np.int32)
+    for n in range(lab.shape[0]):
+        for k, q in enumerate(cls):
+            g = lab[n] == q
+            if not g.any() or g.all():
+                continue
+            # the transform is exact, so the square of the float64 distance it returns rounds to the integer it came from
+            outside = np.rint(ndi.distance_transform_edt(~g) ** 2).astype(np.int32)
+            inside = np.rint(ndi.distance_transform_edt(g) ** 2).astype(np.int32)
+            out[n, k] = np.where(g, -inside, outside)
+    return torch.from_numpy(out)
+
+
+def _phi_of_squares(d2):
+    """float32(sqrt(float64(d2))) outside, minus (that - 1) in float32 inside."""
+    root = d2.abs().double().sqrt().float()
+    return torch.where(d2 < 0, -(root - 1.0), root)
+
+
+def signed_distance_map(target, num_classes, classes=None, squared=False):
+    """(N, A, B, Z) integer labels -> (N, len(classes), A, B, Z) float32 signed distance maps phi as defined above, slot
+    order following `classes` (default 1 .. num_classes - 1); squared=True gives the int32 signed squares instead: +d2
+    outside, -d2 inside, 0 for a degenerate volume.  Unit spacing only: anisotropic `sampling` is not supported.  HIP
+    tensors go through the kernels (all maps in one launch sequence, no host synchronisation); host tensors go through
+    the numpy twin built on scipy.ndimage.distance_transform_edt - the definition written down."""
+    if target.dim() != 4 or target.is_floating_point() or target.is_complex() or target.dtype == torch.bool:
+        raise N.Ru3dError("signed_distance_map: target must be (N, A, B, Z) integer labels, not %s %s"
+                          % (target.dtype, tuple(target.shape)))
+    c = int(num_classes)
+    if c < 2 or c > N.MAX_CLASSES:
+        raise N.Ru3dError("signed_distance_map: %d classes (2 .. %d)" % (c, N.MAX_CLASSES))
+    cls = _boundary_classes(classes, c)
+    if not target.is_cuda:
+        d2 = _signed_squares_host(target, cls)
+        return d2 if squared else _phi_of_squares(d2)
+    N.require_device(target, "signed_distance_map target")
+    if target.dtype in (torch.int64, torch.uint8):
+        lab = target.contiguous()
+    else:
+        lab = target.long().contiguous()
+    lab_code = N.LABEL_I64 if lab.dtype == torch.int64 else N.LABEL_U8
+    n, a, b, z = lab.shape
+    dev = lab.device
+    nsel = len(cls)
+    out = torch.empty((n, nsel, a, b, z), dtype=torch.int32 if squared else torch.float32, device=dev)
+    need = N.lib.ru3d_boundary_workspace_bytes(n * nsel, a, b, z)
+    ws = N.workspace(max(need, 1), dev)
+    carr = (N.ctypes.c_int * nsel)(*cls)
+    check(N.lib.ru3d_signed_distance(ptr(lab), lab_code, n, a, b, z, c, N.ctypes.cast(carr, N.ctypes.c_void_p), nsel,
+                                     ptr(out) if squared else None, None if squared else ptr(out), ptr(ws),
+                                     ws.numel() if need else 0, stream()), "signed_distance")
+    return out
+
+
+def _boundary_weights(weight_v, cls, c, dtype):
+    if weight_v is not None and len(weight_v) != c:
+        raise RuntimeError("weight_v has %d entries for %d classes" % (len(weight_v), c))
+    w = torch.tensor([1.0 if weight_v is None else float(weight_v[q]) for q in cls], dtype=dtype)
+    return w / w.abs().sum().clamp_min(1e-12)
+
+
+def _boundary_host(input, target, classes, weight_v):
+    """The definition on host tensors, in the logits' dtype (what the device path is tested against)."""
+    c = input.shape[1]
+    cls = _boundary_classes(classes, c)
+    w = _boundary_weights(weight_v, cls, c, input.dtype)
+    if tuple(target.shape) != (input.shape[0],) + tuple(input.shape[2:]):
+        raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape), tuple(input.shape)))
+    p = torch.softmax(input, dim=1)[:, list(cls)]
+    phi = signed_distance_map(target.long(), c, cls).to(input.dtype)
+    return (w * (p * phi).sum((0, 2, 3, 4))).sum() / (input.shape[0] * input[0, 0].numel())
+
+
+class _BoundaryFn(torch.autograd.Function):
+    """(1 - a) Hybird + a boundary in one node (hyb = (gamma, weight_v, alpha, beta, smooth), `a` a one-element float32
+    device tensor read by device ops only, so a captured step follows it), or the boundary term alone (hyb None): the
+    boundary backward adds into the gradient the Hybird backward wrote."""
+
+    @staticmethod
+    def forward(ctx, input, target, hyb, a, classes, weight_v, check_labels):
+        _boundary_shape_check(input)
+        x, st, lab, lab_code, n, c, v = _loss_operands(input, target, check_labels)
+        cls = _boundary_classes(classes, c)
+        raise_on_bad_labels()
+        dev = x.device
+        sa, sb, sz = x.shape[2:]
+        nsel = len(cls)
+        saved = [x, lab]
+        if hyb is not None:
+            gamma, hyb_weight, alpha, beta, hyb_smooth = hyb
+            state_h = torch.empty(N.lib.ru3d_loss_state_bytes(c), dtype=torch.uint8, device=dev)
+            out_h = torch.empty((), dtype=torch.float32, device=dev)
+            ws = N.workspace(N.lib.ru3d_loss_workspace_bytes(n, v, c), dev)
+            wh = _weight_array(hyb_weight, c)
+            check(N.lib.ru3d_loss_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, N.LOSS_HYBIRD,
+                                      float(gamma), N.ctypes.cast(wh, N.ctypes.c_void_p) if wh is not None else None,
+                                      float(alpha), float(beta), float(hyb_smooth), ptr(state_h), ptr(out_h), ptr(ws),
+                                      ws.numel(), stream()), "loss_fwd")
+        phi = torch.empty(n * nsel * v, dtype=torch.float32, device=dev)
+        state_b = torch.empty(N.lib.ru3d_boundary_state_bytes(), dtype=torch.uint8, device=dev)
+        out_b = torch.empty((), dtype=torch.float32, device=dev)
+        need = N.lib.ru3d_boundary_workspace_bytes(n * nsel, sa, sb, sz)
+        ws = N.workspace(max(need, 1), dev)
+        carr = (N.ctypes.c_int * nsel)(*cls)
+        wv = _weight_array(weight_v, c)
+        check(N.lib.ru3d_boundary_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, sa, sb, sz, c,
+                                      N.ctypes.cast(carr, N.ctypes.c_void_p), nsel,
+                                      N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None, ptr(phi),
+                                      ptr(state_b), ptr(out_b), ptr(ws), ws.numel() if need else 0, stream()),
+              "boundary_fwd")
+        if not check_labels:
+            _note_label_flag(state_b if hyb is None else state_h)
+        saved += [phi, state_b]
+        if hyb is not None:
+            a = a.detach().reshape(()).clone()        # the weight of THIS forward, whatever is set before the backward
+            saved += [state_h, a]
+        ctx.save_for_backward(*saved)
+        ctx.meta = (st, lab_code, n, v, c, cls, None if hyb is None else float(hyb[0]), input.dtype)
+        if hyb is None:
+            return out_b
+        return out_h * (1.0 - a) + out_b * a
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, lab, phi, state_b = ctx.saved_tensors[:4]
+        st, lab_code, n, v, c, cls, gamma, in_dtype = ctx.meta
+        g = gout.detach()
+        if g.dtype != torch.float32 or g.device != x.device:
+            g = g.to(device=x.device, dtype=torch.float32)
+        g = g.reshape(1).contiguous()
+        dev = x.device
+        N.note_device(dev)
+        sa, sb, sz = x.shape[2:]
+        dz = torch.empty_like(x)
+        if dz.stride() != x.stride():
+            dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=dev)
+        accumulate = 0
+        if gamma is not None:
+            state_h, a = ctx.saved_tensors[4:6]
+            gh = g * (1.0 - a)
+            g = g * a
+            check(N.lib.ru3d_loss_bwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, gamma, ptr(state_h),
+                                      ptr(gh), ptr(dz), N.F32, stream()), "loss_bwd")
+            accumulate = 1
+        nsel = len(cls)
+        carr = (N.ctypes.c_int * nsel)(*cls)
+        check(N.lib.ru3d_boundary_bwd(ptr(x), st[0], st[1], st[2], n, sa, sb, sz, c,
+                                      N.ctypes.cast(carr, N.ctypes.c_void_p), nsel, ptr(phi), ptr(state_b), ptr(g), 1.0,
+                                      accumulate, ptr(dz), stream()), "boundary_bwd")
+        if in_dtype != torch.float32:
+            dz = dz.to(in_dtype)
+        return dz, None, None, None, None, None, None
+
+
+class BoundaryLoss(_FusedLoss):
+    """sum_{c in classes} w_c / (N V) sum_n sum_v P_c[n, v] phi_c[n, v]: the boundary term alone, P = softmax(logits), phi the
+    signed distance maps of the labels (signed_distance_map; unit spacing; a class absent from a sample, or filling it,
+    contributes nothing there), w = weight_v restricted to `classes` (default 1 .. C-1) over the sum of its absolute
+    values.  The term is not bounded below: it is meant to be mixed into a region loss (HybirdBoundaryLoss).  Host
+    tensors take the torch twin of the definition."""
+
+    def __init__(self, weight_v=None, classes=None):
+        super().__init__()
+        self.weight_v = weight_v
+        self.classes = classes
+
+    def forward(self, input, target):
+        if not input.is_cuda:
+            _boundary_shape_check(input)
+            return _boundary_host(input, target, self.classes, self.weight_v)
+        return _BoundaryFn.apply(input, target, None, None, self.classes, self.weight_v,
+                                 getattr(self, "check_labels", _CHECK_LABELS))
+
+
+class HybirdBoundaryLoss(_FusedLoss):
+    """(1 - a) HybirdLoss(gamma, weight_c, weight_v, alpha, beta, smooth) + a BoundaryLoss(weight_v, classes), one autograd
+    node.  `a` lives in a registered one-element float32 buffer and enters through device ops only, so a captured step
+    (graph.GraphedTrainStep) follows it: set_boundary_weight(value) writes the buffer in place, stream-ordered, and the
+    next replay uses the new value without a recapture - Kervadec's schedule raises it every epoch.  `boundary_weight`
+    is the last value set, kept on the host (no read-back).  Both terms are always launched, whatever `a` is.  Device
+    tensors only (host tensors raise, as with the other fused losses; BoundaryLoss has the host twin)."""
+    _kind = N.LOSS_HYBIRD
+
+    def __init__(self, boundary_weight=0.01, classes=None, gamma=2, weight_c=None, weight_v=None, alpha=0.5, beta=0.5,
+                 smooth=1e-7):
+        super().__init__()
+        self._boundary_weight = float(boundary_weight)
+        self.register_buffer("boundary_weight_buffer", torch.full((1,), self._boundary_weight, dtype=torch.float32))
+        self.classes = classes
+        self.gamma = gamma
+        self.weight_c = weight_c      # accepted, no effect (reference behaviour)
+        self.weight_v = weight_v
+        self.alpha = alpha
+        self.beta = beta
+        self.smooth = smooth
+
+    @property
+    def boundary_weight(self):
+        return self._boundary_weight
+
+    def set_boundary_weight(self, value):
+        """Write the weight into the device buffer in place (a fill on the current stream: ordered in front of the next
+        step or replay, no synchronisation, no recapture)."""
+        self._boundary_weight = float(value)
+        self.boundary_weight_buffer.fill_(self._boundary_weight)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        saved = state_dict.get(prefix + "boundary_weight_buffer")
+        if saved is not None and saved.numel() == 1:
+            self._boundary_weight = float(saved)      # the checkpoint's tensor, not the device buffer
+
+    def forward(self, input, target):
+        N.require_device(input, "loss input")
+        if self.boundary_weight_buffer.device != input.device:
+            # first call (an eager one: a captured step is warmed up first): the buffer follows the logits
+            self.boundary_weight_buffer = self.boundary_weight_buffer.to(input.device)
+        hyb = (self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)
+        return _BoundaryFn.apply(input, target, hyb, self.boundary_weight_buffer, self.classes, self.weight_v,
+                                 getattr(self, "check_labels", _CHECK_LABELS))

@@ -556,6 +556,49 @@ int ru3d_cldice_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int
                     const float* skel_g, const void* state, const float* grad_out, float scale, int accumulate,
                     float* dlogits, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ signed distance maps, boundary loss */
+/* The signed distance maps of a label patch labels[n][A][B][Z] (uint8 or int64 as in ru3d_loss_fwd, Z fastest), one per
+ * sample and per selected class, all of them in ONE launch sequence whatever n and num_selected are.  `classes` is a
+ * HOST array of num_selected distinct class numbers of [0, num_classes), 2 <= num_classes <= 8; volume (n, slot) lies at
+ * index n * num_selected + slot of the outputs.  For sample n, class q = classes[slot], G = {u : labels[n][u] == q}:
+ *   v outside G:  d2[v] = min over u in G     of |v - u|^2,  phi[v] = +sqrt(d2[v]),        d2_out[v] = +d2[v]
+ *   v inside G:   d2[v] = min over u not in G of |v - u|^2,  phi[v] = -(sqrt(d2[v]) - 1),  d2_out[v] = -d2[v]
+ *   (a foreground voxel on the boundary has phi = 0);
+ *   G empty, or G the whole volume of that sample: phi = 0 and d2_out = 0 for that (n, slot) - no loss and no gradient
+ *   from an absent class (Kervadec et al., MIDL 2019).  Decided on the device, per (n, slot), never by a host read.
+ * Distances are in voxels: unit spacing on every axis, there is no `sampling` argument.  Nothing outside the patch exists
+ * and the patch faces are not a boundary.  A label outside [0, num_classes) matches no class (it is background of every
+ * selected class).  d2 is an exact integer, computed in int32; phi = float32(sqrt(d2)) correctly rounded and, inside,
+ * the float32 difference to 1 negated.  No extent may exceed RU3D_BOUNDARY_MAX_AXIS (one column of a scanned axis is
+ * held in LDS; 3 (L - 1)^2 stays below 2^24) and A*B*Z < 2^31: ru3d_boundary_workspace_bytes returns 0 and the entry
+ * points an error status beyond that.  d2_out (int32) and phi_out (float32) hold nvol * A*B*Z elements, nvol =
+ * n * num_selected; either may be NULL, not both.  Stream-ordered, allocates nothing, integer atomics only (two runs
+ * give the same bits), may be captured. */
+#define RU3D_BOUNDARY_MAX_AXIS 2048
+size_t ru3d_boundary_workspace_bytes(int nvol, int A, int B, int Z);
+int ru3d_signed_distance(const void* labels, int label_dtype, int n, int A, int B, int Z, int num_classes,
+                         const int* classes, int num_selected, int32_t* d2_out, float* phi_out, void* ws,
+                         size_t ws_bytes, void* stream);
+/* Boundary loss.  P = softmax(logits) in float32 (logits addressed as in ru3d_loss_fwd, C = num_classes >= 2):
+ *   loss = sum_{q in classes} w_q / (n V) sum_n sum_v P_q[n][v] phi_q[n][v],  V = A*B*Z,
+ *   w = weight_v (HOST array of C floats, NULL: ones) restricted to `classes` over the sum of its absolute values.
+ * The forward makes the maps (as above) into phi - a caller-owned buffer of n * num_selected * V float32 - and the
+ * backward reads them: nothing is transformed twice.  The sum is taken in float64 over a partition fixed by the shape
+ * and a fixed tree: the same bits in every run and under every CU budget.  state: ru3d_boundary_state_bytes() bytes; the
+ * count of labels outside [0, C) sits at ru3d_loss_state_bad_labels_offset() as in the fused losses' state (the loss is
+ * NaN then).  loss_out: 1 float32 on the device.  Workspace: ru3d_boundary_workspace_bytes(n * num_selected, ...). */
+size_t ru3d_boundary_state_bytes(void);
+int ru3d_boundary_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
+                      int label_dtype, int n, int A, int B, int Z, int num_classes, const int* classes, int num_selected,
+                      const float* weight_v, float* phi, void* state, float* loss_out, void* ws, size_t ws_bytes,
+                      void* stream);
+/* dlogits_j[n][v] (float32, the logits' strides) = or, with accumulate != 0, +=
+ *   grad_out[0] * scale / (n V) * P_j (w_j phi_j [j in classes] - sum_q w_q P_q phi_q)
+ * (grad_out: device float32 or NULL for 1; phi and state as the forward left them). */
+int ru3d_boundary_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, int n, int A, int B,
+                      int Z, int num_classes, const int* classes, int num_selected, const float* phi, const void* state,
+                      const float* grad_out, float scale, int accumulate, float* dlogits, void* stream);
+
 /* ------------------------------------------------------------------ surface meshes */
 /* The anatomy as closed triangle meshes: the faces between a set voxel and an unset one of a packed mask (the
  * "cuberille"), Taubin smoothing on the lattice's own edge graph, area and enclosed volume.  Masks are the packed masks
