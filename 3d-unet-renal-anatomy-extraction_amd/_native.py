@@ -232,6 +232,16 @@ SIGNATURES = {
     "ru3d_adam_multi_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ru3d_adam_multi_amp": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "ru3d_amp_update": (_i, [_vp, _f, _f, _i, _f, _f, _vp]),
+    "ru3d_grad_sumsq": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "ru3d_grad_norm_finish": (_i, [_vp, _i, _f, _vp, _f, _vp, _vp]),
+    "ru3d_grad_norm": (_i, [_vp, _vp, _i, _i, _vp, _f, _f, _vp, _vp]),
+    "ru3d_grad_scale_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "ru3d_sgd_multi": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _i, _f, _vp, _vp]),
+    "ru3d_sgd_multi_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "ru3d_adamw_multi": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _vp, _vp]),
+    "ru3d_adamw_multi_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "ru3d_adam_multi_clip": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _vp, _vp]),
+    "ru3d_adam_multi_clip_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "ru3d_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "ru3d_augment_workspace_bytes": (_sz, [_i, _i, _i]),
     "ru3d_augment_label_presence": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32),

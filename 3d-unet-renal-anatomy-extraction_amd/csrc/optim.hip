@@ -1,0 +1,354 @@
+// The optimisation recipe around the fused Adam of loss.hip: the global L2 norm of the gradients with the clipping
+// coefficient of torch.nn.utils.clip_grad_norm_, SGD with (Nesterov) momentum and weight decay, AdamW, and Adam with a
+// clipped gradient.  Every kernel walks the ru3d_adam_tensor table through the (tensor, chunk) block map of
+// ru3d_adam_multi: 256 threads, chunk_elems a multiple of 1024, an aligned f32x4 path and a scalar path for tails and
+// for tensors that do not sit on 16-byte boundaries, rows with a null `grad` skipped.
+//
+// Bits: each update rule is ONE per-element function compiled with floating-point contraction off, called from the
+// vector path and from the scalar path, by the kernel that takes its scalars as arguments and by the one that reads
+// them from the 8-float device row of a captured step - the four give identical bits (adam_multi_body's lesson, see
+// loss.hip).  No floating-point atomics: the norm is a float64 sum of float64 squares, thread -> wave butterfly -> the
+// four waves of a block in order -> one workgroup over the per-block partials in order.
+#include "common.h"
+#include <stddef.h>
+
+// --------------------------------------------------------------------------- the table walk
+// rule.first(): the rule keeps a first buffer in `exp_avg` (momentum / first moment); Rule::kSecond: it keeps `exp_avg_sq`
+template <class Rule>
+__device__ __forceinline__ void multi_body(const ru3d_adam_tensor* __restrict__ tensors,
+                                           const int32_t* __restrict__ block_map, int chunk_elems, const Rule rule,
+                                           const float* __restrict__ coef) {
+    const ru3d_adam_tensor t = tensors[block_map[2 * blockIdx.x]];
+    if (!t.grad) return;
+    const bool first = rule.first();
+    if ((first && !t.exp_avg) || (Rule::kSecond && !t.exp_avg_sq)) return;      // a row without its state is left alone
+    const int64_t begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
+    int64_t end = begin + chunk_elems;
+    if (end > t.count) end = t.count;
+    const float c = coef ? *coef : 1.f;          // x * 1.0f is x: the unclipped step needs no second body
+    uintptr_t bits = ((uintptr_t)t.param) | ((uintptr_t)t.grad);
+    if (first) bits |= (uintptr_t)t.exp_avg;
+    if (Rule::kSecond) bits |= (uintptr_t)t.exp_avg_sq;
+    int64_t i = begin + (int64_t)threadIdx.x * 4;
+    if ((bits & 15) == 0) {
+        for (; i + 3 < end; i += 1024) {
+            f32x4 p = *reinterpret_cast<const f32x4*>(t.param + i);
+            const f32x4 g = *reinterpret_cast<const f32x4*>(t.grad + i);
+            f32x4 m = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
+            if (first) m = *reinterpret_cast<const f32x4*>(t.exp_avg + i);
+            if (Rule::kSecond) v = *reinterpret_cast<const f32x4*>(t.exp_avg_sq + i);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                float pk = p[k], mk = m[k], vk = v[k];
+                rule.elem(pk, g[k], c, mk, vk);
+                p[k] = pk; m[k] = mk; v[k] = vk;
+            }
+            *reinterpret_cast<f32x4*>(t.param + i) = p;
+            if (first) *reinterpret_cast<f32x4*>(t.exp_avg + i) = m;
+            if (Rule::kSecond) *reinterpret_cast<f32x4*>(t.exp_avg_sq + i) = v;
+        }
+    }
+    // scalar tail (or unaligned tensors): this thread's remaining elements of its 4-wide slots
+    for (; i < end; i += 1024)
+        for (int k = 0; k < 4 && i + k < end; k++) {
+            float pk = t.param[i + k], mk = first ? t.exp_avg[i + k] : 0.f, vk = Rule::kSecond ? t.exp_avg_sq[i + k] : 0.f;
+            rule.elem(pk, t.grad[i + k], c, mk, vk);
+            t.param[i + k] = pk;
+            if (first) t.exp_avg[i + k] = mk;
+            if (Rule::kSecond) t.exp_avg_sq[i + k] = vk;
+        }
+}
+
+// --------------------------------------------------------------------------- SGD
+// torch.optim.SGD with dampening = 0, maximize = False:  gh = g * gscale * coef;  d = gh + wd * p;
+// b = mu * b + d (mu != 0; a zero buffer makes the first step torch's b = d);  u = nesterov ? d + mu * b : b  (u = d
+// when mu == 0);  p -= lr * u.  The momentum buffer travels in the `exp_avg` slot.
+struct SgdRule {
+    float lr, mu, wd, gscale;
+    bool nesterov;
+    static constexpr bool kSecond = false;
+    __device__ __forceinline__ bool first() const { return mu != 0.f; }
+    __device__ __forceinline__ void elem(float& p, float g, float c, float& b, float&) const {
+#pragma clang fp contract(off)
+        const float gh = g * gscale * c;
+        float d = gh;
+        if (wd != 0.f) d = gh + wd * p;
+        float u = d;
+        if (mu != 0.f) {
+            b = mu * b + d;
+            u = nesterov ? d + mu * b : b;
+        }
+        p -= lr * u;
+    }
+};
+
+// hyper row of a captured SGD step: {lr, momentum, weight_decay, nesterov (0 / 1), -, -, grad_scale, -}
+__device__ __forceinline__ SgdRule sgd_rule(float lr, float mu, float wd, float nesterov, float gscale) {
+    SgdRule r;
+    r.lr = lr; r.mu = mu; r.wd = wd; r.gscale = gscale; r.nesterov = nesterov != 0.f;
+    return r;
+}
+
+__global__ __launch_bounds__(256) void sgd_multi_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                        const int32_t* __restrict__ block_map, int chunk_elems, float lr,
+                                                        float mu, float wd, float nesterov, float gscale,
+                                                        const float* __restrict__ coef) {
+    multi_body(tensors, block_map, chunk_elems, sgd_rule(lr, mu, wd, nesterov, gscale), coef);
+}
+
+__global__ __launch_bounds__(256) void sgd_multi_dev_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                            const int32_t* __restrict__ block_map, int chunk_elems,
+                                                            const float* __restrict__ hyper,
+                                                            const float* __restrict__ coef) {
+    multi_body(tensors, block_map, chunk_elems, sgd_rule(hyper[0], hyper[1], hyper[2], hyper[3], hyper[6]), coef);
+}
+
+// --------------------------------------------------------------------------- Adam (clipped) and AdamW
+// adam_multi_body's recurrence (loss.hip) on gh = g * gscale * coef; kDecay: torch.optim.AdamW's p *= 1 - lr * wd first.
+template <bool kDecay>
+struct AdamRule {
+    float b1, b2, eps, step, bc2_sqrt, gscale, keep;
+    static constexpr bool kSecond = true;
+    __device__ __forceinline__ bool first() const { return true; }
+    __device__ __forceinline__ void elem(float& p, float g, float c, float& m, float& v) const {
+#pragma clang fp contract(off)
+        const float gi = g * gscale * c;
+        if (kDecay) p = p * keep;
+        m = b1 * m + (1.f - b1) * gi;
+        v = b2 * v + (1.f - b2) * gi * gi;
+        p -= step * (m / (sqrtf(v) / bc2_sqrt + eps));
+    }
+};
+
+template <bool kDecay>
+__device__ __forceinline__ AdamRule<kDecay> adam_rule(float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                                                      float gscale, float wd) {
+#pragma clang fp contract(off)
+    AdamRule<kDecay> r;
+    r.b1 = b1; r.b2 = b2; r.eps = eps; r.bc2_sqrt = bc2_sqrt; r.gscale = gscale;
+    r.step = lr / bc1;
+    r.keep = 1.f - lr * wd;
+    return r;
+}
+
+// Adam with a clipped gradient: the scalars of ru3d_adam_multi (sqrt(bias_corr2) taken on the host) / its hyper row
+__global__ __launch_bounds__(256) void adam_clip_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                        const int32_t* __restrict__ block_map, int chunk_elems, float lr,
+                                                        float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                                                        float gscale, const float* __restrict__ coef) {
+    multi_body(tensors, block_map, chunk_elems, adam_rule<false>(lr, b1, b2, eps, bc1, bc2_sqrt, gscale, 0.f), coef);
+}
+
+__global__ __launch_bounds__(256) void adam_clip_dev_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                            const int32_t* __restrict__ block_map, int chunk_elems,
+                                                            const float* __restrict__ hyper,
+                                                            const float* __restrict__ coef) {
+    multi_body(tensors, block_map, chunk_elems,
+               adam_rule<false>(hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[7], hyper[6], 0.f), coef);
+}
+
+// AdamW: hyper row {lr, beta1, beta2, eps, bias_corr1, bias_corr2, grad_scale, weight_decay} - slot 7 carries the decay,
+// so BOTH forms take sqrtf(bias_corr2) here, on the device
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                          const int32_t* __restrict__ block_map, int chunk_elems, float lr,
+                                                          float b1, float b2, float eps, float wd, float bc1, float bc2,
+                                                          float gscale, const float* __restrict__ coef) {
+    multi_body(tensors, block_map, chunk_elems, adam_rule<true>(lr, b1, b2, eps, bc1, sqrtf(bc2), gscale, wd), coef);
+}
+
+__global__ __launch_bounds__(256) void adamw_multi_dev_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                              const int32_t* __restrict__ block_map, int chunk_elems,
+                                                              const float* __restrict__ hyper,
+                                                              const float* __restrict__ coef) {
+    multi_body(tensors, block_map, chunk_elems,
+               adam_rule<true>(hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], sqrtf(hyper[5]), hyper[6], hyper[7]),
+               coef);
+}
+
+// --------------------------------------------------------------------------- gradient norm
+// the sum of a block's 256 doubles in a fixed order: butterfly inside each wave (every lane ends with the same bits),
+// then wave 0 + wave 1 + wave 2 + wave 3
+__device__ __forceinline__ double block_sum_d(double v, double* lds) {
+    v = wave_sum_d(v);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+// pass 1: partials[block] = sum of the float64 squares of the block's chunk (0 for a row without a gradient).  A thread
+// adds its elements in ascending order in both paths, so the alignment of a gradient does not change the sum.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                         const int32_t* __restrict__ block_map, int chunk_elems,
+                                                         double* __restrict__ partials) {
+    __shared__ double lds[4];
+    const ru3d_adam_tensor t = tensors[block_map[2 * blockIdx.x]];
+    double acc = 0.0;
+    if (t.grad) {
+        const float* g = t.grad;
+        const int64_t begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
+        int64_t end = begin + chunk_elems;
+        if (end > t.count) end = t.count;
+        int64_t i = begin + (int64_t)threadIdx.x * 4;
+        if ((((uintptr_t)g) & 15) == 0) {
+            for (; i + 3 < end; i += 1024) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+                for (int k = 0; k < 4; k++) acc += (double)v[k] * (double)v[k];
+            }
+        }
+        for (; i < end; i += 1024)
+            for (int k = 0; k < 4 && i + k < end; k++) acc += (double)g[i + k] * (double)g[i + k];
+    }
+    const double s = block_sum_d(acc, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// pass 2: one workgroup; thread j adds partials[j], [j + 256], ... in that order.  out = {total, coef}:
+// total = (float)(grad_scale * sqrt(sum)), coef = min(1, max_norm / (total + 1e-6f)) with torch.clamp's NaN (it stays).
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partials, int n,
+                                                               float grad_scale, const float* __restrict__ hyper,
+                                                               float max_norm, float* __restrict__ out) {
+    __shared__ double lds[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += partials[i];
+    const double s = block_sum_d(acc, lds);
+    if (threadIdx.x == 0) {
+        const float gs = hyper ? hyper[6] : grad_scale;
+        const float total = (float)((double)gs * sqrt(s));
+        const float c = max_norm / (total + 1e-6f);
+        out[0] = total;
+        out[1] = c > 1.f ? 1.f : c;
+    }
+}
+
+// g *= *coef over every gradient of the table; nothing is written when the coefficient is exactly 1
+__global__ __launch_bounds__(256) void grad_scale_dev_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                             const int32_t* __restrict__ block_map, int chunk_elems,
+                                                             const float* __restrict__ coef) {
+    const ru3d_adam_tensor t = tensors[block_map[2 * blockIdx.x]];
+    if (!t.grad) return;
+    const float c = *coef;
+    if (c == 1.f) return;
+    float* g = const_cast<float*>(t.grad);
+    const int64_t begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
+    int64_t end = begin + chunk_elems;
+    if (end > t.count) end = t.count;
+    int64_t i = begin + (int64_t)threadIdx.x * 4;
+    if ((((uintptr_t)g) & 15) == 0) {
+        for (; i + 3 < end; i += 1024) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] *= c;
+            *reinterpret_cast<f32x4*>(g + i) = v;
+        }
+    }
+    for (; i < end; i += 1024)
+        for (int k = 0; k < 4 && i + k < end; k++) g[i + k] *= c;
+}
+
+// --------------------------------------------------------------------------- entry points
+#define RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) \
+    ((tensors) && (block_map) && (nblocks) > 0 && (chunk_elems) >= 1024 && ((chunk_elems) % 1024) == 0)
+
+extern "C" int ru3d_grad_sumsq(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                               double* partials, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && partials,
+                 "grad_sumsq: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
+                       chunk_elems, partials);
+    return ru3d_check_launch("grad_sumsq");
+}
+
+extern "C" int ru3d_grad_norm_finish(const double* partials, int npartials, float grad_scale, const float* hyper,
+                                     float max_norm, float* out, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(partials && out && npartials > 0 && max_norm >= 0.f, "grad_norm_finish: bad argument");
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, as_stream(stream), partials, npartials,
+                       grad_scale, hyper, max_norm, out);
+    return ru3d_check_launch("grad_norm_finish");
+}
+
+extern "C" int ru3d_grad_norm(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                              double* partials, float grad_scale, float max_norm, float* out, void* stream) {
+    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && partials && out && max_norm >= 0.f,
+                 "grad_norm: bad argument (chunk_elems must be a positive multiple of 1024)");
+    const int rc = ru3d_grad_sumsq(tensors, block_map, nblocks, chunk_elems, partials, stream);
+    if (rc) return rc;
+    return ru3d_grad_norm_finish(partials, nblocks, grad_scale, nullptr, max_norm, out, stream);
+}
+
+extern "C" int ru3d_grad_scale_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                   int chunk_elems, const float* coef, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && coef,
+                 "grad_scale_dev: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(grad_scale_dev_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
+                       block_map, chunk_elems, coef);
+    return ru3d_check_launch("grad_scale_dev");
+}
+
+extern "C" int ru3d_sgd_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                              float lr, float momentum, float weight_decay, int nesterov, float grad_scale,
+                              const float* coef, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && lr >= 0.f && momentum >= 0.f &&
+                     weight_decay >= 0.f && (nesterov == 0 || (nesterov == 1 && momentum > 0.f)),
+                 "sgd_multi: bad argument (chunk_elems must be a positive multiple of 1024; nesterov needs momentum)");
+    hipLaunchKernelGGL(sgd_multi_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
+                       chunk_elems, lr, momentum, weight_decay, nesterov ? 1.f : 0.f, grad_scale, coef);
+    return ru3d_check_launch("sgd_multi");
+}
+
+extern "C" int ru3d_sgd_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                  int chunk_elems, const float* hyper, const float* coef, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && hyper,
+                 "sgd_multi_dev: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(sgd_multi_dev_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
+                       block_map, chunk_elems, hyper, coef);
+    return ru3d_check_launch("sgd_multi_dev");
+}
+
+extern "C" int ru3d_adamw_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                                float lr, float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
+                                float bias_corr2, float grad_scale, const float* coef, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && lr >= 0.f && eps >= 0.f &&
+                     weight_decay >= 0.f && bias_corr1 > 0.f && bias_corr2 > 0.f,
+                 "adamw_multi: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
+                       chunk_elems, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale, coef);
+    return ru3d_check_launch("adamw_multi");
+}
+
+extern "C" int ru3d_adamw_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                    int chunk_elems, const float* hyper, const float* coef, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && hyper,
+                 "adamw_multi_dev: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(adamw_multi_dev_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
+                       block_map, chunk_elems, hyper, coef);
+    return ru3d_check_launch("adamw_multi_dev");
+}
+
+extern "C" int ru3d_adam_multi_clip(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                    int chunk_elems, float lr, float beta1, float beta2, float eps, float bias_corr1,
+                                    float bias_corr2, float grad_scale, const float* coef, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && bias_corr1 > 0.f && bias_corr2 > 0.f,
+                 "adam_multi_clip: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
+                       chunk_elems, lr, beta1, beta2, eps, bias_corr1, sqrtf(bias_corr2), grad_scale, coef);
+    return ru3d_check_launch("adam_multi_clip");
+}
+
+extern "C" int ru3d_adam_multi_clip_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                        int chunk_elems, const float* hyper, const float* coef, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && hyper,
+                 "adam_multi_clip_dev: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(adam_clip_dev_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
+                       block_map, chunk_elems, hyper, coef);
+    return ru3d_check_launch("adam_multi_clip_dev");
+}

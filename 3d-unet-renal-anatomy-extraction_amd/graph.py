@@ -1,4 +1,4 @@
-"""A whole training step - forward, loss, backward, fused Adam - captured ONCE in a hipGraph and replayed.
+"""A whole training step - forward, loss, backward, fused optimizer - captured ONCE in a hipGraph and replayed.
 
 Why: the step is ~550 kernel launches issued from Python through ctypes; on the benchmark configuration the host needs
 18.7 ms to enqueue what the device executes in 19.6 ms (bench.py `host_enqueue_ms_per_step`), so the device idles
@@ -10,14 +10,18 @@ What makes a captured step the SAME computation as the eager one, step after ste
   * the Dropout3d draws take their counter offset from a device scalar (`ru3d_dropout3d_scale_dev`): replay k adds
     k * (draws per step), i.e. it draws exactly the masks eager step k would have drawn, and the host counter is kept
     in step so eager steps can follow;
-  * the fused Adam reads lr, the bias corrections and grad_scale from device memory (`ru3d_adam_multi_dev`); the 28
-    bytes per parameter group are rewritten before each replay, so step counts and LR schedules are honoured;
+  * the fused optimizer (optim.Adam / AdamW / SGD) reads lr, the bias corrections and grad_scale from device memory
+    (`ru3d_adam_multi_dev`, `ru3d_adamw_multi_dev`, `ru3d_sgd_multi_dev`); the 32 bytes per parameter group are rewritten
+    before each replay, so step counts and LR schedules are honoured.  With `max_grad_norm` the two norm launches are
+    nodes of the graph, in sequence on the capture stream, and the update reads the coefficient from device memory;
   * gradients, activations and workspaces live at fixed addresses of the graph's private memory pool.
 tests/test_gpu_graph.py holds the bit-equality of graphed and eager training.
 
 fp16 storage (round 4): the dynamic loss scaler lives on the device while a step is captured (`ru3d_amp_state`: the update
 kernel skips itself on overflow, `ru3d_amp_update` applies apex's schedule), so the reference's own training mode replays
-too.  Not captured (the caller falls back to the eager step): a batch of another shape, the multi-GPU gradient exchange.
+too - with plain optim.Adam only: `ru3d_adam_multi_amp` is the one update kernel that follows the device-side scaler, so
+fp16 with SGD, AdamW or any `max_grad_norm` is refused at construction (the eager fp16 step takes all of them).
+Not captured (the caller falls back to the eager step): a batch of another shape, the multi-GPU gradient exchange.
 
     step = GraphedTrainStep(model, criterion, optimizer)
     for x, y in loader:
@@ -37,9 +41,12 @@ _RING = 8      # pinned host blocks in flight: a replay's scalars stay untouched
 
 class GraphedTrainStep:
     def __init__(self, model, criterion, optimizer, warmup=2, scaler=None):
-        if not isinstance(optimizer, _optim.Adam):
-            raise TypeError("GraphedTrainStep needs optim.Adam (its update kernel reads the per-step scalars from "
-                            "device memory)")
+        if not isinstance(optimizer, _optim._Fused):
+            raise TypeError("GraphedTrainStep needs optim.Adam, optim.AdamW or optim.SGD (their update kernels read the "
+                            "per-step scalars from device memory)")
+        if scaler is not None and not optimizer.captures_with_scaler():
+            raise TypeError("GraphedTrainStep: a captured fp16 step (device-side loss scaler) needs optim.Adam without "
+                            "max_grad_norm; SGD, AdamW and clipped steps run the eager fp16 loop")
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
         self.scaler = scaler         # optim.LossScaler (fp16 storage): its state moves to the device for the capture
         self.warmup = max(1, int(warmup))    # the first Adam step creates the moment buffers
@@ -167,9 +174,7 @@ class GraphedTrainStep:
         self.optimizer.sync_captured_steps()
         if self.scaler is not None and self.scaler._dev is not None:
             self.scaler.end_capture()
-        self.optimizer._captured = None
-        for key in [k for k in self.optimizer._plans if k[1]]:       # (group, captured=True)
-            del self.optimizer._plans[key]
+        self.optimizer.end_capture()                                 # captured plans and norm buffers go too
         if self.graph is not None or hasattr(self, "stream"):        # captured, or a capture that failed half-way
             self.optimizer.zero_grad(set_to_none=True)
             sid = self.stream.cuda_stream

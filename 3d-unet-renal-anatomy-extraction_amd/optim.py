@@ -1,11 +1,21 @@
-"""Fused Adam for the native path: ONE kernel launch updates every parameter tensor of the model.
+"""Fused optimizers for the native path: ONE kernel launch per param group updates every parameter tensor of the model.
 
-Drop-in for `torch.optim.Adam(params, lr=..., betas=..., eps=...)` as the training scripts construct it
+`Adam` is a drop-in for `torch.optim.Adam(params, lr=..., betas=..., eps=...)` as the training scripts construct it
 (reference nb_train_iia.py:18: Adam(model.parameters(), lr=1e-4); weight_decay / amsgrad / maximize are
 not used by the reference and are rejected here).  The update rule and the state_dict layout
 (`state[p] = {'step', 'exp_avg', 'exp_avg_sq'}`) are torch.optim.Adam's, so checkpoints interchange.
 Parameters whose `.grad` is None are skipped, exactly like torch (the never-used skip_conv weights and the
 conv biases in front of InstanceNorm).
+
+`SGD` (momentum, Nesterov, weight decay) and `AdamW` follow torch.optim.SGD / torch.optim.AdamW the same way (csrc/optim.hip),
+and all three take `max_grad_norm`: the global L2 norm of the gradients of ALL param groups is reduced on the device
+in a fixed order (float64, no atomics), torch.nn.utils.clip_grad_norm_'s coefficient stays in device memory, and the
+update kernels multiply it in while they read the gradient - a clipped step reads the gradients once more and writes
+nothing extra.  `optimizer.last_grad_norm` is that step's norm as a 0-dim device tensor; nothing is read back unless the
+caller reads it (it is a view of one persistent block: the next step overwrites it, `.clone()` a value that is kept).  `clip_grad_norm_` is torch's function on its own.  That is the nnU-Net / KiTS19 recipe (the reference
+trains on KiTS19, nb_train_KITS19.py): SGD(momentum=0.99, nesterov=True, weight_decay=3e-5, max_grad_norm=12) under
+torch.optim.lr_scheduler.PolynomialLR.  In data-parallel training every rank holds the same averaged gradients after
+GradSync.finish_step(), so every rank computes the same norm and no collective is added.
 """
 import ctypes
 
@@ -22,15 +32,56 @@ class _AdamTensor(ctypes.Structure):
                 ("exp_avg_sq", ctypes.c_void_p), ("count", ctypes.c_int64)]
 
 
-class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
-        if weight_decay != 0 or amsgrad:
-            raise ValueError("ru3d optim.Adam implements plain Adam (weight_decay=0, amsgrad=False)")
-        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
-            raise ValueError("invalid Adam hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False))
+def _check_max_grad_norm(max_grad_norm):
+    if max_grad_norm is None:
+        return None
+    max_grad_norm = float(max_grad_norm)
+    if not max_grad_norm >= 0.0:
+        raise ValueError("Invalid max_grad_norm: %r" % (max_grad_norm,))
+    return max_grad_norm
+
+
+class _Fused(torch.optim.Optimizer):
+    """What the fused optimizers share: the pinned table + block map of a param group (`_plan`), the step that fills the
+    tables, reduces the gradient norm when `max_grad_norm` is set and issues one update launch per group, and the captured
+    mode of graph.GraphedTrainStep (`begin_capture` / `replay_scalars` / `sync_captured_steps` / `end_capture`).  A
+    subclass supplies its state (`_slots`), its two launches (`_launch`, `_launch_dev`) and its scalar row (`_row`)."""
+    _NAME = "optim"
+    _COUNTS_STEPS = True        # state[p]['step'] exists and the update depends on it
+
+    def __init__(self, params, defaults, max_grad_norm=None):
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        super().__init__(params, defaults)
         self._plans = {}
+        self._clip = {}             # captured? -> {"partials": float64[blocks of all groups], "norm": self._norm}
+        self._norm = None           # device float32[2] = {total, coef}: ONE block for eager and captured steps
         self._captured = None       # graph.GraphedTrainStep: {"hyper": device float32[groups, 8], "steps": [..]}
+        # 0-dim device tensor: the norm max_grad_norm clipped the last step's gradients at.  It is a VIEW of the one
+        # persistent norm block (a captured step cannot hand out a fresh tensor per replay): the next step, eager or
+        # replayed, overwrites it - `.clone()` a value that is to be kept (a list of norms for logging)
+        self.last_grad_norm = None
+
+    # ---- subclass hooks
+    def _slots(self, p, group, capturing):
+        """Create (first step) and return the state tensors of p that travel in (exp_avg, exp_avg_sq); None for none."""
+        raise NotImplementedError
+
+    def _launch(self, plan, group, step_no, grad_scale, coef):
+        raise NotImplementedError
+
+    def _launch_dev(self, plan, hyper_row, coef):
+        raise NotImplementedError
+
+    def _row(self, row, group, step_no, grad_scale):
+        raise NotImplementedError
+
+    def _check_group(self, group):
+        pass
+
+    def captures_with_scaler(self):
+        """A captured fp16 step needs the update kernel that takes its decisions from the device-side loss scaler
+        (ru3d_adam_multi_amp): plain Adam without clipping only."""
+        return False
 
     def _plan(self, gi, group, captured=False):
         """Static part of the launch: block map + pinned host table (built once per param group; a captured step keeps
@@ -44,7 +95,7 @@ class Adam(torch.optim.Optimizer):
         for ti, p in enumerate(params):
             N.require_device(p, "parameter")
             if p.dtype != torch.float32 or not p.is_contiguous():
-                raise N.Ru3dError("optim.Adam: parameters must be contiguous float32")
+                raise N.Ru3dError("optim.%s: parameters must be contiguous float32" % self._NAME)
             for c in range((p.numel() + _CHUNK - 1) // _CHUNK):
                 blocks += [ti, c]
         bm = torch.tensor(blocks, dtype=torch.int32).to(dev)
@@ -53,6 +104,22 @@ class Adam(torch.optim.Optimizer):
         plan = {"n": len(params), "block_map": bm, "nblocks": len(blocks) // 2, "host": host, "table": table}
         self._plans[(gi, captured)] = plan
         return plan
+
+    def _clip_buffers(self, captured=False):
+        """Device memory of the norm: one float64 partial per block of every group, and the {total, coef} block, which
+        eager and captured steps share (last_grad_norm is a view of it, whichever kind of step ran last).  Sized from the
+        plans of all groups as they are NOW: add_param_group or a group that grew gives new partials."""
+        plans = [self._plan(gi, group, captured) for gi, group in enumerate(self.param_groups) if group["params"]]
+        nblocks = sum(pl["nblocks"] for pl in plans)
+        dev = plans[0]["table"].device
+        if self._norm is None or self._norm.device != dev:
+            self._norm = torch.zeros(2, dtype=torch.float32, device=dev)
+        bufs = self._clip.get(captured)
+        if bufs is None or bufs["partials"].numel() != nblocks or bufs["partials"].device != dev:
+            bufs = {"partials": torch.empty(nblocks, dtype=torch.float64, device=dev)}
+            self._clip[captured] = bufs
+        bufs["norm"] = self._norm
+        return bufs
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
@@ -64,13 +131,17 @@ class Adam(torch.optim.Optimizer):
         capturing = self._captured is not None and torch.cuda.is_current_stream_capturing()
         if self._captured is not None and not capturing:
             self.sync_captured_steps()           # an eager step between replays continues their step count
+        clip = self.max_grad_norm is not None
+        bufs = self._clip_buffers(capturing) if clip and any(g["params"] for g in self.param_groups) else None
+        ready = []                               # (gi, group, plan, step_no): the groups that have a gradient
+        npartials = 0
         for gi, group in enumerate(self.param_groups):
             params = group["params"]
             if not params:
                 continue
+            self._check_group(group)
             plan = self._plan(gi, group, capturing)
             N.note_device(params[0].device)
-            b1, b2 = group["betas"]
             if plan.get("copied") is not None and not capturing:
                 plan["copied"].synchronize()     # previous step's async H2D of the table has left the host buffer
             arr = (_AdamTensor * len(params)).from_buffer(plan["host"].numpy())
@@ -80,33 +151,50 @@ class Adam(torch.optim.Optimizer):
                 if p.grad is None:
                     arr[i] = _AdamTensor(p.data_ptr(), None, None, None, p.numel())
                     continue
-                st = self.state[p]
                 g = p.grad
                 if g.dtype != torch.float32 or not g.is_contiguous():
                     g = g.float().contiguous()
                     p.grad = g
-                if len(st) == 0:
-                    if capturing:
-                        raise N.Ru3dError("optim.Adam: take one eager step before capturing (the moment buffers are "
-                                          "created and zeroed by the first step)")
-                    st["step"] = torch.tensor(0.0)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                step_no = float(st["step"]) if step_no is None else step_no
-                if float(st["step"]) != step_no:
-                    raise N.Ru3dError("optim.Adam: parameters of one group must share the step count")
-                arr[i] = _AdamTensor(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                                     p.numel())
+                first, second = self._slots(p, group, capturing)
+                if self._COUNTS_STEPS:
+                    st = self.state[p]
+                    st["step"] += 1
+                    step_no = float(st["step"]) if step_no is None else step_no
+                    if float(st["step"]) != step_no:
+                        raise N.Ru3dError("optim.%s: parameters of one group must share the step count" % self._NAME)
+                arr[i] = _AdamTensor(p.data_ptr(), g.data_ptr(), None if first is None else first.data_ptr(),
+                                     None if second is None else second.data_ptr(), p.numel())
                 any_grad = True
             if not any_grad:
                 continue
+            step_no = 0.0 if step_no is None else step_no
             plan["table"].copy_(plan["host"], non_blocking=True)
             if capturing:
-                # the captured launch reads lr / bias corrections / grad_scale from the device block that
-                # hyper_for_replay() refreshes in front of every replay; the table copy is part of the graph (the
-                # gradients live at fixed addresses of the graph's memory pool)
+                # the table copy is part of the graph (the gradients live at fixed addresses of the graph's memory pool)
                 plan["copied"] = None
+            else:
+                ev = torch.cuda.Event()
+                ev.record()
+                plan["copied"] = ev
+            if clip:
+                check(N.lib.ru3d_grad_sumsq(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                                            ptr(bufs["partials"][npartials:]), stream()), "grad_sumsq")
+                npartials += plan["nblocks"]
+            ready.append((gi, group, plan, step_no))
+        coef = None
+        if clip and ready:
+            # every group's squares are in: one workgroup adds them up and leaves {norm, coefficient} on the device
+            N.note_device(bufs["norm"].device)
+            hyper0 = self._captured["hyper"][ready[0][0]] if capturing else None
+            check(N.lib.ru3d_grad_norm_finish(ptr(bufs["partials"]), npartials, float(grad_scale), ptr(hyper0),
+                                              self.max_grad_norm, ptr(bufs["norm"]), stream()), "grad_norm_finish")
+            coef = bufs["norm"][1:]
+            self.last_grad_norm = bufs["norm"][0]
+        for gi, group, plan, step_no in ready:
+            N.note_device(plan["table"].device)
+            if capturing:
+                # the captured launch reads lr / bias corrections / grad_scale from the device block that
+                # replay_scalars() refreshes in front of every replay
                 self._captured["steps"][gi] = step_no - 1.0     # the first replay IS this step
                 amp = self._captured.get("amp")
                 if amp is not None:
@@ -115,24 +203,15 @@ class Adam(torch.optim.Optimizer):
                     check(N.lib.ru3d_adam_multi_amp(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
                                                     ptr(self._captured["hyper"][gi]), ptr(amp), stream()), "adam_multi_amp")
                 else:
-                    check(N.lib.ru3d_adam_multi_dev(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
-                                                    ptr(self._captured["hyper"][gi]), stream()), "adam_multi_dev")
+                    self._launch_dev(plan, self._captured["hyper"][gi], coef)
                 continue
-            ev = torch.cuda.Event()
-            ev.record()
-            plan["copied"] = ev
             if self._captured is not None and gi in self._captured["steps"]:
                 self._captured["steps"][gi] = step_no
                 self._captured["amp_base"][gi] = step_no      # (the scaler re-uploads its block with steps = 0)
-            bc1 = 1.0 - b1 ** step_no
-            bc2 = 1.0 - b2 ** step_no
-            check(N.lib.ru3d_adam_multi(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
-                                        float(group["lr"]), float(b1), float(b2), float(group["eps"]), bc1, bc2,
-                                        float(grad_scale), stream()), "adam_multi")
+            self._launch(plan, group, step_no, float(grad_scale), coef)
         import _ops
         _ops.WEIGHTS_EPOCH[0] += 1      # packed copies of the weights are stale now
         return loss
-
 
     # ---- a training step captured in a hipGraph (graph.GraphedTrainStep)
     def begin_capture(self, hyper):
@@ -143,27 +222,25 @@ class Adam(torch.optim.Optimizer):
         for gi, group in enumerate(self.param_groups):       # device-side plan pieces cannot be made while capturing
             if group["params"]:
                 self._plan(gi, group, True)
+        if self.max_grad_norm is not None and any(g["params"] for g in self.param_groups):
+            self._clip_buffers(True)
+
+    def end_capture(self):
+        """Leave captured mode and drop what was allocated for it."""
+        self._captured = None
+        for key in [k for k in self._plans if k[1]]:       # (group, captured=True)
+            del self._plans[key]
+        self._clip.pop(True, None)           # the norm block stays: last_grad_norm keeps the last replay's value
 
     def replay_scalars(self, out, grad_scale=1.0):
         """Advance the step counts of the captured groups by one and write this step's scalars into `out` (CPU float32
-        [groups, 8]: lr, beta1, beta2, eps, bias_corr1, bias_corr2, grad_scale, sqrt(bias_corr2)) - the caller uploads them."""
+        [groups, 8], the row of the subclass's `_row`) - the caller uploads them."""
         cap = self._captured
         cap["dirty"] = True
         for gi, step_no in cap["steps"].items():
             step_no += 1.0
             cap["steps"][gi] = step_no
-            group = self.param_groups[gi]
-            b1, b2 = group["betas"]
-            row = out[gi]
-            row[0] = group["lr"]; row[1] = b1; row[2] = b2; row[3] = group["eps"]
-            row[4] = 1.0 - b1 ** step_no; row[5] = 1.0 - b2 ** step_no; row[6] = grad_scale
-            row[7] = float(row[5]) ** 0.5     # sqrt of the float32 bias_corr2, as ru3d_adam_multi takes it on the host
-            if cap.get("amp") is not None:
-                # device-side loss scaler: the kernel derives the step number from the steps really taken (skips are
-                # decided on the device); slot 5 carries the count before the capture as an int32
-                row[5:6].view(torch.int32)[0] = int(cap["amp_base"].get(gi, 0.0))
-                row[4] = b1 - float(torch.tensor(b1, dtype=torch.float32))      # residuals: beta = float32 value + this
-                row[7] = b2 - float(torch.tensor(b2, dtype=torch.float32))
+            self._row(out[gi], self.param_groups[gi], step_no, grad_scale)
 
     def sync_captured_steps(self):
         """Write the step counts reached by graph replays back into state[p]['step'] (state_dict fidelity)."""
@@ -171,6 +248,8 @@ class Adam(torch.optim.Optimizer):
         if cap is None or not cap.get("dirty"):
             return
         cap["dirty"] = False
+        if not self._COUNTS_STEPS:
+            return
         if cap.get("amp") is not None:
             # the device counted the steps that were not skipped (one 32-byte read-back, on demand only)
             taken = int(cap["amp"].view(torch.int32)[5].item())
@@ -195,23 +274,228 @@ class Adam(torch.optim.Optimizer):
                 st["step"] = st["step"].detach().to("cpu", torch.float32)
 
 
+class _AdamFamily(_Fused):
+    """torch.optim.Adam's state: {'step' (host float32), 'exp_avg', 'exp_avg_sq'}."""
+
+    def _slots(self, p, group, capturing):
+        st = self.state[p]
+        if len(st) == 0:
+            if capturing:
+                raise N.Ru3dError("optim.%s: take one eager step before capturing (the moment buffers are "
+                                  "created and zeroed by the first step)" % self._NAME)
+            st["step"] = torch.tensor(0.0)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st["exp_avg"], st["exp_avg_sq"]
+
+    def _check_group(self, group):
+        if group.get("amsgrad") or group.get("maximize"):
+            raise N.Ru3dError("optim.%s: amsgrad / maximize are not implemented" % self._NAME)
+
+
+class Adam(_AdamFamily):
+    _NAME = "Adam"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, max_grad_norm=None):
+        if weight_decay != 0 or amsgrad:
+            raise ValueError("ru3d optim.Adam implements plain Adam (weight_decay=0, amsgrad=False)")
+        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError("invalid Adam hyper-parameters")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False), max_grad_norm)
+
+    def captures_with_scaler(self):
+        return self.max_grad_norm is None
+
+    def _launch(self, plan, group, step_no, grad_scale, coef):
+        b1, b2 = group["betas"]
+        bc1 = 1.0 - b1 ** step_no
+        bc2 = 1.0 - b2 ** step_no
+        if coef is None:
+            check(N.lib.ru3d_adam_multi(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                                        float(group["lr"]), float(b1), float(b2), float(group["eps"]), bc1, bc2,
+                                        float(grad_scale), stream()), "adam_multi")
+        else:
+            check(N.lib.ru3d_adam_multi_clip(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                                             float(group["lr"]), float(b1), float(b2), float(group["eps"]), bc1, bc2,
+                                             float(grad_scale), ptr(coef), stream()), "adam_multi_clip")
+
+    def _launch_dev(self, plan, hyper_row, coef):
+        if coef is None:
+            check(N.lib.ru3d_adam_multi_dev(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                                            ptr(hyper_row), stream()), "adam_multi_dev")
+        else:
+            check(N.lib.ru3d_adam_multi_clip_dev(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                                                 ptr(hyper_row), ptr(coef), stream()), "adam_multi_clip_dev")
+
+    def _row(self, row, group, step_no, grad_scale):
+        """lr, beta1, beta2, eps, bias_corr1, bias_corr2, grad_scale, sqrt(bias_corr2)"""
+        b1, b2 = group["betas"]
+        row[0] = group["lr"]; row[1] = b1; row[2] = b2; row[3] = group["eps"]
+        row[4] = 1.0 - b1 ** step_no; row[5] = 1.0 - b2 ** step_no; row[6] = grad_scale
+        row[7] = float(row[5]) ** 0.5     # sqrt of the float32 bias_corr2, as ru3d_adam_multi takes it on the host
+        if self._captured.get("amp") is not None:
+            # device-side loss scaler: the kernel derives the step number from the steps really taken (skips are
+            # decided on the device); slot 5 carries the count before the capture as an int32
+            gi = next(i for i, g in enumerate(self.param_groups) if g is group)
+            row[5:6].view(torch.int32)[0] = int(self._captured["amp_base"].get(gi, 0.0))
+            row[4] = b1 - float(torch.tensor(b1, dtype=torch.float32))      # residuals: beta = float32 value + this
+            row[7] = b2 - float(torch.tensor(b2, dtype=torch.float32))
+
+
+class AdamW(_AdamFamily):
+    """torch.optim.AdamW: decoupled weight decay p *= 1 - lr * weight_decay in front of Adam's update."""
+    _NAME = "AdamW"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
+                 max_grad_norm=None):
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {}".format(eps))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+        if not 0.0 <= weight_decay:
+            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
+        if amsgrad:
+            raise ValueError("ru3d optim.AdamW does not implement amsgrad")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False),
+                         max_grad_norm)
+
+    def _launch(self, plan, group, step_no, grad_scale, coef):
+        b1, b2 = group["betas"]
+        check(N.lib.ru3d_adamw_multi(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                                     float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                     float(group["weight_decay"]), 1.0 - b1 ** step_no, 1.0 - b2 ** step_no,
+                                     float(grad_scale), ptr(coef), stream()), "adamw_multi")
+
+    def _launch_dev(self, plan, hyper_row, coef):
+        check(N.lib.ru3d_adamw_multi_dev(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                                         ptr(hyper_row), ptr(coef), stream()), "adamw_multi_dev")
+
+    def _row(self, row, group, step_no, grad_scale):
+        """lr, beta1, beta2, eps, bias_corr1, bias_corr2, grad_scale, weight_decay (the kernel takes sqrt(bias_corr2))"""
+        b1, b2 = group["betas"]
+        row[0] = group["lr"]; row[1] = b1; row[2] = b2; row[3] = group["eps"]
+        row[4] = 1.0 - b1 ** step_no; row[5] = 1.0 - b2 ** step_no; row[6] = grad_scale
+        row[7] = group["weight_decay"]
+
+
+class SGD(_Fused):
+    """torch.optim.SGD with dampening = 0: momentum, Nesterov momentum, (coupled) weight decay.  state[p] =
+    {'momentum_buffer'} as in torch, no entry when momentum == 0."""
+    _NAME = "SGD"
+    _COUNTS_STEPS = False
+
+    def __init__(self, params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=None):
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if momentum < 0.0:
+            raise ValueError("Invalid momentum value: {}".format(momentum))
+        if weight_decay < 0.0:
+            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if dampening != 0:
+            raise ValueError("ru3d optim.SGD does not implement dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay,
+                                      nesterov=bool(nesterov)), max_grad_norm)
+
+    def _check_group(self, group):
+        if group.get("dampening", 0) != 0 or group.get("maximize"):
+            raise N.Ru3dError("optim.SGD: dampening / maximize are not implemented")
+        if group["nesterov"] and group["momentum"] <= 0:
+            raise N.Ru3dError("optim.SGD: Nesterov momentum requires a momentum")
+
+    def _slots(self, p, group, capturing):
+        if group["momentum"] == 0:
+            return None, None
+        st = self.state[p]
+        if st.get("momentum_buffer") is None:
+            if capturing:
+                raise N.Ru3dError("optim.SGD: take one eager step before capturing (the momentum buffers are created "
+                                  "and zeroed by the first step)")
+            # zero, not torch's clone of the first d: momentum * 0 + d is d, bit for bit
+            st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st["momentum_buffer"], None
+
+    def _launch(self, plan, group, step_no, grad_scale, coef):
+        check(N.lib.ru3d_sgd_multi(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                                   float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]),
+                                   int(bool(group["nesterov"])), float(grad_scale), ptr(coef), stream()), "sgd_multi")
+
+    def _launch_dev(self, plan, hyper_row, coef):
+        check(N.lib.ru3d_sgd_multi_dev(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                                       ptr(hyper_row), ptr(coef), stream()), "sgd_multi_dev")
+
+    def _row(self, row, group, step_no, grad_scale):
+        """lr, momentum, weight_decay, nesterov (0 / 1), -, -, grad_scale, -"""
+        row[0] = group["lr"]; row[1] = group["momentum"]; row[2] = group["weight_decay"]
+        row[3] = 1.0 if group["nesterov"] else 0.0
+        row[4] = 0.0; row[5] = 0.0; row[6] = grad_scale; row[7] = 0.0
+
+
+_CLIP_TABLES = {}      # (device, numels) -> table + partials of clip_grad_norm_; a few small entries, dropped beyond eight
+
+
+def clip_grad_norm_(parameters, max_norm):
+    """torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2, error_if_nonfinite=False) for float32 gradients
+    on a HIP device: the gradients are scaled in place by min(1, max_norm / (norm + 1e-6)) and the norm comes back as a
+    0-dim device tensor.  Three launches, a fixed summation order, no host synchronisation."""
+    if torch.is_tensor(parameters):
+        parameters = [parameters]
+    params = [p for p in parameters if p.grad is not None]
+    max_norm = _check_max_grad_norm(max_norm)
+    if max_norm is None:
+        raise ValueError("clip_grad_norm_: max_norm is required")
+    if not params:
+        return torch.zeros(())
+    dev = params[0].grad.device
+    for p in params:
+        N.require_device(p.grad, "gradient")
+        if p.grad.device != dev:
+            raise N.Ru3dError("clip_grad_norm_: gradients must share one device")
+    key = (dev,) + tuple(p.numel() for p in params)      # all that the block map and the table's size depend on
+    entry = _CLIP_TABLES.get(key)
+    if entry is None:
+        if len(_CLIP_TABLES) >= 8:
+            _CLIP_TABLES.clear()
+        entry = _CLIP_TABLES[key] = {"table": _GradTable("clip_grad_norm_")}
+    tab = entry["table"]
+    tab.update(params)
+    if entry.get("partials") is None or entry["partials"].numel() != tab.nblocks:
+        entry["partials"] = torch.empty(tab.nblocks, dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)      # a fresh block: the returned norm stays valid
+    N.note_device(dev)
+    check(N.lib.ru3d_grad_norm(ptr(tab.table), ptr(tab.block_map), tab.nblocks, _CHUNK, ptr(entry["partials"]), 1.0,
+                               max_norm, ptr(out), stream()), "grad_norm")
+    check(N.lib.ru3d_grad_scale_dev(ptr(tab.table), ptr(tab.block_map), tab.nblocks, _CHUNK, ptr(out[1:]), stream()),
+          "grad_scale_dev")
+    return out[0]
+
+
 class _GradTable:
     """Device table of (grad pointer, count) per parameter in ru3d_adam_tensor layout + block map, rebuilt when the
     gradient tensors move (GradSync re-aliases them into its buckets; autograd allocates fresh ones otherwise)."""
 
-    def __init__(self):
+    def __init__(self, who="LossScaler"):
+        self.who = who
         self.key = None
         self.table = self.block_map = None
         self.nblocks = 0
         self.host = None
+        self.numels = None
         self.copied = None
 
     def prepare(self, params, dev):
         """The allocations (pinned host block, device table, block map): not allowed while a stream is capturing, so a
         captured step calls this beforehand (LossScaler.begin_capture)."""
         n = len(params)
-        if self.host is not None and self.host.numel() == n * ctypes.sizeof(_AdamTensor):
+        numels = tuple(p.numel() for p in params)
+        if self.host is not None and self.numels == numels and self.table.device == dev:
             return
+        self.numels = numels
         self.host = torch.empty(n * ctypes.sizeof(_AdamTensor), dtype=torch.uint8).pin_memory()
         self.table = torch.empty(self.host.numel(), dtype=torch.uint8, device=dev)
         blocks = []
@@ -235,7 +519,7 @@ class _GradTable:
         arr = (_AdamTensor * n).from_buffer(self.host.numpy())
         for i, (p, g) in enumerate(zip(params, grads)):
             if g is not None and (g.dtype != torch.float32 or not g.is_contiguous()):
-                raise N.Ru3dError("LossScaler: gradients must be contiguous float32")
+                raise N.Ru3dError("%s: gradients must be contiguous float32" % self.who)
             arr[i] = _AdamTensor(None, None if g is None else g.data_ptr(), None, None, p.numel())
         self.table.copy_(self.host, non_blocking=True)
         if capturing:
@@ -255,8 +539,9 @@ class LossScaler:
         scaler.scale(loss).backward()
         scaler.step(optimizer)        # unscale + inf/nan check on the device, one 4-byte read-back, step or skip
 
-    With optim.Adam the 1/scale factor is applied inside the fused update kernel; any other torch optimizer gets its
-    gradients unscaled in place first.  bf16 storage needs none of this."""
+    With optim.Adam / AdamW / SGD the 1/scale factor is applied inside the fused update kernel (and in the gradient norm
+    of max_grad_norm, which is then the norm of the true gradients); any other torch optimizer gets its gradients
+    unscaled in place first.  bf16 storage needs none of this."""
 
     def __init__(self, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000,
                  min_scale=2.0 ** -24, max_scale=2.0 ** 24):
@@ -277,8 +562,9 @@ class LossScaler:
     def begin_capture(self, optimizer, device):
         """Move the state into a device block and tell optim.Adam to take its decisions from there.  Call after
         optimizer.begin_capture()."""
-        if not isinstance(optimizer, Adam) or optimizer._captured is None:
-            raise TypeError("LossScaler.begin_capture needs an optim.Adam that is being captured")
+        if not isinstance(optimizer, _Fused) or not optimizer.captures_with_scaler() or optimizer._captured is None:
+            raise TypeError("LossScaler.begin_capture needs an optim.Adam without max_grad_norm that is being captured "
+                            "(ru3d_adam_multi_amp is the one update kernel that follows the device-side scaler)")
         self._dev = torch.zeros(32, dtype=torch.uint8, device=device)
         self._upload()
         for gi, group in enumerate(optimizer.param_groups):
@@ -347,7 +633,7 @@ class LossScaler:
         """Returns True when the optimizer stepped, False when the step was skipped because of an overflow."""
         if self._scale_t is None:
             raise RuntimeError("LossScaler.step() before LossScaler.scale(loss).backward()")
-        fused = isinstance(optimizer, Adam)
+        fused = isinstance(optimizer, _Fused)      # Adam, AdamW, SGD: 1 / scale goes into the update (and norm) kernels
         if self._dev is not None:
             if not torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("LossScaler: an eager step while the scaler is in captured mode (end_capture() first)")

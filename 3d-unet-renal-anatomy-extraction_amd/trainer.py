@@ -147,8 +147,9 @@ class Trainer():
         self._scaler = None
         # capture_step: training batches of the usual shape are replayed from a hipGraph of the whole step
         # (graph.GraphedTrainStep - the same kernels on the same data, bit for bit; the host only copies the batch in and
-        # one hipGraphLaunch replaces ~500 launches issued from Python).  Needs optim.Adam (its update kernel reads the
-        # step's scalars from device memory), one process, bf16 / fp32 storage.  None (default): on whenever those hold -
+        # one hipGraphLaunch replaces ~500 launches issued from Python).  Needs optim.Adam / AdamW / SGD (their update
+        # kernels read the step's scalars from device memory), one process; fp16 storage with its loss scaler only with
+        # optim.Adam without max_grad_norm.  None (default): on whenever those hold -
         # with a caller-owned torch.optim.Adam, a loss that is not one of this package's fused losses (a user module may
         # have host-side effects a replay would skip), fp16 loss scaling or several ranks the loop is the eager one, and
         # it stays the fallback if a capture fails.  True: insist (raises when not possible).  False: never.
@@ -210,10 +211,17 @@ class Trainer():
         if self._graphed is None:
             import graph as graph_mod
             import optim as optim_mod
-            if not isinstance(self.optimizer, optim_mod.Adam) or self.device.type != 'cuda':
+            if not isinstance(self.optimizer, optim_mod._Fused) or self.device.type != 'cuda':
                 if self.capture_step:
-                    raise TypeError("Trainer(capture_step=True) needs optim.Adam and a model on a HIP device")
+                    raise TypeError("Trainer(capture_step=True) needs optim.Adam / AdamW / SGD and a model on a HIP device")
                 self._capture_failed = True       # auto mode: a caller-owned optimizer keeps the eager loop
+                return None
+            if self._scaler is not None and not self.optimizer.captures_with_scaler():
+                # fp16: only plain optim.Adam has an update kernel that follows the device-side loss scaler
+                if self.capture_step:
+                    raise TypeError("Trainer(capture_step=True) with fp16 loss scaling needs optim.Adam without "
+                                    "max_grad_norm")
+                self._capture_failed = True
                 return None
             if self.capture_step is None and not isinstance(self.loss, _loss_mod._FusedLoss):
                 # auto mode captures only what it knows to be free of host-side effects: a user-defined loss module (one

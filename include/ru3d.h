@@ -889,6 +889,61 @@ int ru3d_adam_multi_amp(const ru3d_adam_tensor* tensors, const int32_t* block_ma
 int ru3d_amp_update(ru3d_amp_state* amp, float growth_factor, float backoff_factor, int growth_interval, float min_scale,
                     float max_scale, void* stream);
 
+/* The global L2 norm of every gradient a table names (same table / block-map layout as ru3d_adam_multi; only grad and
+ * count are read) and the clipping coefficient of torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False),
+ * without atomics and in a fixed order:
+ *   ru3d_grad_sumsq:       partials[b] = float64 sum of the float64 squares of block b's chunk, 0 for a row whose grad is
+ *                          NULL (partials: nblocks doubles).  Several tables (param groups) write into consecutive
+ *                          stretches of one partials array.
+ *   ru3d_grad_norm_finish: one workgroup adds npartials doubles and writes the norm block out[2] (device floats):
+ *                            out[0] = total = (float)(grad_scale * sqrt(sum))     the norm of the TRUE gradients when
+ *                                                                                 grad_scale is the fp16 path's 1 / loss_scale
+ *                            out[1] = coef  = min(1, max_norm / (total + 1e-6f))  NaN stays NaN (torch.clamp); an inf
+ *                                                                                 total gives 0
+ *                          hyper != NULL: grad_scale is read from hyper[6] of a captured step's scalar row instead.
+ *   ru3d_grad_norm:        both launches for one table (npartials = nblocks).
+ *   ru3d_grad_scale_dev:   g *= *coef in place over the table's gradients (clip_grad_norm_ on its own); writes nothing
+ *                          when *coef == 1. */
+int ru3d_grad_sumsq(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                    double* partials, void* stream);
+int ru3d_grad_norm_finish(const double* partials, int npartials, float grad_scale, const float* hyper, float max_norm,
+                          float* out, void* stream);
+int ru3d_grad_norm(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                   double* partials, float grad_scale, float max_norm, float* out, void* stream);
+int ru3d_grad_scale_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                        const float* coef, void* stream);
+
+/* torch.optim.SGD (dampening = 0, maximize = False) over a ru3d_adam_tensor table, one launch per param group:
+ *   gh = g * grad_scale * coef;  d = gh + weight_decay * p;  b = momentum * b + d  (momentum != 0; a zero buffer gives
+ *   torch's first step b = d);  u = nesterov ? d + momentum * b : b  (u = d when momentum == 0);  p -= lr * u.
+ * The momentum buffer b travels in the table's exp_avg slot (NULL when momentum == 0), exp_avg_sq is NULL.  coef: the
+ * device float ru3d_grad_norm_finish wrote (out + 1), or NULL for an unclipped step - the coefficient is multiplied in
+ * while the gradient is read, the gradients themselves are not written.  No fused multiply-adds: vector path, scalar
+ * path, this form and the _dev form give identical bits.
+ * _dev: hyper[8] = {lr, momentum, weight_decay, nesterov (0 / 1), -, -, grad_scale, -} from device memory (a captured
+ * step; the host rewrites the row before each replay). */
+int ru3d_sgd_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems, float lr,
+                   float momentum, float weight_decay, int nesterov, float grad_scale, const float* coef, void* stream);
+int ru3d_sgd_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                       const float* hyper, const float* coef, void* stream);
+
+/* torch.optim.AdamW: p *= 1 - lr * weight_decay, then ru3d_adam_multi's recurrence on gh = g * grad_scale * coef (coef as
+ * for ru3d_sgd_multi).  _dev: hyper[8] = {lr, beta1, beta2, eps, bias_corr1, bias_corr2, grad_scale, weight_decay}; slot 7
+ * carries the decay, so both forms take sqrtf(bias_corr2) on the device and stay bit-equal to each other. */
+int ru3d_adamw_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems, float lr,
+                     float beta1, float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
+                     float grad_scale, const float* coef, void* stream);
+int ru3d_adamw_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                         const float* hyper, const float* coef, void* stream);
+
+/* ru3d_adam_multi / ru3d_adam_multi_dev (same scalars, same hyper row) with the clipping coefficient multiplied into
+ * the gradient as it is read; with *coef == 1 or coef == NULL the result is ru3d_adam_multi's, bit for bit. */
+int ru3d_adam_multi_clip(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                         float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2,
+                         float grad_scale, const float* coef, void* stream);
+int ru3d_adam_multi_clip_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                             const float* hyper, const float* coef, void* stream);
+
 /* conv3d input gradient FOLLOWED by the InstanceNorm + LeakyReLU backward of the tensor it differentiates (ResBlock
  * backward, network.py:411-416 read backwards: da = conv2^T(dy); dyn = d/dy1 of lrelu(IN(y1)) given da) - the
  * mirror image of ru3d_conv3d_fwd_in.  `act` = lrelu(IN(y1)) as the forward produced it, mean / scale = that
