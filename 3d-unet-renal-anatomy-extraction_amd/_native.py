@@ -81,6 +81,14 @@ class RenderView(ctypes.Structure):
                 ("num_steps", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class DsLevel(ctypes.Structure):
+    """struct ru3d_ds_level"""
+    _fields_ = [("logits", ctypes.c_void_p), ("stride_n", ctypes.c_int64), ("stride_c", ctypes.c_int64),
+                ("stride_v", ctypes.c_int64), ("d", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("shift", ctypes.c_int32)]
+
+
+DS_MAX_LEVELS = 8               # RU3D_DS_MAX_LEVELS: logits tensors of one deep-supervision loss call
 MASK_NE, MASK_EQ, MASK_GT, MASK_GE = 0, 1, 2, 3
 TILE_F32, TILE_U8 = 0, 1
 OVERLAY_FILL, OVERLAY_OUTLINE = 0, 1
@@ -218,6 +226,14 @@ SIGNATURES = {
     "ru3d_boundary_fwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                _sz, _vp]),
     "ru3d_boundary_bwd": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
+    "ru3d_ds_state_bytes": (_sz, []),
+    "ru3d_ds_state_bad_labels_offset": (_sz, []),
+    "ru3d_ds_block_bytes": (_sz, []),
+    "ru3d_ds_loss_workspace_bytes": (_sz, [ctypes.POINTER(DsLevel), _i, _i]),
+    "ru3d_ds_loss_fwd": (_i, [ctypes.POINTER(DsLevel), _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _f, _f, _f, _vp, _vp,
+                              _vp, _vp, _sz, _vp]),
+    "ru3d_ds_loss_bwd": (_i, [ctypes.POINTER(DsLevel), ctypes.POINTER(_vp), _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp,
+                              _vp]),
     "ru3d_mesh_workspace_bytes": (_sz, [_i, _i, _i]),
     "ru3d_mesh_count": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ru3d_mesh_emit": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),

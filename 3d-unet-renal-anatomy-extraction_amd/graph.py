@@ -26,7 +26,8 @@ Not captured (the caller falls back to the eager step): a batch of another shape
     step = GraphedTrainStep(model, criterion, optimizer)
     for x, y in loader:
         loss = step(x, y)          # 0-dim device tensor (a static buffer: read it before the next call)
-        step.logits                # the network output of that step, for metrics
+        step.logits                # the network output of that step, for metrics (the full-resolution tensor when the
+                                   # model returns a deep-supervision list)
 
 `Trainer(..., capture_step=True)` drives its training batches through this.
 """
@@ -34,6 +35,7 @@ import torch
 
 import _native as N
 import _ops
+import loss as _loss
 import optim as _optim
 
 _RING = 8      # pinned host blocks in flight: a replay's scalars stay untouched until its upload has executed
@@ -72,7 +74,7 @@ class GraphedTrainStep:
         # a step the loss scaler skipped (overflow) created no Adam state: it does not count as warm-up
         self.eager_steps += 1 if (stepped or self.graph is not None) else 0
         self.skipped_warmup = getattr(self, "skipped_warmup", 0) + (0 if stepped else 1)
-        self.logits = logits.detach()
+        self.logits = _loss.main_output(logits).detach()      # a deep-supervision net returns a list: its entry 0
         return loss.detach()
 
     def _capture(self, x, y):
@@ -111,7 +113,7 @@ class GraphedTrainStep:
                         self.scaler.scale(loss).backward()
                         self.scaler.step(self.optimizer)
                     self.loss = loss.detach()
-                    self._static_logits = logits.detach()
+                    self._static_logits = _loss_mod.main_output(logits).detach()
             finally:
                 _ops.DROP_OFFSET_BASE[0] = None
                 _loss_mod.CAPTURE_SINK[0] = None

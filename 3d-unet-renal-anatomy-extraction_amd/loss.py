@@ -831,3 +831,271 @@ class HybirdBoundaryLoss(_FusedLoss):
         hyb = (self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)
         return _BoundaryFn.apply(input, target, hyb, self.boundary_weight_buffer, self.classes, self.weight_v,
                                  getattr(self, "check_labels", _CHECK_LABELS))
+
+
+# --------------------------------------------------------------------------- deep supervision
+# nnU-Net's deep supervision: the network returns one logits tensor per supervised decoder level (network.Unet(...,
+# deep_supervision=L), training mode), finest first; level l is judged against the labels at its own resolution and the
+# total is sum_l w_l loss_l.  A level never gets a label tensor of its own: voxel (a, b, c) of level l has the label
+# target[a * 2**l, b * 2**l, c * 2**l] - the strided view downsample_labels returns, with the extents ceil(full / 2**l).
+# Where 2**l divides the extents this is F.interpolate(mode='nearest') of the labels to the level's extents; on an axis
+# it does not divide, it is that of the labels padded to a multiple of 2**l (F.interpolate itself would step by
+# full / ceil(full / 2**l) there).
+def deep_supervision_weights(levels):
+    """[2**-l for l in range(levels)] over their sum: the weights halve per level and add up to 1 (the nnU-Net rule over
+    the levels in use)."""
+    levels = int(levels)
+    if levels < 1 or levels > N.DS_MAX_LEVELS:
+        raise ValueError("deep supervision: %d levels (1 .. %d)" % (levels, N.DS_MAX_LEVELS))
+    raw = [2.0 ** -l for l in range(levels)]
+    total = sum(raw)
+    return [r / total for r in raw]
+
+
+def downsample_labels(target, level):
+    """The labels level `level` of a deep-supervision loss sees: the view target[:, ::2**level, ::2**level, ...] of an
+    (N, d1, ..., dn) label tensor (no copy; extents ceil(d / 2**level)).  Host and HIP tensors."""
+    level = int(level)
+    if level < 0:
+        raise ValueError("downsample_labels: level %d" % level)
+    step = 1 << level
+    return target[(slice(None),) + (slice(None, None, step),) * (target.dim() - 1)]
+
+
+def main_output(y):
+    """The full-resolution logits of a model output: y[0] of the list a deep-supervision net returns in training mode, y
+    itself otherwise."""
+    return y[0] if isinstance(y, (list, tuple)) else y
+
+
+def _region_loss_host(kind, input, target, gamma, weight_v, alpha, beta, smooth):
+    """HybirdLoss / DiceLoss / FocalLoss on host tensors with torch ops, in the logits' dtype: the formulas of the header
+    comment of csrc/loss.hip (what the device path is tested against)."""
+    n, c = input.shape[0], input.shape[1]
+    if tuple(target.shape) != (n,) + tuple(input.shape[2:]):
+        raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape), tuple(input.shape)))
+    if weight_v is not None and len(weight_v) != c:
+        raise RuntimeError("weight_v has %d entries for %d classes" % (len(weight_v), c))
+    z = input.reshape(n, c, -1)
+    t = target.long().reshape(n, -1)
+    if t.numel() and (int(t.max()) >= c or int(t.min()) < 0):
+        raise RuntimeError(_BAD_LABELS)
+    logp = torch.log_softmax(z, dim=1) if c > 1 else F.logsigmoid(z)
+    p = logp.exp()
+    g = F.one_hot(t, num_classes=c).movedim(-1, 1).to(z.dtype)
+    w = torch.tensor([1.0] * c if weight_v is None else [float(a) for a in weight_v], dtype=z.dtype)
+    w = w / w.abs().sum().clamp_min(1e-12)
+    term = torch.zeros(c, dtype=z.dtype)
+    if kind != N.LOSS_FOCAL:
+        tp, sp, sg = (p * g).sum((0, 2)), p.sum((0, 2)), g.sum((0, 2))
+        term = term + 1.0 - (tp + smooth) / (tp + alpha * (sg - tp) + beta * (sp - tp) + smooth)
+    if kind != N.LOSS_DICELOSS:
+        # only the target class of a voxel contributes: gathered, so that log p = -inf of another class never meets a 0
+        lt = logp.gather(1, t[:, None]) if c > 1 else logp
+        per_voxel = -((1.0 - lt.exp()) ** gamma) * lt if gamma != 0 else -lt
+        term = term + (g * per_voxel).sum((0, 2)) * c / (n * z.shape[2])
+    return (w * term).sum()
+
+
+def _ds_levels(outputs, target):
+    """Checks shared by the two routes: a list of (N, C, d, h, w) logits, finest first, level l with the extents
+    ceil(full / 2**l), and (N, D, H, W) labels of level 0's extents."""
+    if torch.is_tensor(outputs):
+        outputs = [outputs]
+    outputs = list(outputs)
+    if not 1 <= len(outputs) <= N.DS_MAX_LEVELS:
+        raise N.Ru3dError("deep supervision: %d outputs (1 .. %d)" % (len(outputs), N.DS_MAX_LEVELS))
+    x0 = outputs[0]
+    if x0.dim() != 5:
+        raise N.Ru3dError("deep supervision: outputs must be (N, C, D, H, W) - three spatial dimensions - not %s"
+                          % (tuple(x0.shape),))
+    n, c = x0.shape[0], x0.shape[1]
+    full = tuple(x0.shape[2:])
+    if tuple(target.shape) != (n,) + full:
+        raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape), tuple(x0.shape)))
+    for l, x in enumerate(outputs):
+        want = (n, c) + tuple(-(-s // (1 << l)) for s in full)
+        if tuple(x.shape) != want:
+            raise N.Ru3dError("deep supervision: output %d has shape %s, level %d of %s is %s"
+                              % (l, tuple(x.shape), l, tuple(x0.shape), want))
+        if x.device != x0.device:
+            raise N.Ru3dError("deep supervision: outputs on %s and %s" % (x0.device, x.device))
+    return outputs
+
+
+class _DeepSupFn(torch.autograd.Function):
+    """All levels in one node: ru3d_ds_loss_fwd (one sums launch + one finalize) and ru3d_ds_loss_bwd (one launch), one
+    gradient per listed logits tensor.  block: the criterion's persistent float32 block (weights | level losses | total)."""
+
+    @staticmethod
+    def forward(ctx, target, hyper, block, check_labels, *outputs):
+        kind, gamma, weight_v, alpha, beta, smooth = hyper
+        x0 = outputs[0]
+        N.require_device(x0, "loss input")
+        if target.device != x0.device:
+            raise N.Ru3dError("loss: target is on %s but input on %s" % (target.device, x0.device))
+        n, c = x0.shape[0], x0.shape[1]
+        if c > N.MAX_CLASSES:
+            raise N.Ru3dError("loss: %d classes (max %d)" % (c, N.MAX_CLASSES))
+        dev = x0.device
+        xs, table = [], (N.DsLevel * len(outputs))()
+        for l, x in enumerate(outputs):
+            x = x.detach()
+            if x.dtype != torch.float32:
+                x = x.float()
+            st = _flat_strides(x)
+            if st is None:
+                x = x.contiguous()
+                st = _flat_strides(x)
+            xs.append(x)
+            table[l] = N.DsLevel(x.data_ptr(), st[0], st[1], st[2], x.shape[2], x.shape[3], x.shape[4], l)
+        if target.dtype == torch.int64:
+            lab, lab_code = target.contiguous(), N.LABEL_I64
+        elif target.dtype == torch.uint8:
+            lab, lab_code = target.contiguous(), N.LABEL_U8
+        else:
+            lab, lab_code = target.long().contiguous(), N.LABEL_I64
+        if check_labels or c == 1:
+            if lab.numel() and (int(lab.max()) >= c or int(lab.min()) < 0):
+                raise RuntimeError(_BAD_LABELS)
+        raise_on_bad_labels()          # an earlier call's verdict, if it has landed (no wait)
+        d, h, w = x0.shape[2:]
+        state = torch.empty(N.lib.ru3d_ds_state_bytes(), dtype=torch.uint8, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        ws = N.workspace(N.lib.ru3d_ds_loss_workspace_bytes(table, len(xs), n), dev)
+        wv = _weight_array(weight_v, c)
+        check(N.lib.ru3d_ds_loss_fwd(table, len(xs), ptr(lab), lab_code, n, d, h, w, c, kind, float(gamma),
+                                     N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None, float(alpha),
+                                     float(beta), float(smooth), ptr(block), ptr(state), ptr(out), ptr(ws), ws.numel(),
+                                     stream()), "ds_loss_fwd")
+        if not (check_labels or c == 1):
+            # _note_label_flag reads the count where the fused losses' state keeps it
+            _note_label_flag(state[_DS_BAD_OFF[0] - _BAD_OFF[0]:])
+        ctx.save_for_backward(lab, state, *xs)
+        ctx.meta = (table, lab_code, n, (d, h, w), c, float(gamma), [x.dtype for x in outputs])
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lab, state = ctx.saved_tensors[:2]
+        xs = ctx.saved_tensors[2:]
+        table, lab_code, n, (d, h, w), c, gamma, in_dtypes = ctx.meta
+        dev = xs[0].device
+        g = gout.detach()
+        if g.dtype != torch.float32 or g.device != dev:
+            g = g.to(device=dev, dtype=torch.float32)
+        g = g.reshape(1).contiguous()
+        N.note_device(dev)
+        dzs = []
+        for x in xs:
+            dz = torch.empty_like(x)   # preserve_format: same (dense) strides as the logits
+            if dz.stride() != x.stride():
+                dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=dev)
+            dzs.append(dz)
+        dptr = (N.ctypes.c_void_p * len(dzs))(*[dz.data_ptr() for dz in dzs])
+        check(N.lib.ru3d_ds_loss_bwd(table, dptr, len(xs), ptr(lab), lab_code, n, d, h, w, c, gamma, ptr(state), ptr(g),
+                                     stream()), "ds_loss_bwd")
+        dzs = [dz if dt == torch.float32 else dz.to(dt) for dz, dt in zip(dzs, in_dtypes)]
+        return (None, None, None, None) + tuple(dzs)
+
+
+_DS_BAD_OFF = [int(N.lib.ru3d_ds_state_bad_labels_offset())]
+assert _DS_BAD_OFF[0] >= _BAD_OFF[0]
+
+
+class DeepSupervisionLoss(_FusedLoss):
+    """sum_l w_l base(outputs[l], downsample_labels(target, l)) over the list a deep-supervision net returns in training
+    mode (finest first; level l has the extents ceil(full / 2**l)), against the full-resolution labels.  `base` is a
+    HybirdLoss, DiceLoss or FocalLoss instance whose hyper-parameters (gamma, weight_v, alpha, beta, smooth) are taken
+    over when this module is built.  weights: one per level (default deep_supervision_weights(len(outputs))).  A single
+    tensor instead of a list is one level with weight 1 - the plain base loss - so the same criterion object serves
+    validation in eval mode.
+
+    HIP tensors: all levels in one forward launch pair and one backward launch (csrc/deepsup.hip), no label copies; the
+    level weights are read from device memory, so set_weights() between the replays of a captured step
+    (graph.GraphedTrainStep) takes effect without a recapture.  Host tensors: the torch twin of the definition."""
+
+    def __init__(self, base, weights=None):
+        super().__init__()
+        if not isinstance(base, (HybirdLoss, DiceLoss, FocalLoss)):
+            raise TypeError("DeepSupervisionLoss wraps a HybirdLoss, DiceLoss or FocalLoss instance, not %s"
+                            % type(base).__name__)
+        self._kind = base._kind
+        self.gamma = getattr(base, "gamma", 2.0)
+        self.weight_v = base.weight_v
+        self.alpha = getattr(base, "alpha", 0.5)
+        self.beta = getattr(base, "beta", 0.5)
+        self.smooth = getattr(base, "smooth", 1e-7)
+        if hasattr(base, "check_labels"):
+            self.check_labels = base.check_labels
+        self._weights = None
+        self._blocks = {}         # (device, levels) -> float32 block [weights 0..7 | level losses 8..15 | total 16]
+        self._last = None         # (block, levels) of the last call
+        if weights is not None:
+            self._weights = self._checked(weights)
+
+    @staticmethod
+    def _checked(ws):
+        ws = [float(w) for w in ws]
+        if not 1 <= len(ws) <= N.DS_MAX_LEVELS:
+            raise ValueError("deep supervision: %d weights (1 .. %d)" % (len(ws), N.DS_MAX_LEVELS))
+        return ws
+
+    @property
+    def weights(self):
+        """The weights last set (host copy; None: the default rule for however many levels a call brings)."""
+        return None if self._weights is None else list(self._weights)
+
+    def _weights_for(self, levels):
+        if levels == 1:
+            return [1.0]
+        if self._weights is None:
+            return deep_supervision_weights(levels)
+        if len(self._weights) != levels:
+            raise ValueError("deep supervision: %d outputs but %d weights" % (levels, len(self._weights)))
+        return self._weights
+
+    @staticmethod
+    def _write(block, ws):
+        # fills with host scalars: stream-ordered, no synchronisation, legal while a step is being captured
+        for l, w in enumerate(ws):
+            block[l:l + 1].fill_(w)
+
+    def _block(self, device, levels):
+        key = (device, levels)
+        block = self._blocks.get(key)
+        if block is None:
+            block = self._blocks[key] = torch.zeros(2 * N.DS_MAX_LEVELS + 1, dtype=torch.float32, device=device)
+            self._write(block, self._weights_for(levels))
+        return block
+
+    def set_weights(self, ws):
+        """New level weights, written in place into the device block(s) the kernels read (fills on the current stream:
+        ordered in front of the next call or replay, no synchronisation, no recapture, no new allocation)."""
+        self._weights = self._checked(ws)
+        for (device, levels), block in self._blocks.items():
+            if levels == len(self._weights) and levels > 1:
+                self._write(block, self._weights)
+
+    @property
+    def last_level_losses(self):
+        """float32 [L]: the levels' un-weighted losses of the last call, on the logits' device.  A view of this module's
+        persistent block, rewritten by the next call (or replay): .clone() it to keep it."""
+        if self._last is None:
+            return None
+        block, levels = self._last
+        return block[N.DS_MAX_LEVELS:N.DS_MAX_LEVELS + levels]
+
+    def forward(self, outputs, target):
+        outputs = _ds_levels(outputs, target)
+        levels = len(outputs)
+        if not outputs[0].is_cuda:
+            ws = self._weights_for(levels)
+            per = [_region_loss_host(self._kind, x, downsample_labels(target, l), self.gamma, self.weight_v, self.alpha,
+                                     self.beta, self.smooth) for l, x in enumerate(outputs)]
+            self._last = (torch.cat([torch.zeros(N.DS_MAX_LEVELS)] + [v.detach().float().reshape(1) for v in per]), levels)
+            return sum(w * v for w, v in zip(ws, per))
+        block = self._block(outputs[0].device, levels)
+        self._last = (block, levels)
+        hyper = (self._kind, self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)
+        return _DeepSupFn.apply(target, hyper, block, getattr(self, "check_labels", _CHECK_LABELS), *outputs)

@@ -498,14 +498,18 @@ class ResBlockStack(nn.Module):
 class Unet(nn.Module):
     """Generic encoder/decoder assembler: stem conv, [encode_i, pool_i] x P, bottom encode,
     [up_i(x, skip_i), decode_i] x P (deepest first), 1x1x1 head.  Block classes are constructor
-    arguments, exactly as in the reference."""
+    arguments, exactly as in the reference.
+
+    deep_supervision=L (beyond the reference; 0 and 1: off, else 2 .. num_pool): decoder levels 1 .. L-1 get a 1x1x1 head
+    each (`ds_heads`) and a training-mode forward returns the list [logits_0, ..., logits_{L-1}], finest first, all
+    float32 - what loss.DeepSupervisionLoss takes.  Eval mode returns the one tensor whatever L is."""
 
     def __init__(self, in_channels, out_channels, paired_features,
                  pool_block=MaxPoolBlock, pool_kwargs={}, pool_kwargs_fn=none_fn,
                  up_block=UpConcat, up_kwargs={}, up_kwargs_fn=none_fn,
                  encode_block=ConvBlockStack, encode_kwargs={}, encode_kwargs_fn=none_fn,
                  decode_block=ConvBlockStack, decode_kwargs={}, decode_kwargs_fn=none_fn,
-                 conv_op=nn.Conv3d):
+                 conv_op=nn.Conv3d, deep_supervision=0):
         super().__init__()
         num_pairs = len(paired_features)
         assert (num_pairs % 2) == 1, 'Number of paired features must be odd number.'
@@ -530,8 +534,19 @@ class Unet(nn.Module):
         self.decode_blocks = nn.ModuleList(decs)
         self.conv = conv_op(in_channels, pf[0][0], kernel_size=3, padding=1)
         self.fc = conv_op(pf[num_pairs - 1][1], out_channels, kernel_size=1)
+        # deep supervision: L supervised outputs counting the full-resolution one (0 and 1: off).  Decoder levels
+        # 1 .. L-1 get a 1x1x1 head of their own - built AFTER every reference parameter, so the RNG stream of the default
+        # initialisation of those is what it is without them (state_dict keys ds_heads.<l-1>.{weight,bias})
+        levels = int(deep_supervision)
+        if levels < 0 or levels > self.num_pool or (levels >= 2 and levels > N.DS_MAX_LEVELS):
+            raise ValueError("deep_supervision=%d: 0 (off) or 2 .. num_pool = %d supervised outputs (decoder levels "
+                             "0 .. %d exist; the bottom encoder has no head)" % (levels, self.num_pool, self.num_pool - 1))
+        self.deep_supervision = levels if levels >= 2 else 0
+        self.ds_heads = nn.ModuleList(conv_op(pf[num_pairs - l - 1][1], out_channels, kernel_size=1)
+                                      for l in range(1, self.deep_supervision))
         self.compute_dtype = _DEFAULT_DTYPE
-        self._native_io = _is_plain_conv3(self.conv) and _is_plain_conv1(self.fc)
+        self._native_io = (_is_plain_conv3(self.conv) and _is_plain_conv1(self.fc)
+                           and all(_is_plain_conv1(h) and h.stride == (1, 1, 1) for h in self.ds_heads))
         self._pad = False
         self._linked = False
         self._bn_blocks = None
@@ -624,6 +639,17 @@ class Unet(nn.Module):
             return ops.ConvFn.apply(x, self.fc.weight, self.fc.bias, 1, x.dtype, torch.float32, self._pad, False)
         return self.fc(x)
 
+    def _supervised_levels(self):
+        """Number of outputs of this forward: the deep-supervision list exists in training mode only."""
+        return getattr(self, "deep_supervision", 0) if self.training else 0
+
+    def _aux_head(self, level, x):
+        """float32 logits of decoder level `level` >= 1 (its output before the next up block): the main head's route."""
+        head = self.ds_heads[level - 1]
+        if self._native_io and x.is_cuda:
+            return ops.ConvFn.apply(x, head.weight, head.bias, 1, x.dtype, torch.float32, self._pad, False)
+        return head(x)
+
     def _prepack(self):
         """One packing pass for the whole model in front of a training step (ops.prepack): every block of the linked
         native chain, the stem and the head."""
@@ -636,6 +662,10 @@ class Unet(nn.Module):
             specs += blk._pack_specs()
         ci = self.fc.weight.shape[1] if self._pad else 0
         specs += [(self.fc.weight, N.ROLE_CONV_FWD, 1, 0, ci), (self.fc.weight, N.ROLE_CONV_DGRAD, 1, 0, ci)]
+        for level in range(1, self._supervised_levels()):
+            w = self.ds_heads[level - 1].weight
+            ci = w.shape[1] if self._pad else 0
+            specs += [(w, N.ROLE_CONV_FWD, 1, 0, ci), (w, N.ROLE_CONV_DGRAD, 1, 0, ci)]
         ops.prepack(specs, sd)
 
     def _set_bn_pad(self, pad):
@@ -681,13 +711,19 @@ class Unet(nn.Module):
             links.append(link)
             x = self.pool_blocks[i](x, in_link=link) if linked else self.pool_blocks[i](x)
         x = self.encode_blocks[-1](x)
+        levels = self._supervised_levels()
+        aux = {}
         for i in reversed(range(self.num_pool)):
             x = self.up_blocks[i](x, skips[i], links[i]) if linked else self.up_blocks[i](x, skips[i])
             if linked and getattr(links[i], "planar_out", False):
                 x = self.decode_blocks[i](x, planar=True)       # the concat as two planes (ops.SkipLink.planar_view)
             else:
                 x = self.decode_blocks[i](x)
+            if 1 <= i < levels:
+                aux[i] = self._aux_head(i, x)      # a second consumer of the level's output: autograd adds the gradients
         ops._DROP_POOL.clear()
+        if levels:
+            return [self._head(x)] + [aux[l] for l in range(1, levels)]
         return self._head(x)
 
 
@@ -705,7 +741,7 @@ class ResUnet3D(_UnetWrapper):
     """Residual 3D U-Net: ResBlockStack encoders (max(level,1) blocks), stride-2 ResBlock pooling,
     ConvTrans3D up-sampling + concat, ResBlock decoders.  This is the model every training script uses."""
 
-    def __init__(self, num_pool=4, num_features=30, in_channels=1, out_channels=1):
+    def __init__(self, num_pool=4, num_features=30, in_channels=1, out_channels=1, deep_supervision=0):
         super().__init__()
         self.num_pool = num_pool
         self.num_features = num_features
@@ -715,13 +751,13 @@ class ResUnet3D(_UnetWrapper):
                         paired_features=generate_paired_features(num_pool, num_features),
                         pool_block=ResBlock, pool_kwargs={'stride': 2},
                         encode_block=ResBlockStack, encode_kwargs_fn=_stacks_by_level,
-                        decode_block=ResBlock)
+                        decode_block=ResBlock, deep_supervision=deep_supervision)
 
 
 class ResAttrUnet3D(_UnetWrapper):
     """ResUnet3D with attention-gated skips (the gate runs on the conv kernels + ru3d_pointwise: ops.AttGateFn)."""
 
-    def __init__(self, num_pool=4, num_features=30, in_channels=1, out_channels=1):
+    def __init__(self, num_pool=4, num_features=30, in_channels=1, out_channels=1, deep_supervision=0):
         super().__init__()
         self.num_pool = num_pool
         self.num_features = num_features
@@ -731,13 +767,13 @@ class ResAttrUnet3D(_UnetWrapper):
                         paired_features=generate_paired_features(num_pool, num_features),
                         pool_block=ResBlock, pool_kwargs={'stride': 2}, up_kwargs={'attention': True},
                         encode_block=ResBlockStack, encode_kwargs_fn=_stacks_by_level,
-                        decode_block=ResBlock)
+                        decode_block=ResBlock, deep_supervision=deep_supervision)
 
 
 class ResAttrUnet3D2(_UnetWrapper):
     """Fixed 30/60/120/240/320 channel plan with attention-gated skips."""
 
-    def __init__(self, in_channels=1, out_channels=1):
+    def __init__(self, in_channels=1, out_channels=1, deep_supervision=0):
         super().__init__()
         self.in_channels = in_channels
         self.out_channels = out_channels
@@ -746,7 +782,7 @@ class ResAttrUnet3D2(_UnetWrapper):
         self.net = Unet(in_channels=in_channels, out_channels=out_channels, paired_features=plan,
                         pool_block=ResBlock, pool_kwargs={'stride': 2}, up_kwargs={'attention': True},
                         encode_block=ResBlockStack, encode_kwargs_fn=_stacks_by_level,
-                        decode_block=ResBlock)
+                        decode_block=ResBlock, deep_supervision=deep_supervision)
 
 
 class ResAttrBNUnet3D(_UnetWrapper):
@@ -755,7 +791,7 @@ class ResAttrBNUnet3D(_UnetWrapper):
     keeps the blocks torch modules as a cross-check).  Inference (eval + no_grad - how the reference's scripts use this
     net, as the coarse model of nb_post_iia.py:20): BatchNorm with running statistics is a per-channel affine map."""
 
-    def __init__(self, num_pool=4, num_features=30, in_channels=1, out_channels=1):
+    def __init__(self, num_pool=4, num_features=30, in_channels=1, out_channels=1, deep_supervision=0):
         super().__init__()
         self.num_pool = num_pool
         self.num_features = num_features
@@ -767,4 +803,4 @@ class ResAttrBNUnet3D(_UnetWrapper):
                         pool_block=ResBlock, pool_kwargs={'stride': 2, **bn},
                         up_kwargs={'attention': True, **bn},
                         encode_block=ResBlockStack, encode_kwargs=bn, encode_kwargs_fn=_stacks_by_level,
-                        decode_block=ResBlock, decode_kwargs=bn)
+                        decode_block=ResBlock, decode_kwargs=bn, deep_supervision=deep_supervision)

@@ -301,9 +301,10 @@ class Trainer():
                     self.optimizer.step()
             scalars = {'loss': loss}
             if self.metrics is not None:
+                y_main = _loss_mod.main_output(y_pred)      # a deep-supervision net trains on a list: metrics see entry 0
                 with torch.no_grad():
                     for key, metric_fn in self.metrics.items():
-                        scalars[key] = metric_fn(y_pred, y)
+                        scalars[key] = metric_fn(y_main, y)
             pending.append({k: (v if torch.is_tensor(v) else torch.tensor(float(v))) for k, v in scalars.items()})
             if len(pending) >= self.sync_every:
                 last = self._flush(pending, results)

@@ -599,6 +599,42 @@ int ru3d_boundary_bwd(const float* logits, int64_t stride_n, int64_t stride_c, i
                       int Z, int num_classes, const int* classes, int num_selected, const float* phi, const void* state,
                       const float* grad_out, float scale, int accumulate, float* dlogits, void* stream);
 
+/* ------------------------------------------------------------------ deep supervision */
+/* The fused loss of ru3d_loss_fwd (kinds HYBIRD, DICELOSS, FOCAL; same formulas, precisions and scalars) on up to
+ * RU3D_DS_MAX_LEVELS logits tensors of falling resolution at once, against ONE label tensor labels[n][D][H][W] (uint8 or
+ * int64, contiguous): voxel (a, b, c) of a level with shift s has the label labels[a << s][b << s][c << s], i.e. the
+ * level sees labels[:, ::2**s, ::2**s, ::2**s].  Level l is an entry of a HOST table: its float32 logits (element
+ * (n, c, v) at logits[n*stride_n + c*stride_c + v*stride_v], v the flat index over d x h x w), its extents and its
+ * shift; (d - 1) << s <= D - 1 (and likewise for h, w) is required, which holds for d = ceil(D / 2**s); level 0 has the
+ * labels' extents and shift 0.
+ *   loss_l as in ru3d_loss_fwd over the level's n * d * h * w voxels;  total = sum_l w_l * loss_l.
+ * block: device float32 [2 * RU3D_DS_MAX_LEVELS + 1] (ru3d_ds_block_bytes): [0 .. 7] the level weights w_l, READ by the
+ * device at execution time (rewrite them between the replays of a captured step); [8 .. 15] receive loss_l, [16] the
+ * total.  state: ru3d_ds_state_bytes() bytes; receives per level the backward coefficients and the w_l of this forward;
+ * the count of labels outside [0, C) - taken once, on level 0, which reads every label - sits at
+ * ru3d_ds_state_bad_labels_offset() (the total and loss_0 are NaN then).  loss_out: 1 float32 on the device.
+ * One sums launch over all levels (a block belongs to one level), one finalize workgroup that reduces the float64
+ * partials of each level in a fixed order: no atomics, the same bits in every run. */
+#define RU3D_DS_MAX_LEVELS 8
+typedef struct ru3d_ds_level {
+    const float* logits;
+    int64_t stride_n, stride_c, stride_v;
+    int32_t d, h, w, shift;
+} ru3d_ds_level;
+size_t ru3d_ds_state_bytes(void);
+size_t ru3d_ds_state_bad_labels_offset(void);
+size_t ru3d_ds_block_bytes(void);
+size_t ru3d_ds_loss_workspace_bytes(const ru3d_ds_level* levels, int num_levels, int n);
+int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, const void* labels, int label_dtype, int n, int D, int H,
+                     int W, int num_classes, int kind, float gamma, const float* weight_v, float alpha, float beta,
+                     float smooth, float* block, void* state, float* loss_out, void* ws, size_t ws_bytes, void* stream);
+/* dlogits[l] (HOST array of num_levels device pointers; float32, the strides of level l's logits) =
+ * w_l * grad_out[0] * d loss_l / d logits_l for every level in one launch; w_l and the coefficients from `state` as the
+ * forward left them, grad_out a device float32 or NULL for 1. */
+int ru3d_ds_loss_bwd(const ru3d_ds_level* levels, void* const* dlogits, int num_levels, const void* labels,
+                     int label_dtype, int n, int D, int H, int W, int num_classes, float gamma, const void* state,
+                     const float* grad_out, void* stream);
+
 /* ------------------------------------------------------------------ surface meshes */
 /* The anatomy as closed triangle meshes: the faces between a set voxel and an unset one of a packed mask (the
  * "cuberille"), Taubin smoothing on the lattice's own edge graph, area and enclosed volume.  Masks are the packed masks
