@@ -111,6 +111,8 @@ _dbl = ctypes.c_double
 SIGNATURES = {
     "ru3d_version": (_i, []),
     "ru3d_last_error": (ctypes.c_char_p, []),
+    "ru3d_launch_log_begin": (None, []),
+    "ru3d_launch_log_end": (ctypes.c_char_p, []),
     "ru3d_packed_weight_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "ru3d_pack_weight": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ru3d_pack_weights": (_i, [ctypes.POINTER(PackItem), _i, _i, _vp]),

@@ -260,6 +260,24 @@ def set_probe(p):
 _PROBE = [None]
 
 
+class launch_log:
+    """Context manager around the library's launch log (ru3d_launch_log_begin / _end): after exit, .names is the list of
+    launch names the library checked on this thread inside the block, in order - for the conv family with the template
+    arguments of the instantiation ("conv_gather_mfma<2,6>"), so a test can assert which kernel it ran."""
+
+    def __init__(self):
+        self.names = []
+
+    def __enter__(self):
+        N.lib.ru3d_launch_log_begin()
+        return self
+
+    def __exit__(self, *exc):
+        s = N.lib.ru3d_launch_log_end().decode("utf-8", "replace")
+        self.names = s.split(";") if s else []
+        return False
+
+
 def _conv_ws(dsrc, ddst, k, stride, dtype, device):
     """(pointer, bytes) of the optional conv scratch (split-K partials on the deepest level), caller-owned."""
     if k != 3 or stride != 1 or dtype == torch.float32:

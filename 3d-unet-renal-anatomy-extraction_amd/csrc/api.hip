@@ -20,7 +20,15 @@ int ru3d_fail(int code, const char* fmt, ...) {
     return code;
 }
 
+// launch log (tests): while armed, the names ru3d_check_launch receives on this thread, joined by ';'
+static thread_local std::string g_launch_log;
+static thread_local bool g_launch_log_armed = false;
+
 int ru3d_check_launch(const char* what) {
+    if (g_launch_log_armed) {
+        if (!g_launch_log.empty()) g_launch_log += ';';
+        g_launch_log += what;
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         ru3d_fail((int)e, "%s: %s", what, hipGetErrorString(e));
@@ -31,6 +39,14 @@ int ru3d_check_launch(const char* what) {
 
 extern "C" int ru3d_version(void) { return RU3D_VERSION; }
 extern "C" const char* ru3d_last_error(void) { return g_last_error.c_str(); }
+extern "C" void ru3d_launch_log_begin(void) {
+    g_launch_log.clear();
+    g_launch_log_armed = true;
+}
+extern "C" const char* ru3d_launch_log_end(void) {
+    g_launch_log_armed = false;
+    return g_launch_log.c_str();
+}
 #endif
 
 namespace RU3D_NS {

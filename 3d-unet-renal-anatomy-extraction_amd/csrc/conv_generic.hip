@@ -650,7 +650,7 @@ int wgrad_reduce_launch(const float* part, float* dw, int chunks, int taps, int 
         else
             hipLaunchKernelGGL(wgrad_reduce_tiled_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, part, dw, chunks, taps,
                                cin, cout, s_o, s_i);
-        return ru3d_check_launch("wgrad_reduce_tiled");
+        return ru3d_check_launch(s_i == taps ? "wgrad_reduce_tiled<true>" : "wgrad_reduce_tiled<false>");
     }
     // few outputs under many slabs: more chunk lanes per output (the launch is latency, not bandwidth)
     const bool deep = chunks >= 128 && (total + 255) / 256 < 512;
@@ -663,7 +663,7 @@ int wgrad_reduce_launch(const float* part, float* dw, int chunks, int taps, int 
     else
         hipLaunchKernelGGL(wgrad_reduce_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, st, part, dw, chunks, taps, cin, cout,
                            s_o, s_i);
-    return ru3d_check_launch("wgrad_reduce");
+    return ru3d_check_launch(deep ? "wgrad_reduce<8>" : "wgrad_reduce<64>");
 }
 
 int wgrad_generic_chunks(const WgradGeom& g) {

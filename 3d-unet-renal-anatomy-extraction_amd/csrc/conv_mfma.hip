@@ -2187,7 +2187,7 @@ __global__ __launch_bounds__(256, 2) void convt_tile_mfma_kernel(DirectArgs a) {
 }
 
 template <int NT, int TD, int TH, int TW>
-static int launch_convt_tile(const DirectArgs& a, int N, hipStream_t st) {
+static int launch_convt_tile(const DirectArgs& a, int N, hipStream_t st, const char* name) {
     const int tw_n = (a.hw + TW - 1) / TW, th_n = (a.hh + TH - 1) / TH, td_n = (a.hd + TD - 1) / TD;
     const int64_t nblk = (int64_t)N * td_n * th_n * tw_n;
     if (nblk > 0x7fffffff) return ru3d_fail(-1, "convt_tile: grid too large");
@@ -2200,7 +2200,7 @@ static int launch_convt_tile(const DirectArgs& a, int N, hipStream_t st) {
         attr_set = true;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk, a.Cout / (NT * 32)), dim3(256), lds, st, a);
-    return ru3d_check_launch("convt_tile_mfma");
+    return ru3d_check_launch(name);
 }
 
 static int launch_direct(const void* x, const void* w, const float* bias, const void* res, void* y, const ConvGeom& g,
@@ -2240,16 +2240,22 @@ static int launch_direct(const void* x, const void* w, const float* bias, const 
         const int64_t tiles = (a.total + 31) / 32;
         dim3 gk((unsigned)tiles, g.Cout / (nt2 ? 64 : 32), g.transposed ? 8 : 1);
         const bool deep = g.k >= 3;
-#define RU3D_KSPLIT_LAUNCH(NTV, TRV)                                                                              \
-    if (deep) hipLaunchKernelGGL((conv_direct_ksplit_kernel<NTV, TRV, 8>), gk, dim3(256), 0, st, a);             \
-    else hipLaunchKernelGGL((conv_direct_ksplit_kernel<NTV, TRV, 2>), gk, dim3(256), 0, st, a)
+        const char* name;
+#define RU3D_KSPLIT_LAUNCH(NTV, TRV, TRN)                                                                         \
+    if (deep) {                                                                                                   \
+        hipLaunchKernelGGL((conv_direct_ksplit_kernel<NTV, TRV, 8>), gk, dim3(256), 0, st, a);                   \
+        name = "conv_direct_ksplit<" #NTV "," TRN ",8>";                                                          \
+    } else {                                                                                                      \
+        hipLaunchKernelGGL((conv_direct_ksplit_kernel<NTV, TRV, 2>), gk, dim3(256), 0, st, a);                   \
+        name = "conv_direct_ksplit<" #NTV "," TRN ",2>";                                                          \
+    }
         if (g.transposed) {
-            if (nt2) { RU3D_KSPLIT_LAUNCH(2, true); } else { RU3D_KSPLIT_LAUNCH(1, true); }
+            if (nt2) { RU3D_KSPLIT_LAUNCH(2, true, "T") } else { RU3D_KSPLIT_LAUNCH(1, true, "T") }
         } else {
-            if (nt2) { RU3D_KSPLIT_LAUNCH(2, false); } else { RU3D_KSPLIT_LAUNCH(1, false); }
+            if (nt2) { RU3D_KSPLIT_LAUNCH(2, false, "F") } else { RU3D_KSPLIT_LAUNCH(1, false, "F") }
         }
 #undef RU3D_KSPLIT_LAUNCH
-        return ru3d_check_launch("conv_direct_ksplit");
+        return ru3d_check_launch(name);
     }
     static const int tile_mode = getenv("RU3D_CONVT_TILE") ? atoi(getenv("RU3D_CONVT_TILE")) : 1;
     if (tile_mode && g.transposed && g.k == 3 && g.pad == 1) {
@@ -2257,15 +2263,17 @@ static int launch_direct(const void* x, const void* w, const float* bias, const 
         if (a.hw >= 24 && g.Cin <= 128) {
             // one cout tile: 256 positions per workgroup (8 column tiles per weight fragment) - the 110 KB of weights a
             // workgroup pulls through its CU's ~10 B/clk are the larger part of what enters it
-            if (!nt2 && g.Cin <= 64 && a.hh >= 4) return launch_convt_tile<1, 2, 4, 32>(a, g.N, st);
-            return nt2 ? launch_convt_tile<2, 2, 2, 32>(a, g.N, st) : launch_convt_tile<1, 2, 2, 32>(a, g.N, st);
+            if (!nt2 && g.Cin <= 64 && a.hh >= 4) return launch_convt_tile<1, 2, 4, 32>(a, g.N, st, "convt_tile_mfma<1,2,4,32>");
+            return nt2 ? launch_convt_tile<2, 2, 2, 32>(a, g.N, st, "convt_tile_mfma<2,2,2,32>")
+                       : launch_convt_tile<1, 2, 2, 32>(a, g.N, st, "convt_tile_mfma<1,2,2,32>");
         }
         if (a.hw >= 12 && g.Cin <= 256) {
             // 64-cout workgroups only when they still fill the chip (16^3 -> 32^3 at N = 2: 64 tiles)
             static const int nt_mode = getenv("RU3D_CONVT_NT") ? atoi(getenv("RU3D_CONVT_NT")) : 1;
             const int64_t t16 = (int64_t)g.N * ((a.hd + 1) / 2) * ((a.hh + 3) / 4) * ((a.hw + 15) / 16);
             const bool wide = nt2 && (nt_mode == 0 || t16 * (g.Cout / 64) >= 200);
-            return wide ? launch_convt_tile<2, 2, 4, 16>(a, g.N, st) : launch_convt_tile<1, 2, 4, 16>(a, g.N, st);
+            return wide ? launch_convt_tile<2, 2, 4, 16>(a, g.N, st, "convt_tile_mfma<2,2,4,16>")
+                        : launch_convt_tile<1, 2, 4, 16>(a, g.N, st, "convt_tile_mfma<1,2,4,16>");
         }
     }
     dim3 grid((unsigned)nblk, g.Cout / (nt2 ? 64 : 32));
@@ -2273,16 +2281,16 @@ static int launch_direct(const void* x, const void* w, const float* bias, const 
         if (g.k >= 3) {
             if (nt2) hipLaunchKernelGGL((conv_gather_mfma_kernel<2, 6>), grid, dim3(256), 0, st, a);
             else hipLaunchKernelGGL((conv_gather_mfma_kernel<1, 6>), grid, dim3(256), 0, st, a);
-        } else {
-            if (nt2) hipLaunchKernelGGL((conv_gather_mfma_kernel<2, 2>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv_gather_mfma_kernel<1, 2>), grid, dim3(256), 0, st, a);
+            return ru3d_check_launch(nt2 ? "conv_gather_mfma<2,6>" : "conv_gather_mfma<1,6>");
         }
-        return ru3d_check_launch("conv_gather_mfma");
+        if (nt2) hipLaunchKernelGGL((conv_gather_mfma_kernel<2, 2>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((conv_gather_mfma_kernel<1, 2>), grid, dim3(256), 0, st, a);
+        return ru3d_check_launch(nt2 ? "conv_gather_mfma<2,2>" : "conv_gather_mfma<1,2>");
     }
     if (!g.transposed) return ru3d_fail(-1, "conv_direct_mfma: no gather kernel for k = %d", g.k);
     if (nt2) hipLaunchKernelGGL((conv_direct_mfma_kernel<2, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((conv_direct_mfma_kernel<1, true>), grid, dim3(256), 0, st, a);
-    return ru3d_check_launch("conv_direct_mfma");
+    return ru3d_check_launch(nt2 ? "conv_direct_mfma<2,T>" : "conv_direct_mfma<1,T>");
 }
 
 static bool aligned_to(const void* p, size_t a) { return (((uintptr_t)p) % a) == 0; }
@@ -2793,7 +2801,7 @@ static int wgrad_staged_launch(const void* x, const void* dy, float* dw, void* w
         hipLaunchKernelGGL((wgrad_staged_mfma_kernel<1, 256>), grid, dim3(256), 0, st, a);
         slabs = a.G * 4;
     }
-    int rc = ru3d_check_launch("wgrad_staged_mfma");
+    int rc = ru3d_check_launch(g.k == 3 ? "wgrad_staged_mfma<27,32>" : "wgrad_staged_mfma<1,256>");
     if (rc) return rc;
     return wgrad_reduce_launch((const float*)ws, dw, slabs, g.taps, g.Cin, g.Cout, g.s_o, g.s_i, st);
 }

@@ -77,6 +77,12 @@ typedef struct ru3d_tensor {
 int ru3d_version(void);
 /* thread-local, valid until the next failing call on this thread */
 const char* ru3d_last_error(void);
+/* Launch log (tests): between _begin and _end the library records, on the calling thread, the name of every kernel
+ * launch it checks - for the conv family the name carries the template arguments of the instantiation, e.g.
+ * "conv_gather_mfma<2,6>".  _begin clears and arms the log; _end disarms it and returns the names joined by ';'
+ * (thread-local, valid until the next _begin on this thread; "" if the log was never armed).  Host side only. */
+void ru3d_launch_log_begin(void);
+const char* ru3d_launch_log_end(void);
 
 /* ------------------------------------------------------------------ weights ----------------- */
 /* Number of bytes of the packed form of a weight (layout is private to the library and depends on

@@ -43,6 +43,36 @@ def test_library_exports_every_declared_symbol():
     assert rc < 0 and b"conv3d_fwd" in N.lib.ru3d_last_error()
 
 
+def test_launch_log_is_empty_until_armed_and_per_thread():
+    """ru3d_launch_log_begin / _end without a launch in between (no device call is made here): "" before the log was
+    ever armed, "" for an empty armed span, and the state belongs to the calling thread - a log armed on one thread
+    reads as never armed from another, and ending it there leaves the first thread's span intact."""
+    import threading
+
+    import _ops as ops
+
+    seen = {}
+
+    def fresh_thread():
+        seen["never_armed"] = N.lib.ru3d_launch_log_end()        # a new thread: nothing was ever armed on it
+
+    t = threading.Thread(target=fresh_thread)
+    t.start()
+    t.join()
+    assert seen["never_armed"] == b""
+    N.lib.ru3d_launch_log_begin()
+    assert N.lib.ru3d_launch_log_end() == b""
+    N.lib.ru3d_launch_log_begin()                                  # armed here ...
+    t = threading.Thread(target=lambda: seen.update(other=N.lib.ru3d_launch_log_end()))
+    t.start()                                                      # ... read (and "ended") on another thread
+    t.join()
+    assert seen["other"] == b""
+    assert N.lib.ru3d_launch_log_end() == b""
+    with ops.launch_log() as log:
+        pass
+    assert log.names == []
+
+
 def test_ndhwc_descriptor_logic():
     t = N.new_act(2, 6, 3, 4, 5, torch.float32, "cpu")
     assert tuple(t.shape) == (2, 6, 3, 4, 5) and N.is_ndhwc(t)
