@@ -28,10 +28,9 @@
 #include <math.h>
 #include <stddef.h>
 #include "common.h"
+#include "loss_core.h"
 
 #pragma clang fp contract(off)
-
-#define RU3D_MAX_CLASSES 8
 
 typedef unsigned long long bd_u64;
 
@@ -92,11 +91,6 @@ static inline int bd_tile_shift(int L, int Z) {
     return s;
 }
 
-__device__ __forceinline__ int bd_label(const void* labels, int label_dtype, int64_t i) {
-    if (label_dtype == RU3D_LABEL_I64) return (int)((const int64_t*)labels)[i];
-    return (int)((const uint8_t*)labels)[i];
-}
-
 // --------------------------------------------------------------------------- pack
 // a wave takes one word a trip; words are numbered (n, a, b, w) with w fastest, so a wave that stays inside one sample
 // gathers the flag bits of its words in registers and hands them over once per slot when the sample ends
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(256) void bd_pack_kernel(const void* __restrict__ l
             seen_n = n;
         }
         const bool in = z < Z;
-        const int t = in ? bd_label(labels, label_dtype, row * Z + z) : -1;
+        const int t = in ? load_label(labels, label_dtype, row * Z + z) : -1;
         const bd_u64 valid = __ballot(in);
         nbad += __popcll(__ballot(in && (t < 0 || t >= C)));
         for (int k = 0; k < cl.K; k++) {
@@ -288,25 +282,6 @@ __global__ __launch_bounds__(BD_THREADS) void bd_x_kernel(const int* __restrict_
 }
 
 // --------------------------------------------------------------------------- the loss
-template <int C>
-__device__ __forceinline__ void bd_softmax(const float* __restrict__ z, int64_t stride_c, float (&p)[C]) {
-    float zz[C];
-#pragma unroll
-    for (int c = 0; c < C; c++) zz[c] = z[c * stride_c];
-    float m = zz[0];
-#pragma unroll
-    for (int c = 1; c < C; c++) m = fmaxf(m, zz[c]);
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        p[c] = expf(zz[c] - m);
-        se += p[c];
-    }
-    const float inv = 1.f / se;
-#pragma unroll
-    for (int c = 0; c < C; c++) p[c] *= inv;
-}
-
 // part[block] = sum over the block's voxels (grid-stride, the grid fixed by the shape) of sum_q w_q P_q phi_q
 template <int C>
 __global__ __launch_bounds__(256) void bd_loss_kernel(const float* __restrict__ logits, int64_t stride_n,
@@ -318,7 +293,7 @@ __global__ __launch_bounds__(256) void bd_loss_kernel(const float* __restrict__ 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t ni = i / V, vi = i - ni * V;
         float p[C];
-        bd_softmax<C>(logits + ni * stride_n + vi * stride_v, stride_c, p);
+        softmax_probs<C>(logits + ni * stride_n + vi * stride_v, stride_c, p);
 #pragma unroll
         for (int c = 0; c < C; c++) {
             const int slot = cl.slot[c];
@@ -374,7 +349,7 @@ __global__ __launch_bounds__(256) void bd_bwd_kernel(const float* __restrict__ l
         const int64_t ni = i / V, vi = i - ni * V;
         const int64_t base = ni * stride_n + vi * stride_v;
         float p[C], u[C];
-        bd_softmax<C>(logits + base, stride_c, p);
+        softmax_probs<C>(logits + base, stride_c, p);
         float su = 0.f;
 #pragma unroll
         for (int c = 0; c < C; c++) {
@@ -393,17 +368,6 @@ __global__ __launch_bounds__(256) void bd_bwd_kernel(const float* __restrict__ l
         }
     }
 }
-
-#define BD_DISPATCH_C(C, CALL)   \
-    switch (C) {                 \
-        case 2: CALL(2); break;  \
-        case 3: CALL(3); break;  \
-        case 4: CALL(4); break;  \
-        case 5: CALL(5); break;  \
-        case 6: CALL(6); break;  \
-        case 7: CALL(7); break;  \
-        default: CALL(8); break; \
-    }
 
 // --------------------------------------------------------------------------- host side
 static int bd_classes(const char* what, int num_classes, const int* classes, int num_selected, BdClasses* cl) {
@@ -543,7 +507,7 @@ extern "C" int ru3d_boundary_fwd(const float* logits, int64_t stride_n, int64_t 
 #define CALL(CC)                                                                                                  \
     hipLaunchKernelGGL(bd_loss_kernel<CC>, dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, stride_v, n, V, \
                        cl, wt, (const float*)phi, part)
-    BD_DISPATCH_C(num_classes, CALL)
+    RU3D_DISPATCH_C(2, num_classes, CALL)
 #undef CALL
     rc = ru3d_check_launch("boundary_loss");
     if (rc) return rc;
@@ -575,7 +539,7 @@ extern "C" int ru3d_boundary_bwd(const float* logits, int64_t stride_n, int64_t 
         hipLaunchKernelGGL((bd_bwd_kernel<CC, false>), dim3(bd_flat_blocks(total)), dim3(256), 0, st, logits,          \
                            stride_n, stride_c, stride_v, n, V, cl, (const BdState*)state, phi, grad_out, scale,        \
                            inv_count, dlogits)
-    BD_DISPATCH_C(num_classes, CALL)
+    RU3D_DISPATCH_C(2, num_classes, CALL)
 #undef CALL
     return ru3d_check_launch("boundary_bwd");
 }

@@ -16,9 +16,9 @@
 // - the scatter of a window's gradient to its extremal voxel written as a gather over the windows that contain u, in a
 // fixed order.  No atomics anywhere: two runs give the same bits.
 #include "common.h"
+#include "loss_core.h"
 #include <stddef.h>
 
-#define RU3D_MAX_CLASSES 8
 #define CD_MAX_ITER 64
 
 // the tile of one workgroup (256 threads: thread = (b, z) column of the tile, looping over a) and its halo
@@ -390,29 +390,6 @@ extern "C" int ru3d_soft_skeleton_bwd(const float* grad_out, int nvol, int A, in
 }
 
 // --------------------------------------------------------------------------- the loss
-template <int C>
-__device__ __forceinline__ void cd_softmax(const float* __restrict__ z, int64_t stride_c, float (&p)[C]) {
-    float zz[C];
-#pragma unroll
-    for (int c = 0; c < C; c++) zz[c] = z[c * stride_c];
-    float m = zz[0];
-#pragma unroll
-    for (int c = 1; c < C; c++) m = fmaxf(m, zz[c]);
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        p[c] = expf(zz[c] - m);
-        se += p[c];
-    }
-    const float inv = 1.f / se;
-#pragma unroll
-    for (int c = 0; c < C; c++) p[c] *= inv;
-}
-
-__device__ __forceinline__ int cd_label(const void* labels, int label_dtype, int64_t i) {
-    if (label_dtype == RU3D_LABEL_I64) return (int)((const int64_t*)labels)[i];
-    return (int)((const uint8_t*)labels)[i];
-}
 
 // P and G planes [n][slot][v] of the selected classes
 template <int C>
@@ -425,8 +402,8 @@ __global__ __launch_bounds__(256) void cd_softmax_kernel(const float* __restrict
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t ni = i / V, vi = i - ni * V;
         float p[C];
-        cd_softmax<C>(logits + ni * stride_n + vi * stride_v, stride_c, p);
-        const int t = cd_label(labels, label_dtype, i);
+        softmax_probs<C>(logits + ni * stride_n + vi * stride_v, stride_c, p);
+        const int t = load_label(labels, label_dtype, i);
 #pragma unroll
         for (int c = 0; c < C; c++) {
             const int slot = cl.slot[c];
@@ -454,7 +431,7 @@ __global__ __launch_bounds__(256) void cd_sums_kernel(const float* __restrict__ 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t ni = i / V, vi = i - ni * V;
         const int64_t o = (ni * cl.K + slot) * V + vi;
-        const int t = cd_label(labels, label_dtype, i);
+        const int t = load_label(labels, label_dtype, i);
         const float sp = SP[o], sg = SG[o];
         if (t == c) acc[0] += sp;
         acc[1] += sp;
@@ -483,7 +460,7 @@ struct CdParams {
 };
 
 // one workgroup: thread (g, q) adds the partials of quantity q over the blocks g, g + NG, ..; the NG group sums are then
-// added in group order (loss.hip's finalize)
+// added in group order (region_reduce_rows of loss_core.h)
 constexpr int CD_FIN_THREADS = 1024;
 __global__ __launch_bounds__(CD_FIN_THREADS) void cd_finalize_kernel(const double* __restrict__ part, int blocks,
                                                                      CdParams P, CdState* __restrict__ st,
@@ -555,7 +532,7 @@ __global__ __launch_bounds__(256) void cd_logits_bwd_kernel(const float* __restr
         const int64_t ni = i / V, vi = i - ni * V;
         const int64_t base = ni * stride_n + vi * stride_v;
         float p[C], u[C];
-        cd_softmax<C>(logits + base, stride_c, p);
+        softmax_probs<C>(logits + base, stride_c, p);
         float su = 0.f;
 #pragma unroll
         for (int c = 0; c < C; c++) {
@@ -578,17 +555,6 @@ __global__ __launch_bounds__(256) void cd_logits_bwd_kernel(const float* __restr
         }
     }
 }
-
-#define CD_DISPATCH_C(C, CALL)   \
-    switch (C) {                 \
-        case 2: CALL(2); break;  \
-        case 3: CALL(3); break;  \
-        case 4: CALL(4); break;  \
-        case 5: CALL(5); break;  \
-        case 6: CALL(6); break;  \
-        case 7: CALL(7); break;  \
-        default: CALL(8); break; \
-    }
 
 static int cd_classes(const char* what, int num_classes, const int* classes, int num_selected, CdClasses* cl) {
     RU3D_REQUIRE(num_classes >= 2 && num_classes <= RU3D_MAX_CLASSES, "%s: %d classes (2 .. %d)", what, num_classes,
@@ -640,7 +606,7 @@ extern "C" int ru3d_cldice_fwd(const float* logits, int64_t stride_n, int64_t st
 #define CALL(CC)                                                                                                 \
     hipLaunchKernelGGL(cd_softmax_kernel<CC>, dim3(cd_flat_blocks(total)), dim3(256), 0, st, logits, stride_n, \
                        stride_c, stride_v, labels, label_dtype, n, g.V, cl, P, G)
-    CD_DISPATCH_C(num_classes, CALL)
+    RU3D_DISPATCH_C(2, num_classes, CALL)
 #undef CALL
     rc = ru3d_check_launch("cldice_softmax");
     if (rc) return rc;
@@ -698,7 +664,7 @@ extern "C" int ru3d_cldice_bwd(const float* logits, int64_t stride_n, int64_t st
         hipLaunchKernelGGL((cd_logits_bwd_kernel<CC, false>), dim3(cd_flat_blocks(total)), dim3(256), 0, st, logits,   \
                            stride_n, stride_c, stride_v, n, g.V, cl, (const CdState*)state, (const float*)gx0, skel_g, \
                            grad_out, scale, dlogits)
-    CD_DISPATCH_C(num_classes, CALL)
+    RU3D_DISPATCH_C(2, num_classes, CALL)
 #undef CALL
     return ru3d_check_launch("cldice_logits_bwd");
 }

@@ -3,7 +3,7 @@
 // tensor.  Level l (shift s) never gets labels of its own: voxel (a, b, c) of that level reads label[a << s][b << s][c << s]
 // (label[:, ::2**s, ::2**s, ::2**s]: nearest-neighbour down-sampling with the integer step 2**s).
 //
-// Same arithmetic and precisions as loss_sums_kernel / loss_finalize_kernel / loss_bwd_kernel, level by level: float32 per
+// The arithmetic and precisions are loss_core.h's, shared with loss.hip's single-tensor kernels, level by level: float32 per
 // voxel, per-thread float32 partials -> wave shuffles -> LDS -> one float64 partial row per block -> a fixed-order finalize
 // by one workgroup (deterministic, no atomics, no host sync).  A block belongs to one level: the kernels' grid is the
 // concatenation of the levels' block ranges, and the level table with the ranges rides in the kernel arguments (the block
@@ -16,19 +16,12 @@
 // shift s >= 1 touches every 2**s-th label of every 2**s-th row - a strided read that wastes most of each line - but all
 // aux levels together hold at most 1/7 of level 0's voxels, so it is left as it is.
 #include "common.h"
-#include <stddef.h>
+#include "loss_core.h"
 
-#define RU3D_MAX_CLASSES 8
-
-// per level: the layout of loss.hip's LossState (sums, backward coefficients, loss, bad label count), so that level 0's
-// count of out-of-range labels sits where every fused loss keeps it
+// per level: the region loss's coefficients first, so that level 0's count of out-of-range labels (no other level counts)
+// sits where every fused loss keeps it
 struct DsLevelState {
-    double sums[4][RU3D_MAX_CLASSES];  // tp, sp, sg, foc
-    float qa[RU3D_MAX_CLASSES];        // dL/dp_c = qa_c * g_c + qb_c  (+ focal term)
-    float qb[RU3D_MAX_CLASSES];
-    float qf[RU3D_MAX_CLASSES];
-    float loss;
-    int bad_labels;                    // level 0 only
+    RegionCoef r;
     float weight;                      // w_l of this forward
     int pad;
 };
@@ -64,44 +57,6 @@ struct DsParams {
     double nv[RU3D_DS_MAX_LEVELS];
 };
 
-__device__ __forceinline__ int ds_load_label(const void* labels, int label_dtype, int64_t i) {
-    if (label_dtype == RU3D_LABEL_I64) return (int)((const int64_t*)labels)[i];
-    return (int)((const uint8_t*)labels)[i];
-}
-
-__device__ __forceinline__ float ds_pow_gamma(float base, float gamma) {
-    if (gamma == 2.f) return base * base;
-    if (gamma == 1.f) return base;
-    if (gamma == 0.f) return 1.f;
-    return powf(base, gamma);
-}
-
-// probabilities + log-probabilities of one voxel (softmax over C, sigmoid for C == 1): loss.hip's voxel_probs
-template <int C>
-__device__ __forceinline__ void ds_voxel_probs(const float* __restrict__ z, int64_t stride_c, float (&p)[C], float (&lp)[C]) {
-    float zz[C];
-#pragma unroll
-    for (int c = 0; c < C; c++) zz[c] = z[c * stride_c];
-    if (C == 1) {
-        const float pr = 1.f / (1.f + __expf(-zz[0]));
-        p[0] = pr;
-        lp[0] = logf(pr);
-        return;
-    }
-    float m = zz[0];
-#pragma unroll
-    for (int c = 1; c < C; c++) m = fmaxf(m, zz[c]);
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; c++) se += expf(zz[c] - m);
-    const float lse = logf(se);
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        lp[c] = zz[c] - m - lse;
-        p[c] = expf(lp[c]);
-    }
-}
-
 // the level a block works on (ranges are consecutive and not empty)
 __device__ __forceinline__ int ds_level_of(const DsArgs& A, int block) {
     int l = 0;
@@ -135,126 +90,31 @@ __global__ __launch_bounds__(256) void ds_sums_kernel(DsArgs A, float gamma, dou
     for (int64_t i = (int64_t)(blockIdx.x - first) * 256 + threadIdx.x; i < total; i += (int64_t)count * 256) {
         const int64_t ni = i / Lv.v, vi = i - ni * Lv.v;
         float p[C], lp[C];
-        ds_voxel_probs<C>(Lv.logits + ni * Lv.stride_n + vi * Lv.stride_v, Lv.stride_c, p, lp);
-        int t = ds_load_label(A.labels, A.label_dtype, ds_label_index(A, Lv, ni, vi));
-        if (t < 0 || t >= C) {
-            bad++;
-            t = -1;
-        }
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            sp[c] += p[c];
-            if (c == t) {
-                tp[c] += p[c];
-                sg[c] += 1.f;
-                fo[c] += -ds_pow_gamma(1.f - p[c], gamma) * lp[c];
-            }
-        }
+        voxel_probs<C>(Lv.logits + ni * Lv.stride_n + vi * Lv.stride_v, Lv.stride_c, p, lp);
+        const int t = load_label(A.labels, A.label_dtype, ds_label_index(A, Lv, ni, vi));
+        region_add<C>(p, lp, t, gamma, tp, sp, sg, fo, bad);
     }
-    __shared__ double sh[4][4 * C + 1];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        const float a = wave_sum(tp[c]), b = wave_sum(sp[c]), d = wave_sum(sg[c]), e = wave_sum(fo[c]);
-        if (lane == 0) {
-            sh[wid][0 * C + c] = a;
-            sh[wid][1 * C + c] = b;
-            sh[wid][2 * C + c] = d;
-            sh[wid][3 * C + c] = e;
-        }
-    }
-    const float fb = wave_sum((float)bad);
-    if (lane == 0) sh[wid][4 * C] = fb;
-    __syncthreads();
-    if (threadIdx.x < 4 * C + 1) {
-        const int q = threadIdx.x;
-        const double s = sh[0][q] + sh[1][q] + sh[2][q] + sh[3][q];
-        // partial layout: [block][4*MAX + 1]
-        const int dst = (q == 4 * C) ? 4 * RU3D_MAX_CLASSES : (q / C) * RU3D_MAX_CLASSES + (q % C);
-        part[(int64_t)blockIdx.x * (4 * RU3D_MAX_CLASSES + 1) + dst] = s;
-    }
+    region_write_row<C>(tp, sp, sg, fo, bad, part + (int64_t)blockIdx.x * REGION_Q);
 }
 
-// One workgroup of 1024 threads, level after level: loss_finalize_kernel's reduction of the level's partial rows (thread
-// (g, q) sums quantity q over the rows g, g + NG, ..., then the NG group sums are added in group order), thread 0 turns the
-// sums into the level's loss and backward coefficients.  block: float32 [0 .. 7] the level weights (read),
-// [8 .. 15] the levels' losses and [16] the total (written).
-constexpr int DS_LF_THREADS = 1024;
-__global__ __launch_bounds__(DS_LF_THREADS) void ds_finalize_kernel(const double* __restrict__ part, DsParams P,
-                                                                    float* __restrict__ block, DsState* __restrict__ st,
-                                                                    float* __restrict__ loss_out) {
-    constexpr int Q = 4 * RU3D_MAX_CLASSES + 1;
-    constexpr int NG = DS_LF_THREADS / Q;
-    __shared__ double red[NG][Q];
-    __shared__ double tot[Q];
+// One workgroup of REGION_LF_THREADS, level after level: the fixed-order reduction of the level's partial rows, then
+// thread 0 turns the sums into the level's loss and backward coefficients.  block: float32 [0 .. 7] the level weights
+// (read), [8 .. 15] the levels' losses and [16] the total (written).
+__global__ __launch_bounds__(REGION_LF_THREADS) void ds_finalize_kernel(const double* __restrict__ part, DsParams P,
+                                                                        float* __restrict__ block, DsState* __restrict__ st,
+                                                                        float* __restrict__ loss_out) {
+    __shared__ double red[REGION_LF_GROUPS][REGION_Q];
+    __shared__ double tot[REGION_Q];
     double total = 0.0;      // thread 0's
     for (int l = 0; l < P.levels; l++) {
-        const double* pl = part + (int64_t)P.blocks[l] * Q;
-        const int blocks = P.blocks[l + 1] - P.blocks[l];
-        const int g = threadIdx.x / Q, q = threadIdx.x % Q;
-        if (g < NG) {
-            double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-            int b = g;
-            for (; b + 3 * NG < blocks; b += 4 * NG) {
-                s0 += pl[(int64_t)b * Q + q];
-                s1 += pl[(int64_t)(b + NG) * Q + q];
-                s2 += pl[(int64_t)(b + 2 * NG) * Q + q];
-                s3 += pl[(int64_t)(b + 3 * NG) * Q + q];
-            }
-            for (; b < blocks; b += NG) s0 += pl[(int64_t)b * Q + q];
-            red[g][q] = (s0 + s1) + (s2 + s3);
-        }
-        __syncthreads();
-        if (threadIdx.x < Q) {
-            const int qq = threadIdx.x, c = qq % RU3D_MAX_CLASSES;
-            double t = 0.0;
-            if (!(qq < 4 * RU3D_MAX_CLASSES && c >= P.C))
-                for (int k = 0; k < NG; k++) t += red[k][qq];
-            tot[qq] = t;
-        }
-        __syncthreads();
+        region_reduce_rows(part + (int64_t)P.blocks[l] * REGION_Q, P.blocks[l + 1] - P.blocks[l], P.C, red, tot);
         if (threadIdx.x == 0) {
             DsLevelState* sl = &st->lev[l];
-            const int C = P.C;
-            double wsum = 0.0;
-            for (int c = 0; c < C; c++) wsum += fabs((double)P.w[c]);
-            if (wsum < 1e-12) wsum = 1e-12;  // F.normalize eps
-            const double NV = P.nv[l];
-            const bool has_dice = P.kind != RU3D_LOSS_FOCAL;
-            const bool has_focal = (P.kind == RU3D_LOSS_HYBIRD) || (P.kind == RU3D_LOSS_FOCAL);
-            double loss = 0.0;
-            for (int c = 0; c < RU3D_MAX_CLASSES; c++) {
-                sl->qa[c] = sl->qb[c] = sl->qf[c] = 0.f;
-                for (int k = 0; k < 4; k++) sl->sums[k][c] = tot[k * RU3D_MAX_CLASSES + c];
-            }
-            for (int c = 0; c < C; c++) {
-                const double w = (double)P.w[c] / wsum;
-                const double tp = tot[0 * RU3D_MAX_CLASSES + c], sp = tot[1 * RU3D_MAX_CLASSES + c],
-                             sg = tot[2 * RU3D_MAX_CLASSES + c], fo = tot[3 * RU3D_MAX_CLASSES + c];
-                double term = 0.0;
-                if (has_dice) {
-                    const double a = P.alpha, b = P.beta, s = P.smooth;
-                    const double den = tp + a * (sg - tp) + b * (sp - tp) + s;
-                    const double dice = (tp + s) / den;
-                    term += 1.0 - dice;
-                    // d dice / d p_c(v) = g * A - B
-                    const double A = (den - (tp + s) * (1.0 - a - b)) / (den * den);
-                    const double B = (tp + s) * b / (den * den);
-                    sl->qa[c] = (float)(-w * A);
-                    sl->qb[c] = (float)(w * B);
-                }
-                if (has_focal) {
-                    term += (double)C * fo / NV;
-                    sl->qf[c] = (float)(w * (double)C / NV);
-                }
-                loss += w * term;
-            }
             // out-of-range labels are counted where every label is read once: on level 0
-            sl->bad_labels = (l == 0) ? (int)tot[4 * RU3D_MAX_CLASSES] : 0;
-            if (sl->bad_labels > 0) loss = nan("");  // F.one_hot would have raised (loss.py:27)
+            const int bad = (l == 0) ? (int)tot[4 * RU3D_MAX_CLASSES] : 0;
+            const double loss = region_coefficients(P.kind, P.C, P.w, P.alpha, P.beta, P.smooth, P.nv[l], tot, bad, &sl->r);
             const float wl = block[l];
             sl->weight = wl;
-            sl->loss = (float)loss;
             sl->pad = 0;
             block[RU3D_DS_MAX_LEVELS + l] = (float)loss;
             total += (double)wl * loss;
@@ -276,50 +136,17 @@ __global__ __launch_bounds__(256) void ds_bwd_kernel(DsArgs A, float gamma, cons
     const int first = Lv.block0;
     const int count = ((l + 1 < A.levels) ? A.lev[l + 1].block0 : A.nblocks) - first;
     const DsLevelState* sl = &st->lev[l];
-    float qa[C], qb[C], qf[C];
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        qa[c] = sl->qa[c];
-        qb[c] = sl->qb[c];
-        qf[c] = sl->qf[c];
-    }
+    const RegionGrad<C> grad(&sl->r);
     const float go = (grad_out ? grad_out[0] : 1.f) * sl->weight;
     const int64_t total = (int64_t)A.n * Lv.v;
     for (int64_t i = (int64_t)(blockIdx.x - first) * 256 + threadIdx.x; i < total; i += (int64_t)count * 256) {
         const int64_t ni = i / Lv.v, vi = i - ni * Lv.v;
         const int64_t base = ni * Lv.stride_n + vi * Lv.stride_v;
-        float p[C], lp[C], u[C];
-        ds_voxel_probs<C>(Lv.logits + base, Lv.stride_c, p, lp);
-        const int t = ds_load_label(A.labels, A.label_dtype, ds_label_index(A, Lv, ni, vi));
-        float su = 0.f;
+        float p[C], lp[C], d[C];
+        voxel_probs<C>(Lv.logits + base, Lv.stride_c, p, lp);
+        grad.voxel(p, lp, load_label(A.labels, A.label_dtype, ds_label_index(A, Lv, ni, vi)), gamma, d);
 #pragma unroll
-        for (int c = 0; c < C; c++) {
-            // u_c = p_c * dL/dp_c, written so that p -> 0 stays finite
-            float uc = p[c] * qb[c];
-            if (c == t) {
-                const float om = 1.f - p[c];
-                uc += p[c] * qa[c];
-                float dfp;  // p * d/dp[ -(1-p)^g log p ] = g (1-p)^(g-1) p log p - (1-p)^g
-                if (gamma == 2.f)
-                    dfp = 2.f * om * p[c] * lp[c] - om * om;
-                else if (gamma == 0.f)
-                    dfp = -1.f;
-                else
-                    dfp = gamma * powf(om, gamma - 1.f) * p[c] * lp[c] - powf(om, gamma);
-                uc += qf[c] * dfp;
-            }
-            u[c] = uc;
-            su += uc;
-        }
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            float d;
-            if (C == 1)
-                d = u[0] * (1.f - p[0]);  // sigmoid: dp/dz = p (1 - p)
-            else
-                d = u[c] - p[c] * su;
-            Lv.dlogits[base + c * Lv.stride_c] = d * go;
-        }
+        for (int c = 0; c < C; c++) Lv.dlogits[base + c * Lv.stride_c] = d[c] * go;
     }
 }
 
@@ -393,27 +220,15 @@ static int ds_fwd_blocks(const ru3d_ds_level* levels, int num_levels, int n) {
 }
 
 extern "C" size_t ru3d_ds_state_bytes(void) { return sizeof(DsState); }
-extern "C" size_t ru3d_ds_state_bad_labels_offset(void) { return offsetof(DsState, lev) + offsetof(DsLevelState, bad_labels); }
+extern "C" size_t ru3d_ds_state_bad_labels_offset(void) { return offsetof(DsState, lev) + offsetof(DsLevelState, r) + offsetof(RegionCoef, bad_labels); }
 extern "C" size_t ru3d_ds_block_bytes(void) { return (2 * RU3D_DS_MAX_LEVELS + 1) * sizeof(float); }
 
 extern "C" size_t ru3d_ds_loss_workspace_bytes(const ru3d_ds_level* levels, int num_levels, int n) {
     if (!levels || num_levels < 1 || num_levels > RU3D_DS_MAX_LEVELS || n < 1) return 0;
     for (int l = 0; l < num_levels; l++)
         if (levels[l].d < 1 || levels[l].h < 1 || levels[l].w < 1) return 0;
-    return (size_t)ds_fwd_blocks(levels, num_levels, n) * (4 * RU3D_MAX_CLASSES + 1) * sizeof(double);
+    return (size_t)ds_fwd_blocks(levels, num_levels, n) * REGION_Q * sizeof(double);
 }
-
-#define DS_DISPATCH_C(C, CALL)   \
-    switch (C) {                 \
-        case 1: CALL(1); break;  \
-        case 2: CALL(2); break;  \
-        case 3: CALL(3); break;  \
-        case 4: CALL(4); break;  \
-        case 5: CALL(5); break;  \
-        case 6: CALL(6); break;  \
-        case 7: CALL(7); break;  \
-        default: CALL(8); break; \
-    }
 
 extern "C" int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, const void* labels, int label_dtype, int n,
                                 int D, int H, int W, int num_classes, int kind, float gamma, const float* weight_v,
@@ -429,11 +244,11 @@ extern "C" int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, con
     int rc = ds_fill_args(A, levels, nullptr, num_levels, labels, label_dtype, n, D, H, W, DS_FWD_PER_BLOCK, DS_FWD_CAP,
                           "ds_loss_fwd");
     if (rc) return rc;
-    RU3D_REQUIRE(ws_bytes >= (size_t)A.nblocks * (4 * RU3D_MAX_CLASSES + 1) * sizeof(double),
+    RU3D_REQUIRE(ws_bytes >= (size_t)A.nblocks * REGION_Q * sizeof(double),
                  "ds_loss_fwd: workspace too small");
     hipStream_t st = as_stream(stream);
 #define CALL(CC) hipLaunchKernelGGL(ds_sums_kernel<CC>, dim3(A.nblocks), dim3(256), 0, st, A, gamma, (double*)ws)
-    DS_DISPATCH_C(num_classes, CALL)
+    RU3D_DISPATCH_C(1, num_classes, CALL)
 #undef CALL
     rc = ru3d_check_launch("ds_loss_sums");
     if (rc) return rc;
@@ -448,7 +263,7 @@ extern "C" int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, con
     for (int c = 0; c < RU3D_MAX_CLASSES; c++) P.w[c] = (c < num_classes) ? (weight_v ? weight_v[c] : 1.f) : 0.f;
     for (int l = 0; l <= RU3D_DS_MAX_LEVELS; l++) P.blocks[l] = (l < num_levels) ? A.lev[l].block0 : A.nblocks;
     for (int l = 0; l < RU3D_DS_MAX_LEVELS; l++) P.nv[l] = (l < num_levels) ? (double)n * (double)A.lev[l].v : 1.0;
-    hipLaunchKernelGGL(ds_finalize_kernel, dim3(1), dim3(DS_LF_THREADS), 0, st, (const double*)ws, P, block,
+    hipLaunchKernelGGL(ds_finalize_kernel, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)ws, P, block,
                        (DsState*)state, loss_out);
     return ru3d_check_launch("ds_loss_finalize");
 }
@@ -466,7 +281,7 @@ extern "C" int ru3d_ds_loss_bwd(const ru3d_ds_level* levels, void* const* dlogit
     hipStream_t st = as_stream(stream);
 #define CALL(CC) \
     hipLaunchKernelGGL(ds_bwd_kernel<CC>, dim3(A.nblocks), dim3(256), 0, st, A, gamma, (const DsState*)state, grad_out)
-    DS_DISPATCH_C(num_classes, CALL)
+    RU3D_DISPATCH_C(1, num_classes, CALL)
 #undef CALL
     return ru3d_check_launch("ds_loss_bwd");
 }

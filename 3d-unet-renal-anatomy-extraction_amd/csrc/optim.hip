@@ -1,13 +1,14 @@
-// The optimisation recipe around the fused Adam of loss.hip: the global L2 norm of the gradients with the clipping
-// coefficient of torch.nn.utils.clip_grad_norm_, SGD with (Nesterov) momentum and weight decay, AdamW, and Adam with a
-// clipped gradient.  Every kernel walks the ru3d_adam_tensor table through the (tensor, chunk) block map of
-// ru3d_adam_multi: 256 threads, chunk_elems a multiple of 1024, an aligned f32x4 path and a scalar path for tails and
-// for tensors that do not sit on 16-byte boundaries, rows with a null `grad` skipped.
+// The optimisers and what surrounds them: fused Adam (single tensor, multi-tensor, captured, and under the on-device fp16
+// loss scaler), the global L2 norm of the gradients with the clipping coefficient of torch.nn.utils.clip_grad_norm_, SGD
+// with (Nesterov) momentum and weight decay, AdamW, Adam with a clipped gradient, and the inf / nan check of loss scaling.
+// Every multi-tensor kernel walks the ru3d_adam_tensor table through the (tensor, chunk) block map of ru3d_adam_multi:
+// 256 threads, chunk_elems a multiple of 1024, an aligned f32x4 path and a scalar path for tails and for tensors that
+// do not sit on 16-byte boundaries, rows with a null `grad` skipped.
 //
 // Bits: each update rule is ONE per-element function compiled with floating-point contraction off, called from the
 // vector path and from the scalar path, by the kernel that takes its scalars as arguments and by the one that reads
-// them from the 8-float device row of a captured step - the four give identical bits (adam_multi_body's lesson, see
-// loss.hip).  No floating-point atomics: the norm is a float64 sum of float64 squares, thread -> wave butterfly -> the
+// them from the 8-float device row of a captured step - the four give identical bits (adam_multi_body's lesson,
+// below).  No floating-point atomics: the norm is a float64 sum of float64 squares, thread -> wave butterfly -> the
 // four waves of a block in order -> one workgroup over the per-block partials in order.
 #include "common.h"
 #include <stddef.h>
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(256) void sgd_multi_dev_kernel(const ru3d_adam_tens
 }
 
 // --------------------------------------------------------------------------- Adam (clipped) and AdamW
-// adam_multi_body's recurrence (loss.hip) on gh = g * gscale * coef; kDecay: torch.optim.AdamW's p *= 1 - lr * wd first.
+// adam_multi_body's recurrence (below) on gh = g * gscale * coef; kDecay: torch.optim.AdamW's p *= 1 - lr * wd first.
 template <bool kDecay>
 struct AdamRule {
     float b1, b2, eps, step, bc2_sqrt, gscale, keep;
@@ -163,6 +164,222 @@ __global__ __launch_bounds__(256) void adamw_multi_dev_kernel(const ru3d_adam_te
     multi_body(tensors, block_map, chunk_elems,
                adam_rule<true>(hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], sqrtf(hyper[5]), hyper[6], hyper[7]),
                coef);
+}
+
+// --------------------------------------------------------------------------- Adam: single tensor, unclipped multi-tensor
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v, int64_t count,
+                                                   float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                                                   float gscale) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) {
+        const float gi = g[i] * gscale;
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        // torch.optim.Adam: denom = sqrt(v)/sqrt(bc2) + eps; p -= lr/bc1 * m/denom
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        p[i] -= (lr / bc1) * (mi / denom);
+    }
+}
+
+extern "C" int ru3d_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t count,
+                              float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2,
+                              float grad_scale, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(param && grad && exp_avg && exp_avg_sq && count > 0, "adam_step: bad argument");
+    int64_t b = (count + 1023) / 1024;
+    if (b > 4096) b = 4096;
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)b), dim3(256), 0, as_stream(stream), param, grad, exp_avg,
+                       exp_avg_sq, count, lr, beta1, beta2, eps, bias_corr1, sqrtf(bias_corr2), grad_scale);
+    return ru3d_check_launch("adam_step");
+}
+
+// multi-tensor form: one launch for the whole model (device-side tensor table + block map)
+__device__ __forceinline__ void adam_multi_body(const ru3d_adam_tensor* __restrict__ tensors,
+                                                const int32_t* __restrict__ block_map, int chunk_elems, float lr,
+                                                float b1, float b2, float eps, float bc1, float bc2_sqrt, float gscale) {
+    // no fused multiply-adds here: this body is compiled into two kernels (scalars as arguments / from device memory) and
+    // into a vector and a scalar path - left to the compiler, the contraction of b2 * v + (1 - b2) * g * g differed
+    // between them by one ulp, on the one parameter whose length is not a multiple of 4 (the head's bias)
+#pragma clang fp contract(off)
+    const ru3d_adam_tensor t = tensors[block_map[2 * blockIdx.x]];
+    if (!t.grad) return;
+    const int64_t begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
+    int64_t end = begin + chunk_elems;
+    if (end > t.count) end = t.count;
+    const float step = lr / bc1;
+    const bool vec = ((((uintptr_t)t.param) | ((uintptr_t)t.grad) | ((uintptr_t)t.exp_avg) | ((uintptr_t)t.exp_avg_sq)) & 15) == 0;
+    int64_t i = begin + (int64_t)threadIdx.x * 4;
+    if (vec) {
+        for (; i + 3 < end; i += 1024) {
+            f32x4 p = *reinterpret_cast<const f32x4*>(t.param + i);
+            const f32x4 g = *reinterpret_cast<const f32x4*>(t.grad + i);
+            f32x4 m = *reinterpret_cast<const f32x4*>(t.exp_avg + i);
+            f32x4 v = *reinterpret_cast<const f32x4*>(t.exp_avg_sq + i);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const float gi = g[k] * gscale;
+                m[k] = b1 * m[k] + (1.f - b1) * gi;
+                v[k] = b2 * v[k] + (1.f - b2) * gi * gi;
+                p[k] -= step * (m[k] / (sqrtf(v[k]) / bc2_sqrt + eps));
+            }
+            *reinterpret_cast<f32x4*>(t.param + i) = p;
+            *reinterpret_cast<f32x4*>(t.exp_avg + i) = m;
+            *reinterpret_cast<f32x4*>(t.exp_avg_sq + i) = v;
+        }
+    }
+    // scalar tail (or unaligned tensors): this thread's remaining elements of its 4-wide slots
+    for (; i < end; i += 1024)
+        for (int k = 0; k < 4 && i + k < end; k++) {
+            const float gi = t.grad[i + k] * gscale;
+            const float mi = b1 * t.exp_avg[i + k] + (1.f - b1) * gi;
+            const float vi = b2 * t.exp_avg_sq[i + k] + (1.f - b2) * gi * gi;
+            t.exp_avg[i + k] = mi;
+            t.exp_avg_sq[i + k] = vi;
+            t.param[i + k] -= step * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+        }
+}
+
+
+__global__ __launch_bounds__(256) void adam_multi_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                         const int32_t* __restrict__ block_map, int chunk_elems,
+                                                         float lr, float b1, float b2, float eps, float bc1,
+                                                         float bc2_sqrt, float gscale) {
+    adam_multi_body(tensors, block_map, chunk_elems, lr, b1, b2, eps, bc1, bc2_sqrt, gscale);
+}
+
+// the per-step scalars from device memory (a captured launch: see ru3d.h)
+__global__ __launch_bounds__(256) void adam_multi_dev_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                             const int32_t* __restrict__ block_map, int chunk_elems,
+                                                             const float* __restrict__ hyper) {
+    adam_multi_body(tensors, block_map, chunk_elems, hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[7], hyper[6]);
+}
+
+extern "C" int ru3d_adam_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                               float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2,
+                               float grad_scale, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(tensors && block_map && nblocks > 0 && chunk_elems >= 1024 && (chunk_elems % 1024) == 0,
+                 "adam_multi: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
+                       chunk_elems, lr, beta1, beta2, eps, bias_corr1, sqrtf(bias_corr2), grad_scale);
+    return ru3d_check_launch("adam_multi");
+}
+
+extern "C" int ru3d_adam_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                   int chunk_elems, const float* hyper, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(tensors && block_map && hyper && nblocks > 0 && chunk_elems >= 1024 && (chunk_elems % 1024) == 0,
+                 "adam_multi_dev: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(adam_multi_dev_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
+                       block_map, chunk_elems, hyper);
+    return ru3d_check_launch("adam_multi_dev");
+}
+
+// ---- fp16 training inside a captured step: the loss scaler lives on the device (ru3d_amp_state, see ru3d.h).  The update
+// kernel skips itself when the gradient check found an overflow, takes 1 / scale and the number of steps really taken
+// from the state block (bias corrections from that count), and a one-thread kernel then moves the scaler: halve + reset
+// on overflow, count a clean step and double after `growth_interval` of them otherwise - apex's schedule
+// (reference trainer.py:492-493, 538-542), without the per-step read-back that kept the fp16 step out of a hipGraph.
+__global__ __launch_bounds__(256) void adam_multi_amp_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                             const int32_t* __restrict__ block_map, int chunk_elems,
+                                                             const float* __restrict__ hyper,
+                                                             const ru3d_amp_state* __restrict__ amp) {
+    if (amp->found_inf != 0.f) return;                                   // overflow: the step is skipped
+    const int t = __float_as_int(hyper[5]) + amp->steps + 1;             // Adam step number of this update
+    // the betas in double (float value + residual in the slots the captured amp launch does not use otherwise): the bias
+    // corrections then equal the host's `1 - beta ** t` to the last bit or two
+    const double b1d = (double)hyper[1] + (double)hyper[4], b2d = (double)hyper[2] + (double)hyper[7];
+    const double bc1 = 1.0 - pow(b1d, (double)t), bc2 = 1.0 - pow(b2d, (double)t);
+    adam_multi_body(tensors, block_map, chunk_elems, hyper[0], hyper[1], hyper[2], hyper[3], (float)bc1, sqrtf((float)bc2),
+                    amp->inv_scale);
+}
+
+__global__ void amp_update_kernel(ru3d_amp_state* amp, float growth, float backoff, int interval, float min_scale,
+                                  float max_scale) {
+    if (threadIdx.x || blockIdx.x) return;
+    if (amp->found_inf != 0.f) {
+        amp->scale = fmaxf(amp->scale * backoff, min_scale);
+        amp->tracker = 0;
+        amp->skipped += 1;
+    } else {
+        amp->steps += 1;
+        amp->tracker += 1;
+        if (amp->tracker >= interval) {
+            amp->scale = fminf(amp->scale * growth, max_scale);
+            amp->tracker = 0;
+        }
+    }
+    amp->inv_scale = 1.f / amp->scale;
+    amp->found_inf = 0.f;
+}
+
+extern "C" int ru3d_adam_multi_amp(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                                   const float* hyper, const ru3d_amp_state* amp, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(tensors && block_map && hyper && amp && nblocks > 0 && chunk_elems >= 1024 && (chunk_elems % 1024) == 0,
+                 "adam_multi_amp: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(adam_multi_amp_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
+                       chunk_elems, hyper, amp);
+    return ru3d_check_launch("adam_multi_amp");
+}
+
+extern "C" int ru3d_amp_update(ru3d_amp_state* amp, float growth_factor, float backoff_factor, int growth_interval,
+                               float min_scale, float max_scale, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(amp && growth_factor >= 1.f && backoff_factor > 0.f && backoff_factor <= 1.f && growth_interval > 0 &&
+                     min_scale > 0.f && max_scale >= min_scale, "amp_update: bad argument");
+    hipLaunchKernelGGL(amp_update_kernel, dim3(1), dim3(64), 0, as_stream(stream), amp, growth_factor, backoff_factor,
+                       growth_interval, min_scale, max_scale);
+    return ru3d_check_launch("amp_update");
+}
+
+// --------------------------------------------------------------------------- loss scaling (fp16 storage)
+// Dynamic loss scaling of the reference's mixed-precision mode (apex O1, trainer.py:492-493, 538-542): gradients are
+// computed on `scale * loss`; before the optimizer step every gradient is checked for inf / nan (an overflow skips the
+// step and halves the scale) and multiplied by 1 / scale.  Same table / block-map layout as ru3d_adam_multi; only the
+// `grad` and `count` fields are read.  scale == 1 checks without writing.
+__global__ __launch_bounds__(256) void grad_scale_check_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                               const int32_t* __restrict__ block_map, int chunk_elems,
+                                                               float scale, float* __restrict__ found_inf) {
+    const ru3d_adam_tensor t = tensors[block_map[2 * blockIdx.x]];
+    if (!t.grad) return;
+    float* g = const_cast<float*>(t.grad);
+    const int64_t begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
+    int64_t end = begin + chunk_elems;
+    if (end > t.count) end = t.count;
+    const bool write = scale != 1.f;
+    bool bad = false;
+    int64_t i = begin + (int64_t)threadIdx.x * 4;
+    if ((((uintptr_t)g) & 15) == 0) {
+        for (; i + 3 < end; i += 1024) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                bad = bad || !(fabsf(v[k]) <= 3.402823466e38f);   // false for inf and nan
+                v[k] *= scale;
+            }
+            if (write) *reinterpret_cast<f32x4*>(g + i) = v;
+        }
+    }
+    for (; i < end; i += 1024)
+        for (int k = 0; k < 4 && i + k < end; k++) {
+            const float v = g[i + k];
+            bad = bad || !(fabsf(v) <= 3.402823466e38f);
+            if (write) g[i + k] = v * scale;
+        }
+    if (__any(bad) && (threadIdx.x & 63) == 0) *found_inf = 1.f;   // every writer stores the same value
+}
+
+extern "C" int ru3d_grad_scale_check(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                     int chunk_elems, float scale, float* found_inf, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(tensors && block_map && found_inf && nblocks > 0 && chunk_elems >= 1024 && (chunk_elems % 1024) == 0,
+                 "grad_scale_check: bad argument (chunk_elems must be a positive multiple of 1024)");
+    hipLaunchKernelGGL(grad_scale_check_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
+                       block_map, chunk_elems, scale, found_inf);
+    return ru3d_check_launch("grad_scale_check");
 }
 
 // --------------------------------------------------------------------------- gradient norm

@@ -7,7 +7,8 @@ not used by the reference and are rejected here).  The update rule and the state
 Parameters whose `.grad` is None are skipped, exactly like torch (the never-used skip_conv weights and the
 conv biases in front of InstanceNorm).
 
-`SGD` (momentum, Nesterov, weight decay) and `AdamW` follow torch.optim.SGD / torch.optim.AdamW the same way (csrc/optim.hip),
+`SGD` (momentum, Nesterov, weight decay) and `AdamW` follow torch.optim.SGD / torch.optim.AdamW the same way (all of them in
+csrc/optim.hip),
 and all three take `max_grad_norm`: the global L2 norm of the gradients of ALL param groups is reduced on the device
 in a fixed order (float64, no atomics), torch.nn.utils.clip_grad_norm_'s coefficient stays in device memory, and the
 update kernels multiply it in while they read the gradient - a clipped step reads the gradients once more and writes

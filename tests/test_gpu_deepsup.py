@@ -5,7 +5,7 @@ Trainer.
 Loss reference: softmax in float64 on the float32 logits of every level, the formulas of csrc/loss.hip's header comment
 against loss.downsample_labels(target, l), total = sum_l w_l loss_l, the gradients by float64 autograd - as
 tests/test_gpu_loss_kernels.py writes its own.  Tolerances are that file's (its header derives them for this arithmetic,
-which deepsup.hip repeats level by level): value 2e-6 * max(1, |ref|); gradient, element by element,
+which deepsup.hip runs level by level): value 2e-6 * max(1, |ref|); gradient, element by element,
 2e-5 * |ref| + 1e-6 * max|ref|.  Both are applied PER LEVEL - every level's loss to its own reference, every level's
 gradient to the maximum of its own reference gradient - so that a coarse level's error cannot hide below level 0's.
 
@@ -191,11 +191,18 @@ def test_single_tensor_is_the_base_loss():
     xs, y = operands(2, 3, (20, 12, 10), 1, 41)
     base = L.HybirdLoss(weight_v=[0.2, 0.3, 0.5])
     crit = check("HybirdLoss", xs, y, "one level", weight_v=[0.2, 0.3, 0.5])
-    plain = base(xs[0], y)
-    assert_value(crit(xs[0], y), float(plain), "DeepSupervisionLoss(single tensor) vs HybirdLoss")
-    assert_value(crit([xs[0]], y), float(plain), "DeepSupervisionLoss([tensor]) vs HybirdLoss")
+    # one level runs the same arithmetic (csrc/loss_core.h) over the same partition in the same finalize order, and the
+    # level weight 1.0 multiplies exactly: not close to the base loss but equal to it, value and gradient
+    plain, gplain = run(base, xs, y)
     # explicit weights are for the list; the single tensor keeps weight 1 (validation with the training criterion)
-    assert_value(L.DeepSupervisionLoss(base, weights=[0.6, 0.4])(xs[0], y), float(plain), "single tensor, explicit weights")
+    cases = (("DeepSupervisionLoss(single tensor)", crit, lambda x: x), ("DeepSupervisionLoss([tensor])", crit, lambda x: [x]),
+             ("single tensor, explicit weights", L.DeepSupervisionLoss(base, weights=[0.6, 0.4]), lambda x: x))
+    for what, c, wrap in cases:
+        x = xs[0].detach().requires_grad_(True)
+        v = c(wrap(x), y)
+        v.backward()
+        assert torch.equal(v.detach(), plain), "%s: value %.9g, HybirdLoss %.9g" % (what, float(v.detach()), float(plain))
+        assert torch.equal(x.grad, gplain[0]), "%s: gradient differs from HybirdLoss's" % what
 
 
 def test_set_weights_takes_effect_in_place():

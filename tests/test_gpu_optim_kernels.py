@@ -1,4 +1,4 @@
-"""The optimizer and loss-scaling kernels of csrc/loss.hip, one at a time, against float64 references on a real MI355X:
+"""The optimizer and loss-scaling kernels of csrc/optim.hip, one at a time, against float64 references on a real MI355X:
 
   ru3d_adam_multi        (through optim.Adam)   vector body / scalar tail, several 16384-element chunks, a row without a
                                                 gradient, unaligned tensors, grad_scale, 60 consecutive step numbers
