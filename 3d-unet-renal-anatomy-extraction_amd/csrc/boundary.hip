@@ -16,8 +16,8 @@
 //                      integer atomicAdd.  A volume whose flag is not 3 is degenerate:
 //                      its maps are zero and the two scan kernels skip it.
 //   bd_zy_kernel       Z and B passes of one a-plane and one tile of T columns of z.  Z pass: the nearest bit of the
-//                      other kind below and above z by clz / ctz over the packed row (the row XOR the voxel's own
-//                      kind).  The [B][T] tile of s lives in LDS; every output scans outward d = 1, 2, .. on both
+//                      other kind below and above z, by bitvol.h's walk over the packed row XOR the voxel's own
+//                      kind.  The [B][T] tile of s lives in LDS; every output scans outward d = 1, 2, .. on both
 //                      sides and stops once d^2 alone reaches the best so far; hard bound d <= max(b, B - 1 - b).
 //   bd_x_kernel        the same scan along A over an [A][T] tile staged in LDS, then the result: the signed square and
 //                      phi = +sqrt(d2) outside, -(sqrt(d2) - 1) inside, the square root correctly rounded.
@@ -28,6 +28,7 @@
 #include <math.h>
 #include <stddef.h>
 #include "common.h"
+#include "bitvol.h"
 #include "loss_core.h"
 
 #pragma clang fp contract(off)
@@ -63,33 +64,27 @@ struct BdWeights {
 
 extern "C" size_t ru3d_boundary_state_bytes(void) { return sizeof(BdState); }
 
+// not bv_shape_ok alone: nvol volumes of it, every axis within the LDS limit, and the words of all of them an int
 static inline bool bd_shape_ok(int nvol, int A, int B, int Z) {
-    return nvol > 0 && A > 0 && B > 0 && Z > 0 && A <= RU3D_BOUNDARY_MAX_AXIS && B <= RU3D_BOUNDARY_MAX_AXIS &&
-           Z <= RU3D_BOUNDARY_MAX_AXIS && (int64_t)A * B * Z < ((int64_t)1 << 31) &&
-           (int64_t)nvol * A * B * ((Z + 63) / 64) < ((int64_t)1 << 31);
+    return nvol > 0 && bv_shape_ok(A, B, Z) && A <= RU3D_BOUNDARY_MAX_AXIS && B <= RU3D_BOUNDARY_MAX_AXIS &&
+           Z <= RU3D_BOUNDARY_MAX_AXIS && (int64_t)nvol * A * B * bv_words(Z) < ((int64_t)1 << 31);
 }
-static inline size_t bd_align(size_t n) { return (n + 255) & ~(size_t)255; }
-static inline int bd_words(int Z) { return (Z + 63) / 64; }
 
 // the workspace: [flags: nvol unsigned, then the count of bad labels][partials: BD_PART doubles][bits][one int32 plane]
-static inline size_t bd_head_bytes(int nvol) { return bd_align(((size_t)nvol + 1) * sizeof(unsigned)); }
-static inline size_t bd_part_bytes() { return bd_align((size_t)BD_PART * sizeof(double)); }
+static inline size_t bd_head_bytes(int nvol) { return bv_align(((size_t)nvol + 1) * sizeof(unsigned)); }
+static inline size_t bd_part_bytes() { return bv_align((size_t)BD_PART * sizeof(double)); }
 static inline size_t bd_bits_bytes(int nvol, int A, int B, int Z) {
-    return bd_align((size_t)nvol * A * B * bd_words(Z) * sizeof(bd_u64));
+    return bv_align((size_t)nvol * A * B * bv_words(Z) * sizeof(bd_u64));
 }
 
 extern "C" size_t ru3d_boundary_workspace_bytes(int nvol, int A, int B, int Z) {
     if (!bd_shape_ok(nvol, A, B, Z)) return 0;
     return bd_head_bytes(nvol) + bd_part_bytes() + bd_bits_bytes(nvol, A, B, Z) +
-           bd_align((size_t)nvol * A * B * Z * sizeof(int));
+           bv_align((size_t)nvol * A * B * Z * sizeof(int));
 }
 
-// log2 of the columns of z a tile of an axis of L voxels holds
-static inline int bd_tile_shift(int L, int Z) {
-    int s = 0;
-    while ((2 << s) <= BD_MAX_COLS && (int64_t)L * (2 << s) <= BD_TILE && (1 << s) < Z) s++;
-    return s;
-}
+// columns of z of a tile of an axis of L voxels, as a shift
+static inline int bd_tile_shift(int L, int Z) { return bv_tile_shift(L, Z, BD_MAX_COLS, BD_TILE); }
 
 // --------------------------------------------------------------------------- pack
 // a wave takes one word a trip; words are numbered (n, a, b, w) with w fastest, so a wave that stays inside one sample
@@ -136,42 +131,12 @@ __global__ __launch_bounds__(256) void bd_pack_kernel(const void* __restrict__ l
 }
 
 // --------------------------------------------------------------------------- scans
-// distance in voxels from z to the nearest bit of the kind the voxel at z is not, -1 when the row has none
+// distance in voxels from z to the nearest bit of the kind the voxel at z is not, -1 when the row has none: the
+// complement is searched for a foreground voxel
 __device__ __forceinline__ int bd_nearest(const bd_u64* __restrict__ row, int W, bd_u64 last, int z, bool* fg) {
-    const int w = z >> 6, b = z & 63;
-    const bd_u64 own = row[w];
-    const bool me = (own >> b) & 1ull;
+    const bool me = (row[z >> 6] >> (z & 63)) & 1ull;
     *fg = me;
-    const bd_u64 inv = me ? ~0ull : 0ull;                                   // search the complement for a foreground voxel
-    const bd_u64 cur = (own ^ inv) & (w == W - 1 ? last : ~0ull);
-    int best = -1;
-    bd_u64 m = cur & (~0ull >> (63 - b));                                   // the bits at or below z
-    if (m) {
-        best = b - (63 - __clzll(m));
-    } else {
-        for (int k = w - 1; k >= 0; k--) {
-            const bd_u64 v = row[k] ^ inv;
-            if (v) {
-                best = z - (64 * k + 63 - __clzll(v));
-                break;
-            }
-        }
-    }
-    m = cur & (~0ull << b);                                                 // the bits at or above z
-    int up = -1;
-    if (m) {
-        up = __ffsll(m) - 1 - b;
-    } else {
-        for (int k = w + 1; k < W; k++) {
-            const bd_u64 v = (row[k] ^ inv) & (k == W - 1 ? last : ~0ull);
-            if (v) {
-                up = 64 * k + __ffsll(v) - 1 - z;
-                break;
-            }
-        }
-    }
-    if (up >= 0 && (best < 0 || up < best)) best = up;
-    return best;
+    return bv_nearest(row, W, last, me ? ~0ull : 0ull, z);
 }
 
 // what the candidate `c` costs a voxel whose own value is `me`: nothing when it is of the other kind
@@ -203,7 +168,7 @@ __global__ __launch_bounds__(BD_THREADS) void bd_zy_kernel(const bd_u64* __restr
                                                            const unsigned* __restrict__ flags) {
     extern __shared__ int bd_tile[];                                        // [B][T]
     const int T = 1 << tshift, n = B << tshift;
-    const bd_u64 last = (Z & 63) ? ~(~0ull << (Z & 63)) : ~0ull;
+    const bd_u64 last = ~bv_tail(Z);
     const int64_t per_vol = (int64_t)A * ZT, tiles = per_vol * nvol;
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t vol = tile / per_vol;
@@ -416,7 +381,7 @@ static int bd_flat_blocks(int64_t total) {
 // the whole transform; everything was checked by the caller
 static int bd_transform(const void* labels, int label_dtype, int n, int A, int B, int Z, int num_classes,
                         const BdClasses& cl, int* d2_out, float* phi_out, void* ws, hipStream_t st) {
-    const int nvol = n * cl.K, W = bd_words(Z);
+    const int nvol = n * cl.K, W = bv_words(Z);
     unsigned* flags = (unsigned*)ws;
     int* bad = (int*)(flags + nvol);
     bd_u64* bits = (bd_u64*)((char*)ws + bd_head_bytes(nvol) + bd_part_bytes());

@@ -10,7 +10,8 @@
 //   2. cc_seam_kernel      one thread per voxel on a tile face: unite it with its neighbour across the face.
 //   3. cc_flatten_roots    tile roots only: L[r] = find(r).  Everything else still points at its tile root, so
 //   4. cc_flatten_count    L[i] = find(i) is at most two hops; the same pass counts the roots of each 2048-voxel chunk.
-//   5. cc_scan_kernel      exclusive scan of the chunk counts (one workgroup), K -> the caller's device int.
+//   5. cc_scan_kernel      the scan of the chunk counts (bitvol.h, as the sums of 4. and the ranks of 6.), K -> the
+//                          caller's device int.
 //   6. cc_rank_kernel      roots in linear-index order get their number (stored as -(number) - 1 in place),
 //   7. cc_finalize_kernel  every voxel reads its root's number.
 // Inside a launch other workgroups change L.  Every loop here reads L with agent-scope relaxed atomic loads, decides only
@@ -21,6 +22,7 @@
 // Statistics / filter / region accumulate / cascade merge are streaming passes; the statistics reduce per tile in an
 // LDS table first and issue one global atomic per (tile, component).
 #include "common.h"
+#include "bitvol.h"
 #include <limits.h>
 
 #define CC_TX 8
@@ -29,7 +31,6 @@
 #define CC_ROWS (CC_TX * CC_TY)
 #define CC_TILE (CC_ROWS * CC_TZ)
 #define CC_CHUNK 2048                       // voxels (or components) per workgroup of the numbering passes
-#define CC_SCAN_THREADS 1024
 #define CC_HASH 256                         // per-tile statistics table (entries)
 #define CC_PROBES 8
 #define CC_MAX_CLASSES 8
@@ -214,60 +215,30 @@ __global__ __launch_bounds__(256) void cc_flatten_roots_kernel(int* __restrict__
     }
 }
 
-__device__ __forceinline__ int cc_block_sum(int v, int* s_part) {
-    v = __popcll(__ballot(v != 0));                          // callers pass 0 / 1
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_part[wave] = v;
-    __syncthreads();
-    const int total = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-    __syncthreads();
-    return total;
-}
-
 __global__ __launch_bounds__(256) void cc_flatten_count_kernel(int* __restrict__ L, int64_t n, int* __restrict__ counts) {
-    __shared__ int s_part[4];
     const int64_t base = (int64_t)blockIdx.x * CC_CHUNK;
-    int roots = 0;
+    int roots = 0;                                           // of this lane's eight voxels
     for (int k = 0; k < CC_CHUNK / 256; k++) {
         const int64_t i = base + k * 256 + threadIdx.x;
-        int is_root = 0;
         if (i < n) {
             const int v = cc_load(L + i);
             if (v == (int)i) {
-                is_root = 1;
+                roots++;
             } else if (v >= 0) {
                 const int r = cc_find(L, v);
                 if (r != v) cc_store(L + i, r);
             }
         }
-        roots += cc_block_sum(is_root, s_part);
     }
-    if (threadIdx.x == 0) counts[blockIdx.x] = roots;
+    bv_chunk_sum(roots, counts);
 }
 
 // ------------------------------------------------------------------------------------------------ 5. scan
-// counts[0 .. n) -> exclusive prefix sums in place, the grand total -> *total_out.  One workgroup.
-__global__ __launch_bounds__(CC_SCAN_THREADS) void cc_scan_kernel(int* __restrict__ counts, int n, int* __restrict__ total_out) {
-    __shared__ int s_sum[CC_SCAN_THREADS];
-    const int per = (n + CC_SCAN_THREADS - 1) / CC_SCAN_THREADS;
-    const int lo = min(n, (int)threadIdx.x * per), hi = min(n, lo + per);
-    int sum = 0;
-    for (int i = lo; i < hi; i++) sum += counts[i];
-    s_sum[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < CC_SCAN_THREADS; off <<= 1) {     // inclusive Hillis-Steele over the per-thread sums
-        const int v = (int)threadIdx.x >= off ? s_sum[threadIdx.x - off] : 0;
-        __syncthreads();
-        s_sum[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = s_sum[threadIdx.x] - sum;
-    for (int i = lo; i < hi; i++) {
-        const int c = counts[i];
-        counts[i] = run;
-        run += c;
-    }
-    if (threadIdx.x == CC_SCAN_THREADS - 1) *total_out = s_sum[CC_SCAN_THREADS - 1];
+// bv_scan_chunks over the chunk counts, the grand total -> *total_out
+__global__ __launch_bounds__(BV_SCAN_THREADS) void cc_scan_kernel(int* __restrict__ counts, int n, int* __restrict__ total_out) {
+    __shared__ int s_sum[BV_SCAN_THREADS];
+    const int sum = bv_scan_chunks(counts, n, s_sum);
+    if (threadIdx.x == BV_SCAN_THREADS - 1) *total_out = sum;
 }
 
 // ------------------------------------------------------------------------------------------------ 6. rank
@@ -278,21 +249,16 @@ enum { CC_RANK_ROOTS = 0, CC_RANK_KEEP = 1 };
 template <int MODE>
 __global__ __launch_bounds__(256) void cc_rank_kernel(int* __restrict__ L, const int* __restrict__ sizes, int threshold,
                                                       int64_t n, const int* __restrict__ offsets) {
-    __shared__ int s_part[4];
+    __shared__ int s_part[BV_CHUNK_WAVES];
     const int64_t base = (int64_t)blockIdx.x * CC_CHUNK;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int run = offsets[blockIdx.x];
     for (int k = 0; k < CC_CHUNK / 256; k++) {
         const int64_t i = base + k * 256 + threadIdx.x;
         bool flag = false;
         if (i < n) flag = MODE == CC_RANK_ROOTS ? (L[i] == (int)i) : (sizes[i] >= threshold);
-        const cc_u64 m = __ballot(flag);
-        if (lane == 0) s_part[wave] = __popcll(m);
-        __syncthreads();
-        int before = __popcll(m & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; w++) before += s_part[w];
-        const int slab = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-        __syncthreads();
+        int slab;
+        const int before = bv_ballot_rank(flag, s_part, &slab);
+        __syncthreads();                                     // s_part is written again in the next trip
         if (i < n) {
             const int number = run + before + 1;
             if (MODE == CC_RANK_ROOTS) {
@@ -327,14 +293,13 @@ __global__ __launch_bounds__(256) void cc_finalize_kernel(int* __restrict__ L, i
 // keep[k] = sizes[k] >= threshold, counted per chunk
 __global__ __launch_bounds__(256) void cc_keep_count_kernel(const int* __restrict__ sizes, int threshold, int64_t n,
                                                             int* __restrict__ counts) {
-    __shared__ int s_part[4];
     const int64_t base = (int64_t)blockIdx.x * CC_CHUNK;
     int kept = 0;
     for (int k = 0; k < CC_CHUNK / 256; k++) {
         const int64_t i = base + k * 256 + threadIdx.x;
-        kept += cc_block_sum((i < n && sizes[i] >= threshold) ? 1 : 0, s_part);
+        kept += (i < n && sizes[i] >= threshold) ? 1 : 0;
     }
-    if (threadIdx.x == 0) counts[blockIdx.x] = kept;
+    bv_chunk_sum(kept, counts);
 }
 
 __global__ __launch_bounds__(256) void cc_filter_apply_kernel(const int* __restrict__ labels, int64_t n, int count,
@@ -498,32 +463,24 @@ __global__ __launch_bounds__(256) void cc_cascade_merge_kernel(const double* __r
 
 // ------------------------------------------------------------------------------------------------ host side
 static inline int cc_div_up(int a, int b) { return (a + b - 1) / b; }
-static inline size_t cc_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline int cc_stream_blocks(int64_t n) {
     int64_t b = (n + 255) / 256;
     return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
 }
-static inline bool cc_shape_ok(int X, int Y, int Z) {
-    return X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31);
-}
 static inline size_t cc_rootbits_bytes(int X, int Y, int Z) {
-    return cc_align((size_t)X * Y * cc_div_up(Z, CC_TZ) * sizeof(cc_u64));
+    return bv_align((size_t)X * Y * cc_div_up(Z, CC_TZ) * sizeof(cc_u64));
 }
 static inline int64_t cc_chunks(int64_t n) { return (n + CC_CHUNK - 1) / CC_CHUNK; }
 
-#define CC_REQUIRE_SHAPE(what)                                                                                       \
-    RU3D_REQUIRE(cc_shape_ok(X, Y, Z), what ": a %dx%dx%d volume is not supported (every extent positive, X*Y*Z < 2^31)", \
-                 X, Y, Z)
-
 extern "C" size_t ru3d_components_workspace_bytes(int X, int Y, int Z) {
-    if (!cc_shape_ok(X, Y, Z)) return 0;
-    return cc_rootbits_bytes(X, Y, Z) + cc_align((size_t)cc_chunks((int64_t)X * Y * Z) * sizeof(int));
+    if (!bv_shape_ok(X, Y, Z)) return 0;
+    return cc_rootbits_bytes(X, Y, Z) + bv_align((size_t)cc_chunks((int64_t)X * Y * Z) * sizeof(int));
 }
 
 extern "C" int ru3d_label_components(const uint8_t* mask, int X, int Y, int Z, int32_t* labels, int32_t* count_dev,
                                      void* ws, size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    CC_REQUIRE_SHAPE("label_components");
+    BV_REQUIRE_SHAPE("label_components");
     RU3D_REQUIRE(mask && labels && count_dev && ws, "label_components: bad argument (null pointer)");
     RU3D_REQUIRE(ws_bytes >= ru3d_components_workspace_bytes(X, Y, Z), "label_components: workspace of %zu bytes, %zu needed",
                  ws_bytes, ru3d_components_workspace_bytes(X, Y, Z));
@@ -546,7 +503,7 @@ extern "C" int ru3d_label_components(const uint8_t* mask, int X, int Y, int Z, i
     hipLaunchKernelGGL(cc_flatten_roots_kernel, dim3(cc_stream_blocks(words * 64)), dim3(256), 0, st, L, rootbits, Z, ZT,
                        words);
     hipLaunchKernelGGL(cc_flatten_count_kernel, dim3(chunks), dim3(256), 0, st, L, n, counts);
-    hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(CC_SCAN_THREADS), 0, st, counts, chunks, count_dev);
+    hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(BV_SCAN_THREADS), 0, st, counts, chunks, count_dev);
     hipLaunchKernelGGL((cc_rank_kernel<CC_RANK_ROOTS>), dim3(chunks), dim3(256), 0, st, L, (const int*)nullptr, 0, n,
                        counts);
     hipLaunchKernelGGL(cc_finalize_kernel, dim3(cc_stream_blocks(n)), dim3(256), 0, st, L, n);
@@ -556,7 +513,7 @@ extern "C" int ru3d_label_components(const uint8_t* mask, int X, int Y, int Z, i
 extern "C" int ru3d_component_stats(const int32_t* labels, int X, int Y, int Z, int count, int32_t* sizes, int32_t* boxes,
                                     void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    CC_REQUIRE_SHAPE("component_stats");
+    BV_REQUIRE_SHAPE("component_stats");
     RU3D_REQUIRE(count >= 0, "component_stats: count %d", count);
     if (count == 0) return 0;
     RU3D_REQUIRE(labels && sizes && boxes, "component_stats: bad argument (null pointer)");
@@ -572,14 +529,14 @@ extern "C" int ru3d_component_stats(const int32_t* labels, int X, int Y, int Z, 
 
 extern "C" size_t ru3d_filter_components_workspace_bytes(int count) {
     if (count <= 0) return 0;
-    return cc_align((size_t)count * sizeof(int)) + cc_align((size_t)cc_chunks(count) * sizeof(int));
+    return bv_align((size_t)count * sizeof(int)) + bv_align((size_t)cc_chunks(count) * sizeof(int));
 }
 
 extern "C" int ru3d_filter_components(const int32_t* labels, int X, int Y, int Z, int count, const int32_t* sizes,
                                       int threshold, uint8_t* mask_inout, int32_t* labels_out, int32_t* kept_dev, void* ws,
                                       size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    CC_REQUIRE_SHAPE("filter_components");
+    BV_REQUIRE_SHAPE("filter_components");
     RU3D_REQUIRE(count >= 0, "filter_components: count %d", count);
     RU3D_REQUIRE(labels && kept_dev && (count == 0 || sizes), "filter_components: bad argument (null pointer)");
     RU3D_REQUIRE(mask_inout || labels_out, "filter_components: neither a mask nor a label output");
@@ -596,10 +553,10 @@ extern "C" int ru3d_filter_components(const int32_t* labels, int X, int Y, int Z
         return ru3d_check_launch("filter_components");
     }
     int* remap = (int*)ws;
-    int* counts = (int*)((char*)ws + cc_align((size_t)count * sizeof(int)));
+    int* counts = (int*)((char*)ws + bv_align((size_t)count * sizeof(int)));
     const int chunks = (int)cc_chunks(count);
     hipLaunchKernelGGL(cc_keep_count_kernel, dim3(chunks), dim3(256), 0, st, sizes, threshold, (int64_t)count, counts);
-    hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(CC_SCAN_THREADS), 0, st, counts, chunks, kept_dev);
+    hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(BV_SCAN_THREADS), 0, st, counts, chunks, kept_dev);
     hipLaunchKernelGGL((cc_rank_kernel<CC_RANK_KEEP>), dim3(chunks), dim3(256), 0, st, remap, sizes, threshold,
                        (int64_t)count, counts);
     hipLaunchKernelGGL(cc_filter_apply_kernel, dim3(cc_stream_blocks(n)), dim3(256), 0, st, labels, n, count, remap,
@@ -610,7 +567,7 @@ extern "C" int ru3d_filter_components(const int32_t* labels, int X, int Y, int Z
 extern "C" int ru3d_region_accumulate(const float* prob, int rx, int ry, int rz, int num_classes, int bx, int by, int bz,
                                       double* total, int32_t* hits, int X, int Y, int Z, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    CC_REQUIRE_SHAPE("region_accumulate");
+    BV_REQUIRE_SHAPE("region_accumulate");
     RU3D_REQUIRE(prob && total && hits, "region_accumulate: bad argument (null pointer)");
     RU3D_REQUIRE(rx > 0 && ry > 0 && rz > 0, "region_accumulate: region of %dx%dx%d", rx, ry, rz);
     RU3D_REQUIRE(num_classes >= 1 && num_classes <= CC_MAX_CLASSES, "region_accumulate: %d classes (max %d)", num_classes,
@@ -634,7 +591,7 @@ static int cc_merge_launch(const double* total, const int* hits, int64_t n, uint
 extern "C" int ru3d_cascade_merge(const double* total, const int32_t* hits, int X, int Y, int Z, int num_classes,
                                   uint8_t* out, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    CC_REQUIRE_SHAPE("cascade_merge");
+    BV_REQUIRE_SHAPE("cascade_merge");
     RU3D_REQUIRE(total && hits && out, "cascade_merge: bad argument (null pointer)");
     RU3D_REQUIRE(num_classes >= 1 && num_classes <= CC_MAX_CLASSES, "cascade_merge: %d classes (max %d)", num_classes,
                  CC_MAX_CLASSES);

@@ -19,6 +19,7 @@
 //
 // No atomics, no host synchronisation; every barrier sits in a loop whose bounds are uniform over the workgroup.
 #include "common.h"
+#include "bitvol.h"
 #include <math.h>
 
 namespace {
@@ -261,8 +262,6 @@ __global__ __launch_bounds__(256) void degrade_finish_kernel(const float* src, f
     }
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 int blur_radius(double sigma) { return (int)(4.0 * sigma + 0.5); }
 
 }  // namespace
@@ -270,7 +269,7 @@ int blur_radius(double sigma) { return (int)(4.0 * sigma + 0.5); }
 extern "C" size_t ru3d_augment_degrade_workspace_bytes(int C, int px, int py, int pz) {
     if (C <= 0 || px <= 0 || py <= 0 || pz <= 0) return 0;
     const size_t total = (size_t)px * py * pz;
-    return align256(total * C * sizeof(float)) + align256(((size_t)px + py + pz) * sizeof(LowResTap)) + 256;
+    return bv_align(total * C * sizeof(float)) + bv_align(((size_t)px + py + pz) * sizeof(LowResTap)) + 256;
 }
 
 extern "C" int ru3d_augment_degrade(float* image, int C, int px, int py, int pz, const ru3d_degrade_params* p, void* ws,
@@ -302,7 +301,7 @@ extern "C" int ru3d_augment_degrade(float* image, int C, int px, int py, int pz,
     const hipStream_t st = as_stream(stream);
     const int64_t count = total * C;
     float* other = (float*)ws;
-    LowResTap* tab = (LowResTap*)((char*)ws + align256((size_t)count * sizeof(float)));
+    LowResTap* tab = (LowResTap*)((char*)ws + bv_align((size_t)count * sizeof(float)));
     float* cur = image;
     if (p->do_noise) {
         const int64_t calls = (count + 3) >> 2;

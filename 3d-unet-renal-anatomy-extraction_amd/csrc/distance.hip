@@ -1,7 +1,7 @@
 // Exact squared Euclidean distance transform of a bit-packed mask, the surface of a packed mask, the gather of a
 // float64 volume at the set bits of a packed mask and the reductions the surface-distance metrics need (Hausdorff
-// distance, its percentile, average symmetric surface distance, surface Dice).  Packed masks are those of
-// morphology.hip: 64 voxels of the contiguous Z axis per 64-bit word, zero bits at z >= Z.
+// distance, its percentile, average symmetric surface distance, surface Dice).  Packed masks, the nearest-bit walk of
+// the Z pass, the tile width and the count / scan / rank pieces of the gather are those of bitvol.h.
 //
 // The contract of the transform (include/ru3d.h): out[p] = min over the feature voxels f of fl(A + fl(B + C)) with
 // A = fl(fl(sx (px - fx))^2), B and C alike for y and z, in float64.  Rounding is monotone, so the separable form
@@ -20,13 +20,14 @@
 //                      pass returns at once when the ZY pass met no feature at all (one flag in the workspace).
 //   ed_surface_kernel  mask & ~erode(mask) with the 6-neighbour cross and border 0, one word per lane.
 //   ed_count / ed_scan / ed_gather   values[r] = sq[p_r] for the set bits p_r of a query mask in element order (x
-//                      outermost, z fastest): word popcounts per 256-word chunk, one exclusive scan, then every lane
-//                      writes the values of its word at their ranks.
+//                      outermost, z fastest): bitvol.h's compaction over the word popcounts of 256-word chunks, every
+//                      lane writes the values of its word at their ranks.
 //   ed_reduce_partial / ed_reduce_final   (n, max, #{v <= tau^2}, sum of sqrt(v)) of the first n = min(*count,
 //                      capacity) values.  Fixed partition (2048 values per partial whatever the grid) and fixed trees:
 //                      the float64 sum has the same bits in every run and under every CU budget.
 #include <math.h>
 #include "common.h"
+#include "bitvol.h"
 
 #pragma clang fp contract(off)
 
@@ -36,7 +37,6 @@ typedef unsigned long long ed_u64;
 #define ED_TILE 4096                      // doubles of one LDS tile: 32 KiB, four workgroups a CU
 #define ED_MAX_COLS 16                    // columns of z per tile at most: 128-byte segments of the float64 volume
 #define ED_GCHUNK 256                     // words of a gather chunk = threads of its workgroup
-#define ED_SCAN_THREADS 1024
 #define ED_RTHREADS 256
 #define ED_RCHUNK 2048                    // values per partial of the reductions
 
@@ -44,40 +44,6 @@ typedef unsigned long long ed_u64;
 __device__ __forceinline__ double ed_sq(double s, int d) {
     const double t = s * (double)d;
     return t * t;
-}
-
-// distance in voxels from z to the nearest set bit of a packed row of W words, -1 when the row has none
-__device__ __forceinline__ int ed_nearest(const ed_u64* __restrict__ row, int W, ed_u64 tail, int z) {
-    const int w = z >> 6, b = z & 63;
-    const ed_u64 cur = w == W - 1 ? row[w] & ~tail : row[w];
-    int best = -1;
-    ed_u64 m = cur & (~0ull >> (63 - b));                                   // the bits at or below z
-    if (m) {
-        best = b - (63 - __clzll(m));
-    } else {
-        for (int k = w - 1; k >= 0; k--) {
-            const ed_u64 v = row[k];
-            if (v) {
-                best = z - (64 * k + 63 - __clzll(v));
-                break;
-            }
-        }
-    }
-    m = cur & (~0ull << b);                                                 // the bits at or above z
-    int up = -1;
-    if (m) {
-        up = __ffsll(m) - 1 - b;
-    } else {
-        for (int k = w + 1; k < W; k++) {
-            const ed_u64 v = k == W - 1 ? row[k] & ~tail : row[k];
-            if (v) {
-                up = 64 * k + __ffsll(v) - 1 - z;
-                break;
-            }
-        }
-    }
-    if (up >= 0 && (best < 0 || up < best)) best = up;
-    return best;
 }
 
 // min over l' of fl(fl(fl(s (l - l'))^2) + tile[l'][t]) for one output of an [L][T] tile (T = 1 << tshift)
@@ -99,7 +65,7 @@ __global__ __launch_bounds__(ED_THREADS) void ed_zy_kernel(const ed_u64* __restr
                                                            double* __restrict__ out, unsigned* __restrict__ flag) {
     extern __shared__ double ed_tile[];                                     // [Y][T]
     const int T = 1 << tshift, n = Y << tshift;
-    const ed_u64 tail = (Z & 63) ? (~0ull << (Z & 63)) : 0ull;
+    const ed_u64 last = ~bv_tail(Z);
     const int64_t tiles = (int64_t)X * ZT;
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int x = (int)(tile / ZT), z0 = (int)(tile - (int64_t)x * ZT) << tshift;
@@ -108,7 +74,7 @@ __global__ __launch_bounds__(ED_THREADS) void ed_zy_kernel(const ed_u64* __restr
             const int y = e >> tshift, z = z0 + (e & (T - 1));
             double v = INFINITY;
             if (z < Z) {
-                const int dz = ed_nearest(bits + ((int64_t)x * Y + y) * W, W, tail, z);
+                const int dz = bv_nearest(bits + ((int64_t)x * Y + y) * W, W, last, 0ull, z);
                 if (dz >= 0) {
                     v = ed_sq(sz, dz);
                     any = 1;
@@ -155,7 +121,7 @@ __global__ __launch_bounds__(ED_THREADS) void ed_x_kernel(double* __restrict__ o
 // ------------------------------------------------------------------------------------------------ surface
 __global__ __launch_bounds__(256) void ed_surface_kernel(const ed_u64* __restrict__ src, ed_u64* __restrict__ dst, int X,
                                                          int Y, int Z, int W, int64_t words) {
-    const ed_u64 tail = (Z & 63) ? (~0ull << (Z & 63)) : 0ull;
+    const ed_u64 tail = bv_tail(Z);
     const int64_t xstep = (int64_t)Y * W;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / W;
@@ -165,7 +131,7 @@ __global__ __launch_bounds__(256) void ed_surface_kernel(const ed_u64* __restric
         if (m && x > 0 && x < X - 1 && y > 0 && y < Y - 1) {                // a face voxel has a neighbour outside: 0
             const ed_u64 below = w > 0 ? src[i - 1] : 0ull;
             const ed_u64 above = w < W - 1 ? (w + 1 == W - 1 ? src[i + 1] & ~tail : src[i + 1]) : 0ull;
-            e = m & (m << 1 | below >> 63) & (m >> 1 | above << 63);        // z - 1 and z + 1
+            e = m & bv_zdown(below, m) & bv_zup(m, above);                  // z - 1 and z + 1
             e &= src[i - xstep] & src[i + xstep] & src[i - W] & src[i + W];
         }
         dst[i] = m & ~e;
@@ -180,58 +146,24 @@ __device__ __forceinline__ ed_u64 ed_query_word(const ed_u64* __restrict__ q, in
 
 __global__ __launch_bounds__(ED_GCHUNK) void ed_count_kernel(const ed_u64* __restrict__ q, int64_t words, int W, ed_u64 tail,
                                                              int* __restrict__ counts) {
-    __shared__ int s_part[ED_GCHUNK / 64];
-    int c = __popcll(ed_query_word(q, (int64_t)blockIdx.x * ED_GCHUNK + threadIdx.x, words, W, tail));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    bv_chunk_sum(__popcll(ed_query_word(q, (int64_t)blockIdx.x * ED_GCHUNK + threadIdx.x, words, W, tail)), counts);
 }
 
-// counts[0 .. chunks) -> exclusive prefix sums in place, the total -> *total.  One workgroup.
-__global__ __launch_bounds__(ED_SCAN_THREADS) void ed_scan_kernel(int* __restrict__ counts, int chunks,
+// bv_scan_chunks over the chunk counts, the total -> *total
+__global__ __launch_bounds__(BV_SCAN_THREADS) void ed_scan_kernel(int* __restrict__ counts, int chunks,
                                                                   long long* __restrict__ total) {
-    __shared__ int s_sum[ED_SCAN_THREADS];
-    const int per = (chunks + ED_SCAN_THREADS - 1) / ED_SCAN_THREADS;
-    const int lo = min(chunks, (int)threadIdx.x * per), hi = min(chunks, lo + per);
-    int sum = 0;
-    for (int i = lo; i < hi; i++) sum += counts[i];
-    s_sum[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < ED_SCAN_THREADS; off <<= 1) {
-        const int v = (int)threadIdx.x >= off ? s_sum[threadIdx.x - off] : 0;
-        __syncthreads();
-        s_sum[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = s_sum[threadIdx.x] - sum;
-    for (int i = lo; i < hi; i++) {
-        const int c = counts[i];
-        counts[i] = run;
-        run += c;
-    }
-    if (threadIdx.x == ED_SCAN_THREADS - 1) *total = (long long)s_sum[ED_SCAN_THREADS - 1];
+    __shared__ int s_sum[BV_SCAN_THREADS];
+    const int sum = bv_scan_chunks(counts, chunks, s_sum);
+    if (threadIdx.x == BV_SCAN_THREADS - 1) *total = (long long)sum;
 }
 
 __global__ __launch_bounds__(ED_GCHUNK) void ed_gather_kernel(const double* __restrict__ sq, const ed_u64* __restrict__ q,
                                                               int64_t words, int W, int Z, ed_u64 tail,
                                                               const int* __restrict__ offsets, double* __restrict__ values,
                                                               long long capacity) {
-    __shared__ int s_part[ED_GCHUNK / 64];
     const int64_t i = (int64_t)blockIdx.x * ED_GCHUNK + threadIdx.x;
     ed_u64 m = ed_query_word(q, i, words, W, tail);
-    const int c = __popcll(m), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = c;                                                           // inclusive scan over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    long long rank = (long long)offsets[blockIdx.x] + (incl - c);
-    for (int k = 0; k < wave; k++) rank += s_part[k];
+    long long rank = (long long)offsets[blockIdx.x] + bv_chunk_rank(__popcll(m));
     if (!m) return;
     const int64_t row = i / W;
     const double* base = sq + row * Z + 64 * (int)(i - row * W);
@@ -251,18 +183,9 @@ __device__ __forceinline__ ed_stats ed_join(const ed_stats& a, const ed_stats& b
     ed_stats r = {fmax(a.mx, b.mx), a.cnt + b.cnt, a.sum + b.sum};
     return r;
 }
-// the workgroup's total in thread 0: a butterfly inside each wave, then the four waves in order
+// the workgroup's total in thread 0, in bv_block_join's fixed order
 __device__ __forceinline__ ed_stats ed_block_join(ed_stats v, ed_stats* s_part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ed_stats w = {__shfl_xor(v.mx, o, 64), __shfl_xor(v.cnt, o, 64), __shfl_xor(v.sum, o, 64)};
-        v = ed_join(v, w);
-    }
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) v = ed_join(ed_join(s_part[0], s_part[1]), ed_join(s_part[2], s_part[3]));
-    __syncthreads();
-    return v;
+    return bv_block_join(v, s_part, [](const ed_stats& a, const ed_stats& b) { return ed_join(a, b); });
 }
 __device__ __forceinline__ long long ed_used(const long long* count, long long capacity) {
     const long long c = *count;
@@ -316,33 +239,18 @@ __global__ __launch_bounds__(ED_RTHREADS) void ed_reduce_final_kernel(const doub
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline bool ed_shape_ok(int X, int Y, int Z) {
-    return X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31);
-}
-static inline int ed_words(int Z) { return (Z + 63) / 64; }
-static inline size_t ed_align(size_t n) { return (n + 255) & ~(size_t)255; }
-static inline ed_u64 ed_tail(int Z) { return (Z & 63) ? (~0ull << (Z & 63)) : 0ull; }
-// log2 of the columns of z a tile of an axis of L voxels holds: the largest power of two with L * T <= ED_TILE, at most
-// ED_MAX_COLS and no more than Z needs
-static inline int ed_tile_shift(int L, int Z) {
-    int s = 0;
-    while ((2 << s) <= ED_MAX_COLS && (int64_t)L * (2 << s) <= ED_TILE && (1 << s) < Z) s++;
-    return s;
-}
-
-#define ED_REQUIRE_SHAPE(what)                                                                                       \
-    RU3D_REQUIRE(ed_shape_ok(X, Y, Z), what ": a %dx%dx%d volume is not supported (every extent positive, X*Y*Z < 2^31)", \
-                 X, Y, Z)
+// columns of z of a tile of an axis of L voxels, as a shift
+static inline int ed_tile_shift(int L, int Z) { return bv_tile_shift(L, Z, ED_MAX_COLS, ED_TILE); }
 
 extern "C" size_t ru3d_edt_workspace_bytes(int X, int Y, int Z) {
-    if (!ed_shape_ok(X, Y, Z) || X > RU3D_EDT_MAX_AXIS || Y > RU3D_EDT_MAX_AXIS) return 0;
-    return ed_align(sizeof(unsigned));
+    if (!bv_shape_ok(X, Y, Z) || X > RU3D_EDT_MAX_AXIS || Y > RU3D_EDT_MAX_AXIS) return 0;
+    return bv_align(sizeof(unsigned));
 }
 
 extern "C" int ru3d_edt_squared(const uint64_t* bits, int X, int Y, int Z, const double* spacing, double* out, void* ws,
                                 size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    ED_REQUIRE_SHAPE("edt_squared");
+    BV_REQUIRE_SHAPE("edt_squared");
     RU3D_REQUIRE(X <= RU3D_EDT_MAX_AXIS && Y <= RU3D_EDT_MAX_AXIS,
                  "edt_squared: a %dx%dx%d volume is beyond the limit of %d voxels along x and y (one column of the axis "
                  "is held in LDS)", X, Y, Z, RU3D_EDT_MAX_AXIS);
@@ -360,7 +268,7 @@ extern "C" int ru3d_edt_squared(const uint64_t* bits, int X, int Y, int Z, const
         const int ts = ed_tile_shift(Y, Z), ZT = (Z + (1 << ts) - 1) >> ts;
         const int64_t tiles = (int64_t)X * ZT;
         hipLaunchKernelGGL(ed_zy_kernel, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(ED_THREADS),
-                           ((size_t)Y << ts) * sizeof(double), st, (const ed_u64*)bits, X, Y, Z, ed_words(Z), ts, ZT,
+                           ((size_t)Y << ts) * sizeof(double), st, (const ed_u64*)bits, X, Y, Z, bv_words(Z), ts, ZT,
                            spacing[1], spacing[2], out, flag);
     }
     if (X > 1) {
@@ -375,10 +283,10 @@ extern "C" int ru3d_edt_squared(const uint64_t* bits, int X, int Y, int Z, const
 
 extern "C" int ru3d_mask_surface(const uint64_t* src, uint64_t* dst, int X, int Y, int Z, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    ED_REQUIRE_SHAPE("mask_surface");
+    BV_REQUIRE_SHAPE("mask_surface");
     RU3D_REQUIRE(src && dst, "mask_surface: bad argument (null pointer)");
     RU3D_REQUIRE(src != dst, "mask_surface: not an in-place operation (src == dst)");
-    const int W = ed_words(Z);
+    const int W = bv_words(Z);
     const int64_t words = (int64_t)X * Y * W, cap = (int64_t)ru3d_get_cu_budget() * 8;
     int64_t blocks = (words + 255) / 256;
     blocks = blocks > cap ? cap : blocks;
@@ -388,36 +296,36 @@ extern "C" int ru3d_mask_surface(const uint64_t* src, uint64_t* dst, int X, int 
 }
 
 extern "C" size_t ru3d_edt_gather_workspace_bytes(int X, int Y, int Z) {
-    if (!ed_shape_ok(X, Y, Z)) return 0;
-    const int64_t words = (int64_t)X * Y * ed_words(Z);
-    return ed_align((size_t)((words + ED_GCHUNK - 1) / ED_GCHUNK) * sizeof(int));
+    if (!bv_shape_ok(X, Y, Z)) return 0;
+    const int64_t words = (int64_t)X * Y * bv_words(Z);
+    return bv_align((size_t)((words + ED_GCHUNK - 1) / ED_GCHUNK) * sizeof(int));
 }
 
 extern "C" int ru3d_edt_gather(const double* sq, const uint64_t* query, int X, int Y, int Z, double* values,
                                int64_t capacity, int64_t* count, void* ws, size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    ED_REQUIRE_SHAPE("edt_gather");
+    BV_REQUIRE_SHAPE("edt_gather");
     RU3D_REQUIRE(query && count && ws && (sq || !values), "edt_gather: bad argument (null pointer)");
     RU3D_REQUIRE(!values || capacity >= 1, "edt_gather: capacity %lld of the output buffer (>= 1)", (long long)capacity);
     RU3D_REQUIRE(ws_bytes >= ru3d_edt_gather_workspace_bytes(X, Y, Z), "edt_gather: workspace of %zu bytes, %zu needed",
                  ws_bytes, ru3d_edt_gather_workspace_bytes(X, Y, Z));
     hipStream_t st = as_stream(stream);
-    const int W = ed_words(Z);
+    const int W = bv_words(Z);
     const int64_t words = (int64_t)X * Y * W;
     const int chunks = (int)((words + ED_GCHUNK - 1) / ED_GCHUNK);
     int* counts = (int*)ws;
-    hipLaunchKernelGGL(ed_count_kernel, dim3(chunks), dim3(ED_GCHUNK), 0, st, (const ed_u64*)query, words, W, ed_tail(Z),
+    hipLaunchKernelGGL(ed_count_kernel, dim3(chunks), dim3(ED_GCHUNK), 0, st, (const ed_u64*)query, words, W, bv_tail(Z),
                        counts);
-    hipLaunchKernelGGL(ed_scan_kernel, dim3(1), dim3(ED_SCAN_THREADS), 0, st, counts, chunks, (long long*)count);
+    hipLaunchKernelGGL(ed_scan_kernel, dim3(1), dim3(BV_SCAN_THREADS), 0, st, counts, chunks, (long long*)count);
     if (values)
         hipLaunchKernelGGL(ed_gather_kernel, dim3(chunks), dim3(ED_GCHUNK), 0, st, sq, (const ed_u64*)query, words, W, Z,
-                           ed_tail(Z), (const int*)counts, values, (long long)capacity);
+                           bv_tail(Z), (const int*)counts, values, (long long)capacity);
     return ru3d_check_launch("edt_gather");
 }
 
 extern "C" size_t ru3d_edt_reduce_workspace_bytes(int64_t capacity) {
     if (capacity < 1 || capacity >= ((int64_t)1 << 40)) return 0;
-    return ed_align((size_t)((capacity + ED_RCHUNK - 1) / ED_RCHUNK) * 3 * sizeof(double));
+    return bv_align((size_t)((capacity + ED_RCHUNK - 1) / ED_RCHUNK) * 3 * sizeof(double));
 }
 
 extern "C" int ru3d_edt_reduce(const double* values, const int64_t* count, int64_t capacity, double tau_sq, double* out,

@@ -1,6 +1,6 @@
 // Triangle mesh of a bit-packed mask: the faces between a set voxel and an unset one (the "cuberille"), the lattice
 // edge graph of its vertices, umbrella smoothing on that graph and the area / enclosed volume of a triangle list.
-// Packed masks are those of morphology.hip: 64 voxels of the contiguous Z axis per 64-bit word, zero bits at z >= Z.
+// Packed masks, the bounded word fetch, the z-neighbour view and the count / scan / rank pieces are those of bitvol.h.
 // The contract (vertex, quad and triangle order, the smoothing expression, the sums) is written down in include/ru3d.h;
 // everything up to the smoothing is integers, and the float64 kernels are compiled with contraction off, so a numpy
 // restatement of the contract can be compared with ==.
@@ -11,7 +11,7 @@
 //                      flag = OR(r | s) & ~AND(r & s).  One word per lane, popcounts summed per 256-word chunk.
 //   mh_quad_count_kernel   E_d = w & ~neighbour_d per mask word (four row neighbours, two in-row shifts with carry),
 //                      popcounts summed per chunk.
-//   mh_scan_kernel     exclusive scan of the chunk counts, one workgroup per list (vertices, quads), 64-bit totals.
+//   mh_scan_kernel     bitvol.h's scan of the chunk counts, one workgroup per list (vertices, quads), 64-bit totals.
 //   mh_prefix_kernel   the number of vertices in front of every flag word (int32): a corner's vertex number is
 //                      prefix[word] + popcount(flag & below(k)); no dense volume of corner numbers exists anywhere.
 //   mh_vertex_kernel   per flag word: corners and the six neighbours of its vertices.  A lattice edge belongs to the
@@ -25,13 +25,13 @@
 // Every store is guarded by the caller's capacity, every index read from a caller's table is range-checked.
 #include <math.h>
 #include "common.h"
+#include "bitvol.h"
 
 #pragma clang fp contract(off)
 
 typedef unsigned long long mh_u64;
 
 #define MH_CHUNK 256                      // words of a chunk = threads of its workgroup
-#define MH_SCAN_THREADS 1024
 #define MH_RTHREADS 256
 #define MH_RCHUNK 2048                    // faces per partial of the measures
 
@@ -41,11 +41,9 @@ struct mh_dims {
     mh_u64 tail;                          // the bits at z >= Z of a row's last word
 };
 
-// word w of voxel row (x, y); 0 outside the volume
+// word w of voxel row (x, y) without the caller's tail bits; 0 outside the volume
 __device__ __forceinline__ mh_u64 mh_word(const mh_u64* __restrict__ bits, const mh_dims& g, int x, int y, int w) {
-    if ((unsigned)x >= (unsigned)g.X || (unsigned)y >= (unsigned)g.Y || (unsigned)w >= (unsigned)g.W) return 0ull;
-    const mh_u64 v = bits[((int64_t)x * g.Y + y) * g.W + w];
-    return w == g.W - 1 ? v & ~g.tail : v;
+    return bv_word_masked(bits, g.X, g.Y, g.W, g.tail, x, y, w);
 }
 
 // the four voxel rows around corner row (i, j), word cw: n = 0 .. 3 is (i-1, j-1), (i-1, j), (i, j-1), (i, j).
@@ -60,7 +58,7 @@ __device__ __forceinline__ mh_rows mh_load_rows(const mh_u64* __restrict__ bits,
         const int x = i - 1 + (n >> 1), y = j - 1 + (n & 1);
         const mh_u64 cur = mh_word(bits, g, x, y, cw), prev = mh_word(bits, g, x, y, cw - 1);
         v.r[n] = cur;
-        v.s[n] = cur << 1 | prev >> 63;
+        v.s[n] = bv_zdown(prev, cur);
     }
     return v;
 }
@@ -93,35 +91,9 @@ __device__ __forceinline__ mh_faces mh_exposed(const mh_u64* __restrict__ bits, 
     f.e[1] = m & ~mh_word(bits, g, x + 1, y, w);
     f.e[2] = m & ~mh_word(bits, g, x, y - 1, w);
     f.e[3] = m & ~mh_word(bits, g, x, y + 1, w);
-    f.e[4] = m & ~(m << 1 | mh_word(bits, g, x, y, w - 1) >> 63);
-    f.e[5] = m & ~(m >> 1 | mh_word(bits, g, x, y, w + 1) << 63);
+    f.e[4] = m & ~bv_zdown(mh_word(bits, g, x, y, w - 1), m);
+    f.e[5] = m & ~bv_zup(m, mh_word(bits, g, x, y, w + 1));
     return f;
-}
-
-// the workgroup's sum of c into counts[blockIdx.x]
-__device__ __forceinline__ void mh_chunk_sum(int c, int* __restrict__ counts) {
-    __shared__ int s_part[MH_CHUNK / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-}
-// the sum of c over the lanes of the workgroup in front of this one
-__device__ __forceinline__ int mh_chunk_rank(int c) {
-    __shared__ int s_part[MH_CHUNK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    int rank = incl - c;
-    for (int k = 0; k < wave; k++) rank += s_part[k];
-    return rank;
 }
 
 __global__ __launch_bounds__(MH_CHUNK) void mh_flag_kernel(const mh_u64* __restrict__ bits, mh_dims g,
@@ -133,7 +105,7 @@ __global__ __launch_bounds__(MH_CHUNK) void mh_flag_kernel(const mh_u64* __restr
         f = mh_flag(mh_load_rows(bits, g, (int)(row / (g.Y + 1)), (int)(row % (g.Y + 1)), (int)(i - row * g.CW)));
         flags[i] = f;
     }
-    mh_chunk_sum(__popcll(f), counts);
+    bv_chunk_sum(__popcll(f), counts);
 }
 
 __global__ __launch_bounds__(MH_CHUNK) void mh_quad_count_kernel(const mh_u64* __restrict__ bits, mh_dims g,
@@ -146,42 +118,23 @@ __global__ __launch_bounds__(MH_CHUNK) void mh_quad_count_kernel(const mh_u64* _
 #pragma unroll
         for (int d = 0; d < 6; d++) c += __popcll(f.e[d]);
     }
-    mh_chunk_sum(c, counts);
+    bv_chunk_sum(c, counts);
 }
 
-// workgroup 0: the vertex chunks, workgroup 1: the quad chunks.  counts[0 .. chunks) -> exclusive prefix sums in place
-// (int32: meaningless once a total reaches 2^31, which the 64-bit totals tell), totals[blockIdx.x] = the sum.
-__global__ __launch_bounds__(MH_SCAN_THREADS) void mh_scan_kernel(int* __restrict__ vcounts, int vchunks,
+// workgroup 0: the vertex chunks, workgroup 1: the quad chunks.  bv_scan_chunks with 64-bit sums (the int32 offsets
+// are meaningless once a total reaches 2^31, which the totals tell), totals[blockIdx.x] = the sum.
+__global__ __launch_bounds__(BV_SCAN_THREADS) void mh_scan_kernel(int* __restrict__ vcounts, int vchunks,
                                                                   int* __restrict__ qcounts, int qchunks,
                                                                   long long* __restrict__ totals) {
-    __shared__ long long s_sum[MH_SCAN_THREADS];
-    int* counts = blockIdx.x == 0 ? vcounts : qcounts;
-    const int chunks = blockIdx.x == 0 ? vchunks : qchunks;
-    const int per = (chunks + MH_SCAN_THREADS - 1) / MH_SCAN_THREADS;
-    const int lo = min(chunks, (int)threadIdx.x * per), hi = min(chunks, lo + per);
-    long long sum = 0;
-    for (int i = lo; i < hi; i++) sum += counts[i];
-    s_sum[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < MH_SCAN_THREADS; off <<= 1) {
-        const long long v = (int)threadIdx.x >= off ? s_sum[threadIdx.x - off] : 0;
-        __syncthreads();
-        s_sum[threadIdx.x] += v;
-        __syncthreads();
-    }
-    long long run = s_sum[threadIdx.x] - sum;
-    for (int i = lo; i < hi; i++) {
-        const int c = counts[i];
-        counts[i] = (int)run;
-        run += c;
-    }
-    if (threadIdx.x == MH_SCAN_THREADS - 1) totals[blockIdx.x] = s_sum[MH_SCAN_THREADS - 1];
+    __shared__ long long s_sum[BV_SCAN_THREADS];
+    const long long sum = bv_scan_chunks(blockIdx.x == 0 ? vcounts : qcounts, blockIdx.x == 0 ? vchunks : qchunks, s_sum);
+    if (threadIdx.x == BV_SCAN_THREADS - 1) totals[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(MH_CHUNK) void mh_prefix_kernel(const mh_u64* __restrict__ flags, int64_t fwords,
                                                              const int* __restrict__ offsets, int* __restrict__ prefix) {
     const int64_t i = (int64_t)blockIdx.x * MH_CHUNK + threadIdx.x;
-    const int rank = mh_chunk_rank(i < fwords ? __popcll(flags[i]) : 0);
+    const int rank = bv_chunk_rank(i < fwords ? __popcll(flags[i]) : 0);
     if (i < fwords) prefix[i] = offsets[blockIdx.x] + rank;
 }
 
@@ -268,7 +221,7 @@ __global__ __launch_bounds__(MH_CHUNK) void mh_quad_kernel(const mh_u64* __restr
 #pragma unroll
         for (int d = 0; d < 6; d++) c += __popcll(f.e[d]);
     }
-    long long rank = (long long)offsets[blockIdx.x] + mh_chunk_rank(c);
+    long long rank = (long long)offsets[blockIdx.x] + bv_chunk_rank(c);
     if (!c) return;
     // flag words and prefixes of the voxel row's four corner rows: word w holds the corners k = z of this word's
     // voxels and all of k = z + 1 but the last, which is bit 0 of word w + 1
@@ -345,18 +298,9 @@ __device__ __forceinline__ mh_sums mh_join(const mh_sums& a, const mh_sums& b) {
     mh_sums r = {a.cross + b.cross, a.triple + b.triple};
     return r;
 }
-// the workgroup's total in thread 0: a butterfly inside each wave, then the four waves in order
+// the workgroup's total in thread 0, in bv_block_join's fixed order
 __device__ __forceinline__ mh_sums mh_block_join(mh_sums v, mh_sums* s_part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mh_sums w = {__shfl_xor(v.cross, o, 64), __shfl_xor(v.triple, o, 64)};
-        v = mh_join(v, w);
-    }
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) v = mh_join(mh_join(s_part[0], s_part[1]), mh_join(s_part[2], s_part[3]));
-    __syncthreads();
-    return v;
+    return bv_block_join(v, s_part, [](const mh_sums& a, const mh_sums& b) { return mh_join(a, b); });
 }
 
 __global__ __launch_bounds__(MH_RTHREADS) void mh_measure_partial_kernel(const double* __restrict__ vertices, long long V,
@@ -409,16 +353,12 @@ __global__ __launch_bounds__(MH_RTHREADS) void mh_measure_final_kernel(const dou
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline bool mh_shape_ok(int X, int Y, int Z) {
-    return X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31);
-}
-static inline size_t mh_align(size_t n) { return (n + 255) & ~(size_t)255; }
 static inline mh_dims mh_make_dims(int X, int Y, int Z) {
     mh_dims g;
-    g.X = X, g.Y = Y, g.Z = Z, g.W = (Z + 63) / 64, g.CW = Z / 64 + 1;
+    g.X = X, g.Y = Y, g.Z = Z, g.W = bv_words(Z), g.CW = Z / 64 + 1;
     g.mwords = (int64_t)X * Y * g.W;
     g.fwords = ((int64_t)X + 1) * ((int64_t)Y + 1) * g.CW;
-    g.tail = (Z & 63) ? (~0ull << (Z & 63)) : 0ull;
+    g.tail = bv_tail(Z);
     return g;
 }
 // the workspace: flag words | int32 prefix per flag word | vertex chunk counts | quad chunk counts
@@ -431,19 +371,15 @@ static inline mh_layout mh_make_layout(const mh_dims& g) {
     l.vchunks = (int)((g.fwords + MH_CHUNK - 1) / MH_CHUNK);
     l.qchunks = (int)((g.mwords + MH_CHUNK - 1) / MH_CHUNK);
     l.flags = 0;
-    l.prefix = l.flags + mh_align((size_t)g.fwords * sizeof(mh_u64));
-    l.vcounts = l.prefix + mh_align((size_t)g.fwords * sizeof(int));
-    l.qcounts = l.vcounts + mh_align((size_t)l.vchunks * sizeof(int));
-    l.total = l.qcounts + mh_align((size_t)l.qchunks * sizeof(int));
+    l.prefix = l.flags + bv_align((size_t)g.fwords * sizeof(mh_u64));
+    l.vcounts = l.prefix + bv_align((size_t)g.fwords * sizeof(int));
+    l.qcounts = l.vcounts + bv_align((size_t)l.vchunks * sizeof(int));
+    l.total = l.qcounts + bv_align((size_t)l.qchunks * sizeof(int));
     return l;
 }
 
-#define MH_REQUIRE_SHAPE(what)                                                                                       \
-    RU3D_REQUIRE(mh_shape_ok(X, Y, Z), what ": a %dx%dx%d volume is not supported (every extent positive, X*Y*Z < 2^31)", \
-                 X, Y, Z)
-
 extern "C" size_t ru3d_mesh_workspace_bytes(int X, int Y, int Z) {
-    if (!mh_shape_ok(X, Y, Z)) return 0;
+    if (!bv_shape_ok(X, Y, Z)) return 0;
     return mh_make_layout(mh_make_dims(X, Y, Z)).total;
 }
 
@@ -453,14 +389,14 @@ static void mh_launch_count(const mh_u64* bits, const mh_dims& g, const mh_layou
     hipLaunchKernelGGL(mh_flag_kernel, dim3(l.vchunks), dim3(MH_CHUNK), 0, st, bits, g, (mh_u64*)(ws + l.flags),
                        (int*)(ws + l.vcounts));
     hipLaunchKernelGGL(mh_quad_count_kernel, dim3(l.qchunks), dim3(MH_CHUNK), 0, st, bits, g, (int*)(ws + l.qcounts));
-    hipLaunchKernelGGL(mh_scan_kernel, dim3(2), dim3(MH_SCAN_THREADS), 0, st, (int*)(ws + l.vcounts), l.vchunks,
+    hipLaunchKernelGGL(mh_scan_kernel, dim3(2), dim3(BV_SCAN_THREADS), 0, st, (int*)(ws + l.vcounts), l.vchunks,
                        (int*)(ws + l.qcounts), l.qchunks, counts);
 }
 
 extern "C" int ru3d_mesh_count(const uint64_t* bits, int X, int Y, int Z, int64_t* counts, void* ws, size_t ws_bytes,
                                void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    MH_REQUIRE_SHAPE("mesh_count");
+    BV_REQUIRE_SHAPE("mesh_count");
     RU3D_REQUIRE(bits && counts && ws, "mesh_count: bad argument (null pointer)");
     const mh_dims g = mh_make_dims(X, Y, Z);
     const mh_layout l = mh_make_layout(g);
@@ -473,7 +409,7 @@ extern "C" int ru3d_mesh_emit(const uint64_t* bits, int X, int Y, int Z, int32_t
                               int64_t vcap, int32_t* faces, int64_t qcap, int64_t* counts, void* ws, size_t ws_bytes,
                               void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    MH_REQUIRE_SHAPE("mesh_emit");
+    BV_REQUIRE_SHAPE("mesh_emit");
     RU3D_REQUIRE(vcap >= 0 && vcap < ((int64_t)1 << 31), "mesh_emit: vertex capacity %lld (0 .. 2^31 - 1)",
                  (long long)vcap);
     RU3D_REQUIRE(qcap >= 0 && qcap < ((int64_t)1 << 30), "mesh_emit: quad capacity %lld (0 .. 2^30 - 1: two triangles a "
@@ -517,7 +453,7 @@ extern "C" int ru3d_mesh_smooth(const double* src, double* dst, const int32_t* n
 
 extern "C" size_t ru3d_mesh_measure_workspace_bytes(int64_t F) {
     if (F < 1 || F >= ((int64_t)1 << 31)) return 0;
-    return mh_align((size_t)((F + MH_RCHUNK - 1) / MH_RCHUNK) * 2 * sizeof(double));
+    return bv_align((size_t)((F + MH_RCHUNK - 1) / MH_RCHUNK) * 2 * sizeof(double));
 }
 
 extern "C" int ru3d_mesh_measure(const double* vertices, int64_t V, const int32_t* faces, int64_t F, double* out, void* ws,

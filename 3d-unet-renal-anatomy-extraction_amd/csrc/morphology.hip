@@ -1,9 +1,8 @@
 // Binary morphology on bit-packed masks and the confusion table of two label volumes (reference nb_post.py:88-112,
 // nb.py:11-37): the clean-up and the evaluation of a prediction that stays in HBM.
 //
-// A packed mask holds 64 voxels of the contiguous Z axis in one 64-bit word: bit b of word w of row (x, y) is voxel
-// z = 64 w + b, a row has W = ceil(Z / 64) words, rows follow each other in the volume's [X, Y] order.  Invariant of
-// every packed volume written here: the bits at z >= Z of a row's last word are 0.
+// The packed layout (64 voxels of the contiguous Z axis per 64-bit word) and its geometry helpers are bitvol.h's.
+// Invariant of every packed volume written here: the bits at z >= Z of a row's last word are 0.
 //   mm_pack_kernel      uint8 volume -> bits under a predicate (== k, or > k which also serves != 0 and >= k).  A lane
 //                       compares 16 voxels (one 16-byte load when the rows allow it), four lanes make a word.
 //   mm_unpack_kernel    bits -> uint8 volume: write (bit ? value : 0) or paint (bit ? value : what was there).
@@ -20,6 +19,7 @@
 //                       (label, pred) pairs counted in registers, one int32 table per wave in LDS, flushed with 64-bit
 //                       integer atomics.  No float anywhere: exact and the same in every run.
 #include "common.h"
+#include "bitvol.h"
 
 typedef unsigned long long mm_u64;
 
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void mm_morph_kernel(const mm_u64* __restrict_
     const int w0 = (t % WT) * MM_TW;
     t /= WT;
     const int y0 = (t % YT) * MM_TY, x0 = (t / YT) * MM_TX;
-    const mm_u64 tail = (Z & 63) ? (~0ull << (Z & 63)) : 0ull;          // the bits at z >= Z of a row's last word
+    const mm_u64 tail = bv_tail(Z);
 
     const int staged = PX * PY * MM_SW;
     for (int i = threadIdx.x; i < staged; i += 256) {
@@ -251,30 +251,22 @@ __global__ __launch_bounds__(256) void mm_confusion_kernel(const uint8_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline bool mm_shape_ok(int X, int Y, int Z) {
-    return X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31);
-}
-static inline int mm_words(int Z) { return (Z + 63) / 64; }
 static inline bool mm_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-#define MM_REQUIRE_SHAPE(what)                                                                                       \
-    RU3D_REQUIRE(mm_shape_ok(X, Y, Z), what ": a %dx%dx%d volume is not supported (every extent positive, X*Y*Z < 2^31)", \
-                 X, Y, Z)
-
 extern "C" size_t ru3d_mask_bytes(int X, int Y, int Z) {
-    if (!mm_shape_ok(X, Y, Z)) return 0;
-    return (size_t)X * Y * mm_words(Z) * sizeof(mm_u64);
+    if (!bv_shape_ok(X, Y, Z)) return 0;
+    return (size_t)X * Y * bv_words(Z) * sizeof(mm_u64);
 }
 
 extern "C" int ru3d_mask_pack(const uint8_t* src, int X, int Y, int Z, int op, int value, uint64_t* bits, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    MM_REQUIRE_SHAPE("mask_pack");
+    BV_REQUIRE_SHAPE("mask_pack");
     RU3D_REQUIRE(src && bits, "mask_pack: bad argument (null pointer)");
     RU3D_REQUIRE(op >= RU3D_MASK_NE && op <= RU3D_MASK_GE, "mask_pack: predicate %d (RU3D_MASK_NE .. RU3D_MASK_GE)", op);
     RU3D_REQUIRE(value >= 0 && value <= 255, "mask_pack: value %d is not a uint8", value);
     const int eq = op == RU3D_MASK_EQ;
     const int k = op == RU3D_MASK_NE ? 0 : (op == RU3D_MASK_GE ? value - 1 : value);        // v >= k  <=>  v > k - 1
-    const int W = mm_words(Z);
+    const int W = bv_words(Z);
     const int64_t chunks = (int64_t)X * Y * W * 4;
     const unsigned blocks = (unsigned)((chunks + 255) / 256);
     hipStream_t st = as_stream(stream);
@@ -288,11 +280,11 @@ extern "C" int ru3d_mask_pack(const uint8_t* src, int X, int Y, int Z, int op, i
 extern "C" int ru3d_mask_unpack(const uint64_t* bits, int X, int Y, int Z, int value, int paint, uint8_t* dst,
                                 void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    MM_REQUIRE_SHAPE("mask_unpack");
+    BV_REQUIRE_SHAPE("mask_unpack");
     RU3D_REQUIRE(bits && dst, "mask_unpack: bad argument (null pointer)");
     RU3D_REQUIRE(value >= 0 && value <= 255, "mask_unpack: value %d is not a uint8", value);
     RU3D_REQUIRE(paint == 0 || paint == 1, "mask_unpack: paint %d (0 = write, 1 = paint)", paint);
-    const int W = mm_words(Z);
+    const int W = bv_words(Z);
     const int64_t chunks = (int64_t)X * Y * W * 4;
     const dim3 grid((unsigned)((chunks + 255) / 256)), block(256);
     hipStream_t st = as_stream(stream);
@@ -315,7 +307,7 @@ extern "C" int ru3d_mask_unpack(const uint64_t* bits, int X, int Y, int Z, int v
 extern "C" int ru3d_binary_morph(const uint64_t* src, uint64_t* dst, int X, int Y, int Z, int op, const ru3d_morph_row* rows,
                                  int num_rows, int border_value, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    MM_REQUIRE_SHAPE("binary_morph");
+    BV_REQUIRE_SHAPE("binary_morph");
     RU3D_REQUIRE(src && dst && rows, "binary_morph: bad argument (null pointer)");
     RU3D_REQUIRE(src != dst, "binary_morph: not an in-place operation (src == dst)");
     RU3D_REQUIRE(op == RU3D_MORPH_ERODE || op == RU3D_MORPH_DILATE, "binary_morph: op %d (RU3D_MORPH_ERODE / _DILATE)", op);
@@ -336,7 +328,7 @@ extern "C" int ru3d_binary_morph(const uint64_t* src, uint64_t* dst, int X, int 
         ry = abs(dy) > ry ? abs(dy) : ry;
     }
     for (int i = num_rows; i < RU3D_MORPH_MAX_ROWS; i++) st.row[i] = 0;
-    const int W = mm_words(Z);
+    const int W = bv_words(Z);
     const int XT = (X + MM_TX - 1) / MM_TX, YT = (Y + MM_TY - 1) / MM_TY, WT = (W + MM_TW - 1) / MM_TW;
     const int64_t tiles = (int64_t)XT * YT * WT;
     RU3D_REQUIRE(tiles < ((int64_t)1 << 31), "binary_morph: %lld tiles", (long long)tiles);

@@ -6,11 +6,10 @@
 //                          integer atomicMin / atomicMax per workgroup and bound.  Integer atomics: the same bits whatever
 //                          the arrival order.
 //   pp_fg_count / pp_scan / pp_sample_scatter
-//                          image[..., c][label > 0][::stride] in numpy's element order.  Per 2048-voxel chunk the number
-//                          of foreground voxels (64-bit ballots), an exclusive scan of the chunk counts by one workgroup,
-//                          then the scatter: a voxel's rank among the foreground is its chunk's offset + the waves before
-//                          it + the set ballot bits below its lane, and rank r goes to slot r / stride when
-//                          r % stride == 0.  No atomic decides an output position.
+//                          image[..., c][label > 0][::stride] in numpy's element order: bitvol.h's compaction over
+//                          2048-voxel chunks.  A voxel's rank among the foreground is its chunk's offset + the eight
+//                          ballot ranks of the chunk so far, and rank r goes to slot r / stride when r % stride == 0.
+//                          No atomic decides an output position.
 //   pp_hist / pp_select    exact order statistics by radix select on the order-preserving 32-bit key of a float, eight
 //                          bits per pass, most significant first.  Every rank carries its own prefix; a pass counts, per
 //                          rank, the next digit of the values that match the prefix (LDS histogram, integer atomics, one
@@ -20,12 +19,12 @@
 //                          squared deviations from the mean), per-workgroup partials in a slab, summed by one workgroup
 //                          in a fixed order.  No float atomics: two runs give the same bits.
 #include "common.h"
+#include "bitvol.h"
 #include <limits.h>
 
 #define PP_THREADS 256
 #define PP_WAVES (PP_THREADS / RU3D_WAVE)
 #define PP_CHUNK 2048                        // voxels per workgroup of the masked sample
-#define PP_SCAN_THREADS 1024
 #define PP_BINS 256                          // radix select: 8 bits per pass
 #define PP_PASSES 4
 #define PP_MAX_RANKS RU3D_ORDER_STATS_MAX_RANKS
@@ -34,10 +33,6 @@
 typedef unsigned long long pp_u64;
 
 static inline bool pp_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static inline size_t pp_align(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline bool pp_shape_ok(int X, int Y, int Z) {
-    return X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31);
-}
 // grid of a grid-stride pass over `items` work items, one per thread and trip
 static unsigned pp_stream_blocks(int64_t items) {
     int64_t blocks = (items + PP_THREADS - 1) / PP_THREADS;
@@ -48,7 +43,7 @@ static unsigned pp_stream_blocks(int64_t items) {
 }
 
 #define PP_REQUIRE_SHAPE(what)                                                                                       \
-    RU3D_REQUIRE(pp_shape_ok(X, Y, Z), what ": volume %d x %d x %d is not supported (every extent >= 1, fewer than 2^31 " \
+    RU3D_REQUIRE(bv_shape_ok(X, Y, Z), what ": volume %d x %d x %d is not supported (every extent >= 1, fewer than 2^31 " \
                                             "voxels)", X, Y, Z)
 
 __device__ __forceinline__ int pp_wave_min(int v) {
@@ -59,11 +54,6 @@ __device__ __forceinline__ int pp_wave_min(int v) {
 __device__ __forceinline__ int pp_wave_max(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int pp_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
@@ -138,7 +128,7 @@ __global__ __launch_bounds__(PP_THREADS) void pp_bbox_kernel(const float* __rest
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int a = 0; a < 3; a++) b.lo[a] = pp_wave_min(b.lo[a]), b.hi[a] = pp_wave_max(b.hi[a]);
-    b.cnt = pp_wave_sum(b.cnt);
+    b.cnt = bv_wave_sum(b.cnt);
     if (lane == 0) {
 #pragma unroll
         for (int a = 0; a < 3; a++) s_red[wave][2 * a] = b.lo[a], s_red[wave][2 * a + 1] = b.hi[a];
@@ -162,7 +152,6 @@ __global__ __launch_bounds__(PP_THREADS) void pp_bbox_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------ b. masked sample
 template <typename L>
 __global__ __launch_bounds__(PP_THREADS) void pp_fg_count_kernel(const L* __restrict__ lab, int n, int* __restrict__ counts) {
-    __shared__ int s_part[PP_WAVES];
     const int64_t base = (int64_t)blockIdx.x * PP_CHUNK;
     int c = 0;
 #pragma unroll
@@ -170,37 +159,15 @@ __global__ __launch_bounds__(PP_THREADS) void pp_fg_count_kernel(const L* __rest
         const int64_t i = base + k * PP_THREADS + threadIdx.x;
         if (i < n) c += lab[i] > 0;
     }
-    c = pp_wave_sum(c);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    bv_chunk_sum(c, counts);
 }
 
-// counts[0 .. chunks) -> exclusive prefix sums in place; the number of samples ceil(total / stride) -> *samples_out.
-// One workgroup.
-__global__ __launch_bounds__(PP_SCAN_THREADS) void pp_scan_kernel(int* __restrict__ counts, int chunks, int stride,
+// bv_scan_chunks over the chunk counts; the number of samples ceil(total / stride) -> *samples_out
+__global__ __launch_bounds__(BV_SCAN_THREADS) void pp_scan_kernel(int* __restrict__ counts, int chunks, int stride,
                                                                    long long* __restrict__ samples_out) {
-    __shared__ int s_sum[PP_SCAN_THREADS];
-    const int per = (chunks + PP_SCAN_THREADS - 1) / PP_SCAN_THREADS;
-    const int lo = min(chunks, (int)threadIdx.x * per), hi = min(chunks, lo + per);
-    int sum = 0;
-    for (int i = lo; i < hi; i++) sum += counts[i];
-    s_sum[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < PP_SCAN_THREADS; off <<= 1) {                  // inclusive Hillis-Steele over the per-thread sums
-        const int v = (int)threadIdx.x >= off ? s_sum[threadIdx.x - off] : 0;
-        __syncthreads();
-        s_sum[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = s_sum[threadIdx.x] - sum;
-    for (int i = lo; i < hi; i++) {
-        const int c = counts[i];
-        counts[i] = run;
-        run += c;
-    }
-    if (threadIdx.x == PP_SCAN_THREADS - 1)
-        *samples_out = ((long long)s_sum[PP_SCAN_THREADS - 1] + stride - 1) / stride;
+    __shared__ int s_sum[BV_SCAN_THREADS];
+    const int sum = bv_scan_chunks(counts, chunks, s_sum);
+    if (threadIdx.x == BV_SCAN_THREADS - 1) *samples_out = ((long long)sum + stride - 1) / stride;
 }
 
 template <typename L>
@@ -210,24 +177,15 @@ __global__ __launch_bounds__(PP_THREADS) void pp_sample_scatter_kernel(const flo
                                                                        float* __restrict__ out, long long capacity) {
     __shared__ int s_part[2][PP_WAVES];                                    // two sets: one barrier per trip
     const int64_t base = (int64_t)blockIdx.x * PP_CHUNK;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int run = offsets[blockIdx.x];
 #pragma unroll 1
     for (int k = 0; k < PP_CHUNK / PP_THREADS; k++) {
         const int64_t i = base + k * PP_THREADS + threadIdx.x;
         const bool fg = i < n && lab[i] > 0;
-        const pp_u64 m = __ballot(fg);
-        if (lane == 0) s_part[k & 1][wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < PP_WAVES; w++) {
-            const int c = s_part[k & 1][w];
-            before += w < wave ? c : 0;
-            all += c;
-        }
+        int all;
+        const int before = bv_ballot_rank(fg, s_part[k & 1], &all);
         if (fg) {
-            const int r = run + before + __popcll(m & (((pp_u64)1 << lane) - 1));
+            const int r = run + before;
             const int slot = r / stride;
             if (r - slot * stride == 0 && slot < capacity) out[slot] = img[i * C + channel];
         }
@@ -416,8 +374,8 @@ extern "C" int ru3d_threshold_bbox(const float* image, int X, int Y, int Z, int 
 static inline int pp_chunks(int64_t n) { return (int)((n + PP_CHUNK - 1) / PP_CHUNK); }
 
 extern "C" size_t ru3d_masked_sample_workspace_bytes(int X, int Y, int Z) {
-    if (!pp_shape_ok(X, Y, Z)) return 0;
-    return pp_align((size_t)pp_chunks((int64_t)X * Y * Z) * sizeof(int));
+    if (!bv_shape_ok(X, Y, Z)) return 0;
+    return bv_align((size_t)pp_chunks((int64_t)X * Y * Z) * sizeof(int));
 }
 
 extern "C" int ru3d_masked_sample(const float* image, int X, int Y, int Z, int C, int channel, const void* label,
@@ -441,7 +399,7 @@ extern "C" int ru3d_masked_sample(const float* image, int X, int Y, int Z, int C
         hipLaunchKernelGGL(pp_fg_count_kernel<uint8_t>, grid, block, 0, st, (const uint8_t*)label, n, counts);
     else
         hipLaunchKernelGGL(pp_fg_count_kernel<int64_t>, grid, block, 0, st, (const int64_t*)label, n, counts);
-    hipLaunchKernelGGL(pp_scan_kernel, dim3(1), dim3(PP_SCAN_THREADS), 0, st, counts, chunks, stride, (long long*)count);
+    hipLaunchKernelGGL(pp_scan_kernel, dim3(1), dim3(BV_SCAN_THREADS), 0, st, counts, chunks, stride, (long long*)count);
     if (out) {
         if (label_dtype == RU3D_LABEL_U8)
             hipLaunchKernelGGL(pp_sample_scatter_kernel<uint8_t>, grid, block, 0, st, image, C, channel,
@@ -454,7 +412,7 @@ extern "C" int ru3d_masked_sample(const float* image, int X, int Y, int Z, int C
 }
 
 extern "C" size_t ru3d_order_stats_workspace_bytes(void) {
-    return pp_align(sizeof(pp_select_state)) + pp_align((size_t)PP_PASSES * PP_MAX_RANKS * PP_BINS * sizeof(pp_u64));
+    return bv_align(sizeof(pp_select_state)) + bv_align((size_t)PP_PASSES * PP_MAX_RANKS * PP_BINS * sizeof(pp_u64));
 }
 
 extern "C" int ru3d_order_stats(const float* values, int64_t n, const int64_t* ranks, int num_ranks, float* out, void* ws,
@@ -474,7 +432,7 @@ extern "C" int ru3d_order_stats(const float* values, int64_t n, const int64_t* r
                  ru3d_order_stats_workspace_bytes());
     hipStream_t st = as_stream(stream);
     pp_select_state* state = (pp_select_state*)ws;
-    pp_u64* hist = (pp_u64*)((char*)ws + pp_align(sizeof(pp_select_state)));
+    pp_u64* hist = (pp_u64*)((char*)ws + bv_align(sizeof(pp_select_state)));
     const size_t table = (size_t)PP_MAX_RANKS * PP_BINS;
     if (hipMemsetAsync(hist, 0, PP_PASSES * table * sizeof(pp_u64), st) != hipSuccess)
         return ru3d_check_launch("order_stats (memset)");
@@ -488,7 +446,7 @@ extern "C" int ru3d_order_stats(const float* values, int64_t n, const int64_t* r
     return ru3d_check_launch("order_stats");
 }
 
-extern "C" size_t ru3d_moments_workspace_bytes(void) { return pp_align((size_t)PP_MAX_BLOCKS * 3 * sizeof(double)); }
+extern "C" size_t ru3d_moments_workspace_bytes(void) { return bv_align((size_t)PP_MAX_BLOCKS * 3 * sizeof(double)); }
 
 extern "C" int ru3d_moments(const float* values, int64_t n, double* out, void* ws, size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);

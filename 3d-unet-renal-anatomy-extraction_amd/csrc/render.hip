@@ -8,7 +8,7 @@
 //                       table held in LDS (one walk of at most 256 records per workgroup).  One pixel per lane: one
 //                       gather of the base voxel, per overlay one gather plus four for an outline, three byte stores.
 //   rd_prepare_kernel   one mask word (64 voxels of z) per lane: drawn(label) looked up in an LDS copy of the table's
-//                       alpha column, the word stored in the packed layout of morphology.hip, and a 1 stored into the
+//                       alpha column, the word stored in the packed layout of bitvol.h, and a 1 stored into the
 //                       byte of every 8 x 8 x 8 brick the word touches (same value from every writer: no atomics).
 //   rd_surface_kernel   16 x 16 pixels per workgroup, 8 x 8 per wave so that neighbouring rays share bricks, mask words
 //                       and label lines.  Per ray: clip to the volume (slab test with a margin of two samples), then
@@ -21,6 +21,7 @@
 // Every store is guarded by the caller's extents and every voxel index is range-checked before it is used.
 #include <math.h>
 #include "common.h"
+#include "bitvol.h"
 
 #pragma clang fp contract(off)
 
@@ -134,20 +135,17 @@ struct rd_dims {
     int X, Y, Z, W;                       // W words per voxel row
     int BX, BY, BZ;                       // bricks per axis; BZ = 8 W (a word is eight bricks long)
 };
-static inline bool rd_shape_ok(int X, int Y, int Z) {
-    return X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31);
-}
 static inline rd_dims rd_make_dims(int X, int Y, int Z) {
     rd_dims g;
     g.X = X; g.Y = Y; g.Z = Z;
-    g.W = (Z + 63) / 64;
+    g.W = bv_words(Z);
     g.BX = (X + RD_BRICK - 1) / RD_BRICK;
     g.BY = (Y + RD_BRICK - 1) / RD_BRICK;
     g.BZ = g.W * 8;
     return g;
 }
-static inline size_t rd_mask_bytes(const rd_dims& g) { return ((size_t)g.X * g.Y * g.W * 8 + 255) / 256 * 256; }
-static inline size_t rd_brick_bytes(const rd_dims& g) { return ((size_t)g.BX * g.BY * g.BZ + 255) / 256 * 256; }
+static inline size_t rd_mask_bytes(const rd_dims& g) { return bv_align((size_t)g.X * g.Y * g.W * 8); }
+static inline size_t rd_brick_bytes(const rd_dims& g) { return bv_align((size_t)g.BX * g.BY * g.BZ); }
 
 __global__ __launch_bounds__(RD_THREADS) void rd_prepare_kernel(const uint8_t* __restrict__ labels, rd_dims g,
                                                                 const uint8_t* __restrict__ table,
@@ -297,12 +295,8 @@ __global__ __launch_bounds__(RD_THREADS) void rd_surface_kernel(const uint8_t* _
     depth[(long long)v * W + u] = first;
 }
 
-#define RD_REQUIRE_SHAPE(what)                                                                                       \
-    RU3D_REQUIRE(rd_shape_ok(X, Y, Z), what ": a %dx%dx%d volume is not supported (every extent positive, X*Y*Z < 2^31)", \
-                 X, Y, Z)
-
 extern "C" size_t ru3d_render_surface_workspace_bytes(int X, int Y, int Z) {
-    if (!rd_shape_ok(X, Y, Z)) return 0;
+    if (!bv_shape_ok(X, Y, Z)) return 0;
     const rd_dims g = rd_make_dims(X, Y, Z);
     return rd_mask_bytes(g) + rd_brick_bytes(g);
 }
@@ -310,7 +304,7 @@ extern "C" size_t ru3d_render_surface_workspace_bytes(int X, int Y, int Z) {
 extern "C" int ru3d_render_surface_prepare(const uint8_t* labels, int X, int Y, int Z, const uint8_t* table, void* ws,
                                            size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RD_REQUIRE_SHAPE("render_surface_prepare");
+    BV_REQUIRE_SHAPE("render_surface_prepare");
     RU3D_REQUIRE(labels && table && ws, "render_surface_prepare: bad argument (null pointer)");
     RU3D_REQUIRE(((uintptr_t)ws & 7) == 0, "render_surface_prepare: the workspace must be 8-byte aligned");
     const rd_dims g = rd_make_dims(X, Y, Z);
@@ -331,7 +325,7 @@ extern "C" int ru3d_render_surface(const uint8_t* labels, int X, int Y, int Z, c
                                    const ru3d_render_view* view, uint8_t* rgb, int32_t* depth, int H, int W, const void* ws,
                                    size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RD_REQUIRE_SHAPE("render_surface");
+    BV_REQUIRE_SHAPE("render_surface");
     RU3D_REQUIRE(labels && table && view && rgb && depth && ws, "render_surface: bad argument (null pointer)");
     RU3D_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)depth & 3) == 0,
                  "render_surface: the workspace must be 8-byte aligned and the depth image 4-byte aligned");

@@ -2,8 +2,8 @@
 // end and junction voxels, graph length, radius statistics).  The contract is written down in include/ru3d.h; the numpy
 // twin that defines the result is transform._skeleton_numpy.
 //
-// Masks are the packed masks of morphology.hip: bit b of word w of row (x, y) is voxel z = 64 w + b, the bits at z >= Z
-// are 0, which is also what "outside the volume is background" needs along z.
+// Masks are the packed masks of bitvol.h, read with its bounded word fetch and z-neighbour view: the bits at z >= Z are
+// 0, which is also what "outside the volume is background" needs along z.
 //   sk_mark_kernel      candidates of a direction d: cand = m & ~shift(m, d), one word per lane.  +-x and +-y read the
 //                       neighbouring row's word, +-z shift across the word boundary.
 //   sk_subpass_kernel   one (direction, subfield) sub-pass, in place.  A workgroup owns 8 x 8 rows of the subfield's (x, y)
@@ -27,6 +27,7 @@
 // Integer atomics (vector memory operations) and fixed-order float64 sums only: the same bits in every run.
 #include <math.h>
 #include "common.h"
+#include "bitvol.h"
 
 #pragma clang fp contract(off)
 
@@ -83,14 +84,6 @@ __device__ __forceinline__ unsigned sk_three(sk_u64 prev, sk_u64 cur, sk_u64 nex
     return t & 7u;
 }
 
-__device__ __forceinline__ sk_u64 sk_word(const sk_u64* __restrict__ m, int X, int Y, int W, int x, int y, int w) {
-    return (x >= 0 && x < X && y >= 0 && y < Y && w >= 0 && w < W) ? m[((int64_t)x * Y + y) * W + w] : 0ull;
-}
-// the row's bits seen from one voxel further along z: bit b = voxel z + dz
-__device__ __forceinline__ sk_u64 sk_shift(sk_u64 prev, sk_u64 cur, sk_u64 next, int dz) {
-    return dz == 0 ? cur : (dz > 0 ? (cur >> 1) | (next << 63) : (cur << 1) | (prev >> 63));
-}
-
 // ------------------------------------------------------------------------------------------------ thinning
 __global__ __launch_bounds__(256) void sk_mark_kernel(const sk_u64* __restrict__ mask, sk_u64* __restrict__ cand, int X, int Y,
                                                       int W, int d, int64_t words) {
@@ -106,8 +99,8 @@ __global__ __launch_bounds__(256) void sk_mark_kernel(const sk_u64* __restrict__
                 case 1: n = x < X - 1 ? mask[i + xstep] : 0ull; break;
                 case 2: n = y > 0 ? mask[i - W] : 0ull; break;
                 case 3: n = y < Y - 1 ? mask[i + W] : 0ull; break;
-                case 4: n = (m << 1) | (w > 0 ? mask[i - 1] >> 63 : 0ull); break;
-                default: n = (m >> 1) | (w < W - 1 ? mask[i + 1] << 63 : 0ull); break;
+                case 4: n = bv_zdown(w > 0 ? mask[i - 1] : 0ull, m); break;
+                default: n = bv_zup(m, w < W - 1 ? mask[i + 1] : 0ull); break;
             }
         }
         cand[i] = m & ~n;
@@ -132,7 +125,7 @@ __global__ __launch_bounds__(256) void sk_subpass_kernel(sk_u64* __restrict__ ma
     for (int i = threadIdx.x; i < SK_SX * SK_SY * SK_SW; i += 256) {
         const int k = i % SK_SW, r = i / SK_SW;
         const int hx = r / SK_SY, hy = r - hx * SK_SY;
-        tile[r * SK_PITCH + k] = sk_word(mask, X, Y, W, x0 - 1 + hx, y0 - 1 + hy, w0 - 1 + k);
+        tile[r * SK_PITCH + k] = bv_word(mask, X, Y, W, x0 - 1 + hx, y0 - 1 + hy, w0 - 1 + k);
     }
     __syncthreads();
 
@@ -156,9 +149,7 @@ __global__ __launch_bounds__(256) void sk_subpass_kernel(sk_u64* __restrict__ ma
         }
         if (kill) mask[at] = rows[4][1] & ~kill;
     }
-    int n = __popcll(kill);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    const int n = bv_wave_sum(__popcll(kill));
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(deleted, (unsigned long long)n);
 }
 
@@ -177,12 +168,12 @@ __global__ __launch_bounds__(256) void sk_classify_kernel(const sk_u64* __restri
 #pragma unroll
             for (int r = 0; r < 9; r++) {
                 const int nx = x + r / 3 - 1, ny = y + r % 3 - 1;
-                const sk_u64 prev = sk_word(mask, X, Y, W, nx, ny, w - 1), cur = sk_word(mask, X, Y, W, nx, ny, w),
-                             next = sk_word(mask, X, Y, W, nx, ny, w + 1);
+                const sk_u64 prev = bv_word(mask, X, Y, W, nx, ny, w - 1), cur = bv_word(mask, X, Y, W, nx, ny, w),
+                             next = bv_word(mask, X, Y, W, nx, ny, w + 1);
 #pragma unroll
                 for (int dz = -1; dz <= 1; dz++) {
                     if (r == 4 && dz == 0) continue;
-                    const sk_u64 v = sk_shift(prev, cur, next, dz);
+                    const sk_u64 v = bv_zview(prev, cur, next, dz);
                     const sk_u64 carry = c0 & v;
                     c0 ^= v;
                     sat |= c1 & carry;
@@ -198,12 +189,7 @@ __global__ __launch_bounds__(256) void sk_classify_kernel(const sk_u64* __restri
         ne += __popcll(e);
         nj += __popcll(j);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        nv += __shfl_xor(nv, o, 64);
-        ne += __shfl_xor(ne, o, 64);
-        nj += __shfl_xor(nj, o, 64);
-    }
+    nv = bv_wave_sum(nv), ne = bv_wave_sum(ne), nj = bv_wave_sum(nj);
     if ((threadIdx.x & 63) == 0) {
         if (nv) atomicAdd(&counts[0], (unsigned long long)nv);
         if (ne) atomicAdd(&counts[1], (unsigned long long)ne);
@@ -229,20 +215,18 @@ __global__ __launch_bounds__(256) void sk_pairs_kernel(const sk_u64* __restrict_
 #pragma unroll
         for (int r = 4; r < 9; r++) {                                       // the rows (0, 0), (0, 1), (1, -1), (1, 0), (1, 1)
             const int nx = x + r / 3 - 1, ny = y + r % 3 - 1;
-            const sk_u64 prev = sk_word(mask, X, Y, W, nx, ny, w - 1), cur = r == 4 ? m : sk_word(mask, X, Y, W, nx, ny, w),
-                         next = sk_word(mask, X, Y, W, nx, ny, w + 1);
+            const sk_u64 prev = bv_word(mask, X, Y, W, nx, ny, w - 1), cur = r == 4 ? m : bv_word(mask, X, Y, W, nx, ny, w),
+                         next = bv_word(mask, X, Y, W, nx, ny, w + 1);
 #pragma unroll
             for (int dz = -1; dz <= 1; dz++) {
                 const int cell = 3 * r + dz + 1;
-                if (cell > 13) n[cell - 14] += __popcll(m & sk_shift(prev, cur, next, dz));
+                if (cell > 13) n[cell - 14] += __popcll(m & bv_zview(prev, cur, next, dz));
             }
         }
     }
 #pragma unroll
     for (int k = 0; k < 13; k++) {
-        int v = n[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        const int v = bv_wave_sum(n[k]);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&pairs[k], (unsigned long long)v);
     }
 }
@@ -264,12 +248,7 @@ __global__ __launch_bounds__(256) void sk_overlap_kernel(const sk_u64* __restric
         nb += __popcll(vb);
         nab += __popcll(va & vb);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        na += __shfl_xor(na, o, 64);
-        nb += __shfl_xor(nb, o, 64);
-        nab += __shfl_xor(nab, o, 64);
-    }
+    na = bv_wave_sum(na), nb = bv_wave_sum(nb), nab = bv_wave_sum(nab);
     if ((threadIdx.x & 63) == 0) {
         if (na) atomicAdd(&counts[0], (unsigned long long)na);
         if (nb) atomicAdd(&counts[1], (unsigned long long)nb);
@@ -309,11 +288,6 @@ __global__ __launch_bounds__(SK_RTHREADS) void sk_radius_kernel(const double* __
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline bool sk_shape_ok(int X, int Y, int Z) {
-    return X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31);
-}
-static inline int sk_words(int Z) { return (Z + 63) / 64; }
-static inline size_t sk_align(size_t n) { return (n + 255) & ~(size_t)255; }
 static inline unsigned sk_blocks(int64_t words) {
     const int64_t cap = (int64_t)ru3d_get_cu_budget() * 8;
     int64_t blocks = (words + 255) / 256;
@@ -321,25 +295,22 @@ static inline unsigned sk_blocks(int64_t words) {
     return (unsigned)(blocks < 1 ? 1 : blocks);
 }
 
-#define SK_REQUIRE_SHAPE(what)                                                                                       \
-    RU3D_REQUIRE(sk_shape_ok(X, Y, Z), what ": a %dx%dx%d volume is not supported (every extent positive, X*Y*Z < 2^31)", \
-                 X, Y, Z)
 #define SK_COUNTERS 256                   // bytes of integer counters at the head of the workspace
 
 extern "C" size_t ru3d_skeleton_workspace_bytes(int X, int Y, int Z) {
-    if (!sk_shape_ok(X, Y, Z)) return 0;
-    return SK_COUNTERS + sk_align((size_t)X * Y * sk_words(Z) * sizeof(sk_u64));
+    if (!bv_shape_ok(X, Y, Z)) return 0;
+    return SK_COUNTERS + bv_align((size_t)X * Y * bv_words(Z) * sizeof(sk_u64));
 }
 
 extern "C" int ru3d_skeleton_thin(uint64_t* mask, int X, int Y, int Z, int max_iterations, void* ws, size_t ws_bytes,
                                   void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    SK_REQUIRE_SHAPE("skeleton_thin");
+    BV_REQUIRE_SHAPE("skeleton_thin");
     RU3D_REQUIRE(mask && ws, "skeleton_thin: bad argument (null pointer)");
     RU3D_REQUIRE(ws_bytes >= ru3d_skeleton_workspace_bytes(X, Y, Z), "skeleton_thin: workspace of %zu bytes, %zu needed",
                  ws_bytes, ru3d_skeleton_workspace_bytes(X, Y, Z));
     hipStream_t st = as_stream(stream);
-    const int W = sk_words(Z);
+    const int W = bv_words(Z);
     const int64_t words = (int64_t)X * Y * W;
     unsigned long long* deleted = (unsigned long long*)ws;
     sk_u64* cand = (sk_u64*)((char*)ws + SK_COUNTERS);
@@ -378,11 +349,11 @@ extern "C" int ru3d_skeleton_thin(uint64_t* mask, int X, int Y, int Z, int max_i
 extern "C" int ru3d_skeleton_classify(const uint64_t* skel, int X, int Y, int Z, uint64_t* ends, uint64_t* junctions,
                                       int64_t* counts, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    SK_REQUIRE_SHAPE("skeleton_classify");
+    BV_REQUIRE_SHAPE("skeleton_classify");
     RU3D_REQUIRE(skel && ends && junctions && counts, "skeleton_classify: bad argument (null pointer)");
     RU3D_REQUIRE(skel != ends && skel != junctions && ends != junctions, "skeleton_classify: the three masks must be distinct");
     hipStream_t st = as_stream(stream);
-    const int W = sk_words(Z);
+    const int W = bv_words(Z);
     const int64_t words = (int64_t)X * Y * W;
     if (hipMemsetAsync(counts, 0, 3 * sizeof(int64_t), st) != hipSuccess) return ru3d_check_launch("skeleton_classify (memset)");
     hipLaunchKernelGGL(sk_classify_kernel, dim3(sk_blocks(words)), dim3(256), 0, st, (const sk_u64*)skel, (sk_u64*)ends,
@@ -393,7 +364,7 @@ extern "C" int ru3d_skeleton_classify(const uint64_t* skel, int X, int Y, int Z,
 extern "C" int ru3d_skeleton_length(const uint64_t* skel, int X, int Y, int Z, const double* spacing, double* out, void* ws,
                                     size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    SK_REQUIRE_SHAPE("skeleton_length");
+    BV_REQUIRE_SHAPE("skeleton_length");
     RU3D_REQUIRE(skel && spacing && out && ws, "skeleton_length: bad argument (null pointer)");
     RU3D_REQUIRE(ws_bytes >= SK_COUNTERS, "skeleton_length: workspace of %zu bytes, %d needed", ws_bytes, SK_COUNTERS);
     for (int a = 0; a < 3; a++)
@@ -407,7 +378,7 @@ extern "C" int ru3d_skeleton_length(const uint64_t* skel, int X, int Y, int Z, c
         steps.mm[k] = sqrt(a + bc);
     }
     hipStream_t st = as_stream(stream);
-    const int W = sk_words(Z);
+    const int W = bv_words(Z);
     const int64_t words = (int64_t)X * Y * W;
     unsigned long long* pairs = (unsigned long long*)ws;
     if (hipMemsetAsync(pairs, 0, 13 * sizeof(unsigned long long), st) != hipSuccess)
@@ -419,10 +390,10 @@ extern "C" int ru3d_skeleton_length(const uint64_t* skel, int X, int Y, int Z, c
 
 extern "C" int ru3d_skeleton_overlap(const uint64_t* a, const uint64_t* b, int X, int Y, int Z, int64_t* counts, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    SK_REQUIRE_SHAPE("skeleton_overlap");
+    BV_REQUIRE_SHAPE("skeleton_overlap");
     RU3D_REQUIRE(a && b && counts, "skeleton_overlap: bad argument (null pointer)");
     hipStream_t st = as_stream(stream);
-    const int64_t words = (int64_t)X * Y * sk_words(Z);
+    const int64_t words = (int64_t)X * Y * bv_words(Z);
     if (hipMemsetAsync(counts, 0, 3 * sizeof(int64_t), st) != hipSuccess) return ru3d_check_launch("skeleton_overlap (memset)");
     hipLaunchKernelGGL(sk_overlap_kernel, dim3(sk_blocks(words)), dim3(256), 0, st, (const sk_u64*)a, (const sk_u64*)b, words,
                        (unsigned long long*)counts);

@@ -169,6 +169,19 @@ def test_gather_is_numpy_boolean_indexing(dev, shape):
     assert np.array_equal(buf[:small].cpu().numpy(), sq[query][:small]) and bool((buf[small:] == -1.0).all())
 
 
+@pytest.mark.parametrize("shape", [(513, 512, 1), (300, 440, 65)])
+def test_gather_scans_more_than_1024_chunk_counts(dev, shape):
+    """1026 and 1032 chunks of 256 words (the second shape with a tail word): the one-workgroup scan of the chunk counts
+    gives a thread two chunks, and the chunk count is no multiple of its 1024 threads."""
+    rng = np.random.RandomState(shape[0])
+    sq = rng.rand(*shape)
+    query = rng.rand(*shape) < 0.3
+    n = int(query.sum())
+    values, count = distance.gather(torch.from_numpy(sq).to(dev), packed(query, dev), capacity=n + 5)
+    assert int(count.item()) == n
+    assert np.array_equal(values[:n].cpu().numpy(), sq[query])
+
+
 def test_reductions_over_a_gathered_vector(dev):
     rng = np.random.RandomState(9)
     for n, cap in ((1, 1), (5000, 5000), (5000, 9000), (2048, 4096), (70001, 70001)):

@@ -72,6 +72,21 @@ def test_extract_equals_the_numpy_route_on_random_masks(shape):
     assert volume == float(m.sum()) and area == float(len(host.faces) // 2)
 
 
+def test_extract_scans_more_than_1024_chunk_counts():
+    """(513, 512, 1): 1031 chunks of corner words and 1026 of mask words, so both lists of the one-workgroup-per-list scan
+    give a thread two chunks and neither count is a multiple of its 1024 threads.  Sparse, so the numpy route stays quick."""
+    shape = (513, 512, 1)
+    m = random_mask(shape, sum(shape), density=0.02)
+    host = transform.extract_mesh(m, 0)
+    dev = transform.extract_mesh(torch.from_numpy(m).to(DEV), 0)
+    same_mesh(dev, host)
+    assert mesh.count(torch.from_numpy(m).to(DEV)) == (len(host.corners), len(host.faces) // 2)
+    packed = morphology.pack(torch.from_numpy(m.astype(np.uint8)).to(DEV))
+    same_mesh(mesh.extract(packed), host)
+    area, volume = mesh.measure(dev.vertices, dev.faces).tolist()
+    assert volume == float(m.sum()) and area == float(len(host.faces) // 2)
+
+
 def test_extract_of_empty_full_and_single_voxel_volumes():
     empty = transform.extract_mesh(torch.zeros((7, 5, 70), dtype=torch.uint8, device=DEV))
     assert tuple(empty.corners.shape) == (0, 3) and tuple(empty.faces.shape) == (0, 3)

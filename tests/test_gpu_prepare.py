@@ -84,6 +84,18 @@ def test_masked_sample_is_numpy_fancy_indexing(dtype, stride):
             assert got.dtype == torch.float32 and np.array_equal(got.cpu().numpy(), want)
 
 
+@pytest.mark.parametrize("stride", [1, 7])
+def test_masked_sample_scans_more_than_1024_chunk_counts(stride):
+    """(129, 128, 128): 1032 chunks of 2048 voxels, so the one-workgroup scan of the chunk counts gives a thread two
+    chunks and the chunk count is no multiple of its 1024 threads."""
+    rng = np.random.RandomState(stride)
+    shape = (129, 128, 128, 1)
+    img = rng.randn(*shape).astype(np.float32)
+    lab = (rng.rand(*shape[:3]) < 0.3).astype(np.uint8)
+    got = prepare.masked_sample(_dev(img), _dev(lab), 0, stride)
+    assert got.dtype == torch.float32 and np.array_equal(got.cpu().numpy(), img[..., 0][lab > 0][::stride])
+
+
 def test_masked_sample_counts_and_buffers():
     rng = np.random.RandomState(0)
     img = rng.randn(20, 21, 23, 1).astype(np.float32)
