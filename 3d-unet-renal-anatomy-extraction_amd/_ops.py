@@ -593,6 +593,57 @@ def skip1x1_in_lrelu_fwd(x, pw, bias, y, mean, scale, out=None):
     return out
 
 
+def head_tail_mode():
+    """RU3D_HEAD_TAIL, read at every call: "0" keeps the head an autograd node of its own (network.ResBlock.takes_head);
+    "fwd" / "bwd" fuse that half only - the other half runs its unfused launches inside the block's node - so one process
+    can time the halves apart; anything else fuses both."""
+    return os.environ.get("RU3D_HEAD_TAIL", "1")
+
+
+def skip1x1_in_lrelu_head_fwd(x, pw, bias, y, mean, scale, head_pw, head_bias, head_cout):
+    """skip1x1_in_lrelu_fwd that also hands out the fp32 logits of the network's 1x1x1 head on its result
+    (ru3d_skip1x1_in_lrelu_head_fwd; head_pw: the head's forward pack): (z, logits), or None when the shapes have no
+    fused kernel."""
+    code = N.dtype_code(y.dtype)
+    if code == N.F32 or head_cout > 4:
+        return None
+    n, c, d, h, w = y.shape
+    out = N.new_act(n, c, d, h, w, y.dtype, y.device)
+    logits = N.new_act(n, head_cout, d, h, w, torch.float32, y.device)
+    dx, dy, do, dl = desc(x), desc(y), desc(out), desc(logits)
+    if not N.lib.ru3d_skip1x1_in_lrelu_head_fwd_supported(ref(dx), ref(dy), ref(do), ref(dl), code):
+        return None
+    check(N.lib.ru3d_skip1x1_in_lrelu_head_fwd(ref(dx), ptr(pw), ptr(_bias(bias)), ref(dy), ptr(mean), ptr(scale), ref(do),
+                                               ptr(head_pw), ptr(_bias(head_bias)), ref(dl), LRELU_SLOPE, code, stream()),
+          "skip1x1_in_lrelu_head_fwd")
+    return out, logits
+
+
+def head_in_bwd(z, gy, weight, want_bias, y, mean, scale, key=None):
+    """head_bwd on (z, gy) followed by in_lrelu_bwd(., z, y, mean, scale, want_gpre, want_gpre_sum) in one reduction pass
+    (ru3d_head_in_bwd: the head's input gradient is never stored): (dy, gpre, gpre_sum, dW, db), or None when the shapes
+    have no fused kernel."""
+    if gy.dtype != torch.float32 or z.dtype == torch.float32 or not N.is_ndhwc(gy) or weight.dtype != torch.float32:
+        return None
+    n, c, d, h, w = z.shape
+    dy = N.new_act(n, c, d, h, w, z.dtype, z.device)
+    gpre = N.new_act(n, c, d, h, w, z.dtype, z.device)
+    dz, dg, dyy, dp, ddy = desc(z), desc(gy), desc(y), desc(gpre), desc(dy)
+    code = N.dtype_code(z.dtype)
+    if not N.lib.ru3d_head_in_bwd_supported(ref(dz), ref(dg), ref(dyy), ref(dp), ref(ddy), code):
+        return None
+    cout, cin = weight.shape[0], weight.shape[1]
+    dw = _grad_out(key, (cout, cin, 1, 1, 1), z.device)
+    db = torch.empty(cout, dtype=torch.float32, device=z.device) if want_bias else None
+    gsum = torch.empty(c, dtype=torch.float32, device=z.device)
+    ws = N.workspace(N.lib.ru3d_head_in_bwd_workspace_bytes(ref(dz), code), z.device)
+    wd = weight.detach()
+    check(N.lib.ru3d_head_in_bwd(ref(dz), ref(dg), ptr(wd if wd.is_contiguous() else wd.contiguous()), cin, ref(dyy),
+                                 ptr(mean), ptr(scale), ref(dp), ref(ddy), ptr(dw), ptr(db), ptr(gsum), ptr(ws), ws.numel(),
+                                 LRELU_SLOPE, code, stream()), "head_in_bwd")
+    return dy, gpre, gsum, dw, db
+
+
 def in_lrelu_bwd(gout, out, y, mean, scale, want_gpre=False, zero_far=False, want_gpre_sum=False, dy_sum=None):
     """dy_sum: optional float32 [C] tensor that receives the channel sums of dy (the producing conv's bias gradient)."""
     n, c, d, h, w = y.shape
@@ -1037,11 +1088,15 @@ class ResBlockFn(torch.autograd.Function):
     checkpoint: only the block's input, output and the InstanceNorm statistics are kept for backward; the three
     interior tensors (conv1 output, its activation, conv2 output) are recomputed there by the same kernels, so the
     gradients are the same bits (BASELINE config 5: activation checkpointing).
+    head_w / head_b: the network's 1x1x1 head (reference network.py:547 fc, Cout <= 4) when it is the only consumer of the
+    block's output: the function then returns the head's fp32 logits instead of the block's output - out of the tail
+    kernel's epilogue in forward, and with the head's backward folded into the InstanceNorm backward's reduction pass -
+    and the two get the head's gradients.  The values are those of ConvFn on the block's output.
     """
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, ws, bs, stride, drop_scale, pad=0, checkpoint=False, in_link=None,
-                out_link=None, planar=False):
+                out_link=None, planar=False, head_w=None, head_b=None):
         """in_link: SkipLink whose parked gradient this block adds to its input gradient (pooling block);
         out_link: SkipLink into whose concat buffer the block writes its output (last encoder block of a level);
         planar: x is a split concat - the [2N, C/2, D, H, W] tensor of its two planes (N.Split, UpFn made it)."""
@@ -1097,9 +1152,19 @@ class ResBlockFn(torch.autograd.Function):
         # (no link buffer then: decoder outputs are not skips); the shapes are skip1x1_fused_eligible's
         tail = (fused is None and ws is not None and stride == 1 and out_link is None and sd != torch.float32
                 and (x.shape[1], cout_p) in ((64, 32), (128, 64)) and n_ * d_ * h_ * w_ >= 65536)
+        logits = head_pack = None
+        if head_w is not None:
+            if head_w.shape[1] != cout or head_w.shape[2] != 1 or out_link is not None:
+                raise N.Ru3dError("ResBlock: the head must be a 1x1x1 conv on the block's %d output channels" % cout)
+            head_pack = pack_weights([(head_w, N.ROLE_CONV_FWD, 1, 0, cout_seg)], sd)[0]
         if tail:
             y2, mean2, scale2 = conv_fwd_in(a1, pw2, b2, cout_p, 3, 1)
-            z = skip1x1_in_lrelu_fwd(x, packs[2], bs, y2, mean2, scale2)
+            both = (skip1x1_in_lrelu_head_fwd(x, packs[2], bs, y2, mean2, scale2, head_pack, head_b, head_w.shape[0])
+                    if (head_w is not None and head_tail_mode() != "bwd") else None)
+            if both is not None:
+                z, logits = both
+            else:
+                z = skip1x1_in_lrelu_fwd(x, packs[2], bs, y2, mean2, scale2)
             if z is None:
                 z = in_lrelu_fwd(y2, mean2, scale2, res=conv_fwd(x, packs[2], bs, cout_p, 1, stride), out=zout)
         else:
@@ -1110,13 +1175,19 @@ class ResBlockFn(torch.autograd.Function):
             else:
                 skip = x
             y2, mean2, scale2, z = conv_fwd_in_act(a1, pw2, b2, cout_p, 3, 1, res=skip, out=zout)
+        if head_w is not None and logits is None:      # no fused kernel for the shapes: the head's own launch
+            logits = conv_fwd(z, head_pack, head_b, head_w.shape[0], 1, 1, out_dtype=torch.float32)
         bwd = packs[nfwd:nw] + [None] * 3
+        hsave = head_w if train else None      # the head's backward reads the fp32 parameter
         if checkpoint and train:
             ctx.save_for_backward(xt, None, None, None, z, mean1, scale1, mean2, scale2, bwd[0], bwd[1], bwd[2],
-                                  pw1, pw2, b1, b2)
+                                  pw1, pw2, b1, b2, hsave)
         else:
             ctx.save_for_backward(xt, y1, a1, y2, z, mean1, scale1, mean2, scale2, bwd[0], bwd[1], bwd[2],
-                                  None, None, None, None)
+                                  None, None, None, None, hsave)
+        ctx.head = head_w is not None
+        ctx.head_bias = head_b is not None
+        ctx.hkey = head_w.data_ptr() if (head_w is not None and not cout_seg) else None
         ctx.planar = bool(planar)
         ctx.dims = (cout, cin, cout_seg, cin_seg)
         ctx.stride = stride
@@ -1127,17 +1198,42 @@ class ResBlockFn(torch.autograd.Function):
         ctx.in_link = in_link if (in_link is not None and ws is not None) else None
         if in_link is not None:
             in_link.fused_grad = ctx.in_link is not None and need_gx      # UpFn parks its share only when it will be used
-        return z
+        return logits if head_w is not None else z
+
+    @staticmethod
+    def _head_backward(ctx, gy, z, head_w, y2, mean2, scale2):
+        """The head's backward and the block's IN + LeakyReLU backward: (dy2, gpre, gbs_sum, dW_head, db_head).  One
+        reduction pass where the fused kernel takes the shapes; otherwise ConvFn.backward's steps followed by
+        in_lrelu_bwd, as two autograd nodes would run them."""
+        cout, cin, cout_seg, cin_seg = ctx.dims
+        sd = z.dtype
+        want_b = ctx.head_bias and ctx.needs_input_grad[15]
+        fused = head_in_bwd(z, gy, head_w, want_b, y2, mean2, scale2, key=ctx.hkey) if head_tail_mode() != "fwd" else None
+        if fused is not None:
+            return fused
+        hb = head_bwd(z, gy, head_w, want_b, key=ctx.hkey)
+        if hb is not None:
+            gz, ghw, ghb = hb
+        else:
+            gy = as_grad(gy, sd)
+            hcout = head_w.shape[0]
+            ghw = unpad_wgrad(conv_wgrad(z, gy, 1, 1, key=ctx.hkey), hcout, cout, 0, cout_seg)
+            ghb = channel_sum(gy)[:hcout] if want_b else None
+            pwd = pack_weights([(head_w, N.ROLE_CONV_DGRAD, 1, 0, cout_seg)], sd)[0]
+            gz = conv_dgrad(gy, pwd, tuple(z.shape), 1, 1)
+        dy2, gpre, gbs_sum = in_lrelu_bwd(gz, z, y2, mean2, scale2, want_gpre=True, want_gpre_sum=True)
+        return dy2, gpre, gbs_sum, ghw, ghb
 
     @staticmethod
     def backward(ctx, gz):
-        (x, y1, a1, y2, z, mean1, scale1, mean2, scale2, pw2d, pw1d, pwsd, pw1, pw2, b1, b2) = ctx.saved_tensors
+        (x, y1, a1, y2, z, mean1, scale1, mean2, scale2, pw2d, pw1d, pwsd, pw1, pw2, b1, b2, head_w) = ctx.saved_tensors
         cout, cin, cout_seg, cin_seg = ctx.dims
         cout_p = padded_dim(cout, cout_seg)
         sd = x.dtype
         dev = x.device
         stride = ctx.stride
-        gz = as_grad(gz, sd)
+        if not ctx.head:
+            gz = as_grad(gz, sd)
         if ctx.planar:
             x = N.Split(x)
         if y1 is None:      # checkpointed: the same kernels on the same inputs give the same bits
@@ -1146,9 +1242,13 @@ class ResBlockFn(torch.autograd.Function):
             y2 = conv_fwd(a1, pw2, b2, cout_p, 3, 1)
         # lrelu(IN(y2) + skip): dy2 and the pre-activation gradient (= d/dskip)
         # sum(gpre) - the skip conv's bias gradient - comes out of the same reduction
-        dy2, gpre, gbs_sum = in_lrelu_bwd(gz, z, y2, mean2, scale2, want_gpre=True, want_gpre_sum=True)
+        ghw = ghb = None
+        if ctx.head:
+            dy2, gpre, gbs_sum, ghw, ghb = ResBlockFn._head_backward(ctx, gz, z, head_w, y2, mean2, scale2)
+        else:
+            dy2, gpre, gbs_sum = in_lrelu_bwd(gz, z, y2, mean2, scale2, want_gpre=True, want_gpre_sum=True)
         del y2
-        return ResBlockFn._backward_tail(ctx, x, a1, y1, dy2, gpre, gbs_sum, mean1, scale1, pw2d, pw1d, pwsd)
+        return ResBlockFn._backward_tail(ctx, x, a1, y1, dy2, gpre, gbs_sum, mean1, scale1, pw2d, pw1d, pwsd) + (ghw, ghb)
 
     @staticmethod
     def _backward_tail(ctx, x, a1, y1, dy2, gpre, gbs_sum, mean1, scale1, pw2d, pw1d, pwsd):

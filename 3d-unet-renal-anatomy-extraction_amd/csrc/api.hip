@@ -465,6 +465,28 @@ extern "C" int ru3d_skip1x1_in_lrelu_fwd(const ru3d_tensor* x, const void* w_pac
     return skip1x1_fused_launch(x, w_packed, bias, y, mean, scale, out, slope, as_stream(stream));
 }
 
+// the same pass with the network's head on its output: the logits leave the kernel's epilogue
+extern "C" int ru3d_skip1x1_in_lrelu_head_fwd_supported(const ru3d_tensor* x, const ru3d_tensor* y, const ru3d_tensor* out,
+                                                        const ru3d_tensor* logits, int dtype) {
+    RU3D_FWD_F16(dtype, ru3d_skip1x1_in_lrelu_head_fwd_supported_f16(x, y, out, logits, dtype));
+    return skip1x1_head_fused_eligible(x, y, out, logits, dtype) ? 1 : 0;
+}
+
+extern "C" int ru3d_skip1x1_in_lrelu_head_fwd(const ru3d_tensor* x, const void* w_packed, const float* bias,
+                                              const ru3d_tensor* y, const float* mean, const float* scale,
+                                              const ru3d_tensor* out, const void* head_w_packed, const float* head_bias,
+                                              const ru3d_tensor* logits, float slope, int dtype, void* stream) {
+    RU3D_FWD_F16(dtype, ru3d_skip1x1_in_lrelu_head_fwd_f16(x, w_packed, bias, y, mean, scale, out, head_w_packed, head_bias,
+                                                           logits, slope, dtype, stream));
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(w_packed && mean && scale && head_w_packed, "skip1x1_in_lrelu_head_fwd: null argument");
+    RU3D_REQUIRE(skip1x1_head_fused_eligible(x, y, out, logits, dtype),
+                 "skip1x1_in_lrelu_head_fwd: shapes have no fused kernel (ask ru3d_skip1x1_in_lrelu_head_fwd_supported first)");
+    RU3D_REQUIRE((((uintptr_t)head_w_packed) % 8) == 0, "skip1x1_in_lrelu_head_fwd: the head's pack must be 8-byte aligned");
+    return skip1x1_fused_launch(x, w_packed, bias, y, mean, scale, out, slope, as_stream(stream), head_w_packed, head_bias,
+                                logits);
+}
+
 // ---- the two stride-2 convs of a pooling ResBlock: forward of both + InstanceNorm sums in one launch (conv_s2.hip, G form)
 extern "C" int ru3d_conv3d_s2_pair_fwd_in_supported(const ru3d_tensor* x, const ru3d_tensor* y3, const ru3d_tensor* y1, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_s2_pair_fwd_in_supported_f16(x, y3, y1, dtype));

@@ -146,8 +146,12 @@ int conv_s2_tile_launch(const void* x, const void* w, const float* bias, void* y
 
 // fused_skip.hip (decoder ResBlock tail: 1x1x1 skip conv + InstanceNorm apply + sum + LeakyReLU in one pass)
 bool skip1x1_fused_eligible(const ru3d_tensor* x, const ru3d_tensor* y2, const ru3d_tensor* out, int dtype);
+// head_w / head_bias / logits: the head-carrying form (the network's 1x1x1 head on the block's output in the same pass)
+bool skip1x1_head_fused_eligible(const ru3d_tensor* x, const ru3d_tensor* y2, const ru3d_tensor* out,
+                                 const ru3d_tensor* logits, int dtype);
 int skip1x1_fused_launch(const ru3d_tensor* x, const void* w, const float* bias, const ru3d_tensor* y2, const float* mean,
-                         const float* scale, const ru3d_tensor* out, float slope, hipStream_t st);
+                         const float* scale, const ru3d_tensor* out, float slope, hipStream_t st,
+                         const void* head_w = nullptr, const float* head_bias = nullptr, const ru3d_tensor* logits = nullptr);
 
 // norm_small.hip (InstanceNorm + LeakyReLU of the small levels).  in_small_mode: 0 = not its shape (norm.hip's three
 // launches), 1 = whole-instance kernel (one launch; can sum a conv's split-K slices itself), 2 = two coalesced kernels.
@@ -200,6 +204,7 @@ bool head_bwd_eligible(int Cin, int Cout, int dtype);
 size_t head_bwd_ws_bytes(int64_t P, int Cin);
 int head_bwd_launch(const void* a, int lda, const float* dlog, int ldd, const float* w, int cin_real, int Cin, int Cout,
                     void* dx, int lddx, float* dw, float* db, void* ws, int64_t P, hipStream_t st);
+// (dx == NULL: dW and db alone - head_bwd_wgrad_kernel, same sums)
 bool head_wgrad_eligible(const WgradGeom& g, int dtype);
 size_t head_wgrad_ws_bytes(const WgradGeom& g);
 int head_wgrad_launch(const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes, const WgradGeom& g,

@@ -43,6 +43,11 @@
     X(ru3d_in_lrelu_fwd) \
     X(ru3d_skip1x1_in_lrelu_fwd_supported) \
     X(ru3d_skip1x1_in_lrelu_fwd) \
+    X(ru3d_skip1x1_in_lrelu_head_fwd_supported) \
+    X(ru3d_skip1x1_in_lrelu_head_fwd) \
+    X(ru3d_head_in_bwd_supported) \
+    X(ru3d_head_in_bwd_workspace_bytes) \
+    X(ru3d_head_in_bwd) \
     X(ru3d_in_lrelu_bwd) \
     X(ru3d_channel_sum) \
     X(ru3d_copy_channels) \
@@ -97,6 +102,11 @@
 #define ru3d_in_lrelu_fwd ru3d_in_lrelu_fwd_f16
 #define ru3d_skip1x1_in_lrelu_fwd_supported ru3d_skip1x1_in_lrelu_fwd_supported_f16
 #define ru3d_skip1x1_in_lrelu_fwd ru3d_skip1x1_in_lrelu_fwd_f16
+#define ru3d_skip1x1_in_lrelu_head_fwd_supported ru3d_skip1x1_in_lrelu_head_fwd_supported_f16
+#define ru3d_skip1x1_in_lrelu_head_fwd ru3d_skip1x1_in_lrelu_head_fwd_f16
+#define ru3d_head_in_bwd_supported ru3d_head_in_bwd_supported_f16
+#define ru3d_head_in_bwd_workspace_bytes ru3d_head_in_bwd_workspace_bytes_f16
+#define ru3d_head_in_bwd ru3d_head_in_bwd_f16
 #define ru3d_in_lrelu_bwd ru3d_in_lrelu_bwd_f16
 #define ru3d_channel_sum ru3d_channel_sum_f16
 #define ru3d_copy_channels ru3d_copy_channels_f16

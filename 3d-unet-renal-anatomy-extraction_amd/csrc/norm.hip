@@ -640,6 +640,159 @@ extern "C" int ru3d_in_lrelu_bwd(const ru3d_tensor* gout, const ru3d_tensor* out
     return ru3d_fail(-1, "in_lrelu_bwd: bad dtype %d", dtype);
 }
 
+// ---- the head's backward and the InstanceNorm + LeakyReLU backward of the residual block in front of it
+// (reference network.py:547 fc behind :414-416).  ru3d_head_bwd stored dz (the head's input gradient) and in_bwd_impl's
+// reduction read it straight back with z and y.  Here dz exists in registers only: head_bwd_wgrad_kernel (small_convs.hip)
+// takes dW and db from (z, dlogits) in ru3d_head_bwd's order, and head_dz_reduce2_kernel is reduce2_kernel MODE 4 - same
+// grid, same voxel order, same sums, same partial layout - with its first operand formed from dlogits and the head's
+// weight the way head_bwd_kernel forms it.  Every value is bit for bit what the two calls give.
+template <int VEC>
+__global__ __launch_bounds__(256) void head_dz_reduce2_kernel(const float* __restrict__ dlog, int ldd,
+                                                              const float* __restrict__ w, int cin_real, int Cout,
+                                                              const bf16* __restrict__ b, int ldb,
+                                                              const bf16* __restrict__ c3, int ldc,
+                                                              const float* __restrict__ mean,
+                                                              const float* __restrict__ scale, float slope,
+                                                              double* __restrict__ part, ChanLoop cl, int C,
+                                                              bf16* __restrict__ gp_out, int ldgp) {
+    static_assert(VEC == 8, "head_bwd_kernel's piece: 8 channels a lane");
+    __shared__ double sh[2][256][4];      // reduced in two halves, as reduce2_kernel does for VEC == 8
+    const int tid = threadIdx.x;
+    const int cgl = tid % cl.Gb, vl = tid / cl.Gb;
+    const int cg = blockIdx.z * cl.Gb + cgl;
+    const int n = blockIdx.y;
+    const bool active = (vl < cl.vpb) && (cg < cl.G);
+    float s1[VEC], s2[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; i++) s1[i] = s2[i] = 0.f;
+    if (active) {
+        float mu[VEC], sc[VEC], wr[4][VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; i++) {
+            mu[i] = mean[n * C + cg * VEC + i];
+            sc[i] = scale[n * C + cg * VEC + i];
+            const int ci = cg * VEC + i;
+#pragma unroll
+            for (int c = 0; c < 4; c++)      // the packed (16-bit) weight, zero beyond the real channels: head_bwd_kernel's wr
+                wr[c][i] = (c < Cout && ci < cin_real) ? (float)(bf16)w[c * cin_real + ci] : 0.f;
+        }
+        const int v0 = blockIdx.x * cl.span;
+        int v1 = v0 + cl.span;
+        if (v1 > cl.V) v1 = cl.V;
+        for (int v = v0 + vl; v < v1; v += cl.vpb) {
+            const int64_t row = (int64_t)n * cl.V + v;
+            float dv[4], av[VEC], ov[VEC], yv[VEC], pv[VEC];
+#pragma unroll
+            for (int c = 0; c < 4; c++) dv[c] = c < Cout ? (float)(bf16)dlog[row * ldd + c] : 0.f;
+            load_vec<bf16, VEC>(b + row * ldb + cg * VEC, ov);
+            load_vec<bf16, VEC>(c3 + row * ldc + cg * VEC, yv);
+#pragma unroll
+            for (int i = 0; i < VEC; i++) av[i] = 0.f;
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+#pragma unroll
+                for (int i = 0; i < VEC; i++) av[i] = fmaf(dv[c], wr[c][i], av[i]);      // head_bwd_kernel's order
+#pragma unroll
+            for (int i = 0; i < VEC; i++) {
+                const float dz = to_f32<bf16>(from_f32<bf16>(av[i]));      // the value head_bwd_kernel stores
+                float gp = ov[i] > 0.f ? dz : dz * slope;
+                gp = to_f32<bf16>(from_f32<bf16>(gp));      // reduce2_kernel MODE 4 from here on
+                pv[i] = gp;
+                const float xh = (yv[i] - mu[i]) * sc[i];
+                s1[i] += gp;
+                s2[i] = fmaf(gp, xh, s2[i]);
+            }
+            store_vec<bf16, VEC>(gp_out + row * ldgp + cg * VEC, pv);
+        }
+    }
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            sh[0][tid][i] = active ? (double)s1[half * 4 + i] : 0.0;
+            sh[1][tid][i] = active ? (double)s2[half * 4 + i] : 0.0;
+        }
+        __syncthreads();
+        if (vl == 0 && cg < cl.G) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                double t1 = 0.0, t2 = 0.0;
+                for (int l = 0; l < cl.vpb; l++) {
+                    t1 += sh[0][l * cl.Gb + cgl][i];
+                    t2 += sh[1][l * cl.Gb + cgl][i];
+                }
+                const int c = cg * VEC + half * 4 + i;
+                double* pp = part + (((int64_t)n * cl.chunks + blockIdx.x) * C + c) * 2;
+                pp[0] = t1;
+                pp[1] = t2;
+            }
+        }
+    }
+}
+
+// workspace: in_bwd_impl's (partials, m12) followed by the head's dW / db partials
+static size_t head_in_red_bytes(const ru3d_tensor* z) { return ((reduce_ws_bytes(z) + 255) / 256) * 256; }
+
+extern "C" int ru3d_head_in_bwd_supported(const ru3d_tensor* z, const ru3d_tensor* dlogits, const ru3d_tensor* y,
+                                          const ru3d_tensor* gpre, const ru3d_tensor* dy, int dtype) {
+    RU3D_FWD_F16(dtype, ru3d_head_in_bwd_supported_f16(z, dlogits, y, gpre, dy, dtype));
+    if (!tensor_ok(z) || !tensor_ok(dlogits) || !tensor_ok(y) || !tensor_ok(gpre) || !tensor_ok(dy)) return 0;
+    if (z->n != dlogits->n || z->d != dlogits->d || z->h != dlogits->h || z->w != dlogits->w) return 0;
+    if (!same_shape(z, y) || !same_shape(z, gpre) || !same_shape(z, dy)) return 0;
+    if ((int64_t)z->d * z->h * z->w >= (1ll << 31) || (((uintptr_t)dlogits->ptr) % 4)) return 0;
+    if (pick_vec<bf16>(z->c, {z, y, gpre, dy}) != 8) return 0;
+    // the small levels' norm backward is another kernel family with sums of its own (norm_small.hip): not mirrored here
+    if (dtype == RU3D_BF16 && in_small_mode(z, true, gpre, y, dy, gpre)) return 0;
+    return head_bwd_eligible(z->c, dlogits->c, dtype) ? 1 : 0;
+}
+
+extern "C" size_t ru3d_head_in_bwd_workspace_bytes(const ru3d_tensor* z, int dtype) {
+    RU3D_FWD_F16(dtype, ru3d_head_in_bwd_workspace_bytes_f16(z, dtype));
+    if (!tensor_ok(z) || (z->c % 8)) return 0;
+    return head_in_red_bytes(z) + head_bwd_ws_bytes(nvox(z), z->c);
+}
+
+extern "C" int ru3d_head_in_bwd(const ru3d_tensor* z, const ru3d_tensor* dlogits, const float* weight, int cin_real,
+                                const ru3d_tensor* y, const float* mean, const float* scale, const ru3d_tensor* gpre,
+                                const ru3d_tensor* dy, float* dw, float* db, float* gpre_sum, void* ws, size_t ws_bytes,
+                                float slope, int dtype, void* stream) {
+    RU3D_FWD_F16(dtype, ru3d_head_in_bwd_f16(z, dlogits, weight, cin_real, y, mean, scale, gpre, dy, dw, db, gpre_sum, ws,
+                                             ws_bytes, slope, dtype, stream));
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(ru3d_head_in_bwd_supported(z, dlogits, y, gpre, dy, dtype),
+                 "head_in_bwd: shapes have no fused kernel (ask ru3d_head_in_bwd_supported first)");
+    RU3D_REQUIRE(weight && dw && mean && scale && ws && cin_real > 0 && cin_real <= z->c, "head_in_bwd: bad argument");
+    RU3D_REQUIRE(ws_bytes >= ru3d_head_in_bwd_workspace_bytes(z, dtype), "head_in_bwd: workspace too small");
+    hipStream_t st = as_stream(stream);
+    const int64_t V = (int64_t)z->d * z->h * z->w;
+    // the head's dW and db: ru3d_head_bwd's pass over (z, dlogits) without its store
+    int rc = head_bwd_launch(z->ptr, z->ld, (const float*)dlogits->ptr, dlogits->ld, weight, cin_real, z->c, dlogits->c,
+                             nullptr, 0, dw, db, (char*)ws + head_in_red_bytes(z), nvox(z), st);
+    if (rc) return rc;
+    // in_bwd_impl's three launches, the first with dz from registers
+    ChanLoop cl = make_chanloop(V, y->c, 8, 64, y->n);
+    dim3 grid(cl.chunks, y->n, (cl.G + cl.Gb - 1) / cl.Gb);
+    double* part = (double*)ws;
+    float* m12 = (float*)((char*)ws + (size_t)y->n * cl.chunks * y->c * 2 * sizeof(double));
+    hipLaunchKernelGGL((head_dz_reduce2_kernel<8>), grid, dim3(256), 0, st, (const float*)dlogits->ptr, dlogits->ld, weight,
+                       cin_real, dlogits->c, (const bf16*)z->ptr, z->ld, (const bf16*)y->ptr, y->ld, mean, scale, slope, part,
+                       cl, y->c, (bf16*)gpre->ptr, gpre->ld);
+    rc = ru3d_check_launch("head_in_bwd_reduce");
+    if (rc) return rc;
+    hipLaunchKernelGGL(bwd_finalize_kernel, dim3((y->c + FIN_CX - 1) / FIN_CX), dim3(256), 0, st, (const double*)part,
+                       cl.chunks, y->c, y->n, 1.0 / (double)V, m12, (double)V, gpre_sum);
+    rc = ru3d_check_launch("head_in_bwd_finalize");
+    if (rc) return rc;
+    ChanLoop ca = make_chanloop(V, y->c, 8, 16, y->n);
+    dim3 grida(ca.chunks, y->n, (ca.G + ca.Gb - 1) / ca.Gb);
+    hipLaunchKernelGGL((in_lrelu_bwd_kernel<bf16, 8, true, true>), grida, dim3(256), 0, st, (const bf16*)nullptr, 0,
+                       (const bf16*)nullptr, 0, (const bf16*)y->ptr, y->ld, mean, scale, (const float*)m12, (bf16*)dy->ptr,
+                       dy->ld, (bf16*)gpre->ptr, gpre->ld, slope, 0, y->d, y->h, y->w, ca, y->c, (const float*)nullptr,
+                       (const float*)nullptr, (double*)nullptr);
+    return ru3d_check_launch("head_in_bwd_apply");
+}
+
 // the apply pass alone, with the two means given (ru3d_conv3d_dgrad_in_bwd: they come out of the conv's epilogue)
 template <typename T>
 static int in_bwd_apply_impl(const ru3d_tensor* gout, const ru3d_tensor* out, const float* mean, const float* scale,

@@ -633,9 +633,12 @@ __global__ __launch_bounds__(256) void head_wgrad_kernel(const T* __restrict__ x
 //     db[co]     = sum_v  d[v][co]
 // Thread = (voxel lane, 8 input channels); the G = Cin / 8 lanes of a voxel share its <= 4 gradient values.
 constexpr int HB_U = 4;
-__global__ __launch_bounds__(256) void head_bwd_kernel(const bf16* __restrict__ a, int lda, const float* __restrict__ dlog,
-                                                       int ldd, const float* __restrict__ w, int cin_real, int Cin, int Cout,
-                                                       bf16* __restrict__ dx, int lddx, float* __restrict__ part, int64_t P) {
+// STORE_DX = false (head_bwd_wgrad_kernel): dW and db alone, same voxel order and sums - for a head whose input gradient
+// is formed again, in registers, by the pass that consumes it (norm.hip head_dz_reduce2_kernel)
+template <bool STORE_DX>
+__device__ __forceinline__ void head_bwd_body(const bf16* __restrict__ a, int lda, const float* __restrict__ dlog, int ldd,
+                                              const float* __restrict__ w, int cin_real, int Cin, int Cout,
+                                              bf16* __restrict__ dx, int lddx, float* __restrict__ part, int64_t P) {
     __shared__ float sh[256][33];
     const int G = Cin / 8, vpb = 256 / G;
     const int tid = threadIdx.x, cg = tid % G, vl = tid / G;
@@ -682,7 +685,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const bf16* __restrict__ 
                 }
                 ab[c] += dv[u][c];
             }
-            if (p < P) store_vec<bf16, 8>(dx + p * lddx + cg * 8, o);
+            if (STORE_DX && p < P) store_vec<bf16, 8>(dx + p * lddx + cg * 8, o);
         }
     }
     // per-block partial: the voxel lanes of a channel group in a fixed order
@@ -710,6 +713,19 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const bf16* __restrict__ 
         for (int l = 0; l < vpb; l++) s += sh[l][tid];
         pp[4 * Cin + tid] = s;
     }
+}
+
+__global__ __launch_bounds__(256) void head_bwd_kernel(const bf16* __restrict__ a, int lda, const float* __restrict__ dlog,
+                                                       int ldd, const float* __restrict__ w, int cin_real, int Cin, int Cout,
+                                                       bf16* __restrict__ dx, int lddx, float* __restrict__ part, int64_t P) {
+    head_bwd_body<true>(a, lda, dlog, ldd, w, cin_real, Cin, Cout, dx, lddx, part, P);
+}
+
+__global__ __launch_bounds__(256) void head_bwd_wgrad_kernel(const bf16* __restrict__ a, int lda,
+                                                             const float* __restrict__ dlog, int ldd,
+                                                             const float* __restrict__ w, int cin_real, int Cin, int Cout,
+                                                             float* __restrict__ part, int64_t P) {
+    head_bwd_body<false>(a, lda, dlog, ldd, w, cin_real, Cin, Cout, nullptr, 0, part, P);
 }
 
 // dW[co][ci < cin_real], db[co] = sums of the per-block partials in block order (double)
@@ -748,9 +764,16 @@ size_t head_bwd_ws_bytes(int64_t P, int Cin) { return (size_t)head_bwd_blocks(P,
 int head_bwd_launch(const void* a, int lda, const float* dlog, int ldd, const float* w, int cin_real, int Cin, int Cout,
                     void* dx, int lddx, float* dw, float* db, void* ws, int64_t P, hipStream_t st) {
     const int blocks = head_bwd_blocks(P, Cin);
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)a, lda, dlog, ldd, w, cin_real, Cin, Cout,
-                       (bf16*)dx, lddx, (float*)ws, P);
-    int rc = ru3d_check_launch("head_bwd");
+    int rc;
+    if (dx) {
+        hipLaunchKernelGGL(head_bwd_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)a, lda, dlog, ldd, w, cin_real, Cin,
+                           Cout, (bf16*)dx, lddx, (float*)ws, P);
+        rc = ru3d_check_launch("head_bwd");
+    } else {      // dW and db alone (ru3d_head_in_bwd)
+        hipLaunchKernelGGL(head_bwd_wgrad_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)a, lda, dlog, ldd, w, cin_real,
+                           Cin, Cout, (float*)ws, P);
+        rc = ru3d_check_launch("head_bwd_wgrad");
+    }
     if (rc) return rc;
     const int vals = 4 * Cin + 4;
     hipLaunchKernelGGL(head_bwd_finalize_kernel, dim3((vals + 3) / 4), dim3(256), 0, st, (const float*)ws, blocks, Cin,

@@ -411,17 +411,42 @@ class ResBlock(nn.Module):
             specs += [(b, N.ROLE_BIAS, 1, cout_seg, 0) for b in biases if b is not None]
         return specs
 
-    def forward(self, x, in_link=None, out_link=None, planar=False):
+    def takes_head(self, x, head, planar=False):
+        """True when this block, given x, runs the decoder tail kernel (ops.ResBlockFn's `tail` shapes) and `head` - the
+        network's 1x1x1 output conv, sole consumer of the block's output - can ride in it: forward(x, head=head) then
+        returns the head's logits.  RU3D_HEAD_TAIL=0 (read per forward) keeps the head a launch of its own, and so does a
+        checkpointed block; either way the values are the same bits."""
+        if ops.head_tail_mode() == "0":
+            return False
+        if not (self._native and x.is_cuda and x.dtype != torch.float32 and self.uses_skip_conv and self.stride == 1):
+            return False
+        if (self._checkpoint and torch.is_grad_enabled()) or self._forward_hooks or self._forward_pre_hooks:
+            return False      # (a hook on the block expects the block's output)
+        if not (_is_plain_conv1(head) and head.stride == (1, 1, 1) and head.out_channels <= 4
+                and head.in_channels == self.out_channels and head.weight.dtype == torch.float32):
+            return False
+        n = x.shape[0] // 2 if planar else x.shape[0]
+        cin = x.shape[1] * 2 if planar else x.shape[1]
+        cout = ops.cpad(self.out_channels) if self._pad else self.out_channels
+        vox = x.shape[2] * x.shape[3] * x.shape[4]
+        return (cin, cout) in ((64, 32), (128, 64)) and n * vox >= 65536 and vox % 16 == 0
+
+    def forward(self, x, in_link=None, out_link=None, planar=False, head=None):
         """in_link / out_link: ops.SkipLink objects Unet passes to the pooling block / the last encoder block of a
         level (see _ops.SkipLink); standalone use leaves them None.  planar: x is the split concat ops.UpFn made on the
-        full-resolution level ([2N, C/2, D, H, W]: the two halves as planes of one buffer)."""
+        full-resolution level ([2N, C/2, D, H, W]: the two halves as planes of one buffer).  head: see takes_head."""
         if self._native and x.is_cuda:
             skip_w = self.skip_conv.weight if self.uses_skip_conv else None
             skip_b = self.skip_conv.bias if self.uses_skip_conv else None
+            head_w = head.weight if head is not None else None
+            head_b = head.bias if head is not None else None
             return ops.ResBlockFn.apply(x, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
                                         skip_w, skip_b, self.stride, self._drop_scale(x, planar),
                                         self._in_segs if self._pad else 0,
-                                        self._checkpoint and torch.is_grad_enabled(), in_link, out_link, planar)
+                                        self._checkpoint and torch.is_grad_enabled(), in_link, out_link, planar,
+                                        head_w, head_b)
+        if head is not None:
+            raise N.Ru3dError("ResBlock: a head rides only in the native block (ask takes_head first)")
         if self._native:
             N.require_device(x, "ResBlock input")
         if self._bn_eval and x.is_cuda and _inference_mode(self):
@@ -713,18 +738,27 @@ class Unet(nn.Module):
         x = self.encode_blocks[-1](x)
         levels = self._supervised_levels()
         aux = {}
+        headed = False
         for i in reversed(range(self.num_pool)):
             x = self.up_blocks[i](x, skips[i], links[i]) if linked else self.up_blocks[i](x, skips[i])
-            if linked and getattr(links[i], "planar_out", False):
-                x = self.decode_blocks[i](x, planar=True)       # the concat as two planes (ops.SkipLink.planar_view)
+            planar = bool(linked and getattr(links[i], "planar_out", False))   # the concat as two planes (ops.SkipLink.planar_view)
+            blk = self.decode_blocks[i]
+            # level 0's output feeds the head alone (the auxiliary heads sit on levels >= 1): the head rides in the block
+            headed = (i == 0 and self._in_chain and self._native_io and isinstance(blk, ResBlock)
+                      and not getattr(self.up_blocks[i], "attention", False) and blk.takes_head(x, self.fc, planar))
+            if headed:
+                x = blk(x, planar=planar, head=self.fc)
+            elif planar:
+                x = blk(x, planar=True)
             else:
-                x = self.decode_blocks[i](x)
+                x = blk(x)
             if 1 <= i < levels:
                 aux[i] = self._aux_head(i, x)      # a second consumer of the level's output: autograd adds the gradients
         ops._DROP_POOL.clear()
+        out = x if headed else self._head(x)
         if levels:
-            return [self._head(x)] + [aux[l] for l in range(1, levels)]
-        return self._head(x)
+            return [out] + [aux[l] for l in range(1, levels)]
+        return out
 
 
 # --------------------------------------------------------------------------- model zoo

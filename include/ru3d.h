@@ -205,6 +205,21 @@ int ru3d_head_bwd_supported(const ru3d_tensor* x, const ru3d_tensor* dlogits, co
 size_t ru3d_head_bwd_workspace_bytes(const ru3d_tensor* x, int dtype);
 int ru3d_head_bwd(const ru3d_tensor* x, const ru3d_tensor* dlogits, const float* weight, int cin_real, const ru3d_tensor* dx,
                   float* dw, float* db, void* ws, size_t ws_bytes, int dtype, void* stream);
+/* ru3d_head_bwd followed by ru3d_in_lrelu_bwd(gpre, gpre_sum) for a head whose input is a residual block's output
+ * z = LeakyReLU((y - mean) * scale + skip), without the head's input gradient dz ever reaching memory: dw and db come from
+ * ru3d_head_bwd's pass over (z, dlogits) without its store, and the reduction pass of the InstanceNorm backward forms dz
+ * in registers from dlogits and the weight instead of reading it (it reads z, y, dlogits and writes gpre = dz *
+ * LeakyReLU'(z)); finalize and apply follow as in ru3d_in_lrelu_bwd.  Grids, voxel orders and summation orders are the
+ * two calls': gpre, dy, dw, db and gpre_sum (optional, C floats) are bit for bit theirs.  `_supported`:
+ * ru3d_head_bwd's conditions, 16-byte rows, and a level ru3d_in_lrelu_bwd runs as three launches (not the small-level
+ * kernels). */
+int ru3d_head_in_bwd_supported(const ru3d_tensor* z, const ru3d_tensor* dlogits, const ru3d_tensor* y,
+                               const ru3d_tensor* gpre, const ru3d_tensor* dy, int dtype);
+size_t ru3d_head_in_bwd_workspace_bytes(const ru3d_tensor* z, int dtype);
+int ru3d_head_in_bwd(const ru3d_tensor* z, const ru3d_tensor* dlogits, const float* weight, int cin_real,
+                     const ru3d_tensor* y, const float* mean, const float* scale, const ru3d_tensor* gpre,
+                     const ru3d_tensor* dy, float* dw, float* db, float* gpre_sum, void* ws, size_t ws_bytes, float slope,
+                     int dtype, void* stream);
 
 /* nn.ConvTranspose3d(k3,s2,p1) followed by ConstantPad3d((0,1,0,1,0,1),0) (network.py:312-314):
  * y has extents 2*x.{d,h,w}; its far planes are written as exact zeros (no bias there). */
@@ -239,6 +254,15 @@ int ru3d_skip1x1_in_lrelu_fwd_supported(const ru3d_tensor* x, const ru3d_tensor*
 int ru3d_skip1x1_in_lrelu_fwd(const ru3d_tensor* x, const void* w_packed, const float* bias, const ru3d_tensor* y,
                               const float* mean, const float* scale, const ru3d_tensor* out, float slope, int dtype,
                               void* stream);
+/* The same pass when `out` feeds only the network's 1x1x1 head (network.py:547 `fc`, Cout <= 4, Cin = out->c): the
+ * head's fp32 logits [N][D][H][W][Cout] are formed from the stored (rounded) `out` in the kernel's epilogue, bit for bit
+ * what ru3d_conv3d_fwd(k = 1) on `out` gives; `out` is still written.  head_w_packed: the head's forward pack
+ * ([cin][cout_pad = 4]); head_bias: fp32 [Cout] or NULL. */
+int ru3d_skip1x1_in_lrelu_head_fwd_supported(const ru3d_tensor* x, const ru3d_tensor* y, const ru3d_tensor* out,
+                                             const ru3d_tensor* logits, int dtype);
+int ru3d_skip1x1_in_lrelu_head_fwd(const ru3d_tensor* x, const void* w_packed, const float* bias, const ru3d_tensor* y,
+                                   const float* mean, const float* scale, const ru3d_tensor* out, const void* head_w_packed,
+                                   const float* head_bias, const ru3d_tensor* logits, float slope, int dtype, void* stream);
 /* out = LeakyReLU((y - mean) * scale (+ res), slope)  (network.py:414,416; 315-316). */
 int ru3d_in_lrelu_fwd(const ru3d_tensor* y, const float* mean, const float* scale, const ru3d_tensor* res,
                       const ru3d_tensor* out, float slope, int dtype, void* stream);
