@@ -51,7 +51,6 @@ extern "C" const char* ru3d_launch_log_end(void) {
 
 namespace RU3D_NS {
 
-static ConvGeom fwd_geom(const ru3d_tensor* x, const ru3d_tensor* y, int k, int stride);
 static bool dtype_ok(int d) { return d == RU3D_F32 || d == RU3D_BF16; }   // fp32 or this build's 16-bit type
 static int conv_out(int in, int k, int s) { return (in + 2 * (k / 2) - k) / s + 1; }
 
@@ -208,9 +207,9 @@ extern "C" int ru3d_unpad_weight_grad(const float* src, float* dst, int cout, in
 }
 #endif
 
-static int run_conv(const ru3d_tensor* x, const void* w, const float* bias, const ru3d_tensor* res,
-                    const ru3d_tensor* y, int k, int stride, int transposed, int flip, int zero_far, int dtype,
-                    int y_dtype, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0) {
+// the geometry of the data-movement form: x is what the kernel gathers from, y what it writes
+static ConvGeom conv_geom(const ru3d_tensor* x, const ru3d_tensor* y, const ru3d_tensor* res, int k, int stride,
+                          int transposed = 0, int flip = 0, int zero_far = 0) {
     ConvGeom g;
     g.N = x->n;
     g.Di = x->d; g.Hi = x->h; g.Wi = x->w; g.Cin = x->c; g.ldx = x->ld;
@@ -220,6 +219,22 @@ static int run_conv(const ru3d_tensor* x, const void* w, const float* bias, cons
     g.k = k; g.stride = stride; g.pad = k / 2;
     g.transposed = transposed; g.zero_far = zero_far; g.flip = flip;
     g.x_cseg = x->cseg; g.x_segstride = x->seg_stride; g.y_cseg = y->cseg; g.y_segstride = y->seg_stride;
+    return g;
+}
+static ConvGeom fwd_geom(const ru3d_tensor* x, const ru3d_tensor* y, int k, int stride) { return conv_geom(x, y, nullptr, k, stride); }
+// the stride-1 input gradient: gather form with reversed taps
+static ConvGeom dgrad_s1_geom(const ru3d_tensor* dy, const ru3d_tensor* da, int k) { return conv_geom(dy, da, nullptr, k, 1, 0, 1); }
+
+// The plan of the 3x3x3 stride-1 MFMA conv of this geometry (conv.h); empty - nothing fused, no scratch - for every other
+// form and dtype.  An entry point makes it once and hands it to whatever it asks and launches.
+static Conv3S1Plan s1_plan_for(const ConvGeom& g, int dtype) {
+    return mfma_conv_eligible(g.Cin, g.Cout, g.k, dtype, dtype) ? conv3_s1_plan(g) : Conv3S1Plan();
+}
+
+static int run_conv(const ru3d_tensor* x, const void* w, const float* bias, const ru3d_tensor* res,
+                    const ru3d_tensor* y, int k, int stride, int transposed, int flip, int zero_far, int dtype,
+                    int y_dtype, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0) {
+    const ConvGeom g = conv_geom(x, y, res, k, stride, transposed, flip, zero_far);
     if (g.x_cseg || g.y_cseg) {      // the planar concat: only the MFMA conv kernels of a decoder ResBlock take it
         if (!(mfma_conv_eligible(g.Cin, g.Cout, k, dtype, y_dtype) && mfma_conv_geometry_ok(g)))
             return ru3d_fail(-1, "conv3d: no kernel takes a split tensor for this shape / dtype");
@@ -249,16 +264,7 @@ static bool res_ok(const ru3d_tensor* res, const ru3d_tensor* y) {
 extern "C" size_t ru3d_conv3d_workspace_bytes(const ru3d_tensor* x, const ru3d_tensor* y, int k, int stride, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_workspace_bytes_f16(x, y, k, stride, dtype));
     if (!tensor_ok_split(x) || !tensor_ok(y) || dtype != RU3D_BF16 || k != 3 || stride != 1) return 0;
-    if (!mfma_conv_eligible(x->c, y->c, k, dtype, dtype)) return 0;
-    ConvGeom g;
-    g.N = x->n;
-    g.Di = x->d; g.Hi = x->h; g.Wi = x->w; g.Cin = x->c; g.ldx = x->ld;
-    g.Do = y->d; g.Ho = y->h; g.Wo = y->w; g.Cout = y->c; g.ldy = y->ld;
-    g.CoutPad = generic_cout_pad(y->c);
-    g.ldr = 0;
-    g.k = k; g.stride = stride; g.pad = k / 2;
-    g.transposed = 0; g.zero_far = 0; g.flip = 0;
-    return conv_mfma_ws_bytes(g);
+    return s1_plan_for(fwd_geom(x, y, k, stride), dtype).ws_bytes;
 }
 
 extern "C" int ru3d_conv3d_fwd(const ru3d_tensor* x, const void* w_packed, const float* bias, const ru3d_tensor* res,
@@ -278,36 +284,37 @@ extern "C" int ru3d_conv3d_fwd(const ru3d_tensor* x, const void* w_packed, const
     return run_conv(x, w_packed, bias, res, y, k, stride, 0, 0, 0, dtype, y_dtype, as_stream(stream), ws, ws_bytes);
 }
 
-static ConvGeom fwd_geom(const ru3d_tensor* x, const ru3d_tensor* y, int k, int stride) {
-    ConvGeom g;
-    g.N = x->n;
-    g.Di = x->d; g.Hi = x->h; g.Wi = x->w; g.Cin = x->c; g.ldx = x->ld;
-    g.Do = y->d; g.Ho = y->h; g.Wo = y->w; g.Cout = y->c; g.ldy = y->ld;
-    g.CoutPad = generic_cout_pad(y->c);
-    g.ldr = 0;
-    g.k = k; g.stride = stride; g.pad = k / 2;
-    g.transposed = 0; g.zero_far = 0; g.flip = 0;
-    g.x_cseg = x->cseg; g.x_segstride = x->seg_stride; g.y_cseg = y->cseg; g.y_segstride = y->seg_stride;
-    return g;
-}
-
-static bool fwd_in_fused(const ru3d_tensor* x, const ru3d_tensor* y, int k, int stride, int dtype) {
-    const ConvGeom g = fwd_geom(x, y, k, stride);
-    return mfma_conv_eligible(g.Cin, g.Cout, k, dtype, dtype) && mfma_conv_can_fuse_stats(g);
+// scratch of ru3d_conv3d_fwd_in: the statistics pass's or the fused slab, and the conv's split-K partials (stream order keeps
+// them apart)
+static size_t fwd_in_ws_bytes(const ru3d_tensor* y, const Conv3S1Plan& p) {
+    size_t need = ru3d_reduce_workspace_bytes(y);
+    if (p.can_stats && p.slab_bytes > need) need = p.slab_bytes;
+    return p.ws_bytes > need ? p.ws_bytes : need;
 }
 
 extern "C" size_t ru3d_conv3d_fwd_in_workspace_bytes(const ru3d_tensor* x, const ru3d_tensor* y, int k, int stride,
                                                      int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_fwd_in_workspace_bytes_f16(x, y, k, stride, dtype));
     if (!tensor_ok_split(x) || !tensor_ok(y)) return 0;
-    size_t need = ru3d_reduce_workspace_bytes(y);
-    if (fwd_in_fused(x, y, k, stride, dtype)) {
-        const size_t slab = mfma_conv_stats_slab_bytes(fwd_geom(x, y, k, stride));
-        if (slab > need) need = slab;
+    return fwd_in_ws_bytes(y, s1_plan_for(fwd_geom(x, y, k, stride), dtype));
+}
+
+static int conv_fwd_in(const ru3d_tensor* x, const void* w_packed, const float* bias, const ru3d_tensor* y, int k, int stride,
+                       int dtype, const float* drop_scale, float* mean, float* scale, void* ws, size_t ws_bytes, float eps,
+                       void* stream, const ConvGeom& g, const Conv3S1Plan& p) {
+    RU3D_REQUIRE(ws_bytes >= fwd_in_ws_bytes(y, p), "conv3d_fwd_in: workspace too small");
+    if (p.can_stats) {
+        RU3D_REQUIRE(x->n == y->n && y->d == x->d && y->h == x->h && y->w == x->w, "conv3d_fwd_in: extents mismatch");
+        int rc = conv_mfma_launch(x->ptr, w_packed, bias, nullptr, y->ptr, g, as_stream(stream), (float*)ws, nullptr, 0, nullptr,
+                                  0, 0.f, nullptr, 0, nullptr, nullptr, &p);
+        if (rc) return rc;
+        return stats_slab_finalize_launch((const float*)ws, p.gx, p.cb, g.N, g.Cout, 1.0 / ((double)g.Do * g.Ho * g.Wo),
+                                          drop_scale, eps, mean, scale, as_stream(stream));
     }
-    const size_t conv_ws = ru3d_conv3d_workspace_bytes(x, y, k, stride, dtype);
-    if (conv_ws > need) need = conv_ws;
-    return need;
+    // the conv's split-K partials and the statistics pass share the workspace (stream order keeps them apart)
+    int rc = ru3d_conv3d_fwd(x, w_packed, bias, nullptr, y, k, stride, dtype, dtype, ws, ws_bytes, stream);
+    if (rc) return rc;
+    return ru3d_instnorm_stats(y, drop_scale, mean, scale, ws, ws_bytes, eps, dtype, stream);
 }
 
 extern "C" int ru3d_conv3d_fwd_in(const ru3d_tensor* x, const void* w_packed, const float* bias, const ru3d_tensor* y,
@@ -316,28 +323,17 @@ extern "C" int ru3d_conv3d_fwd_in(const ru3d_tensor* x, const void* w_packed, co
     RU3D_FWD_F16(dtype, ru3d_conv3d_fwd_in_f16(x, w_packed, bias, y, k, stride, dtype, drop_scale, mean, scale, ws, ws_bytes, eps, stream));
     Ru3dDeviceGuard dev_guard(stream);
     RU3D_REQUIRE(tensor_ok_split(x) && tensor_ok(y) && w_packed && mean && scale && ws, "conv3d_fwd_in: bad argument");
-    RU3D_REQUIRE(ws_bytes >= ru3d_conv3d_fwd_in_workspace_bytes(x, y, k, stride, dtype), "conv3d_fwd_in: workspace too small");
-    if (fwd_in_fused(x, y, k, stride, dtype)) {
-        RU3D_REQUIRE(x->n == y->n && y->d == x->d && y->h == x->h && y->w == x->w, "conv3d_fwd_in: extents mismatch");
-        const ConvGeom g = fwd_geom(x, y, k, stride);
-        int rc = conv_mfma_launch(x->ptr, w_packed, bias, nullptr, y->ptr, g, as_stream(stream), (float*)ws);
-        if (rc) return rc;
-        return mfma_conv_stats_finalize(g, (const float*)ws, drop_scale, eps, mean, scale, as_stream(stream));
-    }
-    // the conv's split-K partials and the statistics pass share the workspace (stream order keeps them apart)
-    int rc = ru3d_conv3d_fwd(x, w_packed, bias, nullptr, y, k, stride, dtype, dtype, ws, ws_bytes, stream);
-    if (rc) return rc;
-    return ru3d_instnorm_stats(y, drop_scale, mean, scale, ws, ws_bytes, eps, dtype, stream);
+    const ConvGeom g = fwd_geom(x, y, k, stride);
+    return conv_fwd_in(x, w_packed, bias, y, k, stride, dtype, drop_scale, mean, scale, ws, ws_bytes, eps, stream, g,
+                       s1_plan_for(g, dtype));
 }
 
 // ---- conv + InstanceNorm statistics + apply (+ residual) + LeakyReLU behind one entry point (reference network.py:
 // 405-416: x = lrelu(IN(dropout(conv1(x)))), lrelu(IN(conv2(x)) + skip)).  On the small levels the statistics, their
 // finalize and the apply are ONE whole-instance kernel (norm_small.hip) that also sums the conv's split-K slices;
 // everywhere else this is ru3d_conv3d_fwd_in followed by ru3d_in_lrelu_fwd.
-static bool small_conv_path(const ru3d_tensor* x, const ru3d_tensor* y, int k, int stride, int dtype) {
-    if (dtype != RU3D_BF16 || k != 3 || stride != 1) return false;
-    const ConvGeom g = fwd_geom(x, y, k, stride);
-    return mfma_conv_eligible(g.Cin, g.Cout, k, dtype, dtype) && mfma_conv_geometry_ok(g) && !mfma_conv_can_fuse_stats(g);
+static bool small_conv_path(const ConvGeom& g, const Conv3S1Plan& p, int dtype) {
+    return g.k == 3 && g.stride == 1 && mfma_conv_eligible(g.Cin, g.Cout, g.k, dtype, dtype) && !p.can_stats;
 }
 
 #ifndef RU3D_STORAGE_F16
@@ -356,19 +352,20 @@ extern "C" int ru3d_conv3d_fwd_in_lrelu(const ru3d_tensor* x, const void* w_pack
     RU3D_REQUIRE(tensor_ok_split(x) && tensor_ok(y) && tensor_ok(out) && w_packed && mean && scale && ws,
                  "conv3d_fwd_in_lrelu: bad argument");
     RU3D_REQUIRE(res_ok(res, y) && res_ok(out, y), "conv3d_fwd_in_lrelu: res / out do not have the shape of y");
-    const int small = (small_conv_path(x, y, k, stride, dtype) && x->n == y->n && y->d == x->d && y->h == x->h &&
+    const ConvGeom g = fwd_geom(x, y, k, stride);
+    const Conv3S1Plan p = s1_plan_for(g, dtype);
+    const int small = (small_conv_path(g, p, dtype) && x->n == y->n && y->d == x->d && y->h == x->h &&
                        y->w == x->w) ? in_small_mode(y, false, res, out) : 0;
     if (small) {
-        RU3D_REQUIRE(ws_bytes >= ru3d_conv3d_fwd_in_workspace_bytes(x, y, k, stride, dtype), "conv3d_fwd_in_lrelu: workspace too small");
-        const ConvGeom g = fwd_geom(x, y, k, stride);
+        RU3D_REQUIRE(ws_bytes >= fwd_in_ws_bytes(y, p), "conv3d_fwd_in_lrelu: workspace too small");
         int ks = 0;      // the whole-instance kernel sums the conv's split-K slices itself; the two-kernel form reads y
         int rc = conv_mfma_launch(x->ptr, w_packed, bias, nullptr, y->ptr, g, as_stream(stream), nullptr, ws, ws_bytes, nullptr,
-                                  0, 0.f, nullptr, 0, nullptr, small == 1 ? &ks : nullptr);
+                                  0, 0.f, nullptr, 0, nullptr, small == 1 ? &ks : nullptr, &p);
         if (rc) return rc;
         return in_small_fwd_launch(y, ks ? (const float*)ws : nullptr, ks, bias, drop_scale, mean, scale, res, out, ws, eps,
                                    slope, as_stream(stream));
     }
-    int rc = ru3d_conv3d_fwd_in(x, w_packed, bias, y, k, stride, dtype, drop_scale, mean, scale, ws, ws_bytes, eps, stream);
+    int rc = conv_fwd_in(x, w_packed, bias, y, k, stride, dtype, drop_scale, mean, scale, ws, ws_bytes, eps, stream, g, p);
     if (rc) return rc;
     return ru3d_in_lrelu_fwd(y, mean, scale, res, out, slope, dtype, stream);
 }
@@ -376,19 +373,17 @@ extern "C" int ru3d_conv3d_fwd_in_lrelu(const ru3d_tensor* x, const void* w_pack
 // ---- can a decoder ResBlock take cat((up, skip)) as a split tensor through all of its kernels? (see ru3d_tensor)
 extern "C" int ru3d_planar_concat_supported(int n, int d, int h, int w, int cseg, int cout, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_planar_concat_supported_f16(n, d, h, w, cseg, cout, dtype));
-    static const int mode = getenv("RU3D_PLANAR_CONCAT") ? atoi(getenv("RU3D_PLANAR_CONCAT")) : 1;
+    static const int mode = ru3d_env_int("RU3D_PLANAR_CONCAT", 1), pair_mode = ru3d_env_int("RU3D_DGRAD_PAIR", 1);
+    static const int skip_mode = ru3d_env_int("RU3D_FUSED_SKIP", 1);
     if (!mode || dtype != RU3D_BF16 || n <= 0 || d <= 0 || h <= 0 || w <= 0 || cseg != 32 || cout != 32) return 0;
     const int64_t V = (int64_t)d * h * w;
     // byte offsets of the sliding kernel's staging: plane distance + one sample below 2^31
     if (((int64_t)n * V + V) * cseg * 2 >= (1ll << 31)) return 0;
-    SlidePlan sp;
-    if (!slide64_conv_plan(n, d, h, w, 2 * cseg, cout, &sp)) return 0;                 // conv1 forward (split input)
-    ConvGeom gd;                                                                       // its input-gradient pair (split output)
-    gd.N = n; gd.Di = gd.Do = d; gd.Hi = gd.Ho = h; gd.Wi = gd.Wo = w; gd.Cin = cout; gd.Cout = 2 * cseg;
-    gd.ldx = cout; gd.ldy = cseg; gd.CoutPad = 2 * cseg; gd.ldr = 0; gd.k = 3; gd.stride = 1; gd.pad = 1;
-    gd.transposed = 0; gd.zero_far = 0; gd.flip = 1;
-    static const int pair_mode = getenv("RU3D_DGRAD_PAIR") ? atoi(getenv("RU3D_DGRAD_PAIR")) : 1;
-    if (!pair_mode || !mfma_conv_eligible(gd.Cin, gd.Cout, 3, dtype, dtype) || !mfma_conv_can_fuse_partner(gd)) return 0;
+    const ru3d_tensor cat = {nullptr, n, d, h, w, 2 * cseg, cseg, 0, 0}, act = {nullptr, n, d, h, w, cout, cout, 0, 0};
+    const Conv3S1Plan fwd = conv3_s1_plan(fwd_geom(&cat, &act, 3, 1));                 // conv1 forward (split input)
+    if (!fwd.count || fwd.choice[0].family != S1_SLIDE64) return 0;
+    const ConvGeom gd = dgrad_s1_geom(&act, &cat, 3);                                  // its input-gradient pair (split output)
+    if (!pair_mode || !s1_plan_for(gd, dtype).can_partner) return 0;
     WgradGeom gw;                                                                      // conv1's weight gradient (split x)
     gw.N = n; gw.Di = gw.Do = d; gw.Hi = gw.Ho = h; gw.Wi = gw.Wo = w; gw.Cin = 2 * cseg; gw.Cout = cout;
     gw.ldx = cseg; gw.lddy = cout; gw.k = 3; gw.taps = 27; gw.stride = 1; gw.pad = 1;
@@ -396,7 +391,6 @@ extern "C" int ru3d_planar_concat_supported(int n, int d, int h, int w, int cseg
     WgradSlidePlan wp;
     if (!wgrad_slide_plan(gw, &wp)) return 0;
     // the fused tail (skip conv + InstanceNorm apply): skip1x1_fused_eligible's shape conditions
-    static const int skip_mode = getenv("RU3D_FUSED_SKIP") ? atoi(getenv("RU3D_FUSED_SKIP")) : 1;
     if (!skip_mode || (V % 16) != 0 || V * n < 65536) return 0;
     return 1;
 }
@@ -421,10 +415,9 @@ extern "C" int ru3d_conv3d_dgrad(const ru3d_tensor* dy, const void* w_packed, co
 }
 
 // ---- decoder ResBlock: input gradient of conv1 (k3 s1) and skip_conv (k1 s1) in one launch (conv_slide32.hip, 28th tap)
-static ConvGeom dgrad_s1_geom(const ru3d_tensor* dy, const ru3d_tensor* da, int k);
 extern "C" int ru3d_conv3d_s1_dgrad_pair_supported(const ru3d_tensor* dy, const ru3d_tensor* dy2, const ru3d_tensor* dx, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_s1_dgrad_pair_supported_f16(dy, dy2, dx, dtype));
-    static const int mode = getenv("RU3D_DGRAD_PAIR") ? atoi(getenv("RU3D_DGRAD_PAIR")) : 1;
+    static const int mode = ru3d_env_int("RU3D_DGRAD_PAIR", 1);
     if (!mode || dtype != RU3D_BF16 || !tensor_ok(dy) || !tensor_ok(dy2) || !tensor_ok_split(dx)) return 0;
     if (dx->cseg && (dx->cseg != 32 || dx->c != 64)) return 0;      // split output: two 32-channel slices, one per grid row
     if (dy2->n != dy->n || dy2->d != dy->d || dy2->h != dy->h || dy2->w != dy->w || dy2->c != dy->c) return 0;
@@ -432,8 +425,7 @@ extern "C" int ru3d_conv3d_s1_dgrad_pair_supported(const ru3d_tensor* dy, const 
     if ((dy->ld % 8) || (dy2->ld % 8) || (dx->ld % 8)) return 0;
     if ((((uintptr_t)dy->ptr) | ((uintptr_t)dy2->ptr) | ((uintptr_t)dx->ptr)) % 16) return 0;
     if ((int64_t)dy->d * dy->h * dy->w * dy->ld >= (1ll << 30)) return 0;
-    const ConvGeom g = dgrad_s1_geom(dy, dx, 3);
-    return (mfma_conv_eligible(g.Cin, g.Cout, 3, dtype, dtype) && mfma_conv_can_fuse_partner(g)) ? 1 : 0;
+    return s1_plan_for(dgrad_s1_geom(dy, dx, 3), dtype).can_partner ? 1 : 0;
 }
 
 extern "C" int ru3d_conv3d_s1_dgrad_pair(const ru3d_tensor* dy, const void* w3_packed, const ru3d_tensor* dy2,
@@ -526,15 +518,7 @@ extern "C" int ru3d_conv3d_s2_pair_fwd_in(const ru3d_tensor* x, const void* w3_p
 
 // ---- the two stride-2 convs of a pooling ResBlock: their input gradients in one launch (conv_s2.hip, T form)
 static ConvGeom s2_dgrad_geom(const ru3d_tensor* dy, const ru3d_tensor* res, const ru3d_tensor* dx) {
-    ConvGeom g;
-    g.N = dy->n;
-    g.Di = dy->d; g.Hi = dy->h; g.Wi = dy->w; g.Cin = dy->c; g.ldx = dy->ld;
-    g.Do = dx->d; g.Ho = dx->h; g.Wo = dx->w; g.Cout = dx->c; g.ldy = dx->ld;
-    g.CoutPad = generic_cout_pad(dx->c);
-    g.ldr = res ? res->ld : 0;
-    g.k = 3; g.stride = 2; g.pad = 1;
-    g.transposed = 1; g.zero_far = 0; g.flip = 0;
-    return g;
+    return conv_geom(dy, dx, res, 3, 2, 1);
 }
 
 extern "C" int ru3d_conv3d_s2_dgrad_pair_supported(const ru3d_tensor* dy, const ru3d_tensor* dy2, const ru3d_tensor* res,
@@ -563,36 +547,27 @@ extern "C" int ru3d_conv3d_s2_dgrad_pair(const ru3d_tensor* dy, const void* w3_p
 }
 
 // ---- conv input gradient followed by the InstanceNorm + LeakyReLU backward of the tensor it differentiates
-static ConvGeom dgrad_s1_geom(const ru3d_tensor* dy, const ru3d_tensor* da, int k) {
-    ConvGeom g = fwd_geom(dy, da, k, 1);
-    g.flip = 1;
-    return g;
+static bool dgrad_in_bwd_fused(const ru3d_tensor* dy, const ru3d_tensor* da, const Conv3S1Plan& p, int dtype) {
+    static const int mode = ru3d_env_int("RU3D_DGRAD_IN_FUSE", 1);
+    return mode && dtype != RU3D_F32 && p.can_bwd_sums && (da->ld % 8) == 0 && (dy->ld % 8) == 0;
 }
 
-static bool dgrad_in_bwd_fused(const ru3d_tensor* dy, const ru3d_tensor* da, int k, int stride, int dtype) {
-    static const int mode = getenv("RU3D_DGRAD_IN_FUSE") ? atoi(getenv("RU3D_DGRAD_IN_FUSE")) : 1;
-    if (!mode || k != 3 || stride != 1 || dtype == RU3D_F32) return false;
-    const ConvGeom g = dgrad_s1_geom(dy, da, k);
-    return mfma_conv_eligible(g.Cin, g.Cout, k, dtype, dtype) && mfma_conv_can_fuse_bwd_sums(g) &&
-           (da->ld % 8) == 0 && (dy->ld % 8) == 0;
+static size_t dgrad_in_bwd_ws_bytes(const ru3d_tensor* dy, const ru3d_tensor* da, const Conv3S1Plan& p, int dtype) {
+    size_t need = ru3d_reduce_workspace_bytes(da);
+    if (dgrad_in_bwd_fused(dy, da, p, dtype)) {
+        // slab of per-(workgroup, wave) sums, then m12[n][c][2]
+        const size_t fused = (p.slab_bytes + 255) / 256 * 256 + (size_t)da->n * da->c * 2 * sizeof(float);
+        if (fused > need) need = fused;
+    }
+    return p.ws_bytes > need ? p.ws_bytes : need;
 }
 
 extern "C" size_t ru3d_conv3d_dgrad_in_bwd_workspace_bytes(const ru3d_tensor* dy, const ru3d_tensor* da, int k,
                                                            int stride, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_dgrad_in_bwd_workspace_bytes_f16(dy, da, k, stride, dtype));
     if (!tensor_ok(dy) || !tensor_ok(da)) return 0;
-    size_t need = ru3d_reduce_workspace_bytes(da);
-    if (dgrad_in_bwd_fused(dy, da, k, stride, dtype)) {
-        // slab of per-(workgroup, wave) sums, then m12[n][c][2]
-        const size_t slab = (mfma_conv_stats_slab_bytes(dgrad_s1_geom(dy, da, k)) + 255) / 256 * 256;
-        const size_t fused = slab + (size_t)da->n * da->c * 2 * sizeof(float);
-        if (fused > need) need = fused;
-    }
-    if (stride == 1) {
-        const size_t conv_ws = ru3d_conv3d_workspace_bytes(dy, da, k, 1, dtype);
-        if (conv_ws > need) need = conv_ws;
-    }
-    return need;
+    // (a plan only for stride 1: the stride-2 input gradient is the transposed form)
+    return dgrad_in_bwd_ws_bytes(dy, da, stride == 1 ? s1_plan_for(dgrad_s1_geom(dy, da, k), dtype) : Conv3S1Plan(), dtype);
 }
 
 extern "C" int ru3d_conv3d_dgrad_in_bwd(const ru3d_tensor* dy, const void* w_packed, const ru3d_tensor* act,
@@ -604,30 +579,29 @@ extern "C" int ru3d_conv3d_dgrad_in_bwd(const ru3d_tensor* dy, const void* w_pac
     RU3D_REQUIRE(tensor_ok(dy) && tensor_ok(act) && tensor_ok(da) && tensor_ok(dyn) && w_packed && mean && scale && ws,
                  "conv3d_dgrad_in_bwd: bad argument");
     RU3D_REQUIRE(res_ok(act, da) && res_ok(dyn, da), "conv3d_dgrad_in_bwd: act / dyn do not have the shape of da");
-    RU3D_REQUIRE(ws_bytes >= ru3d_conv3d_dgrad_in_bwd_workspace_bytes(dy, da, k, stride, dtype),
-                 "conv3d_dgrad_in_bwd: workspace too small");
-    if (dgrad_in_bwd_fused(dy, da, k, stride, dtype) && (act->ld % 8) == 0 && (((uintptr_t)act->ptr) % 16) == 0 &&
+    const ConvGeom g = dgrad_s1_geom(dy, da, k);
+    const Conv3S1Plan p = stride == 1 ? s1_plan_for(g, dtype) : Conv3S1Plan();
+    RU3D_REQUIRE(ws_bytes >= dgrad_in_bwd_ws_bytes(dy, da, p, dtype), "conv3d_dgrad_in_bwd: workspace too small");
+    if (dgrad_in_bwd_fused(dy, da, p, dtype) && (act->ld % 8) == 0 && (((uintptr_t)act->ptr) % 16) == 0 &&
         (((uintptr_t)da->ptr) % 16) == 0 && (((uintptr_t)dy->ptr) % 16) == 0) {
         RU3D_REQUIRE(da->n == dy->n && da->d == dy->d && da->h == dy->h && da->w == dy->w, "conv3d_dgrad_in_bwd: extents mismatch");
-        const ConvGeom g = dgrad_s1_geom(dy, da, k);
-        const size_t slab = (mfma_conv_stats_slab_bytes(g) + 255) / 256 * 256;
-        float* m12 = (float*)((char*)ws + slab);
+        float* m12 = (float*)((char*)ws + (p.slab_bytes + 255) / 256 * 256);
         int rc = conv_mfma_launch(dy->ptr, w_packed, nullptr, nullptr, da->ptr, g, as_stream(stream), (float*)ws, nullptr, 0,
-                                  act->ptr, act->ld, slope);
+                                  act->ptr, act->ld, slope, nullptr, 0, nullptr, nullptr, &p);
         if (rc) return rc;
-        rc = mfma_conv_bwd_sums_finalize(g, (const float*)ws, m12, as_stream(stream));
+        rc = stats_slab_finalize_launch((const float*)ws, p.gx, p.cb, g.N, g.Cout, 1.0 / ((double)g.Do * g.Ho * g.Wo), nullptr,
+                                        0.f, m12, nullptr, as_stream(stream));
         if (rc) return rc;
         return ru3d_in_lrelu_bwd_apply(da, act, mean, scale, m12, dyn, slope, 0, dtype, stream);
     }
     // the small levels: the whole InstanceNorm backward is one kernel, which also sums the conv's split-K slices (da is
     // then never stored: nobody else reads it)
-    const int small = (small_conv_path(dy, da, k, stride, dtype) && da->n == dy->n && da->d == dy->d && da->h == dy->h &&
+    const int small = (stride == 1 && small_conv_path(g, p, dtype) && da->n == dy->n && da->d == dy->d && da->h == dy->h &&
                        da->w == dy->w) ? in_small_mode(act, false, da, dyn) : 0;
     if (small) {
-        const ConvGeom g = dgrad_s1_geom(dy, da, k);
         int ks = 0;
         int rc = conv_mfma_launch(dy->ptr, w_packed, nullptr, nullptr, da->ptr, g, as_stream(stream), nullptr, ws, ws_bytes,
-                                  nullptr, 0, 0.f, nullptr, 0, nullptr, small == 1 ? &ks : nullptr);
+                                  nullptr, 0, 0.f, nullptr, 0, nullptr, small == 1 ? &ks : nullptr, &p);
         if (rc) return rc;
         return in_small_bwd_launch(da, ks ? (const float*)ws : nullptr, ks, act, act, mean, scale, dyn, nullptr, ws, slope, 0,
                                    nullptr, as_stream(stream));
@@ -693,7 +667,7 @@ extern "C" int ru3d_conv3d_wgrad(const ru3d_tensor* x, const ru3d_tensor* dy, fl
 // weight-gradient kernels have one tap slot of their four waves' 28 free, and the centre tap's rows are the rows the 1x1x1
 // conv reads
 static bool wgrad_pair_ok(const ru3d_tensor* x, const ru3d_tensor* dy, const ru3d_tensor* dy2, int stride, int dtype) {
-    static const int mode = getenv("RU3D_WGRAD_PAIR") ? atoi(getenv("RU3D_WGRAD_PAIR")) : 1;      // 0 = two launches
+    static const int mode = ru3d_env_int("RU3D_WGRAD_PAIR", 1);      // 0 = two launches
     if (!mode || dtype != RU3D_BF16 || (stride != 1 && stride != 2)) return false;
     if (!wgrad_shapes_ok(x, dy, 3, stride) || !tensor_ok(dy2)) return false;
     if (dy2->n != dy->n || dy2->d != dy->d || dy2->h != dy->h || dy2->w != dy->w || dy2->c != dy->c) return false;
@@ -805,15 +779,7 @@ extern "C" int ru3d_convtranspose3d_k3s2p1_fwd(const ru3d_tensor* x, const void*
 }
 
 static ConvGeom convt_fwd_geom(const ru3d_tensor* x, const ru3d_tensor* y) {
-    ConvGeom g;
-    g.N = x->n;
-    g.Di = x->d; g.Hi = x->h; g.Wi = x->w; g.Cin = x->c; g.ldx = x->ld;
-    g.Do = y->d; g.Ho = y->h; g.Wo = y->w; g.Cout = y->c; g.ldy = y->ld;
-    g.CoutPad = generic_cout_pad(y->c);
-    g.ldr = 0;
-    g.k = 3; g.stride = 2; g.pad = 1;
-    g.transposed = 1; g.zero_far = 1; g.flip = 0;
-    return g;
+    return conv_geom(x, y, nullptr, 3, 2, 1, 0, 1);
 }
 
 static bool convt_fwd_in_fused(const ru3d_tensor* x, const ru3d_tensor* y, int dtype) {

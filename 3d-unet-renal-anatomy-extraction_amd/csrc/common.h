@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 #include "f16_names.h"
 #include "../../include/ru3d.h"
 
@@ -67,6 +68,12 @@ int ru3d_fail(int code, const char* fmt, ...);   // sets the thread-local error 
 int ru3d_check_launch(const char* what);         // hipGetLastError -> status
 
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
+
+// an integer switch of the environment (unset: dflt).  Callers keep it in a function-local static: read once per process
+static inline int ru3d_env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
 
 // kernel probe (comm.hip): event pair around the main kernel of a conv launch while ru3d_probe_begin's geometry is armed
 void* ru3d_probe_start(int n, int d, int h, int w, int cin, int cout, hipStream_t st);

@@ -84,25 +84,42 @@ bool mfma_conv_geometry_ok(const ConvGeom& g);
 size_t mfma_packed_bytes(int cin, int cout, int taps);
 int pack_mfma_launch(const float* src, void* dst, int cin, int cout, int taps, int64_t s_o, int64_t s_i, int flip,
                      hipStream_t st);
+// The 3x3x3 stride-1 conv (forward, and input gradient with flipped taps): ONE plan per geometry, made by conv3_s1_plan
+// and read by everything that has to agree on it - the launcher, the split-K scratch and statistics-slab queries, the
+// slab finalizers and the "can this be fused" predicates.  choice[] is the order of preference; what only the launch
+// knows (operand alignment, whether scratch / a slab / a residual was passed) picks among them in conv_mfma_launch.
+enum { S1_SLIDE32 = 1, S1_SLIDE64, S1_WS, S1_PC4, S1_PC, S1_SK, S1_TILE };
+struct SlidePlan {
+    int dsplit, DL, tiles_h, tiles_w, units, grid, ny;
+};
+struct Conv3S1Choice {
+    int family;               // S1_*
+    int td, th, tw, mt, nt;   // spatial tile; mt / nt: 32-voxel / 32-cout MFMA tiles per wave (tile and pc kernels)
+    int ks;                   // split-K slices: ks > 1 (S1_WS: any ks) needs ks x voxels x Cout floats of scratch
+    char name[40];            // what the launch log reports (the sliding kernels append their epilogue form)
+};
+struct Conv3S1Plan {
+    int count = 0;            // 0: not a 3x3x3 stride-1 gather with Cin, Cout multiples of 32 (the direct kernels' form)
+    Conv3S1Choice choice[5];
+    SlidePlan slide;          // choice[0] is a sliding kernel: its decomposition
+    int pc_gx = 0, pc_gy = 0; // persistent grid of the producer/consumer choice
+    size_t ws_bytes = 0;      // split-K scratch a launch can use (without it the next choice runs)
+    // fused forms.  can_stats: the first choice sums InstanceNorm statistics into a slab[(y * gx + workgroup) * 4 + wave]
+    // [n][cb][2]; can_bwd_sums / can_partner: it is the 32-channel sliding kernel (backward sums, 1x1x1 partner as a 28th tap)
+    bool can_stats = false, can_bwd_sums = false, can_partner = false;
+    int gx = 0, gy = 0, cb = 0;
+    size_t slab_bytes = 0;
+};
+Conv3S1Plan conv3_s1_plan(const ConvGeom& g);
+// plan: conv3_s1_plan(g) when the caller has it already (NULL: made here)
 int conv_mfma_launch(const void* x, const void* w, const float* bias, const void* res, void* y, const ConvGeom& g,
                      hipStream_t st, float* stat_slab = nullptr, void* ws = nullptr, size_t ws_bytes = 0,
                      const void* bst_act = nullptr, int bst_ld = 0, float slope = 0.f, const void* x2 = nullptr,
-                     int ldx2 = 0, const void* w2 = nullptr, int* defer_ks = nullptr);
-// y = conv3_dgrad(x) + W2^T x2 in one launch: only the 32-channel sliding kernel has the 28th tap
-bool mfma_conv_can_fuse_partner(const ConvGeom& g);
-size_t conv_mfma_ws_bytes(const ConvGeom& g);
-bool mfma_conv_can_fuse_stats(const ConvGeom& g);
-size_t mfma_conv_stats_slab_bytes(const ConvGeom& g);
-int mfma_conv_stats_finalize(const ConvGeom& g, const float* slab, const float* drop, float eps, float* mean,
-                             float* scale, hipStream_t st);
+                     int ldx2 = 0, const void* w2 = nullptr, int* defer_ks = nullptr, const Conv3S1Plan* plan = nullptr);
 // slab[(y * gx + workgroup) * 4 + wave][n][cb][2] of per-wave (sum, sum of squares) -> mean / scale (or, scale == NULL,
-// the two means)
+// the two means m12[n][c] = (mean g', mean g' xhat) of the backward sums)
 int stats_slab_finalize_launch(const float* slab, int gx, int cb, int N, int C, double invV, const float* drop, float eps,
                                float* mean, float* scale, hipStream_t st);
-// the sliding 32-channel kernel can take the InstanceNorm + LeakyReLU backward sums of its output (input-gradient role)
-bool mfma_conv_can_fuse_bwd_sums(const ConvGeom& g);
-// slab of backward sums -> m12[n][c] = (mean g', mean g' xhat)
-int mfma_conv_bwd_sums_finalize(const ConvGeom& g, const float* slab, float* m12, hipStream_t st);
 bool mfma_wgrad_eligible(const WgradGeom& g, int dtype);
 size_t wgrad_mfma_ws_bytes(const WgradGeom& g);
 int wgrad_mfma_launch(const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes, WgradGeom g,
@@ -110,26 +127,24 @@ int wgrad_mfma_launch(const void* x, const void* dy, float* dw, void* ws, size_t
 
 // conv_slide32.hip (3x3x3 stride-1, 32 -> 32 / 64 channels: D-sliding plane ring on v_mfma_f32_16x16x32, a wave = all 32
 // couts of a 4 x 16 quarter of the column, the whole weight resident in AGPRs)
-struct SlidePlan {
-    int dsplit, DL, tiles_h, tiles_w, units, grid, ny;
-};
 bool slide_conv_plan(int N, int D, int H, int W, int Cin, int Cout, SlidePlan* out);
 // bst_act != NULL (input-gradient role): the slab receives the InstanceNorm + LeakyReLU backward sums of the output
 // against the activation bst_act (pitch bst_ld) instead of the forward statistics
 // x2 / ldx2 / w2: a second tensor on the output grid (32 channels) and a packed 1x1x1 input-gradient weight: y += W2^T x2
 int conv_slide_launch(const void* x, const void* w, const float* bias, const void* res, void* y, const ConvGeom& g,
-                      float* stat_slab, hipStream_t st, const void* bst_act = nullptr, int bst_ld = 0, float slope = 0.f,
-                      const void* x2 = nullptr, int ldx2 = 0, const void* w2 = nullptr);
+                      const SlidePlan& p, float* stat_slab, hipStream_t st, const void* bst_act = nullptr, int bst_ld = 0,
+                      float slope = 0.f, const void* x2 = nullptr, int ldx2 = 0, const void* w2 = nullptr);
 
 // conv_slide64.hip (3x3x3 stride-1, 64 -> 64 / 128 channels: the same design on v_mfma_f32_16x16x32, a wave = 16 couts)
-bool slide64_conv_plan(int N, int D, int H, int W, int Cin, int Cout, SlidePlan* out);
+// edge: a last column narrower than the tile may run masked
+bool slide64_conv_plan(int N, int D, int H, int W, int Cin, int Cout, bool edge, SlidePlan* out);
 // whole-sample form of the deepest level (conv_ws.hip): split-K slices for this geometry (0 = not its shape); the kernel
-// writes fp32 partials [slice][voxel][Cout] for conv_ksplit_reduce_kernel
-int conv_ws_slices(int N, int D, int H, int W, int Cin, int Cout);
+// writes fp32 partials [slice][voxel][Cout] for conv_ksplit_reduce_kernel.  mode 2: wherever the shape fits
+int conv_ws_slices(int N, int D, int H, int W, int Cin, int Cout, int mode);
 int conv_ws_launch(const void* x, const void* w, float* part, int N, int D, int H, int W, int Cin, int Cout, int ldx,
                    int flip, int slices, hipStream_t st);
 int conv_slide64_launch(const void* x, const void* w, const float* bias, const void* res, void* y, const ConvGeom& g,
-                        float* stat_slab, hipStream_t st, const void* bst_act = nullptr, int bst_ld = 0, float slope = 0.f);
+                        const SlidePlan& p, float* stat_slab, hipStream_t st);
 
 // conv_s2.hip (the stride-2 forms of the large levels: LDS-DMA plane ring, producer wave, weights in registers)
 bool convt_s2_tile_eligible(const ConvGeom& g);

@@ -1027,47 +1027,6 @@ __global__ __launch_bounds__(512, 2) void conv3_s1_sk_kernel(MfmaConvArgs a) {
 }
 
 
-static void pc_grid(int cout, bool nt2, int64_t nblk, int* gx, int* gy) {
-    *gy = cout / (nt2 ? 64 : 32);
-    int g = ru3d_get_cu_budget() / *gy;   // one persistent workgroup per CU in total (N > 1: minus the CUs left to RCCL)
-    g = g < 8 ? 8 : (g / 8) * 8;        // multiple of 8 so that blockIdx.x % 8 is the XCD label for every y
-    if (g > nblk) g = (int)nblk;
-    *gx = g;
-}
-
-template <int TD, int TH, int TW, int MT>
-static int launch_s1_pc(const MfmaConvArgs& a0, bool nt2, hipStream_t st) {
-    MfmaConvArgs a = a0;
-    a.tiles_d = (a.D + TD - 1) / TD;
-    a.tiles_h = (a.H + TH - 1) / TH;
-    a.tiles_w = (a.W + TW - 1) / TW;
-    const int64_t nblk = (int64_t)a.N * a.tiles_d * a.tiles_h * a.tiles_w;
-    if (nblk > 0x7fffffff) return ru3d_fail(-1, "conv_mfma: grid too large");
-    a.nblk = (int)nblk;
-    int gx, gy;
-    pc_grid(a.Cout, nt2, nblk, &gx, &gy);
-    dim3 grid(gx, gy);
-    if (nt2)
-        hipLaunchKernelGGL((conv3_s1_pc_kernel<TD, TH, TW, MT, 2>), grid, dim3(512), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv3_s1_pc_kernel<TD, TH, TW, MT, 1>), grid, dim3(512), 0, st, a);
-    return ru3d_check_launch("conv3_s1_pc");
-}
-
-static int launch_s1_pc4(const MfmaConvArgs& a0, hipStream_t st) {
-    MfmaConvArgs a = a0;
-    a.tiles_d = (a.D + 3) / 4;
-    a.tiles_h = (a.H + 3) / 4;
-    a.tiles_w = (a.W + 31) / 32;
-    const int64_t nblk = (int64_t)a.N * a.tiles_d * a.tiles_h * a.tiles_w;
-    if (nblk > 0x7fffffff) return ru3d_fail(-1, "conv_mfma: grid too large");
-    a.nblk = (int)nblk;
-    int gx, gy;
-    pc_grid(a.Cout, true, nblk, &gx, &gy);
-    hipLaunchKernelGGL((conv3_s1_pc4_kernel<3>), dim3(gx, gy), dim3(512), 0, st, a);
-    return ru3d_check_launch("conv3_s1_pc4");
-}
-
 // y = bf16(sum_z part[z] + bias) (+ residual): fixed summation order, 8 channels (16 B) per thread
 __global__ __launch_bounds__(256) void conv_ksplit_reduce_kernel(const float* __restrict__ part, int ksplit, int64_t V,
                                                                  int Cout, const float* __restrict__ bias,
@@ -1099,271 +1058,225 @@ __global__ __launch_bounds__(256) void conv_ksplit_reduce_kernel(const float* __
     store_vec<bf16, 8>(y + vox * ldy + c0, v);
 }
 
-template <int TD, int TH, int TW, int MT>
-static int launch_s1(const MfmaConvArgs& a0, bool nt2, hipStream_t st) {
-    MfmaConvArgs a = a0;
-    a.tiles_d = (a.D + TD - 1) / TD;
-    a.tiles_h = (a.H + TH - 1) / TH;
-    a.tiles_w = (a.W + TW - 1) / TW;
-    const int64_t nblk = (int64_t)a.N * a.tiles_d * a.tiles_h * a.tiles_w;
-    if (nblk > 0x7fffffff) return ru3d_fail(-1, "conv_mfma: grid too large");
-    a.nblk = (int)nblk;
-    const int ks = a.part ? a.ksplit : 1;
-    dim3 grid((unsigned)nblk, a.Cout / (nt2 ? 64 : 32), ks);
-    if (nt2) {
-        hipLaunchKernelGGL((conv3_s1_mfma_kernel<TD, TH, TW, MT, 2>), grid, dim3(256), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((conv3_s1_mfma_kernel<TD, TH, TW, MT, 1>), grid, dim3(256), 0, st, a);
+// ---------------------------------------------------------------------------------------------------------
+// Host side of the 3x3x3 stride-1 family: conv3_s1_plan decides, launch_s1_choice launches, conv_mfma_launch_inner (below)
+// walks the plan's choices with what only the launch knows.
+typedef void (*S1Kernel)(MfmaConvArgs);
+
+static int cdiv(int x, int y) { return (x + y - 1) / y; }
+static bool aligned_to(const void* p, size_t a) { return (((uintptr_t)p) % a) == 0; }
+static bool s1_tilefit() {
+    static const int fit_mode = ru3d_env_int("RU3D_CONV_TILEFIT", 1);
+    return fit_mode != 0;
+}
+
+// Width class of the 256-voxel tiles (32: 2 x 4 x 32, 16: 2 x 8 x 16, 8: 4 x 8 x 8; the weight gradient's tiles too): W
+// decides.  Extents that fit none of the tiles (config 4: 160 x 160 x 80 -> 40 x 40 x 20 on the 128-channel level) take
+// the tile with the least padded volume (RU3D_CONV_TILEFIT=0: W alone).
+static int s1_width_class(int D, int H, int W) {
+    const int wc = W >= 24 ? 32 : (W >= 12 ? 16 : 8);
+    if (!s1_tilefit()) return wc;
+    auto vol = [&](int a, int b, int c) { return (int64_t)cdiv(D, a) * a * cdiv(H, b) * b * cdiv(W, c) * c; };
+    const int64_t v32 = vol(2, 4, 32), v16 = vol(2, 8, 16), v8 = vol(4, 8, 8);
+    const int64_t cur = wc == 32 ? v32 : (wc == 16 ? v16 : v8);
+    // a narrower tile has more halo per voxel: it must save an eighth of the padded volume to be chosen
+    if (wc == 32 && v16 * 8 < cur * 7 && v16 <= v8) return 16;
+    if (wc >= 16 && v8 * 8 < cur * 7) return 8;
+    return wc;
+}
+// (TD, TH) of the width class's tile with mt x 128 voxels
+static void s1_tile_dims(int wc, int mt, int* td, int* th) {
+    *th = wc == 32 ? 4 : 8;
+    *td = (wc == 8 ? 4 : 2) * mt / 2;
+}
+
+// persistent grid of the producer/consumer kernels (and the layout of their statistics slab)
+static void pc_grid(int cout, bool nt2, int64_t nblk, int* gx, int* gy) {
+    *gy = cout / (nt2 ? 64 : 32);
+    int g = ru3d_get_cu_budget() / *gy;   // one persistent workgroup per CU in total (N > 1: minus the CUs left to RCCL)
+    g = g < 8 ? 8 : (g / 8) * 8;        // multiple of 8 so that blockIdx.x % 8 is the XCD label for every y
+    if (g > nblk) g = (int)nblk;
+    *gx = g;
+}
+
+static void s1_push(Conv3S1Plan& p, int family, int td, int th, int tw, int mt, int nt, int ks) {
+    Conv3S1Choice& c = p.choice[p.count++];
+    c.family = family; c.td = td; c.th = th; c.tw = tw; c.mt = mt; c.nt = nt; c.ks = ks;
+    switch (family) {
+        case S1_SLIDE32: snprintf(c.name, sizeof(c.name), "conv3_s1_slide32"); break;
+        case S1_SLIDE64: snprintf(c.name, sizeof(c.name), "conv3_s1_slide64"); break;
+        case S1_WS: snprintf(c.name, sizeof(c.name), "conv_ws"); break;
+        case S1_PC4: snprintf(c.name, sizeof(c.name), "conv3_s1_pc4"); break;
+        case S1_SK: snprintf(c.name, sizeof(c.name), "conv3_s1_sk<%d>", tw); break;
+        default:
+            snprintf(c.name, sizeof(c.name), "%s<%d,%d,%d,%d,%d>", family == S1_PC ? "conv3_s1_pc" : "conv3_s1_mfma", td, th,
+                     tw, mt, nt);
     }
-    int rc = ru3d_check_launch("conv3_s1_mfma");
-    if (rc || !a.part) return rc;
-    if (a.defer_ks) {        // the caller's next kernel sums the slices (norm_small.hip)
+}
+
+Conv3S1Plan conv3_s1_plan(const ConvGeom& g) {
+    // the family's switches, each read once per process; 0 = that kernel off
+    static const int slide_mode = ru3d_env_int("RU3D_CONV_SLIDE", 1), slide64_mode = ru3d_env_int("RU3D_CONV_SLIDE64", 1);
+    static const int edge_mode = ru3d_env_int("RU3D_SLIDE64_EDGE", 1);
+    static const int ws_mode = ru3d_env_int("RU3D_CONV_WS", 1);       // 2: wherever the shape fits
+    static const int pc_mode = ru3d_env_int("RU3D_CONV_PC", 1), pc4_mode = ru3d_env_int("RU3D_CONV_PC4", 1);
+    static const int sk_mode = ru3d_env_int("RU3D_CONV_SK", 1);       // 2: also where under 30 % of the MFMAs are useful
+    Conv3S1Plan p;
+    if (!(g.k == 3 && g.stride == 1 && !g.transposed && (g.Cin % 32) == 0 && (g.Cout % 32) == 0)) return p;
+    const int N = g.N, D = g.Do, H = g.Ho, W = g.Wo, Cin = g.Cin, Cout = g.Cout, ldx = g.ldx;
+    const bool buffer_ok = ldx > 0 && (ldx % 8) == 0 && (int64_t)D * H * W * ldx * 2 < (1ll << 31);   // a sample a descriptor can address
+
+    // 1. the large levels with 32 / 64 input channels: the D-sliding kernels
+    if (slide_mode && slide_conv_plan(N, D, H, W, Cin, Cout, &p.slide)) s1_push(p, S1_SLIDE32, 0, 0, 0, 0, 0, 1);
+    else if (slide64_mode && slide64_conv_plan(N, D, H, W, Cin, Cout, edge_mode != 0, &p.slide)) s1_push(p, S1_SLIDE64, 0, 0, 0, 0, 0, 1);
+    const bool slide = p.count > 0;
+    // 2. the deepest level: whole-sample workgroups that read their weight slice once (conv_ws.hip), then the split-K sum
+    if (const int wsl = ws_mode ? conv_ws_slices(N, D, H, W, Cin, Cout, ws_mode) : 0) s1_push(p, S1_WS, 0, 0, 0, 0, 0, wsl);
+
+    // 3. tiles.  W decides the tile's aspect; if the 256-voxel x 64-cout decomposition yields fewer than ~2 workgroups per
+    // CU (deep levels: 16^3, 8^3) the 64-cout slices go; >= 2 (tile, cout-slice) units per CU run on the persistent
+    // producer/consumer kernel
+    const int wc = s1_width_class(D, H, W);
+    int td, th;
+    s1_tile_dims(wc, 2, &td, &th);
+    int64_t nblk_pc = (int64_t)N * cdiv(D, td) * cdiv(H, th) * cdiv(W, wc);     // spatial tiles of the pc decomposition
+    const bool can_nt2 = (Cout % 64) == 0;
+    const bool small = nblk_pc * (Cout / (can_nt2 ? 64 : 32)) < 512;
+    const bool nt2 = can_nt2 && !small;
+    const bool pc = !small && pc_mode >= 1 && (wc >= 16 || s1_tilefit());
+    if (!small) {
+        // the 512-voxel form: no more padded volume than the 2 x 4 x 32 tile, at least 3/4 of the CUs busy
+        const int64_t n4 = (int64_t)N * (D / 4) * (H / 4) * cdiv(W, 32);
+        if (pc && nt2 && wc == 32 && pc4_mode && (D % 4) == 0 && (H % 4) == 0 && buffer_ok &&
+            n4 * (Cout / 64) * 4 >= (int64_t)ru3d_get_cu_budget() * 3) {
+            nblk_pc = n4;
+            s1_push(p, S1_PC4, 4, 4, 32, 2, 2, 1);
+        } else {
+            s1_push(p, pc ? S1_PC : S1_TILE, td, th, wc, 2, nt2 ? 2 : 1, 1);
+        }
+    } else {
+        // deep levels: 128-voxel x 64-cout blocks with the input channels split over the workgroup's waves and, below
+        // 192 blocks, over workgroups (conv3_s1_sk_kernel).  Tile width with the smaller padded volume (ties: the wider
+        // one); ragged extents are masked in the kernel
+        const int64_t v16 = (int64_t)cdiv(D, 2) * 2 * cdiv(H, 4) * 4 * cdiv(W, 16) * 16;
+        const int64_t v8 = (int64_t)cdiv(D, 2) * 2 * cdiv(H, 8) * 8 * cdiv(W, 8) * 8;
+        const int tw = v16 <= v8 ? 16 : 8;
+        const int64_t sk_units = (int64_t)N * cdiv(D, 2) * cdiv(H, 64 / tw) * cdiv(W, tw) * (Cout / 64);
+        if (sk_mode && can_nt2 && (Cin % 64) == 0 && buffer_ok && sk_units <= 512 &&
+            (sk_mode >= 2 || (int64_t)D * H * W * 10 >= (tw == 16 ? v16 : v8) * 3)) {
+            int ks = 1;
+            while (sk_units * ks < 192 && ks < 8 && ((Cin / (ks * 2)) % 64) == 0) ks *= 2;
+            if (sk_units * ks >= 96) s1_push(p, S1_SK, 2, 64 / tw, tw, 0, 0, ks);
+        }
+        // then 256-voxel tiles x 32-cout slices: the deep levels are bound by the weight bytes every workgroup pulls into
+        // its CU, which these halve against the 128-voxel tiles.  One workgroup per CU is the aim: fewer (8^3) split the
+        // 32-channel chunks over gridDim.z (fp32 partials in the caller's scratch).  Splitting further, to two resident
+        // workgroups per CU, measured slower in round 3 (16^3: 38.8 -> 43.1 us, 8^3: 26.8 -> 28.2 us)
+        const int64_t units = nblk_pc * (Cout / 32);
+        int ks = 1;
+        if (units < 256 && Cin >= 64)
+            for (ks = 2; ks * 2 <= Cin / 32 && units * ks < 256;) ks *= 2;
+        if (ks > 1 || units >= 256) s1_push(p, S1_TILE, td, th, wc, 2, 1, ks);
+        // ... and where that needs scratch the caller did not pass, or one chunk is all there is: 128-voxel tiles
+        if (ks > 1 || units < 256) {
+            s1_tile_dims(wc, 1, &td, &th);
+            s1_push(p, S1_TILE, td, th, wc, 1, 1, 1);
+        }
+    }
+
+    pc_grid(Cout, nt2, nblk_pc, &p.pc_gx, &p.pc_gy);
+    // split-K scratch: none when a sliding kernel is the first choice, the whole-sample kernel's when it is; else the most
+    // any choice can use
+    const size_t slice = (size_t)N * D * H * W * Cout * sizeof(float);
+    for (int i = 0; i < p.count && !slide; i++) {
+        const Conv3S1Choice& c = p.choice[i];
+        if (c.family == S1_WS) {
+            p.ws_bytes = c.ks * slice;
+            break;
+        }
+        if (c.ks > 1 && c.ks * slice > p.ws_bytes) p.ws_bytes = c.ks * slice;
+    }
+    // fused forms: the statistics slab follows the grid of the kernel that fills it
+    p.can_bwd_sums = p.can_partner = slide && p.choice[0].family == S1_SLIDE32;
+    p.can_stats = slide || pc;
+    if (slide) {
+        p.gx = p.slide.grid;
+        p.gy = p.slide.ny;
+        p.cb = (p.choice[0].family == S1_SLIDE32 || Cout == 32) ? 32 : 64;
+    } else {
+        p.gx = p.pc_gx;
+        p.gy = p.pc_gy;
+        p.cb = nt2 ? 64 : 32;
+    }
+    p.slab_bytes = (size_t)p.gx * p.gy * 4 * N * p.cb * 2 * sizeof(float);
+    return p;
+}
+
+template <int TD, int TH, int TW, int MT> static S1Kernel s1_tile_kernel(int nt) {
+    return nt == 2 ? conv3_s1_mfma_kernel<TD, TH, TW, MT, 2> : conv3_s1_mfma_kernel<TD, TH, TW, MT, 1>;
+}
+template <int TD, int TH, int TW> static S1Kernel s1_pc_kernel(int nt) {
+    return nt == 2 ? conv3_s1_pc_kernel<TD, TH, TW, 2, 2> : conv3_s1_pc_kernel<TD, TH, TW, 2, 1>;
+}
+// the one (family, tile, mt, nt) -> instantiation ladder
+static S1Kernel s1_kernel(const Conv3S1Choice& c) {
+    switch (c.family) {
+        case S1_PC4: return conv3_s1_pc4_kernel<3>;
+        case S1_SK: return c.tw == 16 ? conv3_s1_sk_kernel<16> : conv3_s1_sk_kernel<8>;
+        case S1_PC:
+            return c.tw == 32 ? s1_pc_kernel<2, 4, 32>(c.nt) : c.tw == 16 ? s1_pc_kernel<2, 8, 16>(c.nt) : s1_pc_kernel<4, 8, 8>(c.nt);
+        default:
+            if (c.mt == 2)
+                return c.tw == 32 ? s1_tile_kernel<2, 4, 32, 2>(c.nt)
+                                  : c.tw == 16 ? s1_tile_kernel<2, 8, 16, 2>(c.nt) : s1_tile_kernel<4, 8, 8, 2>(c.nt);
+            return c.tw == 32 ? s1_tile_kernel<1, 4, 32, 1>(c.nt)
+                              : c.tw == 16 ? s1_tile_kernel<1, 8, 16, 1>(c.nt) : s1_tile_kernel<2, 8, 8, 1>(c.nt);
+    }
+}
+
+// the caller's scratch holds ks slices of partials, and y / res take the 16-byte rows of the sum that follows
+static bool s1_scratch_ok(const MfmaConvArgs& a, int ks) {
+    const size_t bytes = (size_t)ks * a.N * a.D * a.H * a.W * a.Cout * sizeof(float);
+    return a.ws && a.ws_bytes >= bytes && aligned_to(a.ws, 16) && (a.ldy % 8) == 0 && (!a.res || (a.ldr % 8) == 0);
+}
+
+// ks slices of fp32 partials in a.ws -> y: the caller's next kernel sums them (defer_ks: norm_small.hip), or the
+// fixed-order reduce here, with the bias / residual fused
+static int s1_splitk_tail(const MfmaConvArgs& a, int ks, hipStream_t st) {
+    if (a.defer_ks) {
         *a.defer_ks = ks;
         return 0;
     }
     const int64_t V = (int64_t)a.N * a.D * a.H * a.W;
     const int64_t groups = V * (a.Cout / 8);
     hipLaunchKernelGGL(conv_ksplit_reduce_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st,
-                       (const float*)a.part, ks, V, a.Cout, a.bias, a.res, a.ldr, a.y, a.ldy);
+                       (const float*)a.ws, ks, V, a.Cout, a.bias, a.res, a.ldr, a.y, a.ldy);
     return ru3d_check_launch("conv_ksplit_reduce");
 }
 
-// Tile choice: W decides the tile's aspect; if the 256-voxel x 64-cout decomposition yields fewer than ~2
-// workgroups per CU (deep levels: 16^3, 8^3), fall back to 128-voxel tiles and then to 32-cout slices.
-// >= 2 (tile, cout-slice) units per CU run on the persistent producer/consumer kernel.
-struct S1Plan {
-    int wclass;
-    bool nt2, small, pc;
-    bool pc4;          // 512-voxel tiles, 4 x 2 accumulators per wave (conv3_s1_pc4_kernel)
-    int64_t nblk_pc;   // spatial tiles of the producer/consumer decomposition
-};
-
-static S1Plan s1_plan(int N, int D, int H, int W, int Cout, int ldx) {
-    auto cdiv = [](int x, int y) { return (x + y - 1) / y; };
-    S1Plan p;
-    const bool can_nt2 = (Cout % 64) == 0;
-    p.wclass = W >= 24 ? 32 : (W >= 12 ? 16 : 8);
-    // extents that fit none of the tiles (config 4: 160 x 160 x 80 -> 40 x 40 x 20 on the 128-channel level): the tile
-    // with the least padded volume (RU3D_CONV_TILEFIT=0: the width classes above)
-    static const int fit_mode = getenv("RU3D_CONV_TILEFIT") ? atoi(getenv("RU3D_CONV_TILEFIT")) : 1;
-    if (fit_mode) {
-        const int64_t v32 = (int64_t)cdiv(D, 2) * 2 * cdiv(H, 4) * 4 * cdiv(W, 32) * 32;
-        const int64_t v16 = (int64_t)cdiv(D, 2) * 2 * cdiv(H, 8) * 8 * cdiv(W, 16) * 16;
-        const int64_t v8 = (int64_t)cdiv(D, 4) * 4 * cdiv(H, 8) * 8 * cdiv(W, 8) * 8;
-        const int64_t cur = p.wclass == 32 ? v32 : (p.wclass == 16 ? v16 : v8);
-        // a narrower tile has more halo per voxel: it must save an eighth of the padded volume to be chosen
-        if (p.wclass == 32 && v16 * 8 < cur * 7 && v16 <= v8) p.wclass = 16;
-        else if (p.wclass >= 16 && v8 * 8 < cur * 7) p.wclass = 8;
-    }
-    int64_t big;   // workgroups with MT = 2, widest cout slice
-    if (p.wclass == 32) big = (int64_t)N * cdiv(D, 2) * cdiv(H, 4) * cdiv(W, 32);
-    else if (p.wclass == 16) big = (int64_t)N * cdiv(D, 2) * cdiv(H, 8) * cdiv(W, 16);
-    else big = (int64_t)N * cdiv(D, 4) * cdiv(H, 8) * cdiv(W, 8);
-    p.nblk_pc = big;
-    big *= Cout / (can_nt2 ? 64 : 32);
-    p.small = big < 512;
-    p.nt2 = can_nt2 && (!p.small || big * 2 >= 1024);
-    static const int pc_mode = getenv("RU3D_CONV_PC") ? atoi(getenv("RU3D_CONV_PC")) : 1;   // 0 = off
-    p.pc = !p.small && pc_mode >= 1 && (p.wclass >= 16 || fit_mode);
-    // the 512-voxel form: no more padded volume than the 2 x 4 x 32 tile, at least 3/4 of the CUs busy, a sample that
-    // a buffer descriptor can address (RU3D_CONV_PC4=0: off)
-    static const int pc4_mode = getenv("RU3D_CONV_PC4") ? atoi(getenv("RU3D_CONV_PC4")) : 1;
-    p.pc4 = false;
-    if (p.pc && p.nt2 && p.wclass == 32 && pc4_mode && (D % 4) == 0 && (H % 4) == 0 && ldx > 0 && (ldx % 8) == 0) {
-        const int64_t n4 = (int64_t)N * (D / 4) * (H / 4) * cdiv(W, 32);
-        const int64_t sample_bytes = (int64_t)D * H * W * ldx * 2;
-        if (n4 * (Cout / 64) * 4 >= (int64_t)ru3d_get_cu_budget() * 3 && sample_bytes < (1ll << 31)) {
-            p.pc4 = true;
-            p.nblk_pc = n4;
-        }
-    }
-    return p;
-}
-
-// split-K factor of the deepest level (0/1 = none): the 256-voxel x 32-cout decomposition leaves CUs idle
-static int s1_ksplit(const S1Plan& p, int N, int D, int H, int W, int Cin, int Cout) {
-    const int64_t units = p.nblk_pc * (Cout / 32);
-    const int nchunks = Cin / 32;
-    // one workgroup per CU is the aim: splitting further (two resident workgroups per CU) measured slower in round 3
-    // (16^3: 38.8 -> 43.1 us, 8^3: 26.8 -> 28.2 us) - these kernels are bound by what enters the CU, not by its occupancy
-    const int64_t target = 256;
-    if (!p.small || p.nt2 || units >= target || nchunks < 2) return 1;
-    int ks = 2;
-    while (ks * 2 <= nchunks && units * ks < target) ks *= 2;
-    (void)N; (void)D; (void)H; (void)W;
-    return ks;
-}
-
-// the deep levels' in-workgroup split-K form (conv3_s1_sk_kernel)
-struct SkPlan {
-    int tw, ks;
-    int64_t tiles;
-};
-
-static bool sk_plan(int N, int D, int H, int W, int Cin, int Cout, int ldx, SkPlan* p) {
-    static const int mode = getenv("RU3D_CONV_SK") ? atoi(getenv("RU3D_CONV_SK")) : 1;   // 0 = off
-    if (!mode) return false;
-    auto cdiv = [](int x, int y) { return (x + y - 1) / y; };
-    // tile width with the smaller padded volume (ties: the wider one); ragged extents are masked in the kernel
-    const int64_t v16 = (int64_t)cdiv(D, 2) * 2 * cdiv(H, 4) * 4 * cdiv(W, 16) * 16;
-    const int64_t v8 = (int64_t)cdiv(D, 2) * 2 * cdiv(H, 8) * 8 * cdiv(W, 8) * 8;
-    const int tw = v16 <= v8 ? 16 : 8;
-    const int th = 64 / tw;
-    if ((Cout % 64) || (Cin % 64) || ldx <= 0 || (ldx % 8)) return false;
-    if ((int64_t)D * H * W * ldx * 2 >= (1ll << 31)) return false;
-    if (mode < 2 && (int64_t)D * H * W * 10 < (tw == 16 ? v16 : v8) * 3) return false;   // under 30 % of the MFMAs useful
-    const int64_t tiles = (int64_t)N * cdiv(D, 2) * cdiv(H, th) * cdiv(W, tw);
-    const int64_t units = tiles * (Cout / 64);
-    if (units > 512) return false;              // the large levels run on the persistent kernels
-    int ks = 1;
-    while (units * ks < 192 && ks < 8 && ((Cin / (ks * 2)) % 64) == 0) ks *= 2;
-    if (units * ks < 96) return false;
-    p->tw = tw;
-    p->ks = ks;
-    p->tiles = tiles;
-    return true;
-}
-
-static int launch_s1_sk(const MfmaConvArgs& a0, const SkPlan& sp, hipStream_t st) {
+static int launch_s1_choice(const MfmaConvArgs& a0, const Conv3S1Plan& p, const Conv3S1Choice& c, hipStream_t st) {
     MfmaConvArgs a = a0;
-    const int th = 64 / sp.tw;
-    a.tiles_d = (a.D + 1) / 2;
-    a.tiles_h = (a.H + th - 1) / th;
-    a.tiles_w = (a.W + sp.tw - 1) / sp.tw;
-    a.nblk = (int)sp.tiles;
-    a.ksplit = sp.ks;
-    a.part = sp.ks > 1 ? (float*)a.ws : nullptr;
-    dim3 grid((unsigned)(sp.tiles * (a.Cout / 64)), 1, sp.ks);
-    if (sp.tw == 16)
-        hipLaunchKernelGGL((conv3_s1_sk_kernel<16>), grid, dim3(512), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv3_s1_sk_kernel<8>), grid, dim3(512), 0, st, a);
-    int rc = ru3d_check_launch("conv3_s1_sk");
-    if (rc || sp.ks <= 1) return rc;
-    if (a.defer_ks) {        // the caller's next kernel sums the slices (norm_small.hip)
-        *a.defer_ks = sp.ks;
-        return 0;
+    if (c.family == S1_WS) {
+        if (int rc = conv_ws_launch(a.x, a.w, (float*)a.ws, a.N, a.D, a.H, a.W, a.Cin, a.Cout, a.ldx, a.flip, c.ks, st)) return rc;
+        return s1_splitk_tail(a, c.ks, st);
     }
-    const int64_t V = (int64_t)a.N * a.D * a.H * a.W;
-    const int64_t groups = V * (a.Cout / 8);
-    hipLaunchKernelGGL(conv_ksplit_reduce_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st,
-                       (const float*)a.part, sp.ks, V, a.Cout, a.bias, a.res, a.ldr, a.y, a.ldy);
-    return ru3d_check_launch("conv_ksplit_reduce");
-}
-
-// workspace a 3x3x3 stride-1 conv of this geometry can use (split-K partials); 0 = none needed
-size_t conv_mfma_ws_bytes(const ConvGeom& g) {
-    if (!(g.k == 3 && g.stride == 1 && !g.transposed && (g.Cin % 32) == 0 && (g.Cout % 32) == 0)) return 0;
-    SlidePlan sp;
-    if (slide_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp)) return 0;
-    if (slide64_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp)) return 0;
-    if (const int wsl = conv_ws_slices(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout))
-        return (size_t)wsl * g.N * g.Do * g.Ho * g.Wo * g.Cout * sizeof(float);
-    const S1Plan p = s1_plan(g.N, g.Do, g.Ho, g.Wo, g.Cout, g.ldx);
-    int ks = s1_ksplit(p, g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout);
-    SkPlan sk;
-    if (p.small && sk_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, g.ldx, &sk) && sk.ks > ks) ks = sk.ks;
-    return ks > 1 ? (size_t)ks * g.N * g.Do * g.Ho * g.Wo * g.Cout * sizeof(float) : 0;
-}
-
-static int launch_s1_auto(const MfmaConvArgs& a, hipStream_t st) {
-    // the deepest level: whole-sample workgroups that read their weight slice once (conv_ws.hip), then the split-K sum
-    if (const int wsl = conv_ws_slices(a.N, a.D, a.H, a.W, a.Cin, a.Cout)) {
-        const size_t bytes = (size_t)wsl * a.N * a.D * a.H * a.W * a.Cout * sizeof(float);
-        if (!a.stat_slab && a.ws && a.ws_bytes >= bytes && (((uintptr_t)a.ws) % 16) == 0 && (a.ldy % 8) == 0 &&
-            (!a.res || (a.ldr % 8) == 0)) {
-            int rc = conv_ws_launch(a.x, a.w, (float*)a.ws, a.N, a.D, a.H, a.W, a.Cin, a.Cout, a.ldx, a.flip, wsl, st);
-            if (rc) return rc;
-            if (a.defer_ks) {
-                *a.defer_ks = wsl;
-                return 0;
-            }
-            const int64_t V = (int64_t)a.N * a.D * a.H * a.W;
-            const int64_t groups = V * (a.Cout / 8);
-            hipLaunchKernelGGL(conv_ksplit_reduce_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st,
-                               (const float*)a.ws, wsl, V, a.Cout, a.bias, a.res, a.ldr, a.y, a.ldy);
-            return ru3d_check_launch("conv_ksplit_reduce");
-        }
+    a.tiles_d = cdiv(a.D, c.td);
+    a.tiles_h = cdiv(a.H, c.th);
+    a.tiles_w = cdiv(a.W, c.tw);
+    const int64_t nblk = (int64_t)a.N * a.tiles_d * a.tiles_h * a.tiles_w;
+    if (nblk > 0x7fffffff) return ru3d_fail(-1, "conv_mfma: grid too large");
+    a.nblk = (int)nblk;
+    a.ksplit = c.ks;
+    a.part = c.ks > 1 ? (float*)a.ws : nullptr;
+    dim3 grid(p.pc_gx, p.pc_gy), block(512);      // the persistent kernels
+    if (c.family == S1_SK) grid = dim3((unsigned)(nblk * (a.Cout / 64)), 1, c.ks);
+    if (c.family == S1_TILE) {
+        grid = dim3((unsigned)nblk, a.Cout / (32 * c.nt), c.ks);
+        block = dim3(256);
     }
-    const S1Plan p = s1_plan(a.N, a.D, a.H, a.W, a.Cout, a.ldx);
-    if (a.stat_slab && !p.pc) return ru3d_fail(-1, "conv_mfma: fused statistics need the producer/consumer kernel");
-    if (!p.small) {
-        if (p.pc4) return launch_s1_pc4(a, st);
-        if (p.pc && p.wclass == 32) return launch_s1_pc<2, 4, 32, 2>(a, p.nt2, st);
-        if (p.pc && p.wclass == 16) return launch_s1_pc<2, 8, 16, 2>(a, p.nt2, st);
-        if (p.pc && p.wclass == 8) return launch_s1_pc<4, 8, 8, 2>(a, p.nt2, st);
-        if (p.wclass == 32) return launch_s1<2, 4, 32, 2>(a, p.nt2, st);
-        if (p.wclass == 16) return launch_s1<2, 8, 16, 2>(a, p.nt2, st);
-        return launch_s1<4, 8, 8, 2>(a, p.nt2, st);
-    }
-    // deep levels, exact-fit extents: 128-voxel x 64-cout blocks with the input channels split over the workgroup's waves
-    {
-        SkPlan sk;
-        if (!a.stat_slab && sk_plan(a.N, a.D, a.H, a.W, a.Cin, a.Cout, a.ldx, &sk)) {
-            const size_t bytes = (size_t)sk.ks * a.N * a.D * a.H * a.W * a.Cout * sizeof(float);
-            if (sk.ks == 1 || (a.ws && a.ws_bytes >= bytes && (((uintptr_t)a.ws) % 16) == 0 && (a.ldy % 8) == 0 &&
-                               (!a.res || (a.ldr % 8) == 0)))
-                return launch_s1_sk(a, sk, st);
-        }
-    }
-    // deep levels are bound by the weight bytes every workgroup pulls into its CU: when 256-voxel tiles x 32-cout
-    // slices still give one workgroup per CU, they halve that traffic against the 128-voxel tiles
-    const int ks = s1_ksplit(p, a.N, a.D, a.H, a.W, a.Cin, a.Cout);
-    if (ks <= 1 && !p.nt2 && p.nblk_pc * (a.Cout / 32) >= 256) {
-        if (p.wclass == 32) return launch_s1<2, 4, 32, 2>(a, false, st);
-        if (p.wclass == 16) return launch_s1<2, 8, 16, 2>(a, false, st);
-        return launch_s1<4, 8, 8, 2>(a, false, st);
-    }
-    // still fewer than one workgroup per CU (8^3): keep the 256-voxel x 32-cout tiles and split the 32-channel
-    // chunks over gridDim.z; fp32 partials in the caller's workspace, fixed-order reduce with the bias / residual fused
-    if (ks > 1 && (a.ldy % 8) == 0 && (!a.res || (a.ldr % 8) == 0)) {
-        const size_t bytes = (size_t)ks * a.N * a.D * a.H * a.W * a.Cout * sizeof(float);
-        if (a.ws && a.ws_bytes >= bytes && (((uintptr_t)a.ws) % 16) == 0) {
-            MfmaConvArgs b = a;
-            b.part = (float*)a.ws;
-            b.ksplit = ks;
-            if (p.wclass == 32) return launch_s1<2, 4, 32, 2>(b, false, st);
-            if (p.wclass == 16) return launch_s1<2, 8, 16, 2>(b, false, st);
-            return launch_s1<4, 8, 8, 2>(b, false, st);
-        }
-    }
-    if (p.wclass == 32) return launch_s1<1, 4, 32, 1>(a, p.nt2, st);
-    if (p.wclass == 16) return launch_s1<1, 8, 16, 1>(a, p.nt2, st);
-    return launch_s1<2, 8, 8, 1>(a, p.nt2, st);
-}
-
-// Fused InstanceNorm statistics (producer/consumer kernel only): slab[workgroup][wave][n][cout_local][2] floats.
-bool mfma_conv_can_fuse_stats(const ConvGeom& g) {
-    if (!(g.k == 3 && g.stride == 1 && !g.transposed && (g.Cin % 32) == 0 && (g.Cout % 32) == 0)) return false;
-    SlidePlan sp;
-    if (slide_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp)) return true;
-    if (slide64_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp)) return true;
-    return s1_plan(g.N, g.Do, g.Ho, g.Wo, g.Cout, g.ldx).pc;
-}
-
-static void stats_slab_geom(const ConvGeom& g, int* gx, int* gy, int* cb) {
-    SlidePlan sp;
-    if (slide_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp)) {
-        *gx = sp.grid;
-        *gy = sp.ny;
-        *cb = 32;
-        return;
-    }
-    if (slide64_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp)) {
-        *gx = sp.grid;
-        *gy = sp.ny;
-        *cb = g.Cout == 32 ? 32 : 64;
-        return;
-    }
-    const S1Plan p = s1_plan(g.N, g.Do, g.Ho, g.Wo, g.Cout, g.ldx);
-    pc_grid(g.Cout, p.nt2, p.nblk_pc, gx, gy);
-    *cb = p.nt2 ? 64 : 32;
-}
-
-size_t mfma_conv_stats_slab_bytes(const ConvGeom& g) {
-    int gx, gy, cb;
-    stats_slab_geom(g, &gx, &gy, &cb);
-    return (size_t)gx * gy * 4 * g.N * cb * 2 * sizeof(float);
+    hipLaunchKernelGGL(s1_kernel(c), grid, block, 0, st, a);
+    const int rc = ru3d_check_launch(c.name);
+    return (rc || c.ks <= 1) ? rc : s1_splitk_tail(a, c.ks, st);
 }
 
 // mean / scale from the slabs: one thread block per (n, 4 channels); 64 lanes per channel sum the
@@ -1405,35 +1318,7 @@ int stats_slab_finalize_launch(const float* slab, int gx, int cb, int N, int C, 
                                float* mean, float* scale, hipStream_t st) {
     dim3 grid((C + 3) / 4, N);
     hipLaunchKernelGGL(stats_slab_finalize_kernel, grid, dim3(256), 0, st, slab, gx, cb, N, C, invV, drop, eps, mean, scale);
-    return ru3d_check_launch("stats_slab_finalize");
-}
-
-bool mfma_conv_can_fuse_bwd_sums(const ConvGeom& g) {
-    if (!(g.k == 3 && g.stride == 1 && !g.transposed)) return false;
-    SlidePlan sp;
-    if (g.Cin == 32) return slide_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp);
-    return false;      // (the 64-channel kernel's variant was removed in round 4: time-neutral at best, see conv_slide64.hip)
-}
-
-int mfma_conv_bwd_sums_finalize(const ConvGeom& g, const float* slab, float* m12, hipStream_t st) {
-    int gx, gy, cb;
-    stats_slab_geom(g, &gx, &gy, &cb);
-    dim3 grid((g.Cout + 3) / 4, g.N);
-    const double invV = 1.0 / ((double)g.Do * g.Ho * g.Wo);
-    hipLaunchKernelGGL(stats_slab_finalize_kernel, grid, dim3(256), 0, st, slab, gx, cb, g.N, g.Cout, invV,
-                       (const float*)nullptr, 0.f, m12, (float*)nullptr);
-    return ru3d_check_launch("bwd_sums_slab_finalize");
-}
-
-int mfma_conv_stats_finalize(const ConvGeom& g, const float* slab, const float* drop, float eps, float* mean,
-                             float* scale, hipStream_t st) {
-    int gx, gy, cb;
-    stats_slab_geom(g, &gx, &gy, &cb);
-    dim3 grid((g.Cout + 3) / 4, g.N);
-    const double invV = 1.0 / ((double)g.Do * g.Ho * g.Wo);
-    hipLaunchKernelGGL(stats_slab_finalize_kernel, grid, dim3(256), 0, st, slab, gx, cb, g.N, g.Cout, invV, drop, eps,
-                       mean, scale);
-    return ru3d_check_launch("stats_slab_finalize");
+    return ru3d_check_launch(scale ? "stats_slab_finalize" : "bwd_sums_slab_finalize");
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2257,7 +2142,7 @@ static int launch_direct(const void* x, const void* w, const float* bias, const 
 #undef RU3D_KSPLIT_LAUNCH
         return ru3d_check_launch(name);
     }
-    static const int tile_mode = getenv("RU3D_CONVT_TILE") ? atoi(getenv("RU3D_CONVT_TILE")) : 1;
+    static const int tile_mode = ru3d_env_int("RU3D_CONVT_TILE", 1);
     if (tile_mode && g.transposed && g.k == 3 && g.pad == 1) {
         // (TD+1)(TH+1)(TW+1) rows of Cin*2+16 bytes must fit in LDS: Cin <= 256 with the 16-wide tile, 128 with the 32-wide
         if (a.hw >= 24 && g.Cin <= 128) {
@@ -2269,7 +2154,7 @@ static int launch_direct(const void* x, const void* w, const float* bias, const 
         }
         if (a.hw >= 12 && g.Cin <= 256) {
             // 64-cout workgroups only when they still fill the chip (16^3 -> 32^3 at N = 2: 64 tiles)
-            static const int nt_mode = getenv("RU3D_CONVT_NT") ? atoi(getenv("RU3D_CONVT_NT")) : 1;
+            static const int nt_mode = ru3d_env_int("RU3D_CONVT_NT", 1);
             const int64_t t16 = (int64_t)g.N * ((a.hd + 1) / 2) * ((a.hh + 3) / 4) * ((a.hw + 15) / 16);
             const bool wide = nt2 && (nt_mode == 0 || t16 * (g.Cout / 64) >= 200);
             return wide ? launch_convt_tile<2, 2, 4, 16>(a, g.N, st, "convt_tile_mfma<2,2,4,16>")
@@ -2293,88 +2178,50 @@ static int launch_direct(const void* x, const void* w, const float* bias, const 
     return ru3d_check_launch(nt2 ? "conv_direct_mfma<2,T>" : "conv_direct_mfma<1,T>");
 }
 
-static bool aligned_to(const void* p, size_t a) { return (((uintptr_t)p) % a) == 0; }
-
 // Every data-movement form with MFMA-friendly channel counts runs on MFMA: the 3x3x3 stride-1 gather with
 // Cin % 32 == 0 on the LDS-halo kernel, everything else on the direct kernel (same packed-weight layout).
 bool mfma_conv_geometry_ok(const ConvGeom& g) { return !g.transposed || g.stride == 2; }
 
-bool mfma_conv_can_fuse_partner(const ConvGeom& g) {
-    if (!(g.k == 3 && g.stride == 1 && !g.transposed && g.Cin == 32)) return false;
-    SlidePlan sp;
-    return slide_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp);
-}
-
 static int conv_mfma_launch_inner(const void* x, const void* w, const float* bias, const void* res, void* y,
-                                  const ConvGeom& g, hipStream_t st, float* stat_slab, void* ws, size_t ws_bytes,
-                                  const void* bst_act, int bst_ld, float slope, const void* x2, int ldx2, const void* w2,
-                                  int* defer_ks);
+                                  const ConvGeom& g, const Conv3S1Plan& p, hipStream_t st, float* stat_slab, void* ws,
+                                  size_t ws_bytes, const void* bst_act, int bst_ld, float slope, const void* x2, int ldx2,
+                                  const void* w2, int* defer_ks);
 
 int conv_mfma_launch(const void* x, const void* w, const float* bias, const void* res, void* y, const ConvGeom& g,
                      hipStream_t st, float* stat_slab, void* ws, size_t ws_bytes, const void* bst_act, int bst_ld,
-                     float slope, const void* x2, int ldx2, const void* w2, int* defer_ks) {
+                     float slope, const void* x2, int ldx2, const void* w2, int* defer_ks, const Conv3S1Plan* plan) {
     // bench.py's kernel probe: an event pair around the conv kernel itself (ru3d_probe_begin; comm.hip)
     void* stop = (g.k == 3 && g.stride == 1 && !g.transposed)
                      ? ru3d_probe_start(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, st) : nullptr;
-    const int rc = conv_mfma_launch_inner(x, w, bias, res, y, g, st, stat_slab, ws, ws_bytes, bst_act, bst_ld, slope, x2, ldx2,
-                                          w2, defer_ks);
+    const int rc = conv_mfma_launch_inner(x, w, bias, res, y, g, plan ? *plan : conv3_s1_plan(g), st, stat_slab, ws, ws_bytes,
+                                          bst_act, bst_ld, slope, x2, ldx2, w2, defer_ks);
     ru3d_probe_stop(stop, st);
     return rc;
 }
 
 static int conv_mfma_launch_inner(const void* x, const void* w, const float* bias, const void* res, void* y,
-                                  const ConvGeom& g, hipStream_t st, float* stat_slab, void* ws, size_t ws_bytes,
-                                  const void* bst_act, int bst_ld, float slope, const void* x2, int ldx2, const void* w2,
-                                  int* defer_ks) {
+                                  const ConvGeom& g, const Conv3S1Plan& p, hipStream_t st, float* stat_slab, void* ws,
+                                  size_t ws_bytes, const void* bst_act, int bst_ld, float slope, const void* x2, int ldx2,
+                                  const void* w2, int* defer_ks) {
     if (defer_ks) *defer_ks = 0;
     if (!mfma_conv_geometry_ok(g)) return ru3d_fail(-1, "conv_mfma: geometry not supported");
+    const int first = p.count ? p.choice[0].family : 0;
     if (g.x_cseg || g.y_cseg) {
         // planar concat (see ru3d_tensor): the decoder block's conv1 on the 64-channel sliding kernel (split input), its
         // input gradient pair on the 32-channel sliding kernel (split output: one plane per 32-channel slice)
-        SlidePlan sp;
-        const bool in_ok = g.x_cseg && !g.y_cseg && g.k == 3 && g.stride == 1 && !g.transposed &&
-                           slide64_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp);
-        const bool out_ok = g.y_cseg && !g.x_cseg && x2 && mfma_conv_can_fuse_partner(g);
+        const bool in_ok = g.x_cseg && !g.y_cseg && first == S1_SLIDE64;
+        const bool out_ok = g.y_cseg && !g.x_cseg && x2 && p.can_partner;
         if (!in_ok && !out_ok) return ru3d_fail(-1, "conv_mfma: no kernel takes this split tensor");
     }
-    if (x2 && !mfma_conv_can_fuse_partner(g)) return ru3d_fail(-1, "conv_mfma: no fused 1x1 partner for this shape");
+    if (x2 && !p.can_partner) return ru3d_fail(-1, "conv_mfma: no fused 1x1 partner for this shape");
     if ((g.ldx % 8) || (g.ldy % 4) || (res && (g.ldr % 4)) || !aligned_to(x, 16) || !aligned_to(y, 8) ||
         (res && !aligned_to(res, 8)) || (bias && !aligned_to(bias, 16)) || !aligned_to(w, 16))
         return ru3d_fail(-1, "conv_mfma: operands must be 16-byte (x, w, bias) / 8-byte (y, res) aligned");
-    if (bst_act && !mfma_conv_can_fuse_bwd_sums(g))
+    if (bst_act && !p.can_bwd_sums)
         return ru3d_fail(-1, "conv_mfma: fused backward sums are not available for this shape");
-    if (!(g.k == 3 && g.stride == 1 && !g.transposed && (g.Cin % 32) == 0)) {
+    if (!p.count) {
         if (stat_slab) return ru3d_fail(-1, "conv_mfma: fused statistics not available for this form");
         return launch_direct(x, w, bias, res, y, g, st);
-    }
-    {
-        SlidePlan sp;
-        if (slide_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp)) {
-            // 16-byte stores; a sample within the 30-bit element range of the staging loads' buffer offsets
-            const bool aligned = (g.ldy % 8) == 0 && (!res || (g.ldr % 8) == 0) && aligned_to(y, 16) &&
-                                 (!res || aligned_to(res, 16)) && (g.ldx % 8) == 0 && aligned_to(x, 16) &&
-                                 (int64_t)g.Do * g.Ho * g.Wo * g.ldx < (1ll << 30);
-            if (aligned && (!bst_act || ((bst_ld % 8) == 0 && aligned_to(bst_act, 16))))
-                return conv_slide_launch(x, w, bias, res, y, g, stat_slab, st, bst_act, bst_ld, slope, x2, ldx2, w2);
-            if (bst_act) return ru3d_fail(-1, "conv_mfma: the fused backward sums need 16-byte aligned operands");
-            if (x2) return ru3d_fail(-1, "conv_mfma: the fused 1x1 partner needs 16-byte aligned operands");
-            // the statistics slab (size, layout) was planned for the sliding kernel's grid: falling back to the
-            // producer/consumer kernel here would fill it with another geometry
-            if (stat_slab)
-                return ru3d_fail(-1, "conv_mfma: fused statistics need y (and res) 16-byte aligned with a pitch that is "
-                                     "a multiple of 8 on this shape");
-        }
-        if (slide64_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp)) {
-            const bool aligned = (g.ldy % 8) == 0 && (!res || (g.ldr % 8) == 0) && aligned_to(y, 16) &&
-                                 (!res || aligned_to(res, 16)) && (g.ldx % 8) == 0 && aligned_to(x, 16) &&
-                                 (int64_t)g.Do * g.Ho * g.Wo * g.ldx < (1ll << 30);
-            if (aligned && (!bst_act || ((bst_ld % 8) == 0 && aligned_to(bst_act, 16))))
-                return conv_slide64_launch(x, w, bias, res, y, g, stat_slab, st, bst_act, bst_ld, slope);
-            if (bst_act) return ru3d_fail(-1, "conv_mfma: the fused backward sums need 16-byte aligned operands");
-            if (stat_slab)
-                return ru3d_fail(-1, "conv_mfma: fused statistics need y (and res) 16-byte aligned with a pitch that is "
-                                     "a multiple of 8 on this shape");
-        }
     }
     MfmaConvArgs a;
     a.x = (const bf16*)x;
@@ -2391,7 +2238,37 @@ static int conv_mfma_launch_inner(const void* x, const void* w, const float* bia
     a.defer_ks = (res || stat_slab) ? nullptr : defer_ks;
     a.ws = ws;
     a.ws_bytes = ws_bytes;
-    return launch_s1_auto(a, st);
+    // The first choice whose launch-time conditions hold runs; the last one has none.
+    for (int i = 0; i < p.count; i++) {
+        const Conv3S1Choice& c = p.choice[i];
+        if (c.family == S1_SLIDE32 || c.family == S1_SLIDE64) {
+            // 16-byte stores; a sample within the 30-bit element range of the staging loads' buffer offsets
+            const bool aligned = (g.ldy % 8) == 0 && (!res || (g.ldr % 8) == 0) && aligned_to(y, 16) &&
+                                 (!res || aligned_to(res, 16)) && (g.ldx % 8) == 0 && aligned_to(x, 16) &&
+                                 (int64_t)g.Do * g.Ho * g.Wo * g.ldx < (1ll << 30) &&
+                                 (!bst_act || ((bst_ld % 8) == 0 && aligned_to(bst_act, 16)));
+            if (aligned)
+                return c.family == S1_SLIDE32
+                           ? conv_slide_launch(x, w, bias, res, y, g, p.slide, stat_slab, st, bst_act, bst_ld, slope, x2, ldx2, w2)
+                           : conv_slide64_launch(x, w, bias, res, y, g, p.slide, stat_slab, st);
+            if (bst_act) return ru3d_fail(-1, "conv_mfma: the fused backward sums need 16-byte aligned operands");
+            if (x2) return ru3d_fail(-1, "conv_mfma: the fused 1x1 partner needs 16-byte aligned operands");
+            // the statistics slab (size, layout) was planned for the sliding kernel's grid: falling back to the
+            // producer/consumer kernel here would fill it with another geometry
+            if (stat_slab)
+                return ru3d_fail(-1, "conv_mfma: fused statistics need y (and res) 16-byte aligned with a pitch that is "
+                                     "a multiple of 8 on this shape");
+            continue;
+        }
+        if (c.family == S1_WS) {
+            if (stat_slab || !s1_scratch_ok(a, c.ks)) continue;
+        } else if (c.family == S1_SK || c.family == S1_TILE) {
+            if (stat_slab) return ru3d_fail(-1, "conv_mfma: fused statistics need the producer/consumer kernel");
+            if (c.ks > 1 && !s1_scratch_ok(a, c.ks)) continue;
+        }
+        return launch_s1_choice(a, p, c, st);
+    }
+    return ru3d_fail(-1, "conv_mfma: the plan has no choice for this launch");
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2735,18 +2612,8 @@ bool mfma_wgrad_eligible(const WgradGeom& g, int dtype) {
 }
 
 static void wgrad_tiles(const WgradGeom& g, int* td, int* th, int* tw) {
-    if (g.Wo >= 24) { *td = 2; *th = 4; *tw = 32; }
-    else if (g.Wo >= 12) { *td = 2; *th = 8; *tw = 16; }
-    else { *td = 4; *th = 8; *tw = 8; }
-    // extents that fit none of the tiles (40 x 40 x 20): the tile with the least padded volume, as in s1_plan
-    static const int fit_mode = getenv("RU3D_CONV_TILEFIT") ? atoi(getenv("RU3D_CONV_TILEFIT")) : 1;
-    if (!fit_mode) return;
-    auto cdiv = [](int x, int y) { return (x + y - 1) / y; };
-    auto vol = [&](int a, int b, int c) { return (int64_t)cdiv(g.Do, a) * a * cdiv(g.Ho, b) * b * cdiv(g.Wo, c) * c; };
-    const int64_t cur = vol(*td, *th, *tw);
-    const int64_t v16 = vol(2, 8, 16), v8 = vol(4, 8, 8);
-    if (*tw == 32 && v16 * 8 < cur * 7 && v16 <= v8) { *td = 2; *th = 8; *tw = 16; }
-    else if (*tw >= 16 && v8 * 8 < cur * 7) { *td = 4; *th = 8; *tw = 8; }
+    *tw = s1_width_class(g.Do, g.Ho, g.Wo);
+    s1_tile_dims(*tw, 2, td, th);
 }
 
 static int wgrad_mfma_groups(const WgradGeom& g) {
@@ -2759,7 +2626,7 @@ static int wgrad_mfma_groups(const WgradGeom& g) {
     if (G > ntiles) G = ntiles;
     // one workgroup per CU already and few tiles each (512 -> 512 on 8^3: 256 pairs x 4 tiles): a single workgroup per
     // pair writes the gradient itself (RU3D_WGRAD_DIRECT=0: two slabs + the reduce pass)
-    static const int direct = getenv("RU3D_WGRAD_DIRECT") ? atoi(getenv("RU3D_WGRAD_DIRECT")) : 1;
+    static const int direct = ru3d_env_int("RU3D_WGRAD_DIRECT", 1);
     if (direct && pairs >= 224 && ntiles <= 8) G = 1;
     return (int)G;
 }
@@ -2845,7 +2712,7 @@ int wgrad_mfma_launch(const void* x, const void* dy, float* dw, void* ws, size_t
         hipLaunchKernelGGL((wgrad3_s1_mfma_kernel<2, 8, 16>), grid, dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL((wgrad3_s1_mfma_kernel<4, 8, 8>), grid, dim3(256), 0, st, a);
-    int rc = ru3d_check_launch("wgrad3_s1_mfma");
+    int rc = ru3d_check_launch(tw == 32 ? "wgrad3_s1_mfma<2,4,32>" : tw == 16 ? "wgrad3_s1_mfma<2,8,16>" : "wgrad3_s1_mfma<4,8,8>");
     if (rc || a.dw) return rc;
     return wgrad_reduce_launch((const float*)ws, dw, a.G, 27, g.Cin, g.Cout, g.s_o, g.s_i, st);
 }

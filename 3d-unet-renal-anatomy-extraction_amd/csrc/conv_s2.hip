@@ -745,7 +745,7 @@ __global__ __launch_bounds__(320) void conv3_s2_tile_kernel(S2Args a) {
 // --------------------------------------------------------------------------------------------------- host: T form
 // Work decomposition: units = N x dsplit x ceil(Hi / 4) x ceil(Wi / TW) columns of DL input planes each.
 static bool t_plan(int N, int Di, int Hi, int Wi, int Cin, int Cout, int* tw_out, SlidePlan* out) {
-    static const int mode = getenv("RU3D_CONV_S2") ? atoi(getenv("RU3D_CONV_S2")) : 1;
+    static const int mode = ru3d_env_int("RU3D_CONV_S2", 1);
     if (!mode || Cin != 64 || (Cout % 32) || Cout > 64 || Di < 2) return false;
     const int ny = Cout / 32;
     int64_t best_cost = -1;
@@ -866,7 +866,7 @@ int convt_s2_tile_launch(const void* x, const void* w, const float* bias, const 
     a.ldx = g.ldx; a.ldy = g.ldy; a.ldr = res ? g.ldr : g.ldy; a.ldx2 = x2 ? ldx2 : g.ldx; a.ldy2 = 0;
     a.flip = g.flip; a.zero_far = g.zero_far; a.cout_total = g.Cout;
     a.tiles_h = p.tiles_h; a.tiles_w = p.tiles_w; a.dsplit = p.dsplit; a.DL = p.DL; a.units = p.units;
-    static const int dbg = getenv("RU3D_S2_DBG") ? atoi(getenv("RU3D_S2_DBG")) : 0;
+    static const int dbg = ru3d_env_int("RU3D_S2_DBG", 0);
     a.dbg = dbg;
     (void)tw;
     return t_launch<64, 16>(a, p, res != nullptr, stat_slab != nullptr, x2 != nullptr, st);
@@ -874,7 +874,7 @@ int convt_s2_tile_launch(const void* x, const void* w, const float* bias, const 
 
 // --------------------------------------------------------------------------------------------------- host: G form
 static bool g_plan(int N, int Do, int Ho, int Wo, int Cin, int Cout, SlidePlan* out) {
-    static const int mode = getenv("RU3D_CONV_S2") ? atoi(getenv("RU3D_CONV_S2")) : 1;
+    static const int mode = ru3d_env_int("RU3D_CONV_S2", 1);
     if (!mode || Cin != 32 || (Cout % 64) || Cout > 128 || Do < 2) return false;
     const int ny = Cout / 64;
     const int64_t cols = (int64_t)N * ((Ho + TH - 1) / TH) * ((Wo + GW - 1) / GW);
@@ -948,7 +948,7 @@ int conv_s2_tile_launch(const void* x, const void* w, const float* bias, void* y
     a.ldx = g.ldx; a.ldy = g.ldy; a.ldr = g.ldy; a.ldx2 = g.ldx; a.ldy2 = y2 ? ldy2 : g.ldy;
     a.flip = g.flip; a.zero_far = 0; a.cout_total = g.Cout;
     a.tiles_h = p.tiles_h; a.tiles_w = p.tiles_w; a.dsplit = p.dsplit; a.DL = p.DL; a.units = p.units;
-    static const int dbg = getenv("RU3D_S2_DBG") ? atoi(getenv("RU3D_S2_DBG")) : 0;
+    static const int dbg = ru3d_env_int("RU3D_S2_DBG", 0);
     a.dbg = dbg;
     const dim3 grid(p.grid, p.ny), block(320);
     const size_t lds = (size_t)GGeom<32>::RING * GGeom<32>::PLANE_B;

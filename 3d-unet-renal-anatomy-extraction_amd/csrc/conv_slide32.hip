@@ -466,8 +466,7 @@ extern "C" void ru3d_debug_slide_stamps(long long* dev_buf) { g_slide_stamps = d
 // times Cout/32 output-channel slices (grid.y).  dsplit is the divisor of D (DL a multiple of 4) with the shortest
 // makespan on 256 CUs.
 bool slide_conv_plan(int N, int D, int H, int W, int Cin, int Cout, SlidePlan* out) {
-    static const int mode = getenv("RU3D_CONV_SLIDE") ? atoi(getenv("RU3D_CONV_SLIDE")) : 1;
-    if (mode == 0 || Cin != 32 || (Cout != 32 && Cout != 64) || (H % TH) || (W % 16) || D < 4) return false;
+    if (Cin != 32 || (Cout != 32 && Cout != 64) || (H % TH) || (W % 16) || D < 4) return false;
     // the staging loads address a sample with 30-bit element offsets; the input may sit in a buffer of twice its channels
     // (the decoder's concat): shapes that could exceed that go to the other kernels consistently (launch, slab, workspace)
     if ((int64_t)D * H * W * Cin * 2 >= (1ll << 30)) return false;
@@ -508,11 +507,8 @@ bool slide_conv_plan(int N, int D, int H, int W, int Cin, int Cout, SlidePlan* o
 }
 
 int conv_slide_launch(const void* x, const void* w, const float* bias, const void* res, void* y, const ConvGeom& g,
-                      float* stat_slab, hipStream_t st, const void* bst_act, int bst_ld, float slope, const void* x2,
-                      int ldx2, const void* w2) {
-    SlidePlan p;
-    if (!slide_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &p))
-        return ru3d_fail(-1, "conv_slide: shape not supported");
+                      const SlidePlan& p, float* stat_slab, hipStream_t st, const void* bst_act, int bst_ld, float slope,
+                      const void* x2, int ldx2, const void* w2) {
     // the staging loads address a sample through a buffer descriptor with 32-bit byte offsets, the top bit marking
     // "outside the volume"
     if ((int64_t)g.Do * g.Ho * g.Wo * g.ldx >= (1ll << 30)) return ru3d_fail(-1, "conv_slide: sample too large");
@@ -557,6 +553,7 @@ int conv_slide_launch(const void* x, const void* w, const float* bias, const voi
     } else if (res) hipLaunchKernelGGL((conv3_s1_slide32_kernel<true, false>), grid, block, 0, st, a);
     else if (stat_slab) hipLaunchKernelGGL((conv3_s1_slide32_kernel<false, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((conv3_s1_slide32_kernel<false, false>), grid, block, 0, st, a);
-    return ru3d_check_launch("conv3_s1_slide32");
+    return ru3d_check_launch(x2 ? "conv3_s1_slide32<partner>" : bst_act ? "conv3_s1_slide32<bst>" : res ? "conv3_s1_slide32<res>"
+                             : stat_slab ? "conv3_s1_slide32<stats>" : "conv3_s1_slide32");
 }
 }  // namespace RU3D_NS

@@ -413,11 +413,9 @@ __global__ __launch_bounds__(256, 1) void conv3_s1_slide64_kernel(Slide64Args a)
 }  // namespace
 
 // units = N x dsplit x (H/4) x (W/32) columns of DL = D/dsplit planes, times Cout/64 output slices (grid.y)
-bool slide64_conv_plan(int N, int D, int H, int W, int Cin, int Cout, SlidePlan* out) {
-    static const int mode = getenv("RU3D_CONV_SLIDE64") ? atoi(getenv("RU3D_CONV_SLIDE64")) : 1;
-    if (mode == 0 || Cin != 64 || (Cout != 32 && Cout != 64 && Cout != 128) || (H % TH) || W < 8 || D < 4) return false;
-    static const int edge_mode = getenv("RU3D_SLIDE64_EDGE") ? atoi(getenv("RU3D_SLIDE64_EDGE")) : 1;
-    if ((W % TW) && (!edge_mode || (W % TW) <= 4)) return false;   // a sliver of a last column is not worth a column's work
+bool slide64_conv_plan(int N, int D, int H, int W, int Cin, int Cout, bool edge, SlidePlan* out) {
+    if (Cin != 64 || (Cout != 32 && Cout != 64 && Cout != 128) || (H % TH) || W < 8 || D < 4) return false;
+    if ((W % TW) && (!edge || (W % TW) <= 4)) return false;   // a sliver of a last column is not worth a column's work
     // the staging loads address a sample with 30-bit element offsets; the input may sit in a buffer of twice its channels
     // (the decoder's concat): shapes that could exceed that go to the other kernels consistently (launch, slab, workspace)
     if ((int64_t)D * H * W * Cin * 2 >= (1ll << 30)) return false;
@@ -465,13 +463,9 @@ bool slide64_conv_plan(int N, int D, int H, int W, int Cin, int Cout, SlidePlan*
 }
 
 int conv_slide64_launch(const void* x, const void* w, const float* bias, const void* res, void* y, const ConvGeom& g,
-                        float* stat_slab, hipStream_t st, const void* bst_act, int bst_ld, float slope) {
-    SlidePlan p;
-    if (!slide64_conv_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &p))
-        return ru3d_fail(-1, "conv_slide64: shape not supported");
+                        const SlidePlan& p, float* stat_slab, hipStream_t st) {
     if ((int64_t)g.Do * g.Ho * g.Wo * g.ldx >= (1ll << 30)) return ru3d_fail(-1, "conv_slide64: sample too large");
     if (res && stat_slab) return ru3d_fail(-1, "conv_slide64: residual and fused statistics cannot be combined");
-    if (bst_act) return ru3d_fail(-1, "conv_slide64: no fused backward sums on the 64-channel kernel");
     Slide64Args a;
     a.x = (const bf16*)x;
     a.w = (const bf16x8*)w;
@@ -494,7 +488,6 @@ int conv_slide64_launch(const void* x, const void* w, const float* bias, const v
     a.flip = g.flip;
     a.cout_total = g.Cout;
     a.tiles_h = p.tiles_h; a.tiles_w = p.tiles_w; a.dsplit = p.dsplit; a.DL = p.DL; a.units = p.units;
-    (void)bst_ld; (void)slope;
     a.light_last = (g.Wo % TW) != 0 && (g.Wo % TW) <= 16 && p.tiles_w > 1;
     const dim3 grid(p.grid, p.ny), block(256);
 #define RU3D_S64_LAUNCH(VGV, EDGEV)                                                                                      \
@@ -512,7 +505,11 @@ int conv_slide64_launch(const void* x, const void* w, const float* bias, const v
         else RU3D_S64_LAUNCH(1, false);
     }
 #undef RU3D_S64_LAUNCH
-    return ru3d_check_launch("conv3_s1_slide64");
+    // <VG, epilogue, edge>: the template arguments of the instantiation that ran
+    char name[48];
+    snprintf(name, sizeof(name), "conv3_s1_slide64<%d%s%s>", g.Cout == 32 ? 2 : 1, res ? ",res" : stat_slab ? ",stats" : "",
+             edge ? ",edge" : "");
+    return ru3d_check_launch(name);
 }
 
 }  // namespace RU3D_NS

@@ -215,8 +215,7 @@ __global__ __launch_bounds__(256, 1) void conv3_s1_ws_kernel(WsArgs a) {
 }  // namespace
 
 // slices (split-K factor) of the whole-sample kernel for this geometry, 0 = not this kernel's shape
-int conv_ws_slices(int N, int D, int H, int W, int Cin, int Cout) {
-    static const int mode = getenv("RU3D_CONV_WS") ? atoi(getenv("RU3D_CONV_WS")) : 1;
+int conv_ws_slices(int N, int D, int H, int W, int Cin, int Cout, int mode) {
     if (!mode || (Cin % 32) || (Cout % 32)) return 0;
     const int64_t V = (int64_t)D * H * W, PV = (int64_t)(D + 2) * (H + 2) * (W + 2);
     if (V > WS_MAXT * 64 || PV > WS_ROWS || V < 64) return 0;
@@ -249,7 +248,7 @@ int conv_ws_launch(const void* x, const void* w, float* part, int N, int D, int 
     a.mWP = magic(W + 2); a.mPP = magic((H + 2) * (W + 2)); a.mW = magic(W); a.mHW = magic(H * W);
     if ((int64_t)D * H * W * ldx * 2 >= (1ll << 31)) return ru3d_fail(-1, "conv_ws: sample too large");
     hipLaunchKernelGGL(conv3_s1_ws_kernel, dim3(Cout / 32, slices, N), dim3(256), 0, st, a);
-    return ru3d_check_launch("conv3_s1_ws");
+    return ru3d_check_launch("conv_ws");
 }
 
 }  // namespace RU3D_NS

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256) void skip1x1_in_lrelu_fwd_kernel(SkipArgs a) {
 }  // namespace
 
 bool skip1x1_fused_eligible(const ru3d_tensor* x, const ru3d_tensor* y2, const ru3d_tensor* out, int dtype) {
-    static const int mode = getenv("RU3D_FUSED_SKIP") ? atoi(getenv("RU3D_FUSED_SKIP")) : 1;
+    static const int mode = ru3d_env_int("RU3D_FUSED_SKIP", 1);
     if (!mode || dtype != RU3D_BF16) return false;
     if (!tensor_ok_split(x) || !tensor_ok(y2) || !tensor_ok(out)) return false;
     if (x->cseg && (x->cseg % 32)) return false;

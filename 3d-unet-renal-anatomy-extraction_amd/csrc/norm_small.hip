@@ -517,7 +517,7 @@ void two_geom(const ru3d_tensor* y, int* PL, int* S, dim3* grid) {
 // (the skip conv's bias gradient) is wanted from the same call.
 int in_small_mode(const ru3d_tensor* y, bool all_samples, const ru3d_tensor* a, const ru3d_tensor* b, const ru3d_tensor* c,
                   const ru3d_tensor* d) {
-    static const int mode = getenv("RU3D_IN_SMALL") ? atoi(getenv("RU3D_IN_SMALL")) : 1;
+    static const int mode = ru3d_env_int("RU3D_IN_SMALL", 1);
     if (!mode || !y) return 0;
     const int64_t V = (int64_t)y->d * y->h * y->w;
     if (V > 8192 || (y->c % 8) != 0) return 0;

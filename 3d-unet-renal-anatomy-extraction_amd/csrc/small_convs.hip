@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void stem_fwd_mfma_kernel(const bf16* __restri
 }
 
 static bool stem_fwd_mfma_ok(const ConvGeom& g, int dtype) {
-    static const int mode = getenv("RU3D_STEM_MFMA") ? atoi(getenv("RU3D_STEM_MFMA")) : 1;
+    static const int mode = ru3d_env_int("RU3D_STEM_MFMA", 1);
     return mode && dtype == RU3D_BF16 && (g.Cout % 32) == 0 && g.Do == g.Di && g.Ho == g.Hi && g.Wo == g.Wi &&
            g.pad == 1 && (g.ldy % 8) == 0;
 }
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_mfma_kernel(const bf16* __rest
 }
 
 static bool stem_wgrad_mfma_ok(const WgradGeom& g, int dtype) {
-    static const int mode = getenv("RU3D_STEM_MFMA") ? atoi(getenv("RU3D_STEM_MFMA")) : 1;
+    static const int mode = ru3d_env_int("RU3D_STEM_MFMA", 1);
     return mode && dtype == RU3D_BF16 && g.Do == g.Di && g.Ho == g.Hi && g.Wo == g.Wi && g.pad == 1;
 }
 
@@ -754,7 +754,7 @@ static int head_bwd_blocks(int64_t P, int Cin) {
 }
 
 bool head_bwd_eligible(int Cin, int Cout, int dtype) {
-    static const int mode = getenv("RU3D_HEAD_FUSED") ? atoi(getenv("RU3D_HEAD_FUSED")) : 1;
+    static const int mode = ru3d_env_int("RU3D_HEAD_FUSED", 1);
     const int G = Cin / 8;
     return mode && dtype == RU3D_BF16 && Cout >= 1 && Cout <= 4 && (Cin % 8) == 0 && G >= 1 && G <= 64 && (G & (G - 1)) == 0;
 }

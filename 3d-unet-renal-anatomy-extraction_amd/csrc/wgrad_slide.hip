@@ -316,13 +316,13 @@ __global__ __launch_bounds__(256, 1) void wgrad3_s1_slide_kernel(WSlideArgs a) {
 
 // units per pair = N x dsplit x (H/8) x (W/32); G persistent workgroups per pair (= slabs), pairs on grid.y.
 bool wgrad_slide_plan(const WgradGeom& g, WgradSlidePlan* out) {
-    static const int mode = getenv("RU3D_WGRAD_SLIDE") ? atoi(getenv("RU3D_WGRAD_SLIDE")) : 1;
+    static const int mode = ru3d_env_int("RU3D_WGRAD_SLIDE", 1);
     if (!mode || g.k != 3 || g.stride != 1 || (g.Cin % 32) || (g.Cout % 32) || (g.Ho % TH) || (g.Wo % 8) || g.Wo < 16) return false;   // dy positions beyond W are masked one by one
     if (g.Do != g.Di || g.Ho != g.Hi || g.Wo != g.Wi || (g.ldx % 8) || (g.lddy % 8)) return false;
     // buffer-descriptor byte offsets of a sample, the top bit marking "outside the volume"
     if ((int64_t)g.Do * g.Ho * g.Wo * (g.ldx > g.lddy ? g.ldx : g.lddy) >= (1ll << 30)) return false;
     const int pairs = (g.Cin / 32) * (g.Cout / 32);
-    static const int max_pairs = getenv("RU3D_WGRAD_SLIDE_PAIRS") ? atoi(getenv("RU3D_WGRAD_SLIDE_PAIRS")) : 32;
+    static const int max_pairs = ru3d_env_int("RU3D_WGRAD_SLIDE_PAIRS", 32);
     if (pairs > max_pairs) return false;      // up to 256 -> 128 channels (round 3: 8 -> 16 pairs, 89 -> 62 us at 32^3)
     const int tw_n = (g.Wo + TW - 1) / TW;
     const bool light = (g.Wo % TW) != 0 && (g.Wo % TW) <= 16 && tw_n > 1;
