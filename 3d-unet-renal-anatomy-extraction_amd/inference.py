@@ -28,7 +28,10 @@ Beyond the reference (keyword-only options of `predict_per_patch`; at their defa
     lexicographic, the empty set first), the input mirrored on the way into the model and the probabilities
     mirrored back on the way into `acc`, both by index arithmetic inside `ru3d_predict_gather` /
     `ru3d_predict_accumulate_weighted` - no flipped copies of inputs or logits exist;
-  * `model` may be a list: all members add into the same `acc` / `cnt`.
+  * `model` may be a list: all members add into the same `acc` / `cnt`;
+  * `groups`: the channels are overlapping label groups (loss.GroupHybirdLoss) - every window goes through
+    `ru3d_predict_accumulate_groups` (an independent sigmoid per channel, on the reference route and on the blended one)
+    and the label map is decoded by `ru3d_predict_merge_groups` (the last group above its threshold wins, 0 otherwise).
 Summation order (fixed): models in list order, outermost; inside a model the windows in loop order (x outer, z inner);
 inside a window the mirror subsets in `mirror_subsets` order.  Every term is one accumulate launch on one stream and a
 launch owns each voxel of its window once, so there are no atomics and no races; `patch_batch` only decides how many
@@ -213,9 +216,26 @@ def resolve_options(model, placement='reference', weighting='uniform', mirror_ax
     return models, given
 
 
-def _blend_windows(vol, models, num_classes, patch_size, origins, flips, tables, acc, cnt, patch_batch, bar):
+def _group_decode(groups, group_labels, threshold, num_classes, who):
+    """None without groups; otherwise the checked (K label values, K thresholds) of a driver's group arguments."""
+    if groups is None:
+        if group_labels is not None:
+            raise ValueError("%s: group_labels without groups" % who)
+        return None
+    import transform
+    decode = transform._checked_decode(groups, group_labels, threshold)
+    if int(num_classes) != len(decode[0]):
+        raise ValueError("%s: num_classes is %d but there are %d groups" % (who, num_classes, len(decode[0])))
+    return decode
+
+
+def _blend_windows(vol, models, num_classes, patch_size, origins, flips, tables, acc, cnt, patch_batch, bar,
+                   groups=False):
     """The mirrored / weighted / ensemble window loop.  vol: dense fp32 [X, Y, Z, Cin] on the device.  Terms are
-    issued in the fixed order (model, window, mirror subset); `patch_batch` consecutive terms share one forward."""
+    issued in the fixed order (model, window, mirror subset); `patch_batch` consecutive terms share one forward.
+    groups: the channels are label groups - an independent sigmoid each instead of the softmax."""
+    accumulate, what = (N.lib.ru3d_predict_accumulate_groups, "predict_accumulate_groups") if groups else \
+        (N.lib.ru3d_predict_accumulate_weighted, "predict_accumulate_weighted")
     device = vol.device
     X, Y, Z, cin = (int(v) for v in vol.shape)
     px, py, pz = patch_size
@@ -239,15 +259,15 @@ def _blend_windows(vol, models, num_classes, patch_size, origins, flips, tables,
             logits = N.to_ndhwc(logits)
             d = N.desc(logits)
             for i, ((ox, oy, oz), f) in enumerate(group):
-                check(N.lib.ru3d_predict_accumulate_weighted(ctypes.byref(d), N.dtype_code(logits.dtype), i, f, gx, gy,
-                                                             gz, ptr(acc), ptr(cnt), X, Y, Z, ox, oy, oz, stream()),
-                      "predict_accumulate_weighted")
+                check(accumulate(ctypes.byref(d), N.dtype_code(logits.dtype), i, f, gx, gy, gz, ptr(acc), ptr(cnt), X, Y,
+                                 Z, ox, oy, oz, stream()), what)
             if bar is not None:
                 bar.update(len(group))
 
 
 def predict_per_patch(input, model, num_classes=3, patch_size=(96, 96, 96), step_per_patch=4, verbose=True,
                       one_hot=False, patch_batch=1, return_device=False, *,
+                      groups=None, group_labels=None, threshold=0.5,
                       placement='reference', weighting='uniform', mirror_axes=(), sigma_scale=0.125):
     """input: numpy (or torch, host or device) [X, Y, Z, C_in] (the reference's W,H,D,C case layout).  Returns the
     uint8 mask [X, Y, Z] (or the float32 [X, Y, Z, num_classes] probability map when one_hot) at the input's own shape,
@@ -258,7 +278,14 @@ def predict_per_patch(input, model, num_classes=3, patch_size=(96, 96, 96), step
     differ).  placement: 'reference' (the reference's windows and crop, uncovered NaN border included) or 'cover'
     (every voxel inside a window, result on the input's own grid).  weighting: 'uniform' or 'gaussian' (centre-weighted,
     width sigma_scale * patch per axis).  mirror_axes: subset of (0, 1, 2); every window is also predicted mirrored
-    along every non-empty subset of these axes.  The module docstring has the rules and the summation order."""
+    along every non-empty subset of these axes.  The module docstring has the rules and the summation order.
+
+    groups: the model was trained with the group losses (loss.GroupHybirdLoss): num_classes must equal len(groups), every
+    channel goes through a sigmoid of its own (`ru3d_predict_accumulate_groups`, on both routes), one_hot returns the mean
+    sigmoid probabilities [X, Y, Z, K], and the label map is decoded by `ru3d_predict_merge_groups`: channel k is on iff its
+    mean probability is > threshold (a number or one per group), the voxel gets group_labels[k] (default
+    transform.default_group_labels(groups)) of the last channel that is on, 0 when none is or no window reached it."""
+    decode = _group_decode(groups, group_labels, threshold, num_classes, "predict_per_patch")
     models, opt = resolve_options(model, placement, weighting, mirror_axes, sigma_scale)
     placement, weighting, mirror_axes, sigma_scale = (opt[k] for k in ('placement', 'weighting', 'mirror_axes',
                                                                         'sigma_scale'))
@@ -315,7 +342,8 @@ def predict_per_patch(input, model, num_classes=3, patch_size=(96, 96, 96), step
             tables = None
             if weighting == 'gaussian':
                 tables = [torch.from_numpy(gaussian_profile(p, sigma_scale)).to(device) for p in patch_size]
-            _blend_windows(dense, models, num_classes, patch_size, origins, flips, tables, acc, cnt, patch_batch, bar)
+            _blend_windows(dense, models, num_classes, patch_size, origins, flips, tables, acc, cnt, patch_batch, bar,
+                           groups=decode is not None)
         for b0 in (() if blended else range(0, len(origins), patch_batch)):
             group = origins[b0:b0 + patch_batch]
             x = N.new_act(len(group), cin, px, py, pz, torch.float32, device)
@@ -328,6 +356,11 @@ def predict_per_patch(input, model, num_classes=3, patch_size=(96, 96, 96), step
             logits = N.to_ndhwc(logits)
             d = N.desc(logits)
             for i, (ox, oy, oz) in enumerate(group):
+                if decode is not None:
+                    check(N.lib.ru3d_predict_accumulate_groups(ctypes.byref(d), N.dtype_code(logits.dtype), i, 0, None,
+                                                               None, None, ptr(acc), ptr(cnt), full[0], full[1], full[2],
+                                                               ox, oy, oz, stream()), "predict_accumulate_groups")
+                    continue
                 check(N.lib.ru3d_predict_accumulate(ctypes.byref(d), N.dtype_code(logits.dtype), i, ptr(acc),
                                                     ptr(cnt), full[0], full[1], full[2], ox, oy, oz, stream()),
                       "predict_accumulate")
@@ -343,6 +376,13 @@ def predict_per_patch(input, model, num_classes=3, patch_size=(96, 96, 96), step
     else:
         out = torch.empty(original_shape, dtype=torch.uint8, device=device)
     N.note_device(acc.device)
+    if decode is not None and not one_hot:
+        labels, thr = decode
+        check(N.lib.ru3d_predict_merge_groups(ptr(acc), ptr(cnt), full[0], full[1], full[2], num_classes,
+                                              (ctypes.c_int32 * num_classes)(*labels),
+                                              (ctypes.c_float * num_classes)(*[float(t) for t in thr]), co[0], co[1],
+                                              co[2], sx, sy, sz, ptr(out), stream()), "predict_merge_groups")
+        return out if return_device else out.cpu().numpy()
     check(N.lib.ru3d_predict_merge(ptr(acc), ptr(cnt), full[0], full[1], full[2], num_classes, co[0], co[1], co[2],
                                    sx, sy, sz, 1 if one_hot else 0, ptr(out), stream()), "predict_merge")
     return out if return_device else out.cpu().numpy()
@@ -367,14 +407,17 @@ def resample_normalize_image(vol, out_shape, stats):
 
 def predict_case(case, model, target_spacing, normalize_stats, num_classes=3, patch_size=(96, 96, 96),
                  step_per_patch=4, verbose=True, one_hot=False, patch_batch=1, return_device=False, *,
+                 groups=None, group_labels=None, threshold=0.5,
                  placement='reference', weighting='uniform', mirror_axes=(), sigma_scale=0.125):
     """reference trainer.py:101-133: resample the case to `target_spacing` and normalise it (data.py:222-283), run the
     sliding-window prediction, resize the prediction back to the case's shape.  Everything between the upload of the
     image and the download of the prediction runs on the device: the two resamplings are the order-1 zoom kernel of
     the augmentation path (label rule included), the sliding window is predict_per_patch.  `case['image']` may already
     be a HIP tensor (no upload), and `return_device` leaves `case['pred']` in HBM (no download): the cascade chains its
-    stages that way.  `model` may be a list; placement / weighting / mirror_axes / sigma_scale go to predict_per_patch."""
+    stages that way.  `model` may be a list; placement / weighting / mirror_axes / sigma_scale and groups / group_labels
+    / threshold go to predict_per_patch."""
     import augment
+    _group_decode(groups, group_labels, threshold, num_classes, "predict_case")
     models, opt = resolve_options(model, placement, weighting, mirror_axes, sigma_scale, "predict_case")
     device = next(models[0].parameters()).device
     image = case['image'] if torch.is_tensor(case['image']) else np.asarray(case['image'])
@@ -395,7 +438,8 @@ def predict_case(case, model, target_spacing, normalize_stats, num_classes=3, pa
     if verbose:
         print('Predicting the case...')
     pred = predict_per_patch(vol, models, num_classes, patch_size, step_per_patch, verbose, one_hot,
-                             patch_batch=patch_batch, return_device=True, **opt)
+                             patch_batch=patch_batch, return_device=True, groups=groups, group_labels=group_labels,
+                             threshold=threshold, **opt)
     if verbose:
         print('Resizing the case to origial shape...')
     if one_hot:

@@ -21,6 +21,9 @@ counts them into its state block, those 4 bytes ride to pinned host memory behin
 the loss scalars - raises as soon as that copy has landed (the loss value of such a step is NaN).
 `check_labels=True` / RU3D_CHECK_LABELS=1 checks before the launch instead (one sync per call).  With
 C == 1 the reference only works for all-zero targets and so does this.
+
+Beyond the reference: nested or overlapping structures train one sigmoid channel per group of label values with
+`GroupHybirdLoss` / `GroupDiceLoss` / `GroupFocalLoss` / `GroupDice` (the section "overlapping label groups" below).
 """
 import collections
 import os
@@ -145,9 +148,10 @@ def _flat_strides(x):
     return x.stride(0), x.stride(1), sv
 
 
-def _loss_operands(input, target, check_labels):
+def _loss_operands(input, target, check_labels, one_hot=True):
     """What every fused loss does to its operands before it launches: float32 logits with a single spatial stride,
-    contiguous int64 / uint8 labels, and the blocking label check where one is asked for."""
+    contiguous int64 / uint8 labels, and the blocking label check where one is asked for.  one_hot=False (the group
+    losses): the labels are no class indices of the C channels, so neither that check nor the C == 1 rule applies."""
     N.require_device(input, "loss input")
     if target.device != input.device:
         raise N.Ru3dError("loss: target is on %s but input on %s" % (target.device, input.device))
@@ -175,7 +179,7 @@ def _loss_operands(input, target, check_labels):
         lab, lab_code = target.contiguous(), N.LABEL_U8
     else:
         lab, lab_code = target.long().contiguous(), N.LABEL_I64
-    if check_labels or c == 1:
+    if one_hot and (check_labels or c == 1):
         # reference: F.one_hot(target, C) raises for labels >= C (always hit by C == 1 with labels {0,1})
         if lab.numel() and (int(lab.max()) >= c or int(lab.min()) < 0):
             raise RuntimeError(_BAD_LABELS)
@@ -1099,3 +1103,226 @@ class DeepSupervisionLoss(_FusedLoss):
         self._last = (block, levels)
         hyper = (self._kind, self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)
         return _DeepSupFn.apply(target, hyper, block, getattr(self, "check_labels", _CHECK_LABELS), *outputs)
+
+
+# --------------------------------------------------------------------------- overlapping label groups
+# One sigmoid channel per GROUP of label values (the KiTS / BraTS recipe of nnU-Net).  groups = ((1, 2), (2,)) reads
+# "whole kidney, tumour": a voxel labelled 2 is a target of both channels.  member[t] has bit k set iff label value t is in
+# group k; the kernels read the target of channel k as that bit of member[label], so no multi-hot tensor exists.  Over the
+# counted voxels (those not carrying ignore_label; M of them, max(M, 1) where it divides), p = sigmoid(z_k), g the target:
+#   dice_k  = (tp + s) / (tp + alpha (sg - tp) + beta (sp - tp) + s),  tp = sum p g, sp = sum p, sg = sum g
+#   focal_k = (1 / M) sum [ (1-p)^gamma g softplus(-z) + p^gamma (1-g) softplus(z) ]          (gamma 0: binary CE)
+#   w = weight_v / sum|weight_v|;  GroupHybirdLoss = sum_k w_k (1 - dice_k + focal_k), GroupDiceLoss = sum w (1 - dice),
+#   GroupFocalLoss = sum w focal, GroupDice = sum w dice.
+MAX_GROUPS = N.MAX_CLASSES
+MAX_GROUP_LABELS = 32
+
+
+def _checked_groups(groups, num_labels=None):
+    """(tuple of K tuples of ints, T) of a `groups` argument, or ValueError."""
+    try:
+        gs = tuple(tuple(int(t) for t in g) for g in groups)
+    except TypeError:
+        raise ValueError("groups must be a sequence of sequences of label values, got %r" % (groups,))
+    if not 1 <= len(gs) <= MAX_GROUPS:
+        raise ValueError("groups: %d groups (1 .. %d)" % (len(gs), MAX_GROUPS))
+    for k, g in enumerate(gs):
+        if not g:
+            raise ValueError("groups: group %d is empty" % k)
+        if len(set(g)) != len(g):
+            raise ValueError("groups: group %d repeats a label value: %s" % (k, g))
+        if min(g) < 0:
+            raise ValueError("groups: group %d holds a negative label value: %s" % (k, g))
+    if len(set(frozenset(g) for g in gs)) != len(gs):
+        raise ValueError("groups: two groups are equal as sets: %s" % (gs,))
+    top = max(max(g) for g in gs)
+    t = top + 1 if num_labels is None else int(num_labels)
+    if t > MAX_GROUP_LABELS or t < 1:
+        raise ValueError("groups: %d label values (1 .. %d)" % (t, MAX_GROUP_LABELS))
+    if top >= t:
+        raise ValueError("groups: label value %d lies outside [0, %d)" % (top, t))
+    return gs, t
+
+
+def group_table(groups, num_labels=None):
+    """The membership table of `groups`: T = num_labels (default 1 + the largest value) bytes, bit k of byte t set iff
+    label value t is in group k.  Checks the groups (1 .. 8 of them, values in [0, T), T <= 32, no empty group, no
+    repeated value, no two groups equal as sets) with ValueError."""
+    gs, t = _checked_groups(groups, num_labels)
+    table = bytearray(t)
+    for k, g in enumerate(gs):
+        for v in g:
+            table[v] |= 1 << k
+    return bytes(table)
+
+
+def _checked_ignore(ignore_label, t):
+    if ignore_label is None:
+        return None
+    ig = int(ignore_label)
+    if 0 <= ig < t:
+        raise ValueError("ignore_label %d lies inside the label range [0, %d)" % (ig, t))
+    return ig
+
+
+def _group_loss_host(kind, input, target, table, ignore, gamma, weight_v, alpha, beta, smooth):
+    """The definitions above on host tensors with torch ops, differentiable, in the logits' dtype: the twin the kernels
+    are held to."""
+    n, k = input.shape[0], input.shape[1]
+    if tuple(target.shape) != (n,) + tuple(input.shape[2:]):
+        raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape), tuple(input.shape)))
+    z = input.reshape(n, k, -1)
+    t = target.long().reshape(n, 1, -1)
+    counted = torch.ones_like(t, dtype=torch.bool) if ignore is None else t != ignore
+    if t.numel() and bool((((t < 0) | (t >= len(table))) & counted).any()):
+        raise RuntimeError(_BAD_LABELS)
+    member = torch.tensor(list(table), dtype=torch.int64)
+    bits = member[t.clamp(0, len(table) - 1)]
+    g = ((bits >> torch.arange(k).view(1, k, 1)) & 1).to(z.dtype)
+    c = counted.to(z.dtype)
+    g = g * c
+    p = torch.sigmoid(z)
+    w = torch.tensor([1.0] * k if weight_v is None else [float(a) for a in weight_v], dtype=z.dtype)
+    w = w / w.abs().sum().clamp_min(1e-12)
+    term = torch.zeros(k, dtype=z.dtype)
+    if kind != N.LOSS_FOCAL:
+        tp, sp, sg = (p * g).sum((0, 2)), (p * c).sum((0, 2)), g.sum((0, 2))
+        d = (tp + smooth) / (tp + alpha * (sg - tp) + beta * (sp - tp) + smooth)
+        term = term + (d if kind == N.LOSS_DICE else 1.0 - d)
+    if kind in (N.LOSS_HYBIRD, N.LOSS_FOCAL):
+        pos, neg = F.softplus(-z), F.softplus(z)          # -log p, -log(1 - p), from the logit
+        if gamma != 0:
+            pos, neg = (1.0 - p) ** gamma * pos, p ** gamma * neg
+        m = c.sum().clamp_min(1.0)
+        term = term + ((g * pos + (c - g) * neg).sum((0, 2))) / m
+    return (w * term).sum()
+
+
+class _GroupLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, input, target, kind, table, ignore, gamma, weight_v, alpha, beta, smooth, check_labels):
+        k, t = input.shape[1], len(table)
+        N.require_device(input, "loss input")
+        if check_labels and target.numel():
+            lab = target if ignore is None else target[target != ignore]
+            if lab.numel() and (int(lab.max()) >= t or int(lab.min()) < 0):
+                raise RuntimeError(_BAD_LABELS)
+        x, st, lab, lab_code, n, _, v = _loss_operands(input, target, False, one_hot=False)
+        raise_on_bad_labels()          # an earlier call's verdict, if it has landed (no wait)
+        dev = x.device
+        state = torch.empty(N.lib.ru3d_group_loss_state_bytes(), dtype=torch.uint8, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        ws = N.workspace(N.lib.ru3d_group_loss_workspace_bytes(n, v, k), dev)
+        wv = _weight_array(weight_v, k)
+        group = (table, t, 0 if ignore is None else 1, 0 if ignore is None else ignore)
+        check(N.lib.ru3d_group_loss_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, k, *group, kind,
+                                        float(gamma), N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None,
+                                        float(alpha), float(beta), float(smooth), ptr(state), ptr(out), ptr(ws),
+                                        ws.numel(), stream()), "group_loss_fwd")
+        if not check_labels:
+            _note_label_flag(state)
+        ctx.save_for_backward(x, lab, state)
+        ctx.meta = (st, lab_code, n, v, k, group, float(gamma), input.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, lab, state = ctx.saved_tensors
+        st, lab_code, n, v, k, group, gamma, in_dtype = ctx.meta
+        g = gout.detach()
+        if g.dtype != torch.float32 or g.device != x.device:
+            g = g.to(device=x.device, dtype=torch.float32)
+        g = g.reshape(1).contiguous()
+        N.note_device(x.device)
+        dz = torch.empty_like(x)   # preserve_format: same (dense) strides as the logits
+        if dz.stride() != x.stride():
+            dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
+        check(N.lib.ru3d_group_loss_bwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, k, *group, gamma,
+                                        ptr(state), ptr(g), ptr(dz), N.F32, stream()), "group_loss_bwd")
+        if in_dtype != torch.float32:
+            dz = dz.to(in_dtype)
+        return (dz,) + (None,) * 10
+
+
+class _GroupLoss(_FusedLoss):
+    """What the four group losses share: the checked groups, their table, and the route by the logits' device."""
+
+    def _init_groups(self, groups, num_labels, ignore_label, weight_v):
+        self.groups, self.num_labels = _checked_groups(groups, num_labels)
+        self._table = group_table(self.groups, self.num_labels)
+        self.ignore_label = _checked_ignore(ignore_label, self.num_labels)
+        if weight_v is not None and len(weight_v) != len(self.groups):
+            raise ValueError("weight_v has %d entries for %d groups" % (len(weight_v), len(self.groups)))
+        self.weight_v = weight_v
+
+    def _call(self, input, target, gamma, weight_v, alpha, beta, smooth):
+        if input.dim() < 2 or input.shape[1] != len(self.groups):
+            raise ValueError("%s: the logits have shape %s; %d groups need %d channels"
+                             % (type(self).__name__, tuple(input.shape), len(self.groups), len(self.groups)))
+        if not input.is_cuda:
+            return _group_loss_host(self._kind, input, target, self._table, self.ignore_label, gamma, weight_v, alpha,
+                                    beta, smooth)
+        return _GroupLossFn.apply(input, target, self._kind, self._table, self.ignore_label, gamma, weight_v, alpha,
+                                  beta, smooth, getattr(self, "check_labels", _CHECK_LABELS))
+
+
+class GroupDice(_GroupLoss):
+    """sum_k w_k dice_k over the label groups: a metric, higher is better."""
+    _kind = N.LOSS_DICE
+
+    def __init__(self, groups, num_labels=None, ignore_label=None, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7):
+        super().__init__()
+        self._init_groups(groups, num_labels, ignore_label, weight_v)
+        self.alpha = alpha
+        self.beta = beta
+        self.smooth = smooth
+
+    def forward(self, input, target):
+        return self._call(input, target, 2.0, self.weight_v, self.alpha, self.beta, self.smooth)
+
+
+class GroupDiceLoss(_GroupLoss):
+    """sum_k w_k (1 - dice_k) over the label groups."""
+    _kind = N.LOSS_DICELOSS
+
+    def __init__(self, groups, num_labels=None, ignore_label=None, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7):
+        super().__init__()
+        self._init_groups(groups, num_labels, ignore_label, weight_v)
+        self.alpha = alpha
+        self.beta = beta
+        self.smooth = smooth
+
+    def forward(self, input, target):
+        return self._call(input, target, 2.0, self.weight_v, self.alpha, self.beta, self.smooth)
+
+
+class GroupFocalLoss(_GroupLoss):
+    """sum_k w_k focal_k: the binary focal loss of every group channel (gamma = 0: binary cross-entropy)."""
+    _kind = N.LOSS_FOCAL
+
+    def __init__(self, groups, num_labels=None, ignore_label=None, weight_v=None, gamma=2):
+        super().__init__()
+        self._init_groups(groups, num_labels, ignore_label, weight_v)
+        self.gamma = gamma
+
+    def forward(self, input, target):
+        return self._call(input, target, self.gamma, self.weight_v, 0.5, 0.5, 1e-7)
+
+
+class GroupHybirdLoss(_GroupLoss):
+    """sum_k w_k (1 - dice_k + focal_k) over the label groups: HybirdLoss for nested or overlapping structures.  The
+    logits have one channel per group (network out_channels = len(groups)); targets stay the plain label map.  HIP
+    tensors run the kernels of csrc/groups.hip, host tensors the torch twin of the definitions."""
+    _kind = N.LOSS_HYBIRD
+
+    def __init__(self, groups, num_labels=None, ignore_label=None, weight_v=None, gamma=2, alpha=0.5, beta=0.5,
+                 smooth=1e-7):
+        super().__init__()
+        self._init_groups(groups, num_labels, ignore_label, weight_v)
+        self.gamma = gamma
+        self.alpha = alpha
+        self.beta = beta
+        self.smooth = smooth
+
+    def forward(self, input, target):
+        return self._call(input, target, self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)

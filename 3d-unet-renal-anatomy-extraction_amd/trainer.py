@@ -539,6 +539,7 @@ class Trainer():
 # Case-level drivers around predict_case (reference trainer.py:136-400): host glue, the arithmetic is in inference.py.
 def batch_predict_case(load_dir, save_dir, model, target_spacing, normalize_stats, num_classes=3,
                        patch_size=(240, 240, 80), step_per_patch=4, data_range=None, *,
+                       groups=None, group_labels=None, threshold=0.5,
                        placement='reference', weighting='uniform', mirror_axes=(), sigma_scale=0.125):
     """trainer.py:136-161.  `model` may be a list (an ensemble); the keyword-only options are predict_per_patch's."""
     from data import CaseDataset, save_pred
@@ -546,7 +547,8 @@ def batch_predict_case(load_dir, save_dir, model, target_spacing, normalize_stat
     for i in (data_range if data_range is not None else range(len(cases))):
         case = predict_case(cases[i], model, target_spacing, normalize_stats, num_classes, patch_size,
                             step_per_patch, False, placement=placement, weighting=weighting,
-                            mirror_axes=mirror_axes, sigma_scale=sigma_scale)
+                            mirror_axes=mirror_axes, sigma_scale=sigma_scale, groups=groups, group_labels=group_labels,
+                            threshold=threshold)
         save_pred(case, save_dir)
 
 
@@ -813,6 +815,45 @@ def evaluate_metrics(case, smooth=1e-7):
                     'spe': (tn + smooth) / (tn + fp + smooth),
                     'acc': (tp + tn + smooth) / (tp + tn + fn + fp + smooth)})
     return out
+
+
+def evaluate_groups_case(case, groups, smooth=1e-7):
+    """Dice of every label group between case['label'] and case['pred'], both label maps: a voxel is in group k iff its
+    label is a member of groups[k], so a whole organ is scored as one structure beside the structure nested inside it.
+    A list of len(groups) floats, (tp + smooth) / (tp + 0.5 fn + 0.5 fp + smooth) from the integer confusion table of
+    the two volumes (np.bincount on numpy volumes, the confusion kernel when either is a HIP tensor); a group absent
+    from both maps scores smooth / smooth = 1."""
+    gs, _ = _loss_mod._checked_groups(groups)
+    table, _ = _confusion_table(case)
+    out = []
+    for g in gs:
+        members = [t for t in g if t < table.shape[0]]
+        tp = int(table[np.ix_(members, members)].sum())
+        fn = int(table[members, :].sum()) - tp
+        fp = int(table[:, members].sum()) - tp
+        out.append((tp + smooth) / (tp + 0.5 * fn + 0.5 * fp + smooth))
+    return out
+
+
+def evaluate_groups(label_file, pred_file, groups):
+    """evaluate for label groups: evaluate_groups_case of two NIfTI label maps."""
+    import nifti
+    label, _, _ = nifti.load(label_file)
+    pred, _, _ = nifti.load(pred_file)
+    return evaluate_groups_case({'label': label.astype(np.uint8), 'pred': pred.astype(np.uint8)}, groups)
+
+
+def batch_evaluate_groups(label_dir, pred_dir, groups, data_range=None):
+    """batch_evaluate for label groups: one list of len(groups) Dice values per case, the means printed."""
+    from pathlib import Path
+    label_files = sorted(Path(label_dir).glob('*.nii.gz'))
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    results = [evaluate_groups(label_files[i], pred_files[i], groups)
+               for i in (data_range if data_range is not None else range(len(label_files)))]
+    print('\nThe mean dsc of each group:')
+    for i, m in enumerate(np.array(results).mean(axis=0)):
+        print("group_%d %s: %f" % (i, tuple(groups[i]), m))
+    return results
 
 
 def evaluate(label_file, pred_file):

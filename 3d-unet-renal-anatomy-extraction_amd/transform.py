@@ -533,6 +533,71 @@ def combination_labels(input, combinations, num_classes):
     return np.argmax(planes, axis=0).astype(input.dtype)
 
 
+# ------------------------------------------------------------------ overlapping label groups (numpy twins of csrc/groups.hip)
+def labels_to_groups(label, groups, num_labels=None):
+    """Integer label map [...] -> uint8 [K, ...]: plane k is 1 where the voxel's label is a member of groups[k] (the
+    multi-hot targets the group losses read through loss.group_table without ever building them).  A label outside
+    [0, num_labels) is a member of no group."""
+    import loss
+    table = np.frombuffer(loss.group_table(groups, num_labels), dtype=np.uint8)
+    label = np.asarray(label).astype(np.int64)
+    inside = (label >= 0) & (label < len(table))
+    bits = np.where(inside, table[np.clip(label, 0, len(table) - 1)], 0)
+    return np.stack([(bits >> k) & 1 for k in range(len(groups))]).astype(np.uint8)
+
+
+def default_group_labels(groups):
+    """The label value each group decodes to: the smallest member of group k that belongs to no other group nested
+    inside it (a proper subset of it) - the value that tells the group from the structures it contains.
+    ((1, 2), (2,)) -> (1, 2); ((2,), (1, 2)) -> (2, 1).  ValueError when the nested groups use a group up, as group 0 of
+    ((1, 2), (1,), (2,)): pass group_labels then."""
+    import loss
+    gs, _ = loss._checked_groups(groups)
+    sets = [frozenset(g) for g in gs]
+    out = []
+    for k, s in enumerate(sets):
+        own = set(s)
+        for other in sets:
+            if other < s:
+                own -= other
+        if not own:
+            raise ValueError("default_group_labels: every member of group %d %s lies in a group nested inside it; "
+                             "pass group_labels" % (k, gs[k]))
+        out.append(min(own))
+    return tuple(out)
+
+
+def _checked_decode(groups, group_labels, threshold):
+    """(K label values, K float32 thresholds) of the decoding arguments, or ValueError."""
+    import loss
+    groups, _ = loss._checked_groups(groups)
+    k = len(groups)
+    labels = default_group_labels(groups) if group_labels is None else tuple(int(v) for v in group_labels)
+    if len(labels) != k or any(not 0 <= v <= 255 for v in labels):
+        raise ValueError("group_labels must hold %d label values of 0 .. 255, got %r" % (k, labels))
+    thr = np.asarray(threshold, dtype=np.float32)
+    thr = np.full(k, thr, dtype=np.float32) if thr.ndim == 0 else thr
+    if thr.shape != (k,) or np.isnan(thr).any():
+        raise ValueError("threshold must be a number or %d numbers, got %r" % (k, threshold))
+    return labels, thr
+
+
+def groups_to_labels(prob_or_bits, groups, group_labels=None, threshold=0.5):
+    """[..., K] probabilities (float) or on/off bits (bool) -> uint8 label map [...] by the decoding rule of
+    ru3d_predict_merge_groups: channel k is on iff its probability is > threshold (a number, or one per group; a NaN is
+    off), the voxel gets group_labels[k] (default default_group_labels(groups)) of the LAST channel that is on - later
+    groups overwrite earlier ones - and 0 when none is."""
+    labels, thr = _checked_decode(groups, group_labels, threshold)
+    q = np.asarray(prob_or_bits)
+    if q.shape[-1] != len(labels):
+        raise ValueError("groups_to_labels: last axis has %d channels for %d groups" % (q.shape[-1], len(labels)))
+    on = q if q.dtype == np.bool_ else np.asarray(q, dtype=np.float32) > thr
+    out = np.zeros(q.shape[:-1], dtype=np.uint8)
+    for k, v in enumerate(labels):
+        out[on[..., k]] = v
+    return out
+
+
 # ------------------------------------------------------------------ intensity (transform.py:176-193)
 def adjust_contrast(input, factor):
     mean = input.mean()

@@ -367,6 +367,48 @@ int ru3d_predict_accumulate_weighted(const ru3d_tensor* logits, int dtype, int s
                                      const float* gy, const float* gz, float* acc, float* cnt, int X, int Y, int Z,
                                      int ox, int oy, int oz, void* stream);
 
+/* ------------------------------------------------------------------ overlapping label groups */
+/* One sigmoid channel per GROUP of label values (csrc/groups.hip); groups may overlap, e.g. ((1, 2), (2,)) = whole
+ * kidney, tumour.  `table` is a HOST array of num_labels bytes, copied into the launch arguments: bit k of table[t] is
+ * set iff label value t is a member of group k (num_groups 1..8, num_labels 1..32).  The target of channel k at a voxel
+ * with label t is that bit; no multi-hot tensor exists.  has_ignore != 0: voxels whose label equals ignore_label (which
+ * must lie outside [0, num_labels)) enter no sum and get a zero gradient in every channel; M counts the others.  Any
+ * other label outside [0, num_labels) is a bad label: all channels off, counted in the state block, loss NaN.
+ * Over the counted voxels, p = sigmoid(z_k), g the target:
+ *   dice_k  = (tp + s) / (tp + alpha (sg - tp) + beta (sp - tp) + s),  tp = sum p g, sp = sum p, sg = sum g
+ *   focal_k = 1 / max(M, 1) sum [ (1-p)^gamma g softplus(-z) + p^gamma (1-g) softplus(z) ]   (gamma 0: binary CE)
+ *   w = weight_v / sum|weight_v| (HOST array of num_groups floats or NULL = ones), kind as ru3d_loss_fwd:
+ *   HYBIRD sum w (1 - dice + focal), DICELOSS sum w (1 - dice), FOCAL sum w focal, DICE sum w dice.
+ * Operands otherwise as ru3d_loss_fwd / ru3d_loss_bwd: fp32 logits with (stride_n, stride_c, stride_v), int64 or uint8
+ * labels, state of ru3d_group_loss_state_bytes() bytes - it begins like the state of ru3d_loss_fwd, so the bad-label
+ * count sits at ru3d_loss_state_bad_labels_offset() -, loss_out 1 fp32 on the device, dlogits f32 or bf16 with the
+ * logits' strides.  One pass each, fixed-order reductions, no atomics, no host synchronisation: bit-reproducible.
+ * Every argument error is refused before any launch. */
+size_t ru3d_group_loss_state_bytes(void);
+size_t ru3d_group_loss_workspace_bytes(int n, int64_t v, int num_groups);
+int ru3d_group_loss_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
+                        int label_dtype, int n, int64_t v, int num_groups, const uint8_t* table, int num_labels,
+                        int has_ignore, int ignore_label, int kind, float gamma, const float* weight_v, float alpha,
+                        float beta, float smooth, void* state, float* loss_out, void* ws, size_t ws_bytes, void* stream);
+int ru3d_group_loss_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
+                        int label_dtype, int n, int64_t v, int num_groups, const uint8_t* table, int num_labels,
+                        int has_ignore, int ignore_label, float gamma, const void* state, const float* grad_out,
+                        void* dlogits, int dlogits_dtype, void* stream);
+/* accumulate_groups: signature and contract of ru3d_predict_accumulate_weighted (flip, three device tables that may all
+ * be NULL, one thread per window voxel, sums in launch order) with an independent sigmoid per channel in place of the
+ * softmax; f32 or bf16 logits of 1..8 channels.  With flip 0 and NULL tables it serves the reference placement too. */
+int ru3d_predict_accumulate_groups(const ru3d_tensor* logits, int dtype, int sample, int flip, const float* gx,
+                                   const float* gy, const float* gz, float* acc, float* cnt, int X, int Y, int Z,
+                                   int ox, int oy, int oz, void* stream);
+/* merge_groups: uint8 [sx, sy, sz] over the crop, as ru3d_predict_merge takes it.  group_labels and threshold are HOST
+ * arrays of num_groups values (labels 0..255), copied into the launch arguments.  Channel k is on iff
+ * acc_k / cnt > threshold[k]; the voxel gets group_labels[k] of the LAST channel that is on (later groups overwrite
+ * earlier ones), 0 when none is, when cnt == 0 or when the mean is NaN.  The mean probabilities themselves are
+ * ru3d_predict_merge(..., one_hot = 1). */
+int ru3d_predict_merge_groups(const float* acc, const float* cnt, int X, int Y, int Z, int num_groups,
+                              const int32_t* group_labels, const float* threshold, int cx, int cy, int cz, int sx,
+                              int sy, int sz, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------ connected components + cascade merge */
 /* 3D connected-component labelling with 6-connectivity, scipy.ndimage.label's default structure (transform.py:5-11,
  * data.py:464-492).  mask: uint8 [X, Y, Z], Z contiguous, any non-zero byte is foreground.  labels: int32 [X, Y, Z],
