@@ -193,6 +193,17 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _sz, _vp]),
     "ru3d_group_loss_bwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i,
                                  _vp]),
+    "ru3d_topk_select_workspace_bytes": (_sz, [_i64]),
+    "ru3d_topk_select_trip_elements": (_i64, []),
+    "ru3d_topk_select": (_i, [_vp, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "ru3d_topk_loss_state_bytes": (_sz, []),
+    "ru3d_topk_loss_workspace_bytes": (_sz, [_i, _i64, _i]),
+    "ru3d_topk_loss_fwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _i64, _i, _vp, _f, _f, _f, _f, _vp, _vp,
+                                _vp, _vp, _sz, _vp]),
+    "ru3d_topk_loss_fwd_launches": (_i, []),
+    "ru3d_topk_loss_fwd_timed": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _i64, _i, _vp, _f, _f, _f, _f, _vp,
+                                      _vp, _vp, _vp, _sz, _vp, _vp]),
+    "ru3d_topk_loss_bwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "ru3d_predict_accumulate_groups": (_i, [_P, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ru3d_predict_merge_groups": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ru3d_components_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -24,6 +24,10 @@ C == 1 the reference only works for all-zero targets and so does this.
 
 Beyond the reference: nested or overlapping structures train one sigmoid channel per group of label values with
 `GroupHybirdLoss` / `GroupDiceLoss` / `GroupFocalLoss` / `GroupDice` (the section "overlapping label groups" below).
+`TopKLoss` / `HybirdTopKLoss` (the section "top-k cross-entropy" at the end) are nnU-Net's top-k cross-entropy and its
+`DC_and_topk_loss`: the cross-entropy averaged over the hardest k percent of the batch's voxels, selected on the device
+between the forward and the backward.  `DeepSupervisionLoss` does not take them as a base: top-k under deep supervision
+is not implemented.
 """
 import collections
 import os
@@ -1326,3 +1330,151 @@ class GroupHybirdLoss(_GroupLoss):
 
     def forward(self, input, target):
         return self._call(input, target, self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)
+
+
+# --------------------------------------------------------------------------- top-k cross-entropy
+# nnU-Net's TopKLoss and DC_and_topk_loss.  Over the M = N * V voxels of the batch, flattened as nnU-Net flattens them:
+#   ce_v = -log softmax(z_v)[t_v],  K = max(1, int(M * k / 100)),  tau = the K-th largest ce,
+#   G = #{ce > tau},  E = #{ce == tau},  topk = (sum_{ce > tau} ce + (K - G) * tau) / K   (= torch.topk(ce, K).values.mean())
+#   d topk / d z_{v,c} = s_v (p_{v,c} - [c == t_v]) / K,  s_v = 1 if ce_v > tau, (K - G) / E if ce_v == tau, else 0.
+# The voxels tied at the threshold share the remaining weight equally: the loss is deterministic and does not depend on
+# the order of the voxels; it is torch.topk's gradient whenever E == 1.  The tie rule is part of the contract - ties at
+# ce == 0 are real for saturated voxels.  k = 100 is the plain mean cross-entropy.
+#   TopKLoss = topk,  HybirdTopKLoss = sum_c w_c (1 - dice_c) + ce_weight * topk with DiceLoss's w and Tversky dice_c.
+def topk_count(voxels, k):
+    """K of a batch of `voxels` voxels: max(1, int(voxels * k / 100))."""
+    return max(1, int(voxels * k / 100))
+
+
+def _checked_k(k):
+    k = float(k)
+    if not 0.0 < k <= 100.0:
+        raise ValueError("top-k loss: k = %g percent lies outside (0, 100]" % k)
+    return k
+
+
+def _topk_checks(input, weight_v):
+    if input.dim() < 2:
+        raise N.Ru3dError("loss: input must be (N, C, d1, ..., dn)")
+    c = input.shape[1]
+    if c < 2:
+        raise ValueError("top-k loss: C == 1 is not supported (softmax over at least two classes)")
+    if weight_v is not None and len(weight_v) != c:
+        raise ValueError("weight_v has %d entries for %d classes" % (len(weight_v), c))
+
+
+def _topk_loss_host(input, target, k, with_dice=False, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7, ce_weight=1.0):
+    """The definitions above on host tensors with torch ops, differentiable, in the logits' dtype, the tie rule included:
+    the twin the kernels are held to."""
+    _topk_checks(input, weight_v)
+    n, c = input.shape[0], input.shape[1]
+    if tuple(target.shape) != (n,) + tuple(input.shape[2:]):
+        raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape), tuple(input.shape)))
+    z = input.reshape(n, c, -1)
+    t = target.long().reshape(n, -1)
+    if t.numel() and (int(t.max()) >= c or int(t.min()) < 0):
+        raise RuntimeError(_BAD_LABELS)
+    ce = -torch.log_softmax(z, dim=1).gather(1, t[:, None]).reshape(-1)
+    kk = topk_count(ce.numel(), _checked_k(k))
+    held = ce.detach()
+    tau = torch.topk(held, kk).values[-1]
+    above, tied = held > tau, held == tau
+    share = (kk - int(above.sum())) / int(tied.sum())
+    s = above.to(ce.dtype) + tied.to(ce.dtype) * share
+    value = (s * ce).sum() / kk * ce_weight
+    if with_dice:
+        value = value + _region_loss_host(N.LOSS_DICELOSS, input, target, 2.0, weight_v, alpha, beta, smooth)
+    return value
+
+
+class _TopKLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, input, target, kk, with_dice, weight_v, alpha, beta, smooth, ce_weight, check_labels):
+        x, st, lab, lab_code, n, c, v = _loss_operands(input, target, check_labels)
+        raise_on_bad_labels()          # an earlier call's verdict, if it has landed (no wait)
+        dev = x.device
+        state = torch.empty(N.lib.ru3d_topk_loss_state_bytes(), dtype=torch.uint8, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        # the backward compares these stored values with tau: a tensor of this call, not a slice of the shared workspace,
+        # which other calls reuse between a forward and its backward
+        ce = torch.empty(n * v, dtype=torch.float32, device=dev)
+        ws = N.workspace(N.lib.ru3d_topk_loss_workspace_bytes(n, v, c), dev)
+        wv = _weight_array(weight_v, c)
+        check(N.lib.ru3d_topk_loss_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, kk, int(with_dice),
+                                       N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None, float(alpha),
+                                       float(beta), float(smooth), float(ce_weight), ptr(ce), ptr(state), ptr(out),
+                                       ptr(ws), ws.numel(), stream()), "topk_loss_fwd")
+        if not check_labels:
+            _note_label_flag(state)
+        ctx.save_for_backward(x, lab, ce, state)
+        ctx.meta = (st, lab_code, n, v, c, int(with_dice), input.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, lab, ce, state = ctx.saved_tensors
+        st, lab_code, n, v, c, with_dice, in_dtype = ctx.meta
+        g = gout.detach()
+        if g.dtype != torch.float32 or g.device != x.device:
+            g = g.to(device=x.device, dtype=torch.float32)
+        g = g.reshape(1).contiguous()
+        N.note_device(x.device)
+        dz = torch.empty_like(x)   # preserve_format: same (dense) strides as the logits
+        if dz.stride() != x.stride():
+            dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
+        check(N.lib.ru3d_topk_loss_bwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, with_dice, ptr(ce),
+                                       ptr(state), ptr(g), ptr(dz), N.F32, stream()), "topk_loss_bwd")
+        if in_dtype != torch.float32:
+            dz = dz.to(in_dtype)       # rounded once to the logits' type
+        return (dz,) + (None,) * 9
+
+
+class _TopKLoss(_FusedLoss):
+    """What the two top-k losses share: the checked k and the route by the logits' device."""
+    _with_dice = False
+
+    def _call_topk(self, input, target, weight_v, alpha, beta, smooth, ce_weight):
+        _topk_checks(input, weight_v)
+        if not input.is_cuda:
+            return _topk_loss_host(input, target, self.k, self._with_dice, weight_v, alpha, beta, smooth, ce_weight)
+        voxels = input.shape[0]
+        for s in input.shape[2:]:
+            voxels *= s
+        return _TopKLossFn.apply(input, target, topk_count(voxels, self.k), self._with_dice, weight_v, alpha, beta,
+                                 smooth, ce_weight, getattr(self, "check_labels", _CHECK_LABELS))
+
+
+class TopKLoss(_TopKLoss):
+    """The cross-entropy averaged over the hardest k percent of the batch's voxels (nnU-Net's TopKLoss, k = 10): the mean of
+    the K = max(1, int(N * V * k / 100)) largest -log softmax(z_v)[t_v]; k = 100 is the plain mean cross-entropy.  Voxels
+    tied at the threshold share the weight that is left equally (the section comment above).  k is fixed at construction,
+    0 < k <= 100; K is a launch argument of a captured step (graph.GraphedTrainStep), so another k - or another batch
+    shape - means a recapture.  C >= 2.  HIP tensors run the kernels of csrc/topk.hip (no sort, no host round trip
+    between the forward and the backward), host tensors the torch twin of the definitions."""
+
+    def __init__(self, k=10):
+        super().__init__()
+        self.k = _checked_k(k)
+
+    def forward(self, input, target):
+        return self._call_topk(input, target, None, 0.5, 0.5, 1e-7, 1.0)
+
+
+class HybirdTopKLoss(_TopKLoss):
+    """sum_c w_c (1 - dice_c) + ce_weight * topk: DiceLoss(weight_v, alpha, beta, smooth) plus TopKLoss(k), nnU-Net's
+    DC_and_topk_loss, in one forward pass over logits and labels and one backward pass.  k is fixed at construction,
+    0 < k <= 100; K = max(1, int(N * V * k / 100)) is a launch argument of a captured step, so another k - or another
+    batch shape - means a recapture.  C >= 2.  HIP tensors run the kernels of csrc/topk.hip, host tensors the torch twin."""
+    _with_dice = True
+
+    def __init__(self, k=10, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7, ce_weight=1.0):
+        super().__init__()
+        self.k = _checked_k(k)
+        self.weight_v = weight_v
+        self.alpha = alpha
+        self.beta = beta
+        self.smooth = smooth
+        self.ce_weight = ce_weight
+
+    def forward(self, input, target):
+        return self._call_topk(input, target, self.weight_v, self.alpha, self.beta, self.smooth, self.ce_weight)

@@ -394,6 +394,52 @@ int ru3d_group_loss_bwd(const float* logits, int64_t stride_n, int64_t stride_c,
                         int label_dtype, int n, int64_t v, int num_groups, const uint8_t* table, int num_labels,
                         int has_ignore, int ignore_label, float gamma, const void* state, const float* grad_out,
                         void* dlogits, int dlogits_dtype, void* stream);
+/* ------------------------------------------------------------------ top-k cross-entropy */
+/* ru3d_topk_select: exact top-K statistics of n finite device floats (csrc/topk.hip), 1 <= K <= n.  *result (device):
+ * tau = the K-th largest value, count_gt = #{x > tau}, count_eq = #{x == tau}, sum_gt = the sum of the values above tau,
+ * accumulated in float64 from the element on (per-workgroup partial rows added in a fixed order: the same bits every
+ * run).  The two zeros are one value and a zero tau is +0.  mean of the K largest = (sum_gt + (K - count_gt) * tau) / K.
+ * Radix select with 11 / 11 / 10-bit digits: the values are read three times, never moved (what lies above tau in the
+ * last digit is summed from that digit's table); no host synchronisation, capturable.  ru3d_topk_select_trip_elements(): the values one grid-stride trip of its largest grid covers. */
+typedef struct ru3d_topk_result {
+    float tau;
+    int64_t count_gt;
+    int64_t count_eq;
+    double sum_gt;
+} ru3d_topk_result;
+size_t ru3d_topk_select_workspace_bytes(int64_t n);
+int64_t ru3d_topk_select_trip_elements(void);
+int ru3d_topk_select(const float* values, int64_t n, int64_t K, ru3d_topk_result* result, void* ws, size_t ws_bytes,
+                     void* stream);
+/* Top-k cross-entropy loss, alone (with_dice == 0: loss.TopKLoss, ce_weight scales it) or added to DiceLoss's region term
+ * (with_dice != 0: loss.HybirdTopKLoss).  With ce_v = -log softmax(z_v)[t_v] in float32 over the M = n * v voxels of the
+ * batch, tau their K-th largest, G = #{ce > tau}, E = #{ce == tau}:
+ *   topk = (sum_{ce > tau} ce + (K - G) * tau) / K                  (= torch.topk(ce, K).values.mean())
+ *   loss = [sum_c w_c (1 - dice_c)] + ce_weight * topk,  w and the Tversky dice_c as ru3d_loss_fwd's RU3D_LOSS_DICELOSS
+ *   d topk / d z_{v,c} = s_v (p_{v,c} - [c == t_v]) / K,  s_v = 1 if ce_v > tau, (K - G) / E if ce_v == tau, else 0
+ * (voxels tied at the threshold share the remaining weight equally).  Operands as ru3d_loss_fwd / ru3d_loss_bwd, with
+ * 2 <= num_classes <= 8 and 1 <= K <= M.  ce: caller-owned device float32 [M], written by the forward and read by the
+ * backward, which compares the stored values with tau: it must not be touched in between.  state: device buffer of
+ * ru3d_topk_loss_state_bytes() bytes; it begins like the state of ru3d_loss_fwd (the bad-label count sits at
+ * ru3d_loss_state_bad_labels_offset()) and continues with tau (float32, 4 bytes of padding), G, E, K as int64 and the two
+ * backward weights ce_weight / K and ce_weight (K - G) / (E K) as float32.  A label outside [0, C) is counted, its ce is 0 and the loss is NaN.
+ * The forward reads logits and labels once and ce[] twice; no host synchronisation, capturable; K is a launch
+ * argument.  ru3d_topk_loss_fwd_timed (tools): the same forward with an event after every launch; it waits for the stream
+ * and writes the milliseconds of the ru3d_topk_loss_fwd_launches() launches to the HOST array launch_ms. */
+size_t ru3d_topk_loss_state_bytes(void);
+size_t ru3d_topk_loss_workspace_bytes(int n, int64_t v, int num_classes);
+int ru3d_topk_loss_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
+                       int label_dtype, int n, int64_t v, int num_classes, int64_t K, int with_dice,
+                       const float* weight_v, float alpha, float beta, float smooth, float ce_weight, float* ce,
+                       void* state, float* loss_out, void* ws, size_t ws_bytes, void* stream);
+int ru3d_topk_loss_fwd_launches(void);
+int ru3d_topk_loss_fwd_timed(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
+                             int label_dtype, int n, int64_t v, int num_classes, int64_t K, int with_dice,
+                             const float* weight_v, float alpha, float beta, float smooth, float ce_weight, float* ce,
+                             void* state, float* loss_out, void* ws, size_t ws_bytes, float* launch_ms, void* stream);
+int ru3d_topk_loss_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
+                       int label_dtype, int n, int64_t v, int num_classes, int with_dice, const float* ce,
+                       const void* state, const float* grad_out, void* dlogits, int dlogits_dtype, void* stream);
 /* accumulate_groups: signature and contract of ru3d_predict_accumulate_weighted (flip, three device tables that may all
  * be NULL, one thread per window voxel, sums in launch order) with an independent sigmoid per channel in place of the
  * softmax; f32 or bf16 logits of 1..8 channels.  With flip 0 and NULL tables it serves the reference placement too. */
