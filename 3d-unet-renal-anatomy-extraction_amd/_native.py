@@ -107,6 +107,9 @@ _vp, _i, _i64, _f, _sz, _u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c
                                 ctypes.c_uint64)
 _dbl = ctypes.c_double
 
+# how every fused loss entry point begins: logits, stride_n, stride_c, stride_v, labels, label_dtype, n
+_LOSS_VIEW = [_vp, _i64, _i64, _i64, _vp, _i, _i]
+
 # name -> (restype, argtypes): every symbol include/ru3d.h declares
 SIGNATURES = {
     "ru3d_version": (_i, []),
@@ -179,9 +182,8 @@ SIGNATURES = {
     "ru3d_loss_state_bytes": (_sz, [_i]),
     "ru3d_loss_state_bad_labels_offset": (_sz, []),
     "ru3d_loss_workspace_bytes": (_sz, [_i, _i64, _i]),
-    "ru3d_loss_fwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _i, _f, _vp, _f, _f, _f, _vp, _vp, _vp,
-                           _sz, _vp]),
-    "ru3d_loss_bwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _f, _vp, _vp, _vp, _i, _vp]),
+    "ru3d_loss_fwd": (_i, _LOSS_VIEW + [_i64, _i, _i, _f, _vp, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_loss_bwd": (_i, _LOSS_VIEW + [_i64, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "ru3d_tversky": (_i, [_vp, _vp, _i64, _f, _f, _f, _vp, _vp, _sz, _vp]),
     "ru3d_predict_accumulate": (_i, [_P, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ru3d_predict_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -189,21 +191,19 @@ SIGNATURES = {
     "ru3d_predict_accumulate_weighted": (_i, [_P, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ru3d_group_loss_state_bytes": (_sz, []),
     "ru3d_group_loss_workspace_bytes": (_sz, [_i, _i64, _i]),
-    "ru3d_group_loss_fwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _vp, _i, _i, _i, _i, _f, _vp, _f, _f, _f,
-                                 _vp, _vp, _vp, _sz, _vp]),
-    "ru3d_group_loss_bwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i,
-                                 _vp]),
+    "ru3d_group_loss_fwd": (_i, _LOSS_VIEW + [_i64, _i, _vp, _i, _i, _i, _i, _f, _vp, _f, _f, _f, _vp, _vp, _vp, _sz,
+                                              _vp]),
+    "ru3d_group_loss_bwd": (_i, _LOSS_VIEW + [_i64, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "ru3d_topk_select_workspace_bytes": (_sz, [_i64]),
     "ru3d_topk_select_trip_elements": (_i64, []),
     "ru3d_topk_select": (_i, [_vp, _i64, _i64, _vp, _vp, _sz, _vp]),
     "ru3d_topk_loss_state_bytes": (_sz, []),
     "ru3d_topk_loss_workspace_bytes": (_sz, [_i, _i64, _i]),
-    "ru3d_topk_loss_fwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _i64, _i, _vp, _f, _f, _f, _f, _vp, _vp,
-                                _vp, _vp, _sz, _vp]),
+    "ru3d_topk_loss_fwd": (_i, _LOSS_VIEW + [_i64, _i, _i64, _i, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_topk_loss_fwd_launches": (_i, []),
-    "ru3d_topk_loss_fwd_timed": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _i64, _i, _vp, _f, _f, _f, _f, _vp,
-                                      _vp, _vp, _vp, _sz, _vp, _vp]),
-    "ru3d_topk_loss_bwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ru3d_topk_loss_fwd_timed": (_i, _LOSS_VIEW + [_i64, _i, _i64, _i, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _sz,
+                                                   _vp, _vp]),
+    "ru3d_topk_loss_bwd": (_i, _LOSS_VIEW + [_i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "ru3d_predict_accumulate_groups": (_i, [_P, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ru3d_predict_merge_groups": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ru3d_components_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -242,15 +242,14 @@ SIGNATURES = {
     "ru3d_cldice_state_bytes": (_sz, []),
     "ru3d_soft_skeleton_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_soft_skeleton_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ru3d_cldice_fwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _f, _vp, _vp, _vp,
-                             _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ru3d_cldice_bwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                             _vp, _vp, _f, _i, _vp, _vp, _sz, _vp]),
+    "ru3d_cldice_fwd": (_i, _LOSS_VIEW + [_i, _i, _i, _i, _vp, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _sz, _vp]),
+    "ru3d_cldice_bwd": (_i, _LOSS_VIEW + [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp,
+                                          _vp, _sz, _vp]),
     "ru3d_boundary_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ru3d_boundary_state_bytes": (_sz, []),
     "ru3d_signed_distance": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "ru3d_boundary_fwd": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
-                               _sz, _vp]),
+    "ru3d_boundary_fwd": (_i, _LOSS_VIEW + [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_boundary_bwd": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "ru3d_ds_state_bytes": (_sz, []),
     "ru3d_ds_state_bad_labels_offset": (_sz, []),

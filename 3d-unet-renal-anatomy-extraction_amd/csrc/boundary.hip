@@ -52,12 +52,6 @@ struct BdState {
     int pad2[2];
 };
 
-struct BdClasses {
-    int K;                          // selected classes
-    int cls[RU3D_MAX_CLASSES];      // slot -> class
-    int slot[RU3D_MAX_CLASSES];     // class -> slot, -1 when not selected
-};
-
 struct BdWeights {
     float w[RU3D_MAX_CLASSES];      // normalised, slot order
 };
@@ -90,7 +84,7 @@ static inline int bd_tile_shift(int L, int Z) { return bv_tile_shift(L, Z, BD_MA
 // a wave takes one word a trip; words are numbered (n, a, b, w) with w fastest, so a wave that stays inside one sample
 // gathers the flag bits of its words in registers and hands them over once per slot when the sample ends
 __global__ __launch_bounds__(256) void bd_pack_kernel(const void* __restrict__ labels, int label_dtype, int64_t rows,
-                                                      int64_t rows_per_sample, int Z, int W, int C, BdClasses cl,
+                                                      int64_t rows_per_sample, int Z, int W, int C, ClassList cl,
                                                       bd_u64* __restrict__ bits, unsigned* __restrict__ flags,
                                                       int* __restrict__ bad) {
     const int lane = threadIdx.x & 63;
@@ -250,7 +244,7 @@ __global__ __launch_bounds__(BD_THREADS) void bd_x_kernel(const int* __restrict_
 // part[block] = sum over the block's voxels (grid-stride, the grid fixed by the shape) of sum_q w_q P_q phi_q
 template <int C>
 __global__ __launch_bounds__(256) void bd_loss_kernel(const float* __restrict__ logits, int64_t stride_n,
-                                                      int64_t stride_c, int64_t stride_v, int n, int64_t V, BdClasses cl,
+                                                      int64_t stride_c, int64_t stride_v, int n, int64_t V, ClassList cl,
                                                       BdWeights wt, const float* __restrict__ phi,
                                                       double* __restrict__ part) {
     double acc = 0.0;
@@ -296,7 +290,7 @@ __global__ __launch_bounds__(BD_PART) void bd_finalize_kernel(const double* __re
 // dlogits_j (+)= g / (N V) * P_j * (w_j phi_j [j selected] - sum_q w_q P_q phi_q)
 template <int C, bool ACC>
 __global__ __launch_bounds__(256) void bd_bwd_kernel(const float* __restrict__ logits, int64_t stride_n, int64_t stride_c,
-                                                     int64_t stride_v, int n, int64_t V, BdClasses cl,
+                                                     int64_t stride_v, int n, int64_t V, ClassList cl,
                                                      const BdState* __restrict__ st, const float* __restrict__ phi,
                                                      const float* __restrict__ grad_out, float scale, float inv_count,
                                                      float* __restrict__ dz) {
@@ -335,26 +329,6 @@ __global__ __launch_bounds__(256) void bd_bwd_kernel(const float* __restrict__ l
 }
 
 // --------------------------------------------------------------------------- host side
-static int bd_classes(const char* what, int num_classes, const int* classes, int num_selected, BdClasses* cl) {
-    RU3D_REQUIRE(num_classes >= 2 && num_classes <= RU3D_MAX_CLASSES, "%s: %d classes (2 .. %d)", what, num_classes,
-                 RU3D_MAX_CLASSES);
-    RU3D_REQUIRE(classes, "%s: null pointer (classes)", what);
-    RU3D_REQUIRE(num_selected >= 1 && num_selected <= num_classes, "%s: bad class selection (num_selected = %d, 1 .. %d)",
-                 what, num_selected, num_classes);
-    cl->K = num_selected;
-    for (int c = 0; c < RU3D_MAX_CLASSES; c++) {
-        cl->cls[c] = 0;
-        cl->slot[c] = -1;
-    }
-    for (int k = 0; k < num_selected; k++) {
-        const int c = classes[k];
-        RU3D_REQUIRE(c >= 0 && c < num_classes && cl->slot[c] < 0, "%s: class %d out of range or selected twice", what, c);
-        cl->cls[k] = c;
-        cl->slot[c] = k;
-    }
-    return 0;
-}
-
 static int bd_check_geom(const char* what, int n, int K, int A, int B, int Z) {
     RU3D_REQUIRE(n > 0 && A > 0 && B > 0 && Z > 0, "%s: empty volume", what);
     RU3D_REQUIRE(A <= RU3D_BOUNDARY_MAX_AXIS && B <= RU3D_BOUNDARY_MAX_AXIS && Z <= RU3D_BOUNDARY_MAX_AXIS,
@@ -372,15 +346,11 @@ static int bd_loss_blocks(int64_t total) {
     return (int)b;
 }
 
-static int bd_flat_blocks(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    if (b > 16384) b = 16384;
-    return (int)b;
-}
+static int bd_flat_blocks(int64_t total) { return flat_bwd_blocks(total, 16384); }
 
 // the whole transform; everything was checked by the caller
 static int bd_transform(const void* labels, int label_dtype, int n, int A, int B, int Z, int num_classes,
-                        const BdClasses& cl, int* d2_out, float* phi_out, void* ws, hipStream_t st) {
+                        const ClassList& cl, int* d2_out, float* phi_out, void* ws, hipStream_t st) {
     const int nvol = n * cl.K, W = bv_words(Z);
     unsigned* flags = (unsigned*)ws;
     int* bad = (int*)(flags + nvol);
@@ -422,8 +392,10 @@ extern "C" int ru3d_signed_distance(const void* labels, int label_dtype, int n, 
     RU3D_REQUIRE(labels && ws, "signed_distance: null pointer");
     RU3D_REQUIRE(d2_out || phi_out, "signed_distance: null pointer (neither d2_out nor phi_out)");
     RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "signed_distance: bad label dtype");
-    BdClasses cl;
-    int rc = bd_classes("signed_distance", num_classes, classes, num_selected, &cl);
+    RU3D_REQUIRE(num_classes >= 2 && num_classes <= RU3D_MAX_CLASSES, "signed_distance: %d classes (2 .. %d)", num_classes,
+                 RU3D_MAX_CLASSES);
+    ClassList cl;
+    int rc = class_list_check("signed_distance", num_classes, classes, num_selected, &cl);
     if (rc) return rc;
     rc = bd_check_geom("signed_distance", n, cl.K, A, B, Z);
     if (rc) return rc;
@@ -434,7 +406,7 @@ extern "C" int ru3d_signed_distance(const void* labels, int label_dtype, int n, 
 }
 
 // weight_v restricted to the selected classes over the sum of its absolute values
-static BdWeights bd_weights(const float* weight_v, const BdClasses& cl) {
+static BdWeights bd_weights(const float* weight_v, const ClassList& cl) {
     BdWeights wt;
     double wsum = 0.0;
     for (int k = 0; k < cl.K; k++) wsum += fabs(weight_v ? (double)weight_v[cl.cls[k]] : 1.0);
@@ -449,12 +421,13 @@ extern "C" int ru3d_boundary_fwd(const float* logits, int64_t stride_n, int64_t 
                                  const int* classes, int num_selected, const float* weight_v, float* phi, void* state,
                                  float* loss_out, void* ws, size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(logits && labels && phi && state && loss_out && ws, "boundary_fwd: null pointer");
-    RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "boundary_fwd: bad label dtype");
+    int rc = loss_view_check("boundary_fwd", logits && labels && phi && state && loss_out && ws,
+                             n > 0 && A > 0 && B > 0 && Z > 0, label_dtype, num_classes, 2);
+    if (rc) return rc;
     RU3D_REQUIRE(offsetof(BdState, bad_labels) == ru3d_loss_state_bad_labels_offset(),
                  "boundary_fwd: state layouts out of step");
-    BdClasses cl;
-    int rc = bd_classes("boundary_fwd", num_classes, classes, num_selected, &cl);
+    ClassList cl;
+    rc = class_list_check("boundary_fwd", num_classes, classes, num_selected, &cl);
     if (rc) return rc;
     rc = bd_check_geom("boundary_fwd", n, cl.K, A, B, Z);
     if (rc) return rc;
@@ -486,9 +459,12 @@ extern "C" int ru3d_boundary_bwd(const float* logits, int64_t stride_n, int64_t 
                                  const void* state, const float* grad_out, float scale, int accumulate, float* dlogits,
                                  void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
+    // no labels here (the maps of the forward stand for them), so no loss_view_check
     RU3D_REQUIRE(logits && phi && state && dlogits, "boundary_bwd: null pointer");
-    BdClasses cl;
-    int rc = bd_classes("boundary_bwd", num_classes, classes, num_selected, &cl);
+    RU3D_REQUIRE(num_classes >= 2 && num_classes <= RU3D_MAX_CLASSES, "boundary_bwd: %d classes (2 .. %d)", num_classes,
+                 RU3D_MAX_CLASSES);
+    ClassList cl;
+    int rc = class_list_check("boundary_bwd", num_classes, classes, num_selected, &cl);
     if (rc) return rc;
     rc = bd_check_geom("boundary_bwd", n, cl.K, A, B, Z);
     if (rc) return rc;

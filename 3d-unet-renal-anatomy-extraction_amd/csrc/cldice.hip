@@ -43,12 +43,6 @@ struct CdState {
     float cc[RU3D_MAX_CLASSES];        // dL/dP[v] (the plain P of Tsens) = cc S(G)[v]
 };
 
-struct CdClasses {
-    int K;                          // selected classes
-    int cls[RU3D_MAX_CLASSES];      // slot -> class
-    int slot[RU3D_MAX_CLASSES];     // class -> slot, -1 when not selected
-};
-
 extern "C" size_t ru3d_cldice_state_bytes(void) { return sizeof(CdState); }
 
 static inline int64_t cd_ceil(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -72,11 +66,7 @@ static int cd_sum_blocks(int64_t total) {
     return (int)b;
 }
 
-static int cd_flat_blocks(int64_t total) {
-    int64_t b = cd_ceil(total, 256);
-    if (b > 16384) b = 16384;
-    return (int)b;
-}
+static int cd_flat_blocks(int64_t total) { return flat_bwd_blocks(total, 16384); }
 
 constexpr size_t CD_PART_BYTES = (size_t)1024 * 5 * RU3D_MAX_CLASSES * sizeof(double);
 
@@ -243,7 +233,7 @@ static int cd_chain(const float* x0, float* xa, float* xb, int nvol, const CdGeo
 // block: gs[v] = ca G[v] + cb with G read from the labels.
 __global__ __launch_bounds__(256) void cd_bwd_point_kernel(const float* __restrict__ gout,
                                                            const void* __restrict__ labels, int label_dtype,
-                                                           CdClasses cl, const CdState* __restrict__ st,
+                                                           ClassList cl, const CdState* __restrict__ st,
                                                            const float* __restrict__ delta, const float* __restrict__ s,
                                                            float* __restrict__ h, int64_t V, int64_t plane, int k) {
 #pragma clang fp contract(off)
@@ -323,7 +313,7 @@ __global__ __launch_bounds__(256) void cd_bwd_gather_kernel(const float* __restr
 }
 
 // gx_0 into `gx_out`; ws: k + 1 planes h, then two planes gx
-static int cd_chain_bwd(const float* gout, const void* labels, int label_dtype, const CdClasses& cl, const CdState* state,
+static int cd_chain_bwd(const float* gout, const void* labels, int label_dtype, const ClassList& cl, const CdState* state,
                         int nvol, const CdGeom& g, int k, const float* delta, const float* s, const uint8_t* emin,
                         const uint8_t* dmax, float* gx_out, float* ws, hipStream_t st) {
     const int64_t plane = (int64_t)nvol * g.V;
@@ -383,7 +373,7 @@ extern "C" int ru3d_soft_skeleton_bwd(const float* grad_out, int nvol, int A, in
     if (rc) return rc;
     RU3D_REQUIRE(ws_bytes >= ru3d_cldice_workspace_bytes(nvol, A, B, Z, iterations),
                  "soft_skeleton_bwd: workspace too small");
-    CdClasses cl = {};
+    ClassList cl = {};
     cl.K = 1;
     return cd_chain_bwd(grad_out, nullptr, 0, cl, nullptr, nvol, cd_geom(A, B, Z), iterations, delta, s, emin, dmax,
                         grad_x, cd_planes(ws), as_stream(stream));
@@ -396,7 +386,7 @@ template <int C>
 __global__ __launch_bounds__(256) void cd_softmax_kernel(const float* __restrict__ logits, int64_t stride_n,
                                                          int64_t stride_c, int64_t stride_v,
                                                          const void* __restrict__ labels, int label_dtype, int n,
-                                                         int64_t V, CdClasses cl, float* __restrict__ P,
+                                                         int64_t V, ClassList cl, float* __restrict__ P,
                                                          float* __restrict__ G) {
     const int64_t total = (int64_t)n * V;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -419,7 +409,7 @@ __global__ __launch_bounds__(256) void cd_softmax_kernel(const float* __restrict
 // blockIdx.y = slot; partials part[block][slot * 5 + q], q = sum S(P) G, sum S(P), sum S(G) P, sum S(G), bad labels
 __global__ __launch_bounds__(256) void cd_sums_kernel(const float* __restrict__ SP, const float* __restrict__ SG,
                                                       const float* __restrict__ P, const void* __restrict__ labels,
-                                                      int label_dtype, int n, int64_t V, int C, CdClasses cl,
+                                                      int label_dtype, int n, int64_t V, int C, ClassList cl,
                                                       double* __restrict__ part) {
     const int slot = blockIdx.y;
     int c = cl.cls[0];
@@ -514,7 +504,7 @@ __global__ __launch_bounds__(CD_FIN_THREADS) void cd_finalize_kernel(const doubl
 template <int C, bool ACC>
 __global__ __launch_bounds__(256) void cd_logits_bwd_kernel(const float* __restrict__ logits, int64_t stride_n,
                                                             int64_t stride_c, int64_t stride_v, int n, int64_t V,
-                                                            CdClasses cl, const CdState* __restrict__ st,
+                                                            ClassList cl, const CdState* __restrict__ st,
                                                             const float* __restrict__ gx0, const float* __restrict__ SG,
                                                             const float* __restrict__ grad_out, float scale,
                                                             float* __restrict__ dz) {
@@ -556,40 +546,22 @@ __global__ __launch_bounds__(256) void cd_logits_bwd_kernel(const float* __restr
     }
 }
 
-static int cd_classes(const char* what, int num_classes, const int* classes, int num_selected, CdClasses* cl) {
-    RU3D_REQUIRE(num_classes >= 2 && num_classes <= RU3D_MAX_CLASSES, "%s: %d classes (2 .. %d)", what, num_classes,
-                 RU3D_MAX_CLASSES);
-    RU3D_REQUIRE(classes && num_selected >= 1 && num_selected <= num_classes, "%s: bad class selection", what);
-    cl->K = num_selected;
-    for (int c = 0; c < RU3D_MAX_CLASSES; c++) {
-        cl->cls[c] = 0;
-        cl->slot[c] = -1;
-    }
-    for (int k = 0; k < num_selected; k++) {
-        const int c = classes[k];
-        RU3D_REQUIRE(c >= 0 && c < num_classes && cl->slot[c] < 0, "%s: class %d out of range or selected twice", what,
-                     c);
-        cl->cls[k] = c;
-        cl->slot[c] = k;
-    }
-    return 0;
-}
-
 extern "C" int ru3d_cldice_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
                                const void* labels, int label_dtype, int n, int A, int B, int Z, int num_classes,
                                const int* classes, int num_selected, int iterations, const float* weight_v, float smooth,
                                float* delta, float* s, uint8_t* emin, uint8_t* dmax, float* skel_g, void* state,
                                float* loss_out, void* ws, size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(logits && labels && delta && s && emin && dmax && skel_g && state && loss_out && ws,
-                 "cldice_fwd: null pointer");
-    RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "cldice_fwd: bad label dtype");
+    int rc = loss_view_check("cldice_fwd",
+                             logits && labels && delta && s && emin && dmax && skel_g && state && loss_out && ws,
+                             n > 0 && A > 0 && B > 0 && Z > 0, label_dtype, num_classes, 2);
+    if (rc) return rc;
     RU3D_REQUIRE(offsetof(CdState, bad_labels) == ru3d_loss_state_bad_labels_offset(),
                  "cldice_fwd: state layouts out of step");
-    CdClasses cl;
-    int rc = cd_classes("cldice_fwd", num_classes, classes, num_selected, &cl);
+    ClassList cl;
+    rc = class_list_check("cldice_fwd", num_classes, classes, num_selected, &cl);
     if (rc) return rc;
-    RU3D_REQUIRE(n > 0 && (int64_t)n * cl.K < ((int64_t)1 << 31), "cldice_fwd: bad batch");
+    RU3D_REQUIRE((int64_t)n * cl.K < ((int64_t)1 << 31), "cldice_fwd: bad batch");
     const int nvol = n * cl.K;
     rc = cd_check_geom("cldice_fwd", nvol, A, B, Z, iterations);
     if (rc) return rc;
@@ -623,7 +595,7 @@ extern "C" int ru3d_cldice_fwd(const float* logits, int64_t stride_n, int64_t st
     CdParams Pm;
     Pm.K = cl.K;
     Pm.smooth = smooth;
-    for (int k = 0; k < RU3D_MAX_CLASSES; k++) Pm.w[k] = (k < cl.K) ? (weight_v ? weight_v[cl.cls[k]] : 1.f) : 0.f;
+    fill_class_weights(Pm.w, weight_v, cl.K, cl.cls);
     hipLaunchKernelGGL(cd_finalize_kernel, dim3(1), dim3(CD_FIN_THREADS), 0, st, (const double*)part, blocks, Pm,
                        (CdState*)state, loss_out);
     return ru3d_check_launch("cldice_finalize");
@@ -636,13 +608,14 @@ extern "C" int ru3d_cldice_bwd(const float* logits, int64_t stride_n, int64_t st
                                const float* grad_out, float scale, int accumulate, float* dlogits, void* ws,
                                size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(logits && labels && delta && s && emin && dmax && skel_g && state && dlogits && ws,
-                 "cldice_bwd: null pointer");
-    RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "cldice_bwd: bad label dtype");
-    CdClasses cl;
-    int rc = cd_classes("cldice_bwd", num_classes, classes, num_selected, &cl);
+    int rc = loss_view_check("cldice_bwd",
+                             logits && labels && delta && s && emin && dmax && skel_g && state && dlogits && ws,
+                             n > 0 && A > 0 && B > 0 && Z > 0, label_dtype, num_classes, 2);
     if (rc) return rc;
-    RU3D_REQUIRE(n > 0 && (int64_t)n * cl.K < ((int64_t)1 << 31), "cldice_bwd: bad batch");
+    ClassList cl;
+    rc = class_list_check("cldice_bwd", num_classes, classes, num_selected, &cl);
+    if (rc) return rc;
+    RU3D_REQUIRE((int64_t)n * cl.K < ((int64_t)1 << 31), "cldice_bwd: bad batch");
     const int nvol = n * cl.K;
     rc = cd_check_geom("cldice_bwd", nvol, A, B, Z, iterations);
     if (rc) return rc;

@@ -150,14 +150,12 @@ __global__ __launch_bounds__(256) void ds_bwd_kernel(DsArgs A, float gamma, cons
     }
 }
 
-// the levels' block ranges: ceil(n v_l / per_block) blocks each, at most `cap` (a block then strides over its level)
+// the levels' block ranges: level l gets blocks_of(n v_l) blocks (a block strides over its level where that is capped);
+// the caller has made loss_view_check
 static int ds_fill_args(DsArgs& A, const ru3d_ds_level* levels, void* const* dlogits, int num_levels, const void* labels,
-                 int label_dtype, int n, int D, int H, int W, int per_block, int cap, const char* what) {
-    RU3D_REQUIRE(levels && labels, "%s: null pointer", what);
+                        int label_dtype, int n, int D, int H, int W, int (*blocks_of)(int64_t), const char* what) {
     RU3D_REQUIRE(num_levels >= 1 && num_levels <= RU3D_DS_MAX_LEVELS, "%s: %d levels (1 .. %d)", what, num_levels,
                  RU3D_DS_MAX_LEVELS);
-    RU3D_REQUIRE(n > 0 && D > 0 && H > 0 && W > 0, "%s: empty input", what);
-    RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "%s: bad label dtype", what);
     A.levels = num_levels;
     A.n = n;
     A.label_dtype = label_dtype;
@@ -196,26 +194,19 @@ static int ds_fill_args(DsArgs& A, const ru3d_ds_level* levels, void* const* dlo
         Lv.w = in.w;
         Lv.shift = in.shift;
         Lv.block0 = (int)next;
-        int64_t b = ((int64_t)n * Lv.v + per_block - 1) / per_block;
-        if (b > cap) b = cap;
-        if (b < 1) b = 1;
-        next += b;
+        next += blocks_of((int64_t)n * Lv.v);
     }
     A.nblocks = (int)next;
     return 0;
 }
 
-constexpr int DS_FWD_PER_BLOCK = 256 * 8, DS_FWD_CAP = 2048;      // loss_blocks() of loss.hip, per level
-constexpr int DS_BWD_PER_BLOCK = 256 * 2, DS_BWD_CAP = 8192;
+// the backward: 512 voxels a block (two trips of its 256 threads), at most 8192 blocks a level.  ceil(total / 512) is
+// ceil(ceil(total / 2) / 256), and it is at least 1 because the entry point has refused total < 1.
+static int ds_bwd_blocks(int64_t total) { return flat_bwd_blocks((total + 1) / 2, 8192); }
 
 static int ds_fwd_blocks(const ru3d_ds_level* levels, int num_levels, int n) {
     int64_t total = 0;
-    for (int l = 0; l < num_levels; l++) {
-        int64_t b = ((int64_t)n * levels[l].d * levels[l].h * levels[l].w + DS_FWD_PER_BLOCK - 1) / DS_FWD_PER_BLOCK;
-        if (b > DS_FWD_CAP) b = DS_FWD_CAP;
-        if (b < 1) b = 1;
-        total += b;
-    }
+    for (int l = 0; l < num_levels; l++) total += region_fwd_blocks((int64_t)n * levels[l].d * levels[l].h * levels[l].w);
     return (int)total;
 }
 
@@ -235,14 +226,13 @@ extern "C" int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, con
                                 float alpha, float beta, float smooth, float* block, void* state, float* loss_out,
                                 void* ws, size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(block && state && loss_out && ws, "ds_loss_fwd: null pointer");
-    RU3D_REQUIRE(num_classes >= 1 && num_classes <= RU3D_MAX_CLASSES, "ds_loss_fwd: %d classes unsupported (max %d)",
-                 num_classes, RU3D_MAX_CLASSES);
+    int rc = loss_view_check("ds_loss_fwd", levels && labels && block && state && loss_out && ws,
+                             n > 0 && D > 0 && H > 0 && W > 0, label_dtype, num_classes, 1);
+    if (rc) return rc;
     RU3D_REQUIRE(kind == RU3D_LOSS_HYBIRD || kind == RU3D_LOSS_DICELOSS || kind == RU3D_LOSS_FOCAL,
                  "ds_loss_fwd: bad kind %d (HYBIRD, DICELOSS or FOCAL)", kind);
     DsArgs A;
-    int rc = ds_fill_args(A, levels, nullptr, num_levels, labels, label_dtype, n, D, H, W, DS_FWD_PER_BLOCK, DS_FWD_CAP,
-                          "ds_loss_fwd");
+    rc = ds_fill_args(A, levels, nullptr, num_levels, labels, label_dtype, n, D, H, W, region_fwd_blocks, "ds_loss_fwd");
     if (rc) return rc;
     RU3D_REQUIRE(ws_bytes >= (size_t)A.nblocks * REGION_Q * sizeof(double),
                  "ds_loss_fwd: workspace too small");
@@ -260,7 +250,7 @@ extern "C" int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, con
     P.alpha = alpha;
     P.beta = beta;
     P.smooth = smooth;
-    for (int c = 0; c < RU3D_MAX_CLASSES; c++) P.w[c] = (c < num_classes) ? (weight_v ? weight_v[c] : 1.f) : 0.f;
+    fill_class_weights(P.w, weight_v, num_classes);
     for (int l = 0; l <= RU3D_DS_MAX_LEVELS; l++) P.blocks[l] = (l < num_levels) ? A.lev[l].block0 : A.nblocks;
     for (int l = 0; l < RU3D_DS_MAX_LEVELS; l++) P.nv[l] = (l < num_levels) ? (double)n * (double)A.lev[l].v : 1.0;
     hipLaunchKernelGGL(ds_finalize_kernel, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)ws, P, block,
@@ -272,11 +262,11 @@ extern "C" int ru3d_ds_loss_bwd(const ru3d_ds_level* levels, void* const* dlogit
                                 int label_dtype, int n, int D, int H, int W, int num_classes, float gamma,
                                 const void* state, const float* grad_out, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(state && dlogits, "ds_loss_bwd: null pointer");
-    RU3D_REQUIRE(num_classes >= 1 && num_classes <= RU3D_MAX_CLASSES, "ds_loss_bwd: %d classes unsupported", num_classes);
+    int rc = loss_view_check("ds_loss_bwd", levels && labels && state && dlogits, n > 0 && D > 0 && H > 0 && W > 0,
+                             label_dtype, num_classes, 1);
+    if (rc) return rc;
     DsArgs A;
-    int rc = ds_fill_args(A, levels, dlogits, num_levels, labels, label_dtype, n, D, H, W, DS_BWD_PER_BLOCK, DS_BWD_CAP,
-                          "ds_loss_bwd");
+    rc = ds_fill_args(A, levels, dlogits, num_levels, labels, label_dtype, n, D, H, W, ds_bwd_blocks, "ds_loss_bwd");
     if (rc) return rc;
     hipStream_t st = as_stream(stream);
 #define CALL(CC) \

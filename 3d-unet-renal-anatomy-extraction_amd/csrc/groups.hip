@@ -39,19 +39,11 @@ struct GroupState {
 
 extern "C" size_t ru3d_group_loss_state_bytes(void) { return sizeof(GroupState); }
 
-static int group_blocks(int n, int64_t v) {
-    int64_t total = (int64_t)n * v;
-    int64_t b = (total + 256 * 8 - 1) / (256 * 8);
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // a partial row: the REGION_Q quantities of the region losses (rows [blocks][REGION_Q], what region_reduce_rows reads),
 // then the slot of the counted voxels (a second plane [blocks] behind the rows)
 extern "C" size_t ru3d_group_loss_workspace_bytes(int n, int64_t v, int num_groups) {
     (void)num_groups;
-    return (size_t)group_blocks(n, v) * (REGION_Q + 1) * sizeof(double);
+    return (size_t)region_fwd_blocks((int64_t)n * v) * (REGION_Q + 1) * sizeof(double);
 }
 
 // what one channel of one voxel needs, from the logit: p = sigmoid(z), om = 1 - p (each rounded on its own, neither is
@@ -200,10 +192,9 @@ __global__ __launch_bounds__(256) void group_bwd_kernel(const float* __restrict_
     }
 }
 
+// num_groups has been checked (1 .. RU3D_MAX_CLASSES)
 static int group_table_check(const char* who, int num_groups, const uint8_t* table, int num_labels, int has_ignore,
                              int ignore_label, GroupTable* out) {
-    RU3D_REQUIRE(num_groups >= 1 && num_groups <= RU3D_MAX_CLASSES, "%s: %d groups unsupported (1..%d)", who, num_groups,
-                 RU3D_MAX_CLASSES);
     RU3D_REQUIRE(num_labels >= 1 && num_labels <= RU3D_GROUP_MAX_LABELS, "%s: %d label values unsupported (1..%d)", who,
                  num_labels, RU3D_GROUP_MAX_LABELS);
     RU3D_REQUIRE(table, "%s: null membership table", who);
@@ -224,16 +215,16 @@ extern "C" int ru3d_group_loss_fwd(const float* logits, int64_t stride_n, int64_
                                    float gamma, const float* weight_v, float alpha, float beta, float smooth,
                                    void* state, float* loss_out, void* ws, size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(logits && labels && state && loss_out && ws, "group_loss_fwd: null pointer");
-    RU3D_REQUIRE(n > 0 && v > 0, "group_loss_fwd: empty input");
+    int rc = loss_view_check("group_loss_fwd", logits && labels && state && loss_out && ws, n > 0 && v > 0, label_dtype,
+                             num_groups, 1, "groups");
+    if (rc) return rc;
     GroupTable tab;
-    int rc = group_table_check("group_loss_fwd", num_groups, table, num_labels, has_ignore, ignore_label, &tab);
+    rc = group_table_check("group_loss_fwd", num_groups, table, num_labels, has_ignore, ignore_label, &tab);
     if (rc) return rc;
     RU3D_REQUIRE(kind >= 0 && kind <= 3, "group_loss_fwd: bad kind %d", kind);
-    RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "group_loss_fwd: bad label dtype");
     RU3D_REQUIRE(ws_bytes >= ru3d_group_loss_workspace_bytes(n, v, num_groups), "group_loss_fwd: workspace too small");
     hipStream_t st = as_stream(stream);
-    const int blocks = group_blocks(n, v);
+    const int blocks = region_fwd_blocks((int64_t)n * v);
     double* part = (double*)ws;
     double* counted_part = part + (size_t)blocks * REGION_Q;
 #define CALL(KK)                                                                                                     \
@@ -250,7 +241,7 @@ extern "C" int ru3d_group_loss_fwd(const float* logits, int64_t stride_n, int64_
     P.alpha = alpha;
     P.beta = beta;
     P.smooth = smooth;
-    for (int k = 0; k < RU3D_MAX_CLASSES; k++) P.w[k] = (k < num_groups) ? (weight_v ? weight_v[k] : 1.f) : 0.f;
+    fill_class_weights(P.w, weight_v, num_groups);
     hipLaunchKernelGGL(group_finalize_kernel, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)part,
                        (const double*)counted_part, blocks, P, (GroupState*)state, loss_out);
     return ru3d_check_launch("group_loss_finalize");
@@ -262,26 +253,20 @@ extern "C" int ru3d_group_loss_bwd(const float* logits, int64_t stride_n, int64_
                                    const void* state, const float* grad_out, void* dlogits, int dlogits_dtype,
                                    void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(logits && labels && state && dlogits, "group_loss_bwd: null pointer");
-    RU3D_REQUIRE(n > 0 && v > 0, "group_loss_bwd: empty input");
-    GroupTable tab;
-    int rc = group_table_check("group_loss_bwd", num_groups, table, num_labels, has_ignore, ignore_label, &tab);
+    int rc = loss_view_check("group_loss_bwd", logits && labels && state && dlogits, n > 0 && v > 0, label_dtype,
+                             num_groups, 1, "groups");
     if (rc) return rc;
-    RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "group_loss_bwd: bad label dtype");
+    GroupTable tab;
+    rc = group_table_check("group_loss_bwd", num_groups, table, num_labels, has_ignore, ignore_label, &tab);
+    if (rc) return rc;
     RU3D_REQUIRE(dlogits_dtype == RU3D_F32 || dlogits_dtype == RU3D_BF16, "group_loss_bwd: bad dlogits dtype");
     hipStream_t st = as_stream(stream);
-    const int64_t total = (int64_t)n * v;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-#define CALL(KK)                                                                                                      \
-    if (dlogits_dtype == RU3D_F32)                                                                                    \
-        hipLaunchKernelGGL((group_bwd_kernel<KK, float>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, \
-                           stride_v, labels, label_dtype, n, v, gamma, tab, num_labels, has_ignore, ignore_label,     \
-                           (const GroupState*)state, grad_out, (float*)dlogits);                                      \
-    else                                                                                                              \
-        hipLaunchKernelGGL((group_bwd_kernel<KK, bf16>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c,  \
-                           stride_v, labels, label_dtype, n, v, gamma, tab, num_labels, has_ignore, ignore_label,     \
-                           (const GroupState*)state, grad_out, (bf16*)dlogits)
-    RU3D_DISPATCH_C(1, num_groups, CALL)
+    const int blocks = flat_bwd_blocks((int64_t)n * v, 8192);
+#define CALL(KK, TG)                                                                                                 \
+    hipLaunchKernelGGL((group_bwd_kernel<KK, TG>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, stride_v, \
+                       labels, label_dtype, n, v, gamma, tab, num_labels, has_ignore, ignore_label,                 \
+                       (const GroupState*)state, grad_out, (TG*)dlogits)
+    RU3D_DISPATCH_C_DZ(1, num_groups, dlogits_dtype, CALL)
 #undef CALL
     return ru3d_check_launch("group_loss_bwd");
 }

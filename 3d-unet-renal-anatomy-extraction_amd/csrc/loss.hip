@@ -25,17 +25,9 @@ extern "C" size_t ru3d_loss_state_bytes(int num_classes) {
 
 extern "C" size_t ru3d_loss_state_bad_labels_offset(void) { return offsetof(LossState, r) + offsetof(RegionCoef, bad_labels); }
 
-static int loss_blocks(int n, int64_t v) {
-    int64_t total = (int64_t)n * v;
-    int64_t b = (total + 256 * 8 - 1) / (256 * 8);
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 extern "C" size_t ru3d_loss_workspace_bytes(int n, int64_t v, int num_classes) {
     (void)num_classes;
-    return (size_t)loss_blocks(n, v) * REGION_Q * sizeof(double);
+    return (size_t)region_fwd_blocks((int64_t)n * v) * REGION_Q * sizeof(double);
 }
 
 template <int C>
@@ -100,21 +92,19 @@ extern "C" int ru3d_loss_fwd(const float* logits, int64_t stride_n, int64_t stri
                              float gamma, const float* weight_v, float alpha, float beta, float smooth, void* state,
                              float* loss_out, void* ws, size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(logits && labels && state && loss_out && ws, "loss_fwd: null pointer");
-    RU3D_REQUIRE(n > 0 && v > 0, "loss_fwd: empty input");
-    RU3D_REQUIRE(num_classes >= 1 && num_classes <= RU3D_MAX_CLASSES, "loss_fwd: %d classes unsupported (max %d)",
-                 num_classes, RU3D_MAX_CLASSES);
+    int rc = loss_view_check("loss_fwd", logits && labels && state && loss_out && ws, n > 0 && v > 0, label_dtype,
+                             num_classes, 1);
+    if (rc) return rc;
     RU3D_REQUIRE(kind >= 0 && kind <= 3, "loss_fwd: bad kind %d", kind);
-    RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "loss_fwd: bad label dtype");
     RU3D_REQUIRE(ws_bytes >= ru3d_loss_workspace_bytes(n, v, num_classes), "loss_fwd: workspace too small");
     hipStream_t st = as_stream(stream);
-    const int blocks = loss_blocks(n, v);
+    const int blocks = region_fwd_blocks((int64_t)n * v);
 #define CALL(CC)                                                                                                    \
     hipLaunchKernelGGL(loss_sums_kernel<CC>, dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, stride_v, \
                        labels, label_dtype, n, v, gamma, (double*)ws)
     RU3D_DISPATCH_C(1, num_classes, CALL)
 #undef CALL
-    int rc = ru3d_check_launch("loss_sums");
+    rc = ru3d_check_launch("loss_sums");
     if (rc) return rc;
     LossParams P;
     P.kind = kind;
@@ -125,7 +115,7 @@ extern "C" int ru3d_loss_fwd(const float* logits, int64_t stride_n, int64_t stri
     P.alpha = alpha;
     P.beta = beta;
     P.smooth = smooth;
-    for (int c = 0; c < RU3D_MAX_CLASSES; c++) P.w[c] = (c < num_classes) ? (weight_v ? weight_v[c] : 1.f) : 0.f;
+    fill_class_weights(P.w, weight_v, num_classes);
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)ws, blocks, P,
                        (LossState*)state, loss_out);
     return ru3d_check_launch("loss_finalize");
@@ -136,24 +126,15 @@ extern "C" int ru3d_loss_bwd(const float* logits, int64_t stride_n, int64_t stri
                              const void* state, const float* grad_out, void* dlogits, int dlogits_dtype,
                              void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(logits && labels && state && dlogits, "loss_bwd: null pointer");
-    RU3D_REQUIRE(n > 0 && v > 0, "loss_bwd: empty input");
-    RU3D_REQUIRE(num_classes >= 1 && num_classes <= RU3D_MAX_CLASSES, "loss_bwd: %d classes unsupported",
-                 num_classes);
+    int rc = loss_view_check("loss_bwd", logits && labels && state && dlogits, n > 0 && v > 0, label_dtype, num_classes, 1);
+    if (rc) return rc;
     RU3D_REQUIRE(dlogits_dtype == RU3D_F32 || dlogits_dtype == RU3D_BF16, "loss_bwd: bad dlogits dtype");
     hipStream_t st = as_stream(stream);
-    int64_t total = (int64_t)n * v;
-    int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-#define CALL(CC)                                                                                                    \
-    if (dlogits_dtype == RU3D_F32)                                                                                  \
-        hipLaunchKernelGGL((loss_bwd_kernel<CC, float>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, \
-                           stride_v, labels, label_dtype, n, v, gamma, (const LossState*)state, grad_out,           \
-                           (float*)dlogits);                                                                        \
-    else                                                                                                            \
-        hipLaunchKernelGGL((loss_bwd_kernel<CC, bf16>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c,  \
-                           stride_v, labels, label_dtype, n, v, gamma, (const LossState*)state, grad_out,           \
-                           (bf16*)dlogits)
-    RU3D_DISPATCH_C(1, num_classes, CALL)
+    const int blocks = flat_bwd_blocks((int64_t)n * v, 8192);
+#define CALL(CC, TG)                                                                                                  \
+    hipLaunchKernelGGL((loss_bwd_kernel<CC, TG>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, stride_v, \
+                       labels, label_dtype, n, v, gamma, (const LossState*)state, grad_out, (TG*)dlogits)
+    RU3D_DISPATCH_C_DZ(1, num_classes, dlogits_dtype, CALL)
 #undef CALL
     return ru3d_check_launch("loss_bwd");
 }

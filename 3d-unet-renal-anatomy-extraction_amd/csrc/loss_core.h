@@ -1,29 +1,37 @@
-// The one definition of what the fused losses share (loss.hip, deepsup.hip, cldice.hip, boundary.hip): the class limit
-// and dispatch, the label load, the two softmax forms, and the region (softmax + focal + Tversky) loss piece by piece -
-// per-voxel accumulate, block epilogue, fixed-order reduction of the partial rows, sums -> loss and backward
-// coefficients, per-voxel backward.  The formulas are restated in loss.hip's header.  Include this file beside common.h,
-// BEFORE any `#pragma clang fp contract`: the multiply-add chains of the accumulate and of the backward are compiled
-// under the default contraction.
+// The one definition of what the fused losses share (loss.hip, deepsup.hip, groups.hip, topk.hip, cldice.hip,
+// boundary.hip): the class limit and dispatch, the label load, the two softmax forms, and the region (softmax + focal +
+// Tversky) loss piece by piece - per-voxel accumulate, block epilogue, fixed-order reduction of the partial rows, sums ->
+// loss and backward coefficients, per-voxel backward - and, at the end, the host side of their entry points: grid rules,
+// weight fill, argument checks, class list.  The formulas are restated in loss.hip's header.  Include this file beside
+// common.h, BEFORE any `#pragma clang fp contract`: the multiply-add chains of the accumulate and of the backward are
+// compiled under the default contraction.
 #pragma once
 #include "common.h"
 #include <stddef.h>
 
 #define RU3D_MAX_CLASSES 8
 
-// CALL(C) with the class count as a constant, MIN (1 or 2) .. 8; a file that rejects C == 1 passes MIN = 2 and gets no
-// C = 1 kernel
-#define RU3D_DISPATCH_C1_FROM_1(CALL) case 1: CALL(1); break;
-#define RU3D_DISPATCH_C1_FROM_2(CALL)
-#define RU3D_DISPATCH_C(MIN, C, CALL)      \
-    switch (C) {                           \
-        RU3D_DISPATCH_C1_FROM_##MIN(CALL)  \
-        case 2: CALL(2); break;            \
-        case 3: CALL(3); break;            \
-        case 4: CALL(4); break;            \
-        case 5: CALL(5); break;            \
-        case 6: CALL(6); break;            \
-        case 7: CALL(7); break;            \
-        default: CALL(8); break;           \
+// CALL(C, ...) with the class count as a constant, MIN (1 or 2) .. 8; a file that rejects C == 1 passes MIN = 2 and gets
+// no C = 1 kernel.  What follows CALL is handed on to it.
+#define RU3D_DISPATCH_C1_FROM_1(CALL, ...) case 1: CALL(1, ##__VA_ARGS__); break;
+#define RU3D_DISPATCH_C1_FROM_2(CALL, ...)
+#define RU3D_DISPATCH_C(MIN, C, CALL, ...)                   \
+    switch (C) {                                             \
+        RU3D_DISPATCH_C1_FROM_##MIN(CALL, ##__VA_ARGS__)     \
+        case 2: CALL(2, ##__VA_ARGS__); break;               \
+        case 3: CALL(3, ##__VA_ARGS__); break;               \
+        case 4: CALL(4, ##__VA_ARGS__); break;               \
+        case 5: CALL(5, ##__VA_ARGS__); break;               \
+        case 6: CALL(6, ##__VA_ARGS__); break;               \
+        case 7: CALL(7, ##__VA_ARGS__); break;               \
+        default: CALL(8, ##__VA_ARGS__); break;              \
+    }
+// CALL(C, TG) with TG the element type of a dlogits of DTYPE (RU3D_F32, else this build's 16-bit type)
+#define RU3D_DISPATCH_C_DZ(MIN, C, DTYPE, CALL)  \
+    if ((DTYPE) == RU3D_F32) {                   \
+        RU3D_DISPATCH_C(MIN, C, CALL, float)     \
+    } else {                                     \
+        RU3D_DISPATCH_C(MIN, C, CALL, bf16)      \
     }
 
 __device__ __forceinline__ int load_label(const void* labels, int label_dtype, int64_t i) {
@@ -264,3 +272,64 @@ struct RegionGrad {
                                                     : u[c] - p[c] * su;
     }
 };
+
+// --------------------------------------------------------------------------- host side of the entry points
+// grid of a forward over `total` voxels: 8 voxels a thread, 256 threads, at most 2048 blocks (a block then strides)
+static inline int region_fwd_blocks(int64_t total) {
+    int64_t b = (total + 256 * 8 - 1) / (256 * 8);
+    if (b > 2048) b = 2048;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+// grid of a backward over `total` voxels: one voxel a thread, 256 threads, at most `cap` blocks
+static inline int flat_bwd_blocks(int64_t total, int cap) {
+    const int64_t b = (total + 255) / 256;
+    return (int)(b < cap ? b : cap);
+}
+
+// w[k] = weight_v[index ? index[k] : k] for k < count (1 where the caller passed no weights), 0 behind
+static inline void fill_class_weights(float (&w)[RU3D_MAX_CLASSES], const float* weight_v, int count,
+                                      const int* index = nullptr) {
+    for (int k = 0; k < RU3D_MAX_CLASSES; k++) w[k] = (k < count) ? (weight_v ? weight_v[index ? index[k] : k] : 1.f) : 0.f;
+}
+
+// The checks every entry point makes of its logits / labels view, in this order.  who: the entry point, for the
+// message; pointers: the conjunction of its pointer arguments; nonempty: of its extents; count: classes (or `noun`),
+// min_count .. RU3D_MAX_CLASSES.
+static inline int loss_view_check(const char* who, bool pointers, bool nonempty, int label_dtype, int count,
+                                  int min_count, const char* noun = "classes") {
+    RU3D_REQUIRE(pointers, "%s: null pointer", who);
+    RU3D_REQUIRE(nonempty, "%s: empty input", who);
+    RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "%s: bad label dtype", who);
+    RU3D_REQUIRE(count >= min_count && count <= RU3D_MAX_CLASSES, "%s: %d %s unsupported (%d .. %d)", who, count, noun,
+                 min_count, RU3D_MAX_CLASSES);
+    return 0;
+}
+
+// the classes a loss is restricted to (clDice, boundary); goes to kernels by value
+struct ClassList {
+    int K;                          // selected classes
+    int cls[RU3D_MAX_CLASSES];      // slot -> class
+    int slot[RU3D_MAX_CLASSES];     // class -> slot, -1 when not selected
+};
+
+// num_classes has been checked (2 .. RU3D_MAX_CLASSES)
+static inline int class_list_check(const char* what, int num_classes, const int* classes, int num_selected,
+                                   ClassList* cl) {
+    RU3D_REQUIRE(classes, "%s: null pointer (classes)", what);
+    RU3D_REQUIRE(num_selected >= 1 && num_selected <= num_classes, "%s: bad class selection (num_selected = %d, 1 .. %d)",
+                 what, num_selected, num_classes);
+    cl->K = num_selected;
+    for (int c = 0; c < RU3D_MAX_CLASSES; c++) {
+        cl->cls[c] = 0;
+        cl->slot[c] = -1;
+    }
+    for (int k = 0; k < num_selected; k++) {
+        const int c = classes[k];
+        RU3D_REQUIRE(c >= 0 && c < num_classes && cl->slot[c] < 0, "%s: class %d out of range or selected twice", what, c);
+        cl->cls[k] = c;
+        cl->slot[c] = k;
+    }
+    return 0;
+}

@@ -333,13 +333,9 @@ static_assert(offsetof(TopKState, r) == 0 && sizeof(TopKState) == 400, "the stat
 
 extern "C" size_t ru3d_topk_loss_state_bytes(void) { return sizeof(TopKState); }
 
-static int tk_loss_blocks(int n, int64_t v) {
-    int64_t b = ((int64_t)n * v + 256 * 8 - 1) / (256 * 8);
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
+static size_t tk_region_bytes(int n, int64_t v) {
+    return bv_align((size_t)region_fwd_blocks((int64_t)n * v) * REGION_Q * sizeof(double));
 }
-static size_t tk_region_bytes(int n, int64_t v) { return bv_align((size_t)tk_loss_blocks(n, v) * REGION_Q * sizeof(double)); }
 
 extern "C" size_t ru3d_topk_loss_workspace_bytes(int n, int64_t v, int num_classes) {
     (void)num_classes;
@@ -472,18 +468,16 @@ static int tk_loss_forward(const float* logits, int64_t stride_n, int64_t stride
                            int label_dtype, int n, int64_t v, int num_classes, int64_t K, int with_dice,
                            const float* weight_v, float alpha, float beta, float smooth, float ce_weight, float* ce,
                            void* state, float* loss_out, void* ws, size_t ws_bytes, void* stream, hipEvent_t* ev) {
-    RU3D_REQUIRE(logits && labels && ce && state && loss_out && ws, "topk_loss_fwd: null pointer");
-    RU3D_REQUIRE(n > 0 && v > 0, "topk_loss_fwd: empty input");
-    RU3D_REQUIRE(num_classes >= 2 && num_classes <= RU3D_MAX_CLASSES, "topk_loss_fwd: %d classes unsupported (2 .. %d)",
-                 num_classes, RU3D_MAX_CLASSES);
-    RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "topk_loss_fwd: bad label dtype");
+    int rc = loss_view_check("topk_loss_fwd", logits && labels && ce && state && loss_out && ws, n > 0 && v > 0,
+                             label_dtype, num_classes, 2);
+    if (rc) return rc;
     const int64_t m = (int64_t)n * v;
     RU3D_REQUIRE(K >= 1 && K <= m, "topk_loss_fwd: K = %lld of %lld voxels", (long long)K, (long long)m);
     RU3D_REQUIRE(((uintptr_t)ce & 3) == 0 && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)state & 7) == 0,
                  "topk_loss_fwd: ce, workspace or state misaligned");
     RU3D_REQUIRE(ws_bytes >= ru3d_topk_loss_workspace_bytes(n, v, num_classes), "topk_loss_fwd: workspace too small");
     hipStream_t st = as_stream(stream);
-    const int blocks = tk_loss_blocks(n, v);
+    const int blocks = region_fwd_blocks(m);
     double* part = (double*)ws;
     const TkWorkspace w = tk_carve((char*)ws + tk_region_bytes(n, v), m);
     if (ev) (void)hipEventRecord(*ev++, st);
@@ -495,7 +489,7 @@ static int tk_loss_forward(const float* logits, int64_t stride_n, int64_t stride
     RU3D_DISPATCH_C(2, num_classes, CALL)
 #undef CALL
     if (ev) (void)hipEventRecord(*ev++, st);
-    int rc = ru3d_check_launch("topk_loss_ce");
+    rc = ru3d_check_launch("topk_loss_ce");
     if (rc) return rc;
     tk_launch_levels(ce, m, K, w, st, ev);
     if (ev) ev += 2 * (TK_LEVELS - 1);
@@ -510,7 +504,7 @@ static int tk_loss_forward(const float* logits, int64_t stride_n, int64_t stride
     P.beta = beta;
     P.smooth = smooth;
     P.ce_weight = ce_weight;
-    for (int c = 0; c < RU3D_MAX_CLASSES; c++) P.w[c] = (c < num_classes) ? (weight_v ? weight_v[c] : 1.f) : 0.f;
+    fill_class_weights(P.w, weight_v, num_classes);
     hipLaunchKernelGGL(tk_loss_finalize_kernel, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)part, blocks,
                        (const double*)w.rows, P, (const TkSelect*)w.st,
                        (const tk_u64*)(w.hist + (size_t)(TK_LEVELS - 1) * TK_BINS), (TopKState*)state, loss_out);
@@ -562,25 +556,16 @@ extern "C" int ru3d_topk_loss_bwd(const float* logits, int64_t stride_n, int64_t
                                   const float* ce, const void* state, const float* grad_out, void* dlogits,
                                   int dlogits_dtype, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(logits && labels && ce && state && dlogits, "topk_loss_bwd: null pointer");
-    RU3D_REQUIRE(n > 0 && v > 0, "topk_loss_bwd: empty input");
-    RU3D_REQUIRE(num_classes >= 2 && num_classes <= RU3D_MAX_CLASSES, "topk_loss_bwd: %d classes unsupported (2 .. %d)",
-                 num_classes, RU3D_MAX_CLASSES);
-    RU3D_REQUIRE(label_dtype == RU3D_LABEL_I64 || label_dtype == RU3D_LABEL_U8, "topk_loss_bwd: bad label dtype");
+    int rc = loss_view_check("topk_loss_bwd", logits && labels && ce && state && dlogits, n > 0 && v > 0, label_dtype,
+                             num_classes, 2);
+    if (rc) return rc;
     RU3D_REQUIRE(dlogits_dtype == RU3D_F32 || dlogits_dtype == RU3D_BF16, "topk_loss_bwd: bad dlogits dtype");
     hipStream_t st = as_stream(stream);
-    const int64_t total = (int64_t)n * v;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-#define CALL(CC)                                                                                                       \
-    if (dlogits_dtype == RU3D_F32)                                                                                     \
-        hipLaunchKernelGGL((tk_bwd_kernel<CC, float>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c,     \
-                           stride_v, labels, label_dtype, n, v, with_dice, ce, (const TopKState*)state, grad_out,      \
-                           (float*)dlogits);                                                                           \
-    else                                                                                                               \
-        hipLaunchKernelGGL((tk_bwd_kernel<CC, bf16>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c,      \
-                           stride_v, labels, label_dtype, n, v, with_dice, ce, (const TopKState*)state, grad_out,      \
-                           (bf16*)dlogits)
-    RU3D_DISPATCH_C(2, num_classes, CALL)
+    const int blocks = flat_bwd_blocks((int64_t)n * v, 8192);
+#define CALL(CC, TG)                                                                                                   \
+    hipLaunchKernelGGL((tk_bwd_kernel<CC, TG>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, stride_v,   \
+                       labels, label_dtype, n, v, with_dice, ce, (const TopKState*)state, grad_out, (TG*)dlogits)
+    RU3D_DISPATCH_C_DZ(2, num_classes, dlogits_dtype, CALL)
 #undef CALL
     return ru3d_check_launch("topk_loss_bwd");
 }

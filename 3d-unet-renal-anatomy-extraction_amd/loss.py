@@ -152,42 +152,82 @@ def _flat_strides(x):
     return x.stride(0), x.stride(1), sv
 
 
-def _loss_operands(input, target, check_labels, one_hot=True):
-    """What every fused loss does to its operands before it launches: float32 logits with a single spatial stride,
-    contiguous int64 / uint8 labels, and the blocking label check where one is asked for.  one_hot=False (the group
-    losses): the labels are no class indices of the C channels, so neither that check nor the C == 1 rule applies."""
-    N.require_device(input, "loss input")
-    if target.device != input.device:
-        raise N.Ru3dError("loss: target is on %s but input on %s" % (target.device, input.device))
-    if input.dim() < 2:
-        raise N.Ru3dError("loss: input must be (N, C, d1, ..., dn)")
-    n, c = input.shape[0], input.shape[1]
-    if c > N.MAX_CLASSES:
-        raise N.Ru3dError("loss: %d classes (max %d)" % (c, N.MAX_CLASSES))
-    if tuple(target.shape) != (n,) + tuple(input.shape[2:]):
-        raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape),
-                                                                             tuple(input.shape)))
-    x = input.detach()
+def _view(x, st, lab, lab_code):
+    """How every entry point begins: logits, stride_n, stride_c, stride_v, labels, label_dtype."""
+    return ptr(x), st[0], st[1], st[2], ptr(lab), lab_code
+
+
+class _Operands:
+    """What _loss_operands prepares.  x, st: the float32 logits and their flat strides (tuples of them, one per level,
+    when a list of logits came in, and no view then); checked: the labels were range-checked before the launch.  A ctx
+    keeps x and lab by save_for_backward and meta() beside them; its backward makes the _view of those again."""
+    __slots__ = ("x", "lab", "st", "lab_code", "n", "c", "v", "checked", "view")
+
+    def __init__(self, x, lab, st, lab_code, n, c, v, checked):
+        self.x, self.lab, self.st, self.lab_code = x, lab, st, lab_code
+        self.n, self.c, self.v, self.checked = n, c, v, checked
+        self.view = None if isinstance(x, tuple) else _view(x, st, lab, lab_code)
+
+    def meta(self):
+        return self.st, self.lab_code, self.n, self.v, self.c
+
+
+def _flat_logits(x):
+    """Detached float32 logits whose spatial dims share one stride (a copy only where they do not), and the strides."""
+    x = x.detach()
     if x.dtype != torch.float32:
         x = x.float()
     st = _flat_strides(x)
     if st is None:
         x = x.contiguous()
         st = _flat_strides(x)
-    v = 1
-    for s in x.shape[2:]:
-        v *= s
-    if target.dtype == torch.int64:
-        lab, lab_code = target.contiguous(), N.LABEL_I64
-    elif target.dtype == torch.uint8:
-        lab, lab_code = target.contiguous(), N.LABEL_U8
+    return x, st
+
+
+def _label_operand(target):
+    """Contiguous int64 / uint8 labels and their ABI code; any other dtype goes to int64."""
+    if target.dtype in (torch.int64, torch.uint8):
+        lab = target.contiguous()
     else:
-        lab, lab_code = target.long().contiguous(), N.LABEL_I64
-    if one_hot and (check_labels or c == 1):
+        lab = target.long().contiguous()
+    return lab, (N.LABEL_U8 if lab.dtype == torch.uint8 else N.LABEL_I64)
+
+
+def _operand_parts(input, target, check_labels, one_hot):
+    """What every fused loss does to its operands before it launches: float32 logits with a single spatial stride,
+    contiguous int64 / uint8 labels, and the blocking label check where one is asked for.  input: one (N, C, d1, ..., dn)
+    tensor, or - deep supervision - the list of the levels' tensors, finest first: the labels belong to the first, and x
+    and st come back as tuples.  one_hot=False (the group losses): the labels are no class indices of the C channels, so
+    neither that check nor the C == 1 rule applies; check_labels then says that the caller has checked them itself."""
+    many = isinstance(input, (list, tuple))
+    first = input[0] if many else input
+    N.require_device(first, "loss input")
+    if target.device != first.device:
+        raise N.Ru3dError("loss: target is on %s but input on %s" % (target.device, first.device))
+    if first.dim() < 2:
+        raise N.Ru3dError("loss: input must be (N, C, d1, ..., dn)")
+    n, c = first.shape[0], first.shape[1]
+    if c > N.MAX_CLASSES:
+        raise N.Ru3dError("loss: %d classes (max %d)" % (c, N.MAX_CLASSES))
+    if tuple(target.shape) != (n,) + tuple(first.shape[2:]):
+        raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape),
+                                                                             tuple(first.shape)))
+    x, st = zip(*[_flat_logits(level) for level in input]) if many else _flat_logits(input)
+    v = 1
+    for s in first.shape[2:]:
+        v *= s
+    lab, lab_code = _label_operand(target)
+    checked = bool(check_labels or (one_hot and c == 1))
+    if one_hot and checked:
         # reference: F.one_hot(target, C) raises for labels >= C (always hit by C == 1 with labels {0,1})
         if lab.numel() and (int(lab.max()) >= c or int(lab.min()) < 0):
             raise RuntimeError(_BAD_LABELS)
-    return x, st, lab, lab_code, n, c, v
+    return x, lab, st, lab_code, n, c, v, checked
+
+
+def _loss_operands(input, target, check_labels, one_hot=True):
+    """_operand_parts as the object the shared helpers take."""
+    return _Operands(*_operand_parts(input, target, check_labels, one_hot))
 
 
 def _weight_array(weight_v, c):
@@ -198,43 +238,93 @@ def _weight_array(weight_v, c):
     return (N.ctypes.c_float * c)(*[float(w) for w in weight_v])
 
 
+def _forward_scaffold(dev, state_bytes, ws_bytes, weight_v, c, verdict=True):
+    """What every forward does between its operands and its ABI call: an earlier call's verdict on its labels, if it has
+    landed (no wait; verdict=False: the second leg of a mixed loss, whose first has asked); a state block and the 0-dim
+    float32 output; the workspace; weight_v as the pointer the ABI takes (None: all ones)."""
+    if verdict:
+        raise_on_bad_labels()
+    state = torch.empty(state_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    ws = N.workspace(ws_bytes, dev)
+    wv = _weight_array(weight_v, c)
+    return state, out, ws, (N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None)
+
+
+def _note_state(ops, state, other=None, offset=None):
+    """The one rule of the deferred label check: a forward whose labels were not checked before the launch queues the
+    read-back of its count, from `state`, or from `other` where state is None (a mixed loss: its Hybird leg's state
+    where it has one, else its own).  offset: where the state keeps the count, when not where ru3d_loss_fwd's does (deep
+    supervision: inside level 0's block)."""
+    if ops.checked:
+        return
+    if state is None:
+        state = other
+    _note_label_flag(state if offset is None else state[offset - _BAD_OFF[0]:])
+
+
+def _upstream(gout, dev):
+    """The upstream gradient of a 0-dim loss as one contiguous float32 on dev."""
+    g = gout.detach()
+    if g.dtype != torch.float32 or g.device != dev:
+        g = g.to(device=dev, dtype=torch.float32)
+    N.note_device(dev)
+    return g.reshape(1).contiguous()
+
+
+def _empty_grad(x):
+    """An uninitialised gradient with the strides of the logits x."""
+    dz = torch.empty_like(x)   # preserve_format: same (dense) strides as the logits
+    if dz.stride() != x.stride():
+        dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
+    return dz
+
+
+def _backward_prologue(gout, x):
+    """(g, dz) of a backward: _upstream and _empty_grad (deep supervision takes the one once and the other per level)."""
+    return _upstream(gout, x.device), _empty_grad(x)
+
+
+def _backward_epilogue(dz, in_dtype, others=None):
+    """dz rounded once to the logits' dtype.  With `others`: what a Function whose first input is the logits returns -
+    that gradient, then None for each of its other inputs."""
+    if in_dtype != torch.float32:
+        dz = dz.to(in_dtype)
+    return dz if others is None else (dz,) + (None,) * others
+
+
+def _hybird_forward(ops, kind, gamma, weight_v, alpha, beta, smooth):
+    """ru3d_loss_fwd of `kind` on prepared operands -> (state, 0-dim loss)."""
+    state, out, ws, wv = _forward_scaffold(ops.x.device, N.lib.ru3d_loss_state_bytes(ops.c),
+                                           N.lib.ru3d_loss_workspace_bytes(ops.n, ops.v, ops.c), weight_v, ops.c)
+    check(N.lib.ru3d_loss_fwd(*ops.view, ops.n, ops.v, ops.c, kind, float(gamma), wv, float(alpha),
+                              float(beta), float(smooth), ptr(state), ptr(out), ptr(ws), ws.numel(), stream()),
+          "loss_fwd")
+    return state, out
+
+
+def _hybird_backward(view, n, v, c, gamma, state, g, dz):
+    """ru3d_loss_bwd: dz = g * d loss / d logits from the state a _hybird_forward left."""
+    check(N.lib.ru3d_loss_bwd(*view, n, v, c, gamma, ptr(state), ptr(g), ptr(dz), N.F32, stream()), "loss_bwd")
+
+
 class _FusedLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, target, kind, gamma, weight_v, alpha, beta, smooth, check_labels):
-        x, st, lab, lab_code, n, c, v = _loss_operands(input, target, check_labels)
-        raise_on_bad_labels()          # an earlier call's verdict, if it has landed (no wait)
-        dev = x.device
-        state = torch.empty(N.lib.ru3d_loss_state_bytes(c), dtype=torch.uint8, device=dev)
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        ws = N.workspace(N.lib.ru3d_loss_workspace_bytes(n, v, c), dev)
-        wv = _weight_array(weight_v, c)
-        check(N.lib.ru3d_loss_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, kind, float(gamma),
-                                  N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None, float(alpha),
-                                  float(beta), float(smooth), ptr(state), ptr(out), ptr(ws), ws.numel(), stream()),
-              "loss_fwd")
-        if not (check_labels or c == 1):
-            _note_label_flag(state)
-        ctx.save_for_backward(x, lab, state)
-        ctx.meta = (st, lab_code, n, v, c, float(gamma), input.dtype)
+        ops = _loss_operands(input, target, check_labels)
+        state, out = _hybird_forward(ops, kind, gamma, weight_v, alpha, beta, smooth)
+        _note_state(ops, state)
+        ctx.save_for_backward(ops.x, ops.lab, state)
+        ctx.meta = (ops.meta(), float(gamma), input.dtype)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         x, lab, state = ctx.saved_tensors
-        st, lab_code, n, v, c, gamma, in_dtype = ctx.meta
-        g = gout.detach()
-        if g.dtype != torch.float32 or g.device != x.device:
-            g = g.to(device=x.device, dtype=torch.float32)
-        g = g.reshape(1).contiguous()
-        N.note_device(x.device)
-        dz = torch.empty_like(x)   # preserve_format: same (dense) strides as the logits
-        if dz.stride() != x.stride():
-            dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
-        check(N.lib.ru3d_loss_bwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, gamma, ptr(state),
-                                  ptr(g), ptr(dz), N.F32, stream()), "loss_bwd")
-        if in_dtype != torch.float32:
-            dz = dz.to(in_dtype)
-        return dz, None, None, None, None, None, None, None, None
+        (st, lab_code, n, v, c), gamma, in_dtype = ctx.meta
+        g, dz = _backward_prologue(gout, x)
+        _hybird_backward(_view(x, st, lab, lab_code), n, v, c, gamma, state, g, dz)
+        return _backward_epilogue(dz, in_dtype, 8)
 
 
 class _FusedLoss(nn.Module):
@@ -427,25 +517,31 @@ def soft_skeleton(prob, iterations=3):
     return _soft_skeleton_host(prob, k)
 
 
-def _cldice_classes(classes, c):
+def _selected_classes(what, classes, c):
+    """The class selection of clDice and of the boundary loss (`what` names the loss): default 1 .. C-1."""
     cls = tuple(range(1, c)) if classes is None else tuple(int(q) for q in classes)
     if not cls or len(set(cls)) != len(cls) or min(cls) < 0 or max(cls) >= c:
-        raise N.Ru3dError("clDice: classes %s must be distinct class numbers of 0 .. %d" % (cls, c - 1))
+        raise N.Ru3dError("%s: classes %s must be distinct class numbers of 0 .. %d" % (what, cls, c - 1))
     return cls
 
 
-def _cldice_shape_check(input):
+def _class_array(cls):
+    """A class selection as the int array the ABI takes."""
+    return N.ctypes.cast((N.ctypes.c_int * len(cls))(*cls), N.ctypes.c_void_p)
+
+
+def _volume_shape_check(what, input):
     if input.dim() != 5:
-        raise N.Ru3dError("clDice: input must be (N, C, A, B, Z) - three spatial dimensions - not %s"
-                          % (tuple(input.shape),))
+        raise N.Ru3dError("%s: input must be (N, C, A, B, Z) - three spatial dimensions - not %s"
+                          % (what, tuple(input.shape)))
     if input.shape[1] < 2:
-        raise N.Ru3dError("clDice: C == 1 is not supported (softmax over at least two classes)")
+        raise N.Ru3dError("%s: C == 1 is not supported (softmax over at least two classes)" % what)
 
 
 def _soft_cldice_host(input, target, k, classes, weight_v, smooth):
     """The definition on host tensors, in the logits' dtype (what the device path is tested against)."""
     c = input.shape[1]
-    cls = _cldice_classes(classes, c)
+    cls = _selected_classes("clDice", classes, c)
     if weight_v is not None and len(weight_v) != c:
         raise RuntimeError("weight_v has %d entries for %d classes" % (len(weight_v), c))
     w = torch.tensor([1.0 if weight_v is None else float(weight_v[q]) for q in cls], dtype=input.dtype)
@@ -465,44 +561,30 @@ class _ClDiceFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, target, hyb, cl_weight, k, classes, weight_v, smooth, check_labels):
-        _cldice_shape_check(input)
-        x, st, lab, lab_code, n, c, v = _loss_operands(input, target, check_labels)
-        cls = _cldice_classes(classes, c)
-        raise_on_bad_labels()
-        dev = x.device
-        a, b, z = x.shape[2:]
-        nsel = len(cls)
+        _volume_shape_check("clDice", input)
+        ops = _loss_operands(input, target, check_labels)
+        cls = _selected_classes("clDice", classes, ops.c)
+        dev = ops.x.device
+        n, vol, nsel = ops.n, tuple(ops.x.shape[2:]), len(cls)
         lam = float(cl_weight)
         state_h = None
         if hyb is not None:
-            gamma, hyb_weight, alpha, beta, hyb_smooth = hyb
-            state_h = torch.empty(N.lib.ru3d_loss_state_bytes(c), dtype=torch.uint8, device=dev)
-            out_h = torch.empty((), dtype=torch.float32, device=dev)
-            ws = N.workspace(N.lib.ru3d_loss_workspace_bytes(n, v, c), dev)
-            wh = _weight_array(hyb_weight, c)
-            check(N.lib.ru3d_loss_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, N.LOSS_HYBIRD,
-                                      float(gamma), N.ctypes.cast(wh, N.ctypes.c_void_p) if wh is not None else None,
-                                      float(alpha), float(beta), float(hyb_smooth), ptr(state_h), ptr(out_h), ptr(ws),
-                                      ws.numel(), stream()), "loss_fwd")
-        delta, s, emin, dmax = _skeleton_buffers(k, n * nsel * v, dev)
-        skel_g = torch.empty(n * nsel * v, dtype=torch.float32, device=dev)
-        state_c = torch.empty(N.lib.ru3d_cldice_state_bytes(), dtype=torch.uint8, device=dev)
-        out_c = torch.empty((), dtype=torch.float32, device=dev)
-        ws = N.workspace(N.lib.ru3d_cldice_workspace_bytes(n * nsel, a, b, z, k), dev)
-        carr = (N.ctypes.c_int * nsel)(*cls)
-        wv = _weight_array(weight_v, c)
-        check(N.lib.ru3d_cldice_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, a, b, z, c,
-                                    N.ctypes.cast(carr, N.ctypes.c_void_p), nsel, k,
-                                    N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None, float(smooth),
-                                    ptr(delta), ptr(s), ptr(emin), ptr(dmax), ptr(skel_g), ptr(state_c), ptr(out_c),
-                                    ptr(ws), ws.numel(), stream()), "cldice_fwd")
-        if not check_labels:
-            _note_label_flag(state_c if state_h is None else state_h)
-        saved = [x, lab, delta, s, emin, dmax, skel_g, state_c]
+            state_h, out_h = _hybird_forward(ops, N.LOSS_HYBIRD, *hyb)
+        delta, s, emin, dmax = _skeleton_buffers(k, n * nsel * ops.v, dev)
+        skel_g = torch.empty(n * nsel * ops.v, dtype=torch.float32, device=dev)
+        state_c, out_c, ws, wv = _forward_scaffold(dev, N.lib.ru3d_cldice_state_bytes(),
+                                                   N.lib.ru3d_cldice_workspace_bytes(n * nsel, *vol, k), weight_v, ops.c,
+                                                   verdict=hyb is None)
+        carr = _class_array(cls)
+        check(N.lib.ru3d_cldice_fwd(*ops.view, n, *vol, ops.c, carr, nsel, k, wv,
+                                    float(smooth), ptr(delta), ptr(s), ptr(emin), ptr(dmax), ptr(skel_g), ptr(state_c),
+                                    ptr(out_c), ptr(ws), ws.numel(), stream()), "cldice_fwd")
+        _note_state(ops, state_h, state_c)
+        saved = [ops.x, ops.lab, delta, s, emin, dmax, skel_g, state_c]
         if state_h is not None:
             saved.append(state_h)
         ctx.save_for_backward(*saved)
-        ctx.meta = (st, lab_code, n, v, c, cls, k, lam, None if hyb is None else float(hyb[0]), input.dtype)
+        ctx.meta = (ops.meta(), carr, nsel, k, lam, None if hyb is None else float(hyb[0]), input.dtype)
         if state_h is None:
             return out_c
         return out_h * (1.0 - lam) + out_c * lam
@@ -510,34 +592,19 @@ class _ClDiceFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         x, lab, delta, s, emin, dmax, skel_g, state_c = ctx.saved_tensors[:8]
-        st, lab_code, n, v, c, cls, k, lam, gamma, in_dtype = ctx.meta
-        g = gout.detach()
-        if g.dtype != torch.float32 or g.device != x.device:
-            g = g.to(device=x.device, dtype=torch.float32)
-        g = g.reshape(1).contiguous()
-        dev = x.device
-        N.note_device(dev)
-        a, b, z = x.shape[2:]
-        dz = torch.empty_like(x)
-        if dz.stride() != x.stride():
-            dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=dev)
+        (st, lab_code, n, v, c), carr, nsel, k, lam, gamma, in_dtype = ctx.meta
+        view = _view(x, st, lab, lab_code)
+        g, dz = _backward_prologue(gout, x)
         scale, accumulate = 1.0, 0
         if gamma is not None:
-            state_h = ctx.saved_tensors[8]
-            gh = g * (1.0 - lam)
-            check(N.lib.ru3d_loss_bwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, gamma, ptr(state_h),
-                                      ptr(gh), ptr(dz), N.F32, stream()), "loss_bwd")
+            _hybird_backward(view, n, v, c, gamma, ctx.saved_tensors[8], g * (1.0 - lam), dz)
             scale, accumulate = lam, 1
-        nsel = len(cls)
-        ws = N.workspace(N.lib.ru3d_cldice_workspace_bytes(n * nsel, a, b, z, k), dev)
-        carr = (N.ctypes.c_int * nsel)(*cls)
-        check(N.lib.ru3d_cldice_bwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, a, b, z, c,
-                                    N.ctypes.cast(carr, N.ctypes.c_void_p), nsel, k, ptr(delta), ptr(s), ptr(emin),
-                                    ptr(dmax), ptr(skel_g), ptr(state_c), ptr(g), scale, accumulate, ptr(dz), ptr(ws),
-                                    ws.numel(), stream()), "cldice_bwd")
-        if in_dtype != torch.float32:
-            dz = dz.to(in_dtype)
-        return dz, None, None, None, None, None, None, None, None
+        vol = tuple(x.shape[2:])
+        ws = N.workspace(N.lib.ru3d_cldice_workspace_bytes(n * nsel, *vol, k), x.device)
+        check(N.lib.ru3d_cldice_bwd(*view, n, *vol, c, carr, nsel, k, ptr(delta),
+                                    ptr(s), ptr(emin), ptr(dmax), ptr(skel_g), ptr(state_c), ptr(g), scale, accumulate,
+                                    ptr(dz), ptr(ws), ws.numel(), stream()), "cldice_bwd")
+        return _backward_epilogue(dz, in_dtype, 8)
 
 
 class SoftClDiceLoss(_FusedLoss):
@@ -556,7 +623,7 @@ class SoftClDiceLoss(_FusedLoss):
 
     def forward(self, input, target):
         if not input.is_cuda:
-            _cldice_shape_check(input)
+            _volume_shape_check("clDice", input)
             return _soft_cldice_host(input, target, self.iterations, self.classes, self.weight_v, self.smooth)
         return _ClDiceFn.apply(input, target, None, 1.0, self.iterations, self.classes, self.weight_v, self.smooth,
                                getattr(self, "check_labels", _CHECK_LABELS))
@@ -599,21 +666,6 @@ class HybirdClDiceLoss(_FusedLoss):
 #   (a foreground voxel on the boundary has phi = 0);  G empty or the whole volume of that sample: phi = 0, d2 = 0 there -
 #   an absent class gives no loss and no gradient.  Distances are in voxels (unit spacing: there is no `sampling`
 #   argument), nothing outside the patch exists, the patch faces are no boundary, a label outside [0, C) matches no class.
-def _boundary_classes(classes, c):
-    cls = tuple(range(1, c)) if classes is None else tuple(int(q) for q in classes)
-    if not cls or len(set(cls)) != len(cls) or min(cls) < 0 or max(cls) >= c:
-        raise N.Ru3dError("boundary: classes %s must be distinct class numbers of 0 .. %d" % (cls, c - 1))
-    return cls
-
-
-def _boundary_shape_check(input):
-    if input.dim() != 5:
-        raise N.Ru3dError("boundary: input must be (N, C, A, B, Z) - three spatial dimensions - not %s"
-                          % (tuple(input.shape),))
-    if input.shape[1] < 2:
-        raise N.Ru3dError("boundary: C == 1 is not supported (softmax over at least two classes)")
-
-
 def _signed_squares_host(target, cls):
     """The written definition on a host tensor: int32 (N, K, A, B, Z), +d2 outside, -d2 inside, 0 where degenerate."""
     import numpy as np
@@ -650,24 +702,19 @@ def signed_distance_map(target, num_classes, classes=None, squared=False):
     c = int(num_classes)
     if c < 2 or c > N.MAX_CLASSES:
         raise N.Ru3dError("signed_distance_map: %d classes (2 .. %d)" % (c, N.MAX_CLASSES))
-    cls = _boundary_classes(classes, c)
+    cls = _selected_classes("boundary", classes, c)
     if not target.is_cuda:
         d2 = _signed_squares_host(target, cls)
         return d2 if squared else _phi_of_squares(d2)
     N.require_device(target, "signed_distance_map target")
-    if target.dtype in (torch.int64, torch.uint8):
-        lab = target.contiguous()
-    else:
-        lab = target.long().contiguous()
-    lab_code = N.LABEL_I64 if lab.dtype == torch.int64 else N.LABEL_U8
+    lab, lab_code = _label_operand(target)
     n, a, b, z = lab.shape
     dev = lab.device
     nsel = len(cls)
     out = torch.empty((n, nsel, a, b, z), dtype=torch.int32 if squared else torch.float32, device=dev)
     need = N.lib.ru3d_boundary_workspace_bytes(n * nsel, a, b, z)
     ws = N.workspace(max(need, 1), dev)
-    carr = (N.ctypes.c_int * nsel)(*cls)
-    check(N.lib.ru3d_signed_distance(ptr(lab), lab_code, n, a, b, z, c, N.ctypes.cast(carr, N.ctypes.c_void_p), nsel,
+    check(N.lib.ru3d_signed_distance(ptr(lab), lab_code, n, a, b, z, c, _class_array(cls), nsel,
                                      ptr(out) if squared else None, None if squared else ptr(out), ptr(ws),
                                      ws.numel() if need else 0, stream()), "signed_distance")
     return out
@@ -683,7 +730,7 @@ def _boundary_weights(weight_v, cls, c, dtype):
 def _boundary_host(input, target, classes, weight_v):
     """The definition on host tensors, in the logits' dtype (what the device path is tested against)."""
     c = input.shape[1]
-    cls = _boundary_classes(classes, c)
+    cls = _selected_classes("boundary", classes, c)
     w = _boundary_weights(weight_v, cls, c, input.dtype)
     if tuple(target.shape) != (input.shape[0],) + tuple(input.shape[2:]):
         raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape), tuple(input.shape)))
@@ -699,44 +746,29 @@ class _BoundaryFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, target, hyb, a, classes, weight_v, check_labels):
-        _boundary_shape_check(input)
-        x, st, lab, lab_code, n, c, v = _loss_operands(input, target, check_labels)
-        cls = _boundary_classes(classes, c)
-        raise_on_bad_labels()
-        dev = x.device
-        sa, sb, sz = x.shape[2:]
-        nsel = len(cls)
-        saved = [x, lab]
+        _volume_shape_check("boundary", input)
+        ops = _loss_operands(input, target, check_labels)
+        cls = _selected_classes("boundary", classes, ops.c)
+        dev = ops.x.device
+        n, vol, nsel = ops.n, tuple(ops.x.shape[2:]), len(cls)
+        state_h = None
         if hyb is not None:
-            gamma, hyb_weight, alpha, beta, hyb_smooth = hyb
-            state_h = torch.empty(N.lib.ru3d_loss_state_bytes(c), dtype=torch.uint8, device=dev)
-            out_h = torch.empty((), dtype=torch.float32, device=dev)
-            ws = N.workspace(N.lib.ru3d_loss_workspace_bytes(n, v, c), dev)
-            wh = _weight_array(hyb_weight, c)
-            check(N.lib.ru3d_loss_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, N.LOSS_HYBIRD,
-                                      float(gamma), N.ctypes.cast(wh, N.ctypes.c_void_p) if wh is not None else None,
-                                      float(alpha), float(beta), float(hyb_smooth), ptr(state_h), ptr(out_h), ptr(ws),
-                                      ws.numel(), stream()), "loss_fwd")
-        phi = torch.empty(n * nsel * v, dtype=torch.float32, device=dev)
-        state_b = torch.empty(N.lib.ru3d_boundary_state_bytes(), dtype=torch.uint8, device=dev)
-        out_b = torch.empty((), dtype=torch.float32, device=dev)
-        need = N.lib.ru3d_boundary_workspace_bytes(n * nsel, sa, sb, sz)
-        ws = N.workspace(max(need, 1), dev)
-        carr = (N.ctypes.c_int * nsel)(*cls)
-        wv = _weight_array(weight_v, c)
-        check(N.lib.ru3d_boundary_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, sa, sb, sz, c,
-                                      N.ctypes.cast(carr, N.ctypes.c_void_p), nsel,
-                                      N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None, ptr(phi),
+            state_h, out_h = _hybird_forward(ops, N.LOSS_HYBIRD, *hyb)
+        phi = torch.empty(n * nsel * ops.v, dtype=torch.float32, device=dev)
+        need = N.lib.ru3d_boundary_workspace_bytes(n * nsel, *vol)
+        state_b, out_b, ws, wv = _forward_scaffold(dev, N.lib.ru3d_boundary_state_bytes(), max(need, 1), weight_v, ops.c,
+                                                   verdict=hyb is None)
+        carr = _class_array(cls)
+        check(N.lib.ru3d_boundary_fwd(*ops.view, n, *vol, ops.c, carr, nsel, wv, ptr(phi),
                                       ptr(state_b), ptr(out_b), ptr(ws), ws.numel() if need else 0, stream()),
               "boundary_fwd")
-        if not check_labels:
-            _note_label_flag(state_b if hyb is None else state_h)
-        saved += [phi, state_b]
+        _note_state(ops, state_h, state_b)
+        saved = [ops.x, ops.lab, phi, state_b]
         if hyb is not None:
             a = a.detach().reshape(()).clone()        # the weight of THIS forward, whatever is set before the backward
             saved += [state_h, a]
         ctx.save_for_backward(*saved)
-        ctx.meta = (st, lab_code, n, v, c, cls, None if hyb is None else float(hyb[0]), input.dtype)
+        ctx.meta = (ops.meta(), carr, nsel, None if hyb is None else float(hyb[0]), input.dtype)
         if hyb is None:
             return out_b
         return out_h * (1.0 - a) + out_b * a
@@ -744,33 +776,17 @@ class _BoundaryFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         x, lab, phi, state_b = ctx.saved_tensors[:4]
-        st, lab_code, n, v, c, cls, gamma, in_dtype = ctx.meta
-        g = gout.detach()
-        if g.dtype != torch.float32 or g.device != x.device:
-            g = g.to(device=x.device, dtype=torch.float32)
-        g = g.reshape(1).contiguous()
-        dev = x.device
-        N.note_device(dev)
-        sa, sb, sz = x.shape[2:]
-        dz = torch.empty_like(x)
-        if dz.stride() != x.stride():
-            dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=dev)
+        (st, lab_code, n, v, c), carr, nsel, gamma, in_dtype = ctx.meta
+        g, dz = _backward_prologue(gout, x)
         accumulate = 0
         if gamma is not None:
             state_h, a = ctx.saved_tensors[4:6]
-            gh = g * (1.0 - a)
+            _hybird_backward(_view(x, st, lab, lab_code), n, v, c, gamma, state_h, g * (1.0 - a), dz)
             g = g * a
-            check(N.lib.ru3d_loss_bwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, gamma, ptr(state_h),
-                                      ptr(gh), ptr(dz), N.F32, stream()), "loss_bwd")
             accumulate = 1
-        nsel = len(cls)
-        carr = (N.ctypes.c_int * nsel)(*cls)
-        check(N.lib.ru3d_boundary_bwd(ptr(x), st[0], st[1], st[2], n, sa, sb, sz, c,
-                                      N.ctypes.cast(carr, N.ctypes.c_void_p), nsel, ptr(phi), ptr(state_b), ptr(g), 1.0,
+        check(N.lib.ru3d_boundary_bwd(ptr(x), *st, n, *x.shape[2:], c, carr, nsel, ptr(phi), ptr(state_b), ptr(g), 1.0,
                                       accumulate, ptr(dz), stream()), "boundary_bwd")
-        if in_dtype != torch.float32:
-            dz = dz.to(in_dtype)
-        return dz, None, None, None, None, None, None
+        return _backward_epilogue(dz, in_dtype, 6)
 
 
 class BoundaryLoss(_FusedLoss):
@@ -787,7 +803,7 @@ class BoundaryLoss(_FusedLoss):
 
     def forward(self, input, target):
         if not input.is_cuda:
-            _boundary_shape_check(input)
+            _volume_shape_check("boundary", input)
             return _boundary_host(input, target, self.classes, self.weight_v)
         return _BoundaryFn.apply(input, target, None, None, self.classes, self.weight_v,
                                  getattr(self, "check_labels", _CHECK_LABELS))
@@ -938,73 +954,31 @@ class _DeepSupFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, target, hyper, block, check_labels, *outputs):
         kind, gamma, weight_v, alpha, beta, smooth = hyper
-        x0 = outputs[0]
-        N.require_device(x0, "loss input")
-        if target.device != x0.device:
-            raise N.Ru3dError("loss: target is on %s but input on %s" % (target.device, x0.device))
-        n, c = x0.shape[0], x0.shape[1]
-        if c > N.MAX_CLASSES:
-            raise N.Ru3dError("loss: %d classes (max %d)" % (c, N.MAX_CLASSES))
-        dev = x0.device
-        xs, table = [], (N.DsLevel * len(outputs))()
-        for l, x in enumerate(outputs):
-            x = x.detach()
-            if x.dtype != torch.float32:
-                x = x.float()
-            st = _flat_strides(x)
-            if st is None:
-                x = x.contiguous()
-                st = _flat_strides(x)
-            xs.append(x)
-            table[l] = N.DsLevel(x.data_ptr(), st[0], st[1], st[2], x.shape[2], x.shape[3], x.shape[4], l)
-        if target.dtype == torch.int64:
-            lab, lab_code = target.contiguous(), N.LABEL_I64
-        elif target.dtype == torch.uint8:
-            lab, lab_code = target.contiguous(), N.LABEL_U8
-        else:
-            lab, lab_code = target.long().contiguous(), N.LABEL_I64
-        if check_labels or c == 1:
-            if lab.numel() and (int(lab.max()) >= c or int(lab.min()) < 0):
-                raise RuntimeError(_BAD_LABELS)
-        raise_on_bad_labels()          # an earlier call's verdict, if it has landed (no wait)
-        d, h, w = x0.shape[2:]
-        state = torch.empty(N.lib.ru3d_ds_state_bytes(), dtype=torch.uint8, device=dev)
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        ws = N.workspace(N.lib.ru3d_ds_loss_workspace_bytes(table, len(xs), n), dev)
-        wv = _weight_array(weight_v, c)
-        check(N.lib.ru3d_ds_loss_fwd(table, len(xs), ptr(lab), lab_code, n, d, h, w, c, kind, float(gamma),
-                                     N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None, float(alpha),
-                                     float(beta), float(smooth), ptr(block), ptr(state), ptr(out), ptr(ws), ws.numel(),
-                                     stream()), "ds_loss_fwd")
-        if not (check_labels or c == 1):
-            # _note_label_flag reads the count where the fused losses' state keeps it
-            _note_label_flag(state[_DS_BAD_OFF[0] - _BAD_OFF[0]:])
-        ctx.save_for_backward(lab, state, *xs)
-        ctx.meta = (table, lab_code, n, (d, h, w), c, float(gamma), [x.dtype for x in outputs])
+        ops = _loss_operands(outputs, target, check_labels)
+        table = (N.DsLevel * len(outputs))()
+        for l, (x, st) in enumerate(zip(ops.x, ops.st)):
+            table[l] = N.DsLevel(x.data_ptr(), *st, *x.shape[2:], l)
+        n, c, full = ops.n, ops.c, tuple(outputs[0].shape[2:])
+        state, out, ws, wv = _forward_scaffold(ops.lab.device, N.lib.ru3d_ds_state_bytes(),
+                                               N.lib.ru3d_ds_loss_workspace_bytes(table, len(outputs), n), weight_v, c)
+        check(N.lib.ru3d_ds_loss_fwd(table, len(outputs), ptr(ops.lab), ops.lab_code, n, *full, c, kind, float(gamma),
+                                     wv, float(alpha), float(beta), float(smooth), ptr(block), ptr(state), ptr(out),
+                                     ptr(ws), ws.numel(), stream()), "ds_loss_fwd")
+        _note_state(ops, state, offset=_DS_BAD_OFF[0])
+        ctx.save_for_backward(ops.lab, state, *ops.x)
+        ctx.meta = (table, ops.lab_code, n, full, c, float(gamma), [x.dtype for x in outputs])
         return out
 
     @staticmethod
     def backward(ctx, gout):
         lab, state = ctx.saved_tensors[:2]
         xs = ctx.saved_tensors[2:]
-        table, lab_code, n, (d, h, w), c, gamma, in_dtypes = ctx.meta
-        dev = xs[0].device
-        g = gout.detach()
-        if g.dtype != torch.float32 or g.device != dev:
-            g = g.to(device=dev, dtype=torch.float32)
-        g = g.reshape(1).contiguous()
-        N.note_device(dev)
-        dzs = []
-        for x in xs:
-            dz = torch.empty_like(x)   # preserve_format: same (dense) strides as the logits
-            if dz.stride() != x.stride():
-                dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=dev)
-            dzs.append(dz)
+        table, lab_code, n, full, c, gamma, in_dtypes = ctx.meta
+        g, dzs = _upstream(gout, lab.device), [_empty_grad(x) for x in xs]
         dptr = (N.ctypes.c_void_p * len(dzs))(*[dz.data_ptr() for dz in dzs])
-        check(N.lib.ru3d_ds_loss_bwd(table, dptr, len(xs), ptr(lab), lab_code, n, d, h, w, c, gamma, ptr(state), ptr(g),
+        check(N.lib.ru3d_ds_loss_bwd(table, dptr, len(xs), ptr(lab), lab_code, n, *full, c, gamma, ptr(state), ptr(g),
                                      stream()), "ds_loss_bwd")
-        dzs = [dz if dt == torch.float32 else dz.to(dt) for dz, dt in zip(dzs, in_dtypes)]
-        return (None, None, None, None) + tuple(dzs)
+        return (None, None, None, None) + tuple(_backward_epilogue(dz, dt) for dz, dt in zip(dzs, in_dtypes))
 
 
 _DS_BAD_OFF = [int(N.lib.ru3d_ds_state_bad_labels_offset())]
@@ -1203,6 +1177,10 @@ def _group_loss_host(kind, input, target, table, ignore, gamma, weight_v, alpha,
 
 
 class _GroupLossFn(torch.autograd.Function):
+    """Written out in full, not on the scaffolds the other five Functions share: on them its forward + backward cost the
+    host about 0.008 ms more than before (profiles/loss_call_path_check.txt), and no cause was found.  It takes the
+    operands as the plain tuple of _operand_parts."""
+
     @staticmethod
     def forward(ctx, input, target, kind, table, ignore, gamma, weight_v, alpha, beta, smooth, check_labels):
         k, t = input.shape[1], len(table)
@@ -1211,7 +1189,7 @@ class _GroupLossFn(torch.autograd.Function):
             lab = target if ignore is None else target[target != ignore]
             if lab.numel() and (int(lab.max()) >= t or int(lab.min()) < 0):
                 raise RuntimeError(_BAD_LABELS)
-        x, st, lab, lab_code, n, _, v = _loss_operands(input, target, False, one_hot=False)
+        x, lab, st, lab_code, n, _, v, _ = _operand_parts(input, target, False, False)
         raise_on_bad_labels()          # an earlier call's verdict, if it has landed (no wait)
         dev = x.device
         state = torch.empty(N.lib.ru3d_group_loss_state_bytes(), dtype=torch.uint8, device=dev)
@@ -1390,43 +1368,29 @@ def _topk_loss_host(input, target, k, with_dice=False, weight_v=None, alpha=0.5,
 class _TopKLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, target, kk, with_dice, weight_v, alpha, beta, smooth, ce_weight, check_labels):
-        x, st, lab, lab_code, n, c, v = _loss_operands(input, target, check_labels)
-        raise_on_bad_labels()          # an earlier call's verdict, if it has landed (no wait)
-        dev = x.device
-        state = torch.empty(N.lib.ru3d_topk_loss_state_bytes(), dtype=torch.uint8, device=dev)
-        out = torch.empty((), dtype=torch.float32, device=dev)
+        ops = _loss_operands(input, target, check_labels)
+        n, v, c = ops.n, ops.v, ops.c
+        state, out, ws, wv = _forward_scaffold(ops.x.device, N.lib.ru3d_topk_loss_state_bytes(),
+                                               N.lib.ru3d_topk_loss_workspace_bytes(n, v, c), weight_v, c)
         # the backward compares these stored values with tau: a tensor of this call, not a slice of the shared workspace,
         # which other calls reuse between a forward and its backward
-        ce = torch.empty(n * v, dtype=torch.float32, device=dev)
-        ws = N.workspace(N.lib.ru3d_topk_loss_workspace_bytes(n, v, c), dev)
-        wv = _weight_array(weight_v, c)
-        check(N.lib.ru3d_topk_loss_fwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, kk, int(with_dice),
-                                       N.ctypes.cast(wv, N.ctypes.c_void_p) if wv is not None else None, float(alpha),
+        ce = torch.empty(n * v, dtype=torch.float32, device=ops.x.device)
+        check(N.lib.ru3d_topk_loss_fwd(*ops.view, n, v, c, kk, int(with_dice), wv, float(alpha),
                                        float(beta), float(smooth), float(ce_weight), ptr(ce), ptr(state), ptr(out),
                                        ptr(ws), ws.numel(), stream()), "topk_loss_fwd")
-        if not check_labels:
-            _note_label_flag(state)
-        ctx.save_for_backward(x, lab, ce, state)
-        ctx.meta = (st, lab_code, n, v, c, int(with_dice), input.dtype)
+        _note_state(ops, state)
+        ctx.save_for_backward(ops.x, ops.lab, ce, state)
+        ctx.meta = (ops.meta(), int(with_dice), input.dtype)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         x, lab, ce, state = ctx.saved_tensors
-        st, lab_code, n, v, c, with_dice, in_dtype = ctx.meta
-        g = gout.detach()
-        if g.dtype != torch.float32 or g.device != x.device:
-            g = g.to(device=x.device, dtype=torch.float32)
-        g = g.reshape(1).contiguous()
-        N.note_device(x.device)
-        dz = torch.empty_like(x)   # preserve_format: same (dense) strides as the logits
-        if dz.stride() != x.stride():
-            dz = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
-        check(N.lib.ru3d_topk_loss_bwd(ptr(x), st[0], st[1], st[2], ptr(lab), lab_code, n, v, c, with_dice, ptr(ce),
-                                       ptr(state), ptr(g), ptr(dz), N.F32, stream()), "topk_loss_bwd")
-        if in_dtype != torch.float32:
-            dz = dz.to(in_dtype)       # rounded once to the logits' type
-        return (dz,) + (None,) * 9
+        (st, lab_code, n, v, c), with_dice, in_dtype = ctx.meta
+        g, dz = _backward_prologue(gout, x)
+        check(N.lib.ru3d_topk_loss_bwd(*_view(x, st, lab, lab_code), n, v, c, with_dice, ptr(ce), ptr(state),
+                                       ptr(g), ptr(dz), N.F32, stream()), "topk_loss_bwd")
+        return _backward_epilogue(dz, in_dtype, 9)
 
 
 class _TopKLoss(_FusedLoss):
