@@ -370,6 +370,19 @@ extern "C" int ru3d_conv3d_fwd_in_lrelu(const ru3d_tensor* x, const void* w_pack
     return ru3d_in_lrelu_fwd(y, mean, scale, res, out, slope, dtype, stream);
 }
 
+static WgradGeom make_wgrad(const ru3d_tensor* x, const ru3d_tensor* dy, int k, int stride) {
+    WgradGeom g;
+    g.N = x->n;
+    g.Di = x->d; g.Hi = x->h; g.Wi = x->w; g.Cin = x->c; g.ldx = x->ld;
+    g.Do = dy->d; g.Ho = dy->h; g.Wo = dy->w; g.Cout = dy->c; g.lddy = dy->ld;
+    g.k = k; g.taps = k * k * k; g.stride = stride; g.pad = k / 2;
+    g.s_o = (int64_t)x->c * g.taps;
+    g.s_i = g.taps;
+    g.chunk_len = 0;
+    g.x_cseg = x->cseg; g.x_segstride = x->seg_stride;
+    return g;
+}
+
 // ---- can a decoder ResBlock take cat((up, skip)) as a split tensor through all of its kernels? (see ru3d_tensor)
 extern "C" int ru3d_planar_concat_supported(int n, int d, int h, int w, int cseg, int cout, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_planar_concat_supported_f16(n, d, h, w, cseg, cout, dtype));
@@ -384,12 +397,7 @@ extern "C" int ru3d_planar_concat_supported(int n, int d, int h, int w, int cseg
     if (!fwd.count || fwd.choice[0].family != S1_SLIDE64) return 0;
     const ConvGeom gd = dgrad_s1_geom(&act, &cat, 3);                                  // its input-gradient pair (split output)
     if (!pair_mode || !s1_plan_for(gd, dtype).can_partner) return 0;
-    WgradGeom gw;                                                                      // conv1's weight gradient (split x)
-    gw.N = n; gw.Di = gw.Do = d; gw.Hi = gw.Ho = h; gw.Wi = gw.Wo = w; gw.Cin = 2 * cseg; gw.Cout = cout;
-    gw.ldx = cseg; gw.lddy = cout; gw.k = 3; gw.taps = 27; gw.stride = 1; gw.pad = 1;
-    gw.s_o = (int64_t)gw.Cin * 27; gw.s_i = 27; gw.chunk_len = 0;
-    WgradSlidePlan wp;
-    if (!wgrad_slide_plan(gw, &wp)) return 0;
+    if (wgrad_plan(make_wgrad(&cat, &act, 3, 1), dtype).family != WG_SLIDE) return 0;   // conv1's weight gradient (split x)
     // the fused tail (skip conv + InstanceNorm apply): skip1x1_fused_eligible's shape conditions
     if (!skip_mode || (V % 16) != 0 || V * n < 65536) return 0;
     return 1;
@@ -612,19 +620,6 @@ extern "C" int ru3d_conv3d_dgrad_in_bwd(const ru3d_tensor* dy, const void* w_pac
     return ru3d_in_lrelu_bwd(da, act, act, mean, scale, dyn, nullptr, ws, ws_bytes, slope, 0, nullptr, nullptr, dtype, stream);
 }
 
-static WgradGeom make_wgrad(const ru3d_tensor* x, const ru3d_tensor* dy, int k, int stride) {
-    WgradGeom g;
-    g.N = x->n;
-    g.Di = x->d; g.Hi = x->h; g.Wi = x->w; g.Cin = x->c; g.ldx = x->ld;
-    g.Do = dy->d; g.Ho = dy->h; g.Wo = dy->w; g.Cout = dy->c; g.lddy = dy->ld;
-    g.k = k; g.taps = k * k * k; g.stride = stride; g.pad = k / 2;
-    g.s_o = (int64_t)x->c * g.taps;
-    g.s_i = g.taps;
-    g.chunk_len = 0;
-    g.x_cseg = x->cseg; g.x_segstride = x->seg_stride;
-    return g;
-}
-
 static bool wgrad_shapes_ok(const ru3d_tensor* x, const ru3d_tensor* dy, int k, int stride) {
     return tensor_ok_split(x) && tensor_ok(dy) && x->n == dy->n && dy->d == conv_out(x->d, k, stride) &&
            dy->h == conv_out(x->h, k, stride) && dy->w == conv_out(x->w, k, stride);
@@ -634,12 +629,7 @@ extern "C" size_t ru3d_conv3d_wgrad_workspace_bytes(const ru3d_tensor* x, const 
                                                     int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_wgrad_workspace_bytes_f16(x, dy, k, stride, dtype));
     if (!wgrad_shapes_ok(x, dy, k, stride)) return 0;
-    WgradGeom g = make_wgrad(x, dy, k, stride);
-    if (g.x_cseg) return mfma_wgrad_eligible(g, dtype) ? wgrad_mfma_ws_bytes(g) : 0;
-    if (stem_wgrad_eligible(g)) return stem_wgrad_ws_bytes(g);
-    if (head_wgrad_eligible(g, dtype)) return head_wgrad_ws_bytes(g);
-    if (mfma_wgrad_eligible(g, dtype)) return wgrad_mfma_ws_bytes(g);
-    return wgrad_generic_ws_bytes(g);
+    return wgrad_plan(make_wgrad(x, dy, k, stride), dtype).ws_bytes;
 }
 
 extern "C" int ru3d_conv3d_wgrad(const ru3d_tensor* x, const ru3d_tensor* dy, float* dw, void* ws, size_t ws_bytes,
@@ -649,76 +639,68 @@ extern "C" int ru3d_conv3d_wgrad(const ru3d_tensor* x, const ru3d_tensor* dy, fl
     RU3D_REQUIRE((k == 1 || k == 3) && (stride == 1 || stride == 2), "conv3d_wgrad: k=%d stride=%d unsupported", k, stride);
     RU3D_REQUIRE(wgrad_shapes_ok(x, dy, k, stride), "conv3d_wgrad: x/dy shape mismatch");
     RU3D_REQUIRE(dw && dtype_ok(dtype), "conv3d_wgrad: bad argument");
-    WgradGeom g = make_wgrad(x, dy, k, stride);
-    if (g.x_cseg) {      // planar concat: the MFMA kernels only (wgrad_mfma_launch refuses the forms that cannot take it)
-        RU3D_REQUIRE(mfma_wgrad_eligible(g, dtype), "conv3d_wgrad: no kernel takes a split x for this shape / dtype");
-        return wgrad_mfma_launch(x->ptr, dy->ptr, dw, ws, ws_bytes, g, as_stream(stream));
-    }
-    if (stem_wgrad_eligible(g)) return stem_wgrad_launch(x->ptr, dy->ptr, dw, ws, ws_bytes, g, dtype, as_stream(stream));
-    if (head_wgrad_eligible(g, dtype))
-        return head_wgrad_launch(x->ptr, dy->ptr, dw, ws, ws_bytes, g, dtype, as_stream(stream));
-    if (mfma_wgrad_eligible(g, dtype)) return wgrad_mfma_launch(x->ptr, dy->ptr, dw, ws, ws_bytes, g, as_stream(stream));
-    return wgrad_generic_launch(x->ptr, dy->ptr, dw, ws, ws_bytes, g, dtype, as_stream(stream));
+    const WgradGeom g = make_wgrad(x, dy, k, stride);
+    return wgrad_launch(wgrad_plan(g, dtype), x->ptr, dy->ptr, dw, ws, ws_bytes, g, dtype, as_stream(stream));
 }
-
 
 // ---- a ResBlock's two weight gradients on its input x (conv1: 3x3x3, skip_conv: 1x1x1, both with the block's stride;
 // network.py:403-409) from ONE pass over x: the sliding (stride 1: wgrad_slide.hip) and the LDS-DMA (stride 2: wgrad_s2.hip)
 // weight-gradient kernels have one tap slot of their four waves' 28 free, and the centre tap's rows are the rows the 1x1x1
 // conv reads
-static bool wgrad_pair_ok(const ru3d_tensor* x, const ru3d_tensor* dy, const ru3d_tensor* dy2, int stride, int dtype) {
+// the conditions on the three tensors, then the plan's can_pair; *g / *p: the geometry and its plan for the caller
+static bool wgrad_pair_ok(const ru3d_tensor* x, const ru3d_tensor* dy, const ru3d_tensor* dy2, int stride, int dtype,
+                          WgradGeom* g, WgradPlan* p) {
     static const int mode = ru3d_env_int("RU3D_WGRAD_PAIR", 1);      // 0 = two launches
-    if (!mode || dtype != RU3D_BF16 || (stride != 1 && stride != 2)) return false;
+    if (!x || !dy || !dy2 || !mode || dtype != RU3D_BF16 || (stride != 1 && stride != 2)) return false;
     if (!wgrad_shapes_ok(x, dy, 3, stride) || !tensor_ok(dy2)) return false;
     if (dy2->n != dy->n || dy2->d != dy->d || dy2->h != dy->h || dy2->w != dy->w || dy2->c != dy->c) return false;
     if ((dy2->ld % 8) || ((((uintptr_t)x->ptr) | ((uintptr_t)dy->ptr) | ((uintptr_t)dy2->ptr)) % 16)) return false;
     if ((int64_t)dy->d * dy->h * dy->w * dy2->ld >= (1ll << 30)) return false;
-    WgradGeom g = make_wgrad(x, dy, 3, stride);
-    if (g.x_cseg && (g.x_cseg % 32)) return false;
-    if (!mfma_wgrad_eligible(g, dtype)) return false;
-    if (stride == 2) return wgrad_s2_pair_eligible(g);
-    WgradSlidePlan sp;
-    return wgrad_slide_plan(g, &sp);
+    *g = make_wgrad(x, dy, 3, stride);
+    *p = wgrad_plan(*g, dtype);
+    return p->can_pair;
 }
 
 extern "C" int ru3d_conv3d_wgrad_pair_supported(const ru3d_tensor* x, const ru3d_tensor* dy, const ru3d_tensor* dy2, int stride,
                                                 int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_wgrad_pair_supported_f16(x, dy, dy2, stride, dtype));
-    return (x && dy && dy2 && wgrad_pair_ok(x, dy, dy2, stride, dtype)) ? 1 : 0;
+    WgradGeom g;
+    WgradPlan p;
+    return wgrad_pair_ok(x, dy, dy2, stride, dtype, &g, &p) ? 1 : 0;
 }
 
 extern "C" size_t ru3d_conv3d_wgrad_pair_workspace_bytes(const ru3d_tensor* x, const ru3d_tensor* dy, const ru3d_tensor* dy2,
                                                          int stride, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_wgrad_pair_workspace_bytes_f16(x, dy, dy2, stride, dtype));
-    if (!x || !dy || !dy2 || !wgrad_pair_ok(x, dy, dy2, stride, dtype)) return 0;
-    const WgradGeom g = make_wgrad(x, dy, 3, stride);
-    return stride == 2 ? wgrad_s2_pair_ws_bytes(g) : wgrad_slide_pair_ws_bytes(g);
+    WgradGeom g;
+    WgradPlan p;
+    return wgrad_pair_ok(x, dy, dy2, stride, dtype, &g, &p) ? p.pair_ws_bytes : 0;
 }
 
 extern "C" int ru3d_conv3d_wgrad_pair(const ru3d_tensor* x, const ru3d_tensor* dy, const ru3d_tensor* dy2, float* dw,
                                       float* dw2, void* ws, size_t ws_bytes, int stride, int dtype, void* stream) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_wgrad_pair_f16(x, dy, dy2, dw, dw2, ws, ws_bytes, stride, dtype, stream));
     Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(x && dy && dy2 && wgrad_pair_ok(x, dy, dy2, stride, dtype),
+    WgradGeom g;
+    WgradPlan p;
+    RU3D_REQUIRE(wgrad_pair_ok(x, dy, dy2, stride, dtype, &g, &p),
                  "conv3d_wgrad_pair: shapes have no fused kernel (ask ru3d_conv3d_wgrad_pair_supported first)");
     RU3D_REQUIRE(dw && dw2 && ws, "conv3d_wgrad_pair: null output / workspace");
-    WgradGeom g = make_wgrad(x, dy, 3, stride);
-    if (stride == 2) {
-        RU3D_REQUIRE(ws_bytes >= wgrad_s2_pair_ws_bytes(g), "conv3d_wgrad_pair: workspace too small");
-        return wgrad_s2_pair_launch(x->ptr, dy->ptr, dy2->ptr, dy2->ld, dw, dw2, ws, g, as_stream(stream));
-    }
-    RU3D_REQUIRE(ws_bytes >= wgrad_slide_pair_ws_bytes(g), "conv3d_wgrad_pair: workspace too small");
-    return wgrad_slide_pair_launch(x->ptr, dy->ptr, dy2->ptr, dy2->ld, dw, dw2, ws, g, as_stream(stream));
+    return wgrad_launch(p, x->ptr, dy->ptr, dw, ws, ws_bytes, g, dtype, as_stream(stream), dy2->ptr, dy2->ld, dw2);
 }
 
 // ---- weight gradient AND bias gradient (= sum of dy over samples and voxels) of a conv behind one entry point: the stem's
 // MFMA weight-gradient kernel delivers the bias row from the same pass over dy; elsewhere ru3d_conv3d_wgrad + ru3d_channel_sum
+static size_t wgrad_bias_ws_bytes(const ru3d_tensor* dy, const WgradPlan& p) {
+    const size_t b = ru3d_reduce_workspace_bytes(dy);
+    return p.ws_bytes > b ? p.ws_bytes : b;
+}
+
 extern "C" size_t ru3d_conv3d_wgrad_bias_workspace_bytes(const ru3d_tensor* x, const ru3d_tensor* dy, int k, int stride,
                                                          int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_wgrad_bias_workspace_bytes_f16(x, dy, k, stride, dtype));
     if (!wgrad_shapes_ok(x, dy, k, stride)) return 0;
-    const size_t a = ru3d_conv3d_wgrad_workspace_bytes(x, dy, k, stride, dtype), b = ru3d_reduce_workspace_bytes(dy);
-    return a > b ? a : b;
+    return wgrad_bias_ws_bytes(dy, wgrad_plan(make_wgrad(x, dy, k, stride), dtype));
 }
 
 extern "C" int ru3d_conv3d_wgrad_bias(const ru3d_tensor* x, const ru3d_tensor* dy, float* dw, float* db, void* ws,
@@ -728,11 +710,11 @@ extern "C" int ru3d_conv3d_wgrad_bias(const ru3d_tensor* x, const ru3d_tensor* d
     RU3D_REQUIRE((k == 1 || k == 3) && (stride == 1 || stride == 2), "conv3d_wgrad_bias: k=%d stride=%d unsupported", k, stride);
     RU3D_REQUIRE(wgrad_shapes_ok(x, dy, k, stride) && tensor_ok(x), "conv3d_wgrad_bias: x/dy shape mismatch");
     RU3D_REQUIRE(dw && db && dtype_ok(dtype), "conv3d_wgrad_bias: bad argument");
-    RU3D_REQUIRE(ws && ws_bytes >= ru3d_conv3d_wgrad_bias_workspace_bytes(x, dy, k, stride, dtype),
-                 "conv3d_wgrad_bias: workspace too small");
-    WgradGeom g = make_wgrad(x, dy, k, stride);
-    if (stem_wgrad_gives_bias(g, dtype))
-        return stem_wgrad_launch(x->ptr, dy->ptr, dw, ws, ws_bytes, g, dtype, as_stream(stream), db);
+    const WgradGeom g = make_wgrad(x, dy, k, stride);
+    const WgradPlan p = wgrad_plan(g, dtype);
+    RU3D_REQUIRE(ws && ws_bytes >= wgrad_bias_ws_bytes(dy, p), "conv3d_wgrad_bias: workspace too small");
+    if (p.gives_bias)
+        return wgrad_launch(p, x->ptr, dy->ptr, dw, ws, ws_bytes, g, dtype, as_stream(stream), nullptr, 0, nullptr, db);
     int rc = ru3d_conv3d_wgrad(x, dy, dw, ws, ws_bytes, k, stride, dtype, stream);
     if (rc) return rc;
     return ru3d_channel_sum(dy, db, ws, ws_bytes, dtype, stream);
@@ -843,9 +825,7 @@ extern "C" size_t ru3d_convtranspose3d_k3s2p1_wgrad_workspace_bytes(const ru3d_t
                                                                     int dtype) {
     RU3D_FWD_F16(dtype, ru3d_convtranspose3d_k3s2p1_wgrad_workspace_bytes_f16(x, dy, dtype));
     if (!convt_shapes_ok(x, dy)) return 0;
-    WgradGeom g = make_convt_wgrad(x, dy);
-    if (mfma_wgrad_eligible(g, dtype)) return wgrad_mfma_ws_bytes(g);
-    return wgrad_generic_ws_bytes(g);
+    return wgrad_plan(make_convt_wgrad(x, dy), dtype).ws_bytes;
 }
 
 extern "C" int ru3d_convtranspose3d_k3s2p1_wgrad(const ru3d_tensor* x, const ru3d_tensor* dy, float* dw, void* ws,
@@ -854,9 +834,8 @@ extern "C" int ru3d_convtranspose3d_k3s2p1_wgrad(const ru3d_tensor* x, const ru3
     Ru3dDeviceGuard dev_guard(stream);
     RU3D_REQUIRE(convt_shapes_ok(x, dy), "convtranspose3d_wgrad: dy must have extents 2*x");
     RU3D_REQUIRE(dw && dtype_ok(dtype), "convtranspose3d_wgrad: bad argument");
-    WgradGeom g = make_convt_wgrad(x, dy);
-    if (mfma_wgrad_eligible(g, dtype)) return wgrad_mfma_launch(dy->ptr, x->ptr, dw, ws, ws_bytes, g, as_stream(stream));
-    return wgrad_generic_launch(dy->ptr, x->ptr, dw, ws, ws_bytes, g, dtype, as_stream(stream));
+    const WgradGeom g = make_convt_wgrad(x, dy);
+    return wgrad_launch(wgrad_plan(g, dtype), dy->ptr, x->ptr, dw, ws, ws_bytes, g, dtype, as_stream(stream));
 }
 
 }  // namespace RU3D_NS

@@ -72,10 +72,10 @@ int conv_generic_launch(const void* x, const void* w, const float* bias, const v
                         const ConvGeom& g, int dtype, int y_dtype, hipStream_t st);
 int pack_generic_launch(const float* src, void* dst, int cin, int cout, int taps, int64_t s_o, int64_t s_i,
                         int flip, int dtype, hipStream_t st);
-size_t wgrad_generic_ws_bytes(const WgradGeom& g);
+int wgrad_generic_chunks(const WgradGeom& g);
 int wgrad_reduce_launch(const float* part, float* dw, int chunks, int taps, int cin, int cout, int64_t s_o, int64_t s_i,
                         hipStream_t st);
-int wgrad_generic_launch(const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes, WgradGeom g, int dtype,
+int wgrad_generic_launch(const void* x, const void* dy, float* dw, void* ws, int chunks, WgradGeom g, int dtype,
                          hipStream_t st);
 
 // conv_mfma.hip (bf16 MFMA implicit GEMM)
@@ -120,10 +120,39 @@ int conv_mfma_launch(const void* x, const void* w, const float* bias, const void
 // the two means m12[n][c] = (mean g', mean g' xhat) of the backward sums)
 int stats_slab_finalize_launch(const float* slab, int gx, int cb, int N, int C, double invV, const float* drop, float eps,
                                float* mean, float* scale, hipStream_t st);
+// The weight gradient of every conv form: ONE plan per (geometry, dtype), made by wgrad_plan and read by everything that
+// has to agree on it - the launcher, the workspace queries, the pair and bias entry points and the "can this take a split
+// x" question.  The families in order of preference; what only the launch knows (operand alignment, the workspace that
+// was passed, dw's alignment for the direct store) is checked in wgrad_launch.
+enum { WG_STEM_MFMA = 1, WG_STEM, WG_HEAD, WG_SLIDE, WG_S1_TILE, WG_S2, WG_STAGED, WG_GENERIC };
+struct WgradSlidePlan {
+    int dsplit, DL, tiles_h, tiles_w, units, G, pairs;
+};
+struct WgradPlan {
+    int family = 0;           // WG_*; 0: nothing takes this geometry and dtype (refusal says why)
+    const char* refusal = nullptr;
+    int groups = 0;           // slabs the main kernel writes = the count handed to wgrad_reduce_launch
+    WgradSlidePlan slide = {};   // WG_SLIDE: its decomposition
+    int td = 0, th = 0, tw = 0;   // WG_S1_TILE: the halo tile; WG_S2: tw = tile width
+    bool direct = false;      // WG_S1_TILE: a lone workgroup per pair and dw in the Conv3d layout - stored without slabs
+    int nco = 0;              // WG_S2: 32-cout tiles per workgroup
+    bool dma = false;         // WG_S2: the LDS-DMA kernel (else the register-staged one)
+    int pt = 0;               // WG_STAGED: positions per tile (the taps are g.taps)
+    // What the workspace queries report: an upper BOUND, not what `family` writes.  Callers size pooled buffers from it and
+    // the figure predates the plan: max(tile, slide) for the 3x3x3 stride-1 form, max(staged, s2) for the other MFMA forms,
+    // the larger of the stem's two kernels (28 rows: the bias row included).  Set for a refused split x too.
+    size_t ws_bytes = 0;
+    bool can_pair = false;    // the 28-tap pair form (WG_SLIDE / WG_S2 with dma) takes this geometry
+    size_t pair_ws_bytes = 0;
+    bool gives_bias = false;  // the bias row comes from the same pass (WG_STEM_MFMA)
+    char name[40] = "", pair_name[40] = "";   // what the launch log reports (single / pair form)
+};
+WgradPlan wgrad_plan(const WgradGeom& g, int dtype);
+// dy2 / dw2: the pair form (plan.can_pair); db: the bias row (plan.gives_bias)
+int wgrad_launch(const WgradPlan& p, const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes,
+                 const WgradGeom& g, int dtype, hipStream_t st, const void* dy2 = nullptr, int lddy2 = 0,
+                 float* dw2 = nullptr, float* db = nullptr);
 bool mfma_wgrad_eligible(const WgradGeom& g, int dtype);
-size_t wgrad_mfma_ws_bytes(const WgradGeom& g);
-int wgrad_mfma_launch(const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes, WgradGeom g,
-                      hipStream_t st);
 
 // conv_slide32.hip (3x3x3 stride-1, 32 -> 32 / 64 channels: D-sliding plane ring on v_mfma_f32_16x16x32, a wave = all 32
 // couts of a 4 x 16 quarter of the column, the whole weight resident in AGPRs)
@@ -180,25 +209,16 @@ int in_small_bwd_launch(const ru3d_tensor* gout, const float* part, int ksplit, 
                         const ru3d_tensor* y, const float* mean, const float* scale, const ru3d_tensor* dy,
                         const ru3d_tensor* gpre, void* ws, float slope, int zero_far, float* gpre_sum, hipStream_t st);
 
+// The per-family halves of wgrad_plan and wgrad_launch.  A *_plan fills its part of the plan (decomposition, groups) and
+// says whether the family takes the geometry; a *_launch reads it back (dy2 != NULL: the pair form).
 // wgrad_slide.hip (3x3x3 stride-1 weight gradient on the large levels: D-sliding plane ring)
-struct WgradSlidePlan {
-    int dsplit, DL, tiles_h, tiles_w, units, G, pairs;
-};
-bool wgrad_slide_plan(const WgradGeom& g, WgradSlidePlan* out);
-size_t wgrad_slide_ws_bytes(const WgradGeom& g);
-int wgrad_slide_launch(const void* x, const void* dy, float* dw, void* ws, const WgradGeom& g, hipStream_t st);
-size_t wgrad_slide_pair_ws_bytes(const WgradGeom& g);
-int wgrad_slide_pair_launch(const void* x, const void* dy, const void* dy2, int lddy2, float* dw, float* dw2, void* ws,
-                            const WgradGeom& g, hipStream_t st);
-
+bool wgrad_slide_plan(const WgradGeom& g, WgradPlan* p);
+int wgrad_slide_launch(const void* x, const void* dy, const void* dy2, int lddy2, float* dw, float* dw2, void* ws,
+                       const WgradGeom& g, const WgradPlan& p, hipStream_t st);
 // wgrad_s2.hip (3x3x3 stride-2 / ConvTranspose weight gradient on the large levels: one parity-split input tile)
-bool wgrad_s2_eligible(const WgradGeom& g);
-size_t wgrad_s2_ws_bytes(const WgradGeom& g);
-int wgrad_s2_launch(const void* x, const void* dy, float* dw, void* ws, const WgradGeom& g, hipStream_t st);
-bool wgrad_s2_pair_eligible(const WgradGeom& g);
-size_t wgrad_s2_pair_ws_bytes(const WgradGeom& g);
-int wgrad_s2_pair_launch(const void* x, const void* dy, const void* dy2, int lddy2, float* dw, float* dw2, void* ws,
-                         const WgradGeom& g, hipStream_t st);
+bool wgrad_s2_plan(const WgradGeom& g, WgradPlan* p);
+int wgrad_s2_launch(const void* x, const void* dy, const void* dy2, int lddy2, float* dw, float* dw2, void* ws,
+                    const WgradGeom& g, const WgradPlan& p, hipStream_t st);
 
 // small_convs.hip (1-channel stem, 2..4-channel head)
 bool stem_fwd_eligible(const ConvGeom& g, int dtype, int y_dtype, const void* res);
@@ -209,20 +229,17 @@ int head_fwd_launch(const void* x, const void* w, const float* bias, void* y, co
                     int y_dtype, hipStream_t st);
 bool head_dgrad_eligible(const ConvGeom& g, int dtype, int y_dtype, const void* res);
 int head_dgrad_launch(const void* dy, const void* w, void* dx, const ConvGeom& g, int dtype, hipStream_t st);
-bool stem_wgrad_eligible(const WgradGeom& g);
-size_t stem_wgrad_ws_bytes(const WgradGeom& g);
-int stem_wgrad_launch(const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes, const WgradGeom& g,
-                      int dtype, hipStream_t st, float* db = nullptr);
-bool stem_wgrad_gives_bias(const WgradGeom& g, int dtype);
+bool stem_wgrad_plan(const WgradGeom& g, int dtype, WgradPlan* p);
+int stem_wgrad_launch(const void* x, const void* dy, float* dw, float* db, void* ws, const WgradGeom& g,
+                      const WgradPlan& p, int dtype, hipStream_t st);
 // the head's whole backward in one pass over (a, dlogits fp32): dx, dW, db
 bool head_bwd_eligible(int Cin, int Cout, int dtype);
 size_t head_bwd_ws_bytes(int64_t P, int Cin);
 int head_bwd_launch(const void* a, int lda, const float* dlog, int ldd, const float* w, int cin_real, int Cin, int Cout,
                     void* dx, int lddx, float* dw, float* db, void* ws, int64_t P, hipStream_t st);
 // (dx == NULL: dW and db alone - head_bwd_wgrad_kernel, same sums)
-bool head_wgrad_eligible(const WgradGeom& g, int dtype);
-size_t head_wgrad_ws_bytes(const WgradGeom& g);
-int head_wgrad_launch(const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes, const WgradGeom& g,
+bool head_wgrad_plan(const WgradGeom& g, int dtype, WgradPlan* p);
+int head_wgrad_launch(const void* x, const void* dy, float* dw, void* ws, const WgradGeom& g, const WgradPlan& p,
                       int dtype, hipStream_t st);
 
 }  // namespace RU3D_NS

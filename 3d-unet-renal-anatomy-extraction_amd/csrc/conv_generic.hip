@@ -677,15 +677,9 @@ int wgrad_generic_chunks(const WgradGeom& g) {
     return (int)want;
 }
 
-size_t wgrad_generic_ws_bytes(const WgradGeom& g) {
-    return (size_t)wgrad_generic_chunks(g) * g.taps * g.Cin * g.Cout * sizeof(float);
-}
-
-int wgrad_generic_launch(const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes, WgradGeom g, int dtype,
+// chunks: wgrad_generic_chunks(g), as the plan holds it
+int wgrad_generic_launch(const void* x, const void* dy, float* dw, void* ws, int chunks, WgradGeom g, int dtype,
                          hipStream_t st) {
-    const int chunks = wgrad_generic_chunks(g);
-    const size_t need = wgrad_generic_ws_bytes(g);
-    if (!ws || ws_bytes < need) return ru3d_fail(-1, "wgrad: workspace too small (%zu < %zu)", ws_bytes, need);
     const int64_t P = (int64_t)g.N * g.Do * g.Ho * g.Wo;
     int64_t len = (P + chunks - 1) / chunks;
     len = (len + WG_PB - 1) / WG_PB * WG_PB;

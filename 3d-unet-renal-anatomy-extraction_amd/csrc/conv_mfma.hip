@@ -2592,8 +2592,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_staged_mfma_kernel(StagedWgradAr
     }
 }
 
-static bool wgrad_is_halo_form(const WgradGeom& g) { return g.k == 3 && g.stride == 1; }
-
 static int staged_groups(const WgradGeom& g) {
     const int64_t P = (int64_t)g.N * g.Do * g.Ho * g.Wo;
     const int pt = (g.k == 3) ? 32 : 256;
@@ -2611,14 +2609,7 @@ bool mfma_wgrad_eligible(const WgradGeom& g, int dtype) {
            (g.lddy % 8) == 0;
 }
 
-static void wgrad_tiles(const WgradGeom& g, int* td, int* th, int* tw) {
-    *tw = s1_width_class(g.Do, g.Ho, g.Wo);
-    s1_tile_dims(*tw, 2, td, th);
-}
-
-static int wgrad_mfma_groups(const WgradGeom& g) {
-    int td, th, tw;
-    wgrad_tiles(g, &td, &th, &tw);
+static int wgrad_tile_groups(const WgradGeom& g, int td, int th, int tw) {
     const int64_t ntiles = (int64_t)g.N * ((g.Do + td - 1) / td) * ((g.Ho + th - 1) / th) * ((g.Wo + tw - 1) / tw);
     const int pairs = (g.Cin / 32) * (g.Cout / 32);
     int64_t G = 512 / pairs;      // 512 workgroups in all: the tuned optimum (256 / 384 / 768 all slower, round 3)
@@ -2631,19 +2622,8 @@ static int wgrad_mfma_groups(const WgradGeom& g) {
     return (int)G;
 }
 
-size_t wgrad_mfma_ws_bytes(const WgradGeom& g) {
-    if (wgrad_is_halo_form(g)) {
-        const size_t tile = (size_t)wgrad_mfma_groups(g) * 27 * g.Cin * g.Cout * sizeof(float);
-        const size_t slide = wgrad_slide_ws_bytes(g);
-        return tile > slide ? tile : slide;
-    }
-    const int slabs = staged_groups(g) * (g.k == 1 ? 4 : 1);
-    const size_t staged = (size_t)slabs * g.taps * g.Cin * g.Cout * sizeof(float);
-    const size_t s2 = wgrad_s2_ws_bytes(g);
-    return staged > s2 ? staged : s2;
-}
-
-static int wgrad_staged_launch(const void* x, const void* dy, float* dw, void* ws, const WgradGeom& g, hipStream_t st) {
+static int wgrad_staged_launch(const void* x, const void* dy, float* dw, void* ws, const WgradGeom& g, const WgradPlan& p,
+                               hipStream_t st) {
     StagedWgradArgs a;
     a.x = (const bf16*)x;
     a.dy = (const bf16*)dy;
@@ -2652,69 +2632,132 @@ static int wgrad_staged_launch(const void* x, const void* dy, float* dw, void* w
     a.Cin = g.Cin; a.Cout = g.Cout; a.ldx = g.ldx; a.lddy = g.lddy;
     a.stride = g.stride; a.pad = g.pad;
     a.x_cseg = g.x_cseg; a.x_segstride = g.x_segstride;
-    if (g.x_cseg && (g.x_cseg % 32)) return ru3d_fail(-1, "wgrad_staged: split x needs segments of whole 32-channel tiles");
     a.P = (int64_t)g.N * g.Do * g.Ho * g.Wo;
-    const int pt = (g.k == 3) ? 32 : 256;
-    const int64_t ntiles = (a.P + pt - 1) / pt;
+    const int64_t ntiles = (a.P + p.pt - 1) / p.pt;
     if (ntiles > 0x7fffffff) return ru3d_fail(-1, "wgrad_staged: too many tiles");
     a.ntiles = (int)ntiles;
-    a.G = staged_groups(g);
+    a.G = g.k == 3 ? p.groups : p.groups / 4;      // 1x1x1: a slab per wave
     dim3 grid(a.G, (g.Cin / 32) * (g.Cout / 32));
-    int slabs;
-    if (g.k == 3) {
-        hipLaunchKernelGGL((wgrad_staged_mfma_kernel<27, 32>), grid, dim3(256), 0, st, a);
-        slabs = a.G;
-    } else {
-        hipLaunchKernelGGL((wgrad_staged_mfma_kernel<1, 256>), grid, dim3(256), 0, st, a);
-        slabs = a.G * 4;
-    }
-    int rc = ru3d_check_launch(g.k == 3 ? "wgrad_staged_mfma<27,32>" : "wgrad_staged_mfma<1,256>");
+    if (g.k == 3) hipLaunchKernelGGL((wgrad_staged_mfma_kernel<27, 32>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((wgrad_staged_mfma_kernel<1, 256>), grid, dim3(256), 0, st, a);
+    int rc = ru3d_check_launch(p.name);
     if (rc) return rc;
-    return wgrad_reduce_launch((const float*)ws, dw, slabs, g.taps, g.Cin, g.Cout, g.s_o, g.s_i, st);
+    return wgrad_reduce_launch((const float*)ws, dw, p.groups, g.taps, g.Cin, g.Cout, g.s_o, g.s_i, st);
 }
 
-int wgrad_mfma_launch(const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes, WgradGeom g,
-                      hipStream_t st) {
-    const size_t need = wgrad_mfma_ws_bytes(g);
-    if (!ws || ws_bytes < need) return ru3d_fail(-1, "wgrad_mfma: workspace too small (%zu < %zu)", ws_bytes, need);
-    if (!aligned_to(x, 16) || !aligned_to(dy, 16)) return ru3d_fail(-1, "wgrad_mfma: operands must be 16-byte aligned");
-    if (!wgrad_is_halo_form(g)) {
-        if (wgrad_s2_eligible(g)) {
-            if (g.x_cseg) return ru3d_fail(-1, "wgrad_mfma: no stride-2 kernel takes a split x");
-            return wgrad_s2_launch(x, dy, dw, ws, g, st);
-        }
-        return wgrad_staged_launch(x, dy, dw, ws, g, st);
-    }
-    {
-        WgradSlidePlan sp;
-        if (wgrad_slide_plan(g, &sp)) return wgrad_slide_launch(x, dy, dw, ws, g, st);
-    }
-    if (g.x_cseg) return ru3d_fail(-1, "wgrad_mfma: only the sliding kernel takes a split x");
+static int wgrad_tile_launch(const void* x, const void* dy, float* dw, void* ws, const WgradGeom& g, const WgradPlan& p,
+                             hipStream_t st) {
     MfmaWgradArgs a;
     a.x = (const bf16*)x;
     a.dy = (const bf16*)dy;
     a.part = (float*)ws;
     a.N = g.N; a.D = g.Do; a.H = g.Ho; a.W = g.Wo;
     a.Cin = g.Cin; a.Cout = g.Cout; a.ldx = g.ldx; a.lddy = g.lddy;
-    int td, th, tw;
-    wgrad_tiles(g, &td, &th, &tw);
-    a.tiles_d = (g.Do + td - 1) / td;
-    a.tiles_h = (g.Ho + th - 1) / th;
-    a.tiles_w = (g.Wo + tw - 1) / tw;
+    a.tiles_d = (g.Do + p.td - 1) / p.td;
+    a.tiles_h = (g.Ho + p.th - 1) / p.th;
+    a.tiles_w = (g.Wo + p.tw - 1) / p.tw;
     a.ntiles = g.N * a.tiles_d * a.tiles_h * a.tiles_w;
-    a.G = wgrad_mfma_groups(g);
+    a.G = p.groups;
     // the gradient in the Conv3d layout [co][ci][27], 16-byte aligned: a lone workgroup per pair stores it directly
-    a.dw = (a.G == 1 && g.s_i == 27 && g.s_o == (int64_t)g.Cin * 27 && aligned_to(dw, 16)) ? dw : nullptr;
+    a.dw = (p.direct && aligned_to(dw, 16)) ? dw : nullptr;
     dim3 grid(a.G, (g.Cin / 32) * (g.Cout / 32));
-    if (tw == 32)
+    if (p.tw == 32)
         hipLaunchKernelGGL((wgrad3_s1_mfma_kernel<2, 4, 32>), grid, dim3(256), 0, st, a);
-    else if (tw == 16)
+    else if (p.tw == 16)
         hipLaunchKernelGGL((wgrad3_s1_mfma_kernel<2, 8, 16>), grid, dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL((wgrad3_s1_mfma_kernel<4, 8, 8>), grid, dim3(256), 0, st, a);
-    int rc = ru3d_check_launch(tw == 32 ? "wgrad3_s1_mfma<2,4,32>" : tw == 16 ? "wgrad3_s1_mfma<2,8,16>" : "wgrad3_s1_mfma<4,8,8>");
+    int rc = ru3d_check_launch(p.name);
     if (rc || a.dw) return rc;
     return wgrad_reduce_launch((const float*)ws, dw, a.G, 27, g.Cin, g.Cout, g.s_o, g.s_i, st);
+}
+
+// ---- the plan: which family takes (geometry, dtype), its decomposition, what the queries report
+static void wgrad_refuse(WgradPlan& p, const char* why) {
+    p.family = 0;
+    p.can_pair = false;
+    p.refusal = why;
+}
+
+WgradPlan wgrad_plan(const WgradGeom& g, int dtype) {
+    WgradPlan p;
+    // a split (planar concat) x: only the MFMA families, and among them only sliding and staged
+    if (!g.x_cseg && (stem_wgrad_plan(g, dtype, &p) || head_wgrad_plan(g, dtype, &p))) return p;
+    const size_t slab = (size_t)g.taps * g.Cin * g.Cout * sizeof(float);
+    if (!mfma_wgrad_eligible(g, dtype)) {
+        if (g.x_cseg) {
+            wgrad_refuse(p, "conv3d_wgrad: no kernel takes a split x for this shape / dtype");
+            return p;
+        }
+        p.family = WG_GENERIC;
+        p.groups = wgrad_generic_chunks(g);
+        p.ws_bytes = p.groups * slab;
+        snprintf(p.name, sizeof p.name, "wgrad_generic");
+        return p;
+    }
+    const bool seg_ok = !g.x_cseg || (g.x_cseg % 32) == 0;      // segments of whole 32-channel tiles
+    size_t other;                                               // the family that does not run, see ws_bytes
+    if (g.k == 3 && g.stride == 1) {                            // the halo forms: sliding, else tiles
+        p.tw = s1_width_class(g.Do, g.Ho, g.Wo);
+        s1_tile_dims(p.tw, 2, &p.td, &p.th);
+        const int tile_groups = wgrad_tile_groups(g, p.td, p.th, p.tw);
+        other = tile_groups * slab;
+        if (wgrad_slide_plan(g, &p)) {
+            p.family = WG_SLIDE;
+            p.can_pair = true;
+            if (!seg_ok) wgrad_refuse(p, "wgrad_slide: split x needs segments of whole 32-channel tiles");
+        } else {
+            p.family = WG_S1_TILE;
+            p.groups = tile_groups;
+            p.direct = p.groups == 1 && g.s_i == 27 && g.s_o == (int64_t)g.Cin * 27;
+            snprintf(p.name, sizeof p.name, "wgrad3_s1_mfma<%d,%d,%d>", p.td, p.th, p.tw);
+            if (g.x_cseg) wgrad_refuse(p, "wgrad_mfma: only the sliding kernel takes a split x");
+        }
+    } else {                                                    // stride 2, ConvTranspose, 1x1x1: s2, else staged
+        const int staged_slabs = staged_groups(g) * (g.k == 1 ? 4 : 1);
+        other = staged_slabs * slab;
+        if (wgrad_s2_plan(g, &p)) {
+            p.family = WG_S2;
+            p.can_pair = p.dma;
+            if (g.x_cseg) wgrad_refuse(p, "wgrad_mfma: no stride-2 kernel takes a split x");
+        } else {
+            p.family = WG_STAGED;
+            p.groups = staged_slabs;
+            p.pt = g.k == 3 ? 32 : 256;
+            snprintf(p.name, sizeof p.name, "wgrad_staged_mfma<%d,%d>", g.taps, p.pt);
+            if (!seg_ok) wgrad_refuse(p, "wgrad_staged: split x needs segments of whole 32-channel tiles");
+        }
+    }
+    p.ws_bytes = p.groups * slab > other ? p.groups * slab : other;
+    if (p.can_pair) p.pair_ws_bytes = (size_t)p.groups * (g.taps + 1) * g.Cin * g.Cout * sizeof(float);
+    return p;
+}
+
+// ---- the one consumer: launch-time checks, then the family's launcher
+int wgrad_launch(const WgradPlan& p, const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes,
+                 const WgradGeom& g, int dtype, hipStream_t st, const void* dy2, int lddy2, float* dw2, float* db) {
+    if (!p.family) return ru3d_fail(-1, "%s", p.refusal ? p.refusal : "wgrad: no kernel takes this shape / dtype");
+    if (dy2 && !p.can_pair) return ru3d_fail(-1, "wgrad: no pair form for this shape");
+    if (db && !p.gives_bias) return ru3d_fail(-1, "stem_wgrad: no bias gradient from this form");
+    const size_t need = dy2 ? p.pair_ws_bytes : p.ws_bytes;
+    if (!ws || ws_bytes < need) {
+        if (dy2) return ru3d_fail(-1, "conv3d_wgrad_pair: workspace too small");
+        if (p.family <= WG_HEAD) return ru3d_fail(-1, "%s: workspace too small", p.family == WG_HEAD ? "head_wgrad" : "stem_wgrad");
+        return ru3d_fail(-1, "%s: workspace too small (%zu < %zu)", p.family == WG_GENERIC ? "wgrad" : "wgrad_mfma", ws_bytes, need);
+    }
+    const bool mfma = p.family >= WG_SLIDE && p.family <= WG_STAGED;
+    if (mfma && (!aligned_to(x, 16) || !aligned_to(dy, 16) || !aligned_to(dy2, 16)))
+        return ru3d_fail(-1, "wgrad_mfma: operands must be 16-byte aligned");
+    switch (p.family) {
+        case WG_STEM_MFMA:
+        case WG_STEM: return stem_wgrad_launch(x, dy, dw, db, ws, g, p, dtype, st);
+        case WG_HEAD: return head_wgrad_launch(x, dy, dw, ws, g, p, dtype, st);
+        case WG_SLIDE: return wgrad_slide_launch(x, dy, dy2, lddy2, dw, dw2, ws, g, p, st);
+        case WG_S1_TILE: return wgrad_tile_launch(x, dy, dw, ws, g, p, st);
+        case WG_S2: return wgrad_s2_launch(x, dy, dy2, lddy2, dw, dw2, ws, g, p, st);
+        case WG_STAGED: return wgrad_staged_launch(x, dy, dw, ws, g, p, st);
+        default: return wgrad_generic_launch(x, dy, dw, ws, p.groups, g, dtype, st);
+    }
 }
 
 }  // namespace RU3D_NS

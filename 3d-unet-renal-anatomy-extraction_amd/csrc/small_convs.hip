@@ -497,58 +497,40 @@ __global__ __launch_bounds__(256) void stem_wgrad_mfma_kernel(const bf16* __rest
     }
 }
 
-static bool stem_wgrad_mfma_ok(const WgradGeom& g, int dtype) {
-    static const int mode = ru3d_env_int("RU3D_STEM_MFMA", 1);
-    return mode && dtype == RU3D_BF16 && g.Do == g.Di && g.Ho == g.Hi && g.Wo == g.Wi && g.pad == 1;
-}
-
-static int stem_mfma_blocks(const WgradGeom& g) {
-    const int64_t ntiles = (int64_t)g.N * g.Do * ((g.Ho + 7) / 8) * ((g.Wo + 31) / 32);
-    return (int)(ntiles < STEM_MF_BLOCKS ? ntiles : STEM_MF_BLOCKS);
-}
-
-bool stem_wgrad_eligible(const WgradGeom& g) {
-    return g.Cin == 1 && g.k == 3 && g.stride == 1 && (g.Cout % 32) == 0 && (g.lddy % 8) == 0 &&
-           (int64_t)g.N * g.Do * g.Ho * g.Wo < (1ll << 31);
-}
-
-static int stem_chunks(const WgradGeom& g) {
+// The MFMA form (16-bit, same extents; it can deliver the bias gradient - the sum of dy over all positions - from the same
+// pass) or the scalar one.  groups: the slabs of the form that runs.
+bool stem_wgrad_plan(const WgradGeom& g, int dtype, WgradPlan* p) {
     const int64_t P = (int64_t)g.N * g.Do * g.Ho * g.Wo;
-    return (int)((P + STEM_CHUNK - 1) / STEM_CHUNK);
-}
-
-size_t stem_wgrad_ws_bytes(const WgradGeom& g) {
-    // upper bound over both kernels (the MFMA form writes at most STEM_MF_BLOCKS slabs, 28 rows each with the bias row)
-    const size_t chunks = (size_t)stem_chunks(g) > (size_t)STEM_MF_BLOCKS ? (size_t)stem_chunks(g) : (size_t)STEM_MF_BLOCKS;
-    return chunks * 28 * g.Cout * sizeof(float);
-}
-
-// the MFMA form can deliver the bias gradient (sum of dy over all positions) from the same pass
-bool stem_wgrad_gives_bias(const WgradGeom& g, int dtype) {
+    if (g.Cin != 1 || g.k != 3 || g.stride != 1 || (g.Cout % 32) || (g.lddy % 8) || P >= (1ll << 31)) return false;
+    static const int mode = ru3d_env_int("RU3D_STEM_MFMA", 1);
     const int64_t ntiles = (int64_t)g.N * g.Do * ((g.Ho + 7) / 8) * ((g.Wo + 31) / 32);
-    return stem_wgrad_eligible(g) && stem_wgrad_mfma_ok(g, dtype) && ntiles <= 0x7fffffff;
+    const int chunks = (int)((P + STEM_CHUNK - 1) / STEM_CHUNK);
+    p->gives_bias = mode && dtype == RU3D_BF16 && g.Do == g.Di && g.Ho == g.Hi && g.Wo == g.Wi && g.pad == 1 &&
+                    ntiles <= 0x7fffffff;
+    p->family = p->gives_bias ? WG_STEM_MFMA : WG_STEM;
+    p->groups = p->gives_bias ? (int)(ntiles < STEM_MF_BLOCKS ? ntiles : STEM_MF_BLOCKS) : chunks;
+    // the bound over both kernels (the MFMA form writes at most STEM_MF_BLOCKS slabs, 28 rows each with the bias row)
+    p->ws_bytes = (size_t)(chunks > STEM_MF_BLOCKS ? chunks : STEM_MF_BLOCKS) * 28 * g.Cout * sizeof(float);
+    snprintf(p->name, sizeof p->name, p->gives_bias ? "stem_wgrad_mfma" : "stem_wgrad");
+    return true;
 }
 
-int stem_wgrad_launch(const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes, const WgradGeom& g,
-                      int dtype, hipStream_t st, float* db) {
-    if (!ws || ws_bytes < stem_wgrad_ws_bytes(g)) return ru3d_fail(-1, "stem_wgrad: workspace too small");
-    if (db && !stem_wgrad_gives_bias(g, dtype)) return ru3d_fail(-1, "stem_wgrad: no bias gradient from this form");
-    if (stem_wgrad_mfma_ok(g, dtype)) {
-        const int blocks = stem_mfma_blocks(g);
+int stem_wgrad_launch(const void* x, const void* dy, float* dw, float* db, void* ws, const WgradGeom& g,
+                      const WgradPlan& p, int dtype, hipStream_t st) {
+    if (db && !p.gives_bias) return ru3d_fail(-1, "stem_wgrad: no bias gradient from this form");
+    if (p.family == WG_STEM_MFMA) {
+        const int blocks = p.groups;
         const int tiles_h = (g.Ho + 7) / 8, tiles_w = (g.Wo + 31) / 32;
-        const int64_t ntiles = (int64_t)g.N * g.Do * tiles_h * tiles_w;
-        if (ntiles <= 0x7fffffff) {
-            float* bias_part = db ? (float*)ws + (size_t)blocks * 27 * g.Cout : nullptr;
-            hipLaunchKernelGGL(stem_wgrad_mfma_kernel, dim3(blocks, g.Cout / 32), dim3(256), 0, st, (const bf16*)x,
-                               (const bf16*)dy, (float*)ws, g, tiles_h, tiles_w, (int)ntiles, bias_part);
-            int rc = ru3d_check_launch("stem_wgrad_mfma");
-            if (rc) return rc;
-            rc = wgrad_reduce_launch((const float*)ws, dw, blocks, 27, 1, g.Cout, g.s_o, g.s_i, st);
-            if (rc || !db) return rc;
-            return wgrad_reduce_launch(bias_part, db, blocks, 1, 1, g.Cout, 1, 1, st);
-        }
+        float* bias_part = db ? (float*)ws + (size_t)blocks * 27 * g.Cout : nullptr;
+        hipLaunchKernelGGL(stem_wgrad_mfma_kernel, dim3(blocks, g.Cout / 32), dim3(256), 0, st, (const bf16*)x,
+                           (const bf16*)dy, (float*)ws, g, tiles_h, tiles_w, g.N * g.Do * tiles_h * tiles_w, bias_part);
+        int rc = ru3d_check_launch(p.name);
+        if (rc) return rc;
+        rc = wgrad_reduce_launch((const float*)ws, dw, blocks, 27, 1, g.Cout, g.s_o, g.s_i, st);
+        if (rc || !db) return rc;
+        return wgrad_reduce_launch(bias_part, db, blocks, 1, 1, g.Cout, 1, 1, st);
     }
-    const int chunks = stem_chunks(g);
+    const int chunks = p.groups;
     dim3 grid(chunks, g.Cout / 32);
     if (dtype == RU3D_F32)
         hipLaunchKernelGGL(stem_wgrad_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (const float*)dy,
@@ -781,24 +763,21 @@ int head_bwd_launch(const void* a, int lda, const float* dlog, int ldd, const fl
     return ru3d_check_launch("head_bwd_finalize");
 }
 
-bool head_wgrad_eligible(const WgradGeom& g, int dtype) {
+bool head_wgrad_plan(const WgradGeom& g, int dtype, WgradPlan* p) {
     const int vec = dtype == RU3D_BF16 ? 8 : 4;
-    return g.k == 1 && g.stride == 1 && g.Cout <= 4 && (g.Cin % vec) == 0 && (g.Cin / vec) <= 256 &&
-           (g.ldx % vec) == 0;
-}
-
-static int head_chunks(const WgradGeom& g) {
+    if (g.k != 1 || g.stride != 1 || g.Cout > 4 || (g.Cin % vec) || (g.Cin / vec) > 256 || (g.ldx % vec)) return false;
     const int64_t P = (int64_t)g.N * g.Do * g.Ho * g.Wo;
-    return (int)((P + HEAD_SPAN - 1) / HEAD_SPAN);
+    p->family = WG_HEAD;
+    p->groups = (int)((P + HEAD_SPAN - 1) / HEAD_SPAN);
+    p->ws_bytes = (size_t)p->groups * g.Cin * g.Cout * sizeof(float);
+    snprintf(p->name, sizeof p->name, "head_wgrad");
+    return true;
 }
 
-size_t head_wgrad_ws_bytes(const WgradGeom& g) { return (size_t)head_chunks(g) * g.Cin * g.Cout * sizeof(float); }
-
-int head_wgrad_launch(const void* x, const void* dy, float* dw, void* ws, size_t ws_bytes, const WgradGeom& g,
+int head_wgrad_launch(const void* x, const void* dy, float* dw, void* ws, const WgradGeom& g, const WgradPlan& p,
                       int dtype, hipStream_t st) {
-    if (!ws || ws_bytes < head_wgrad_ws_bytes(g)) return ru3d_fail(-1, "head_wgrad: workspace too small");
     if (((uintptr_t)x) % 16) return ru3d_fail(-1, "head_wgrad: x must be 16-byte aligned");
-    const int chunks = head_chunks(g);
+    const int chunks = p.groups;
     if (dtype == RU3D_F32)
         hipLaunchKernelGGL((head_wgrad_kernel<float, 4>), dim3(chunks), dim3(256), 0, st, (const float*)x,
                            (const float*)dy, (float*)ws, g);

@@ -338,57 +338,38 @@ __global__ __launch_bounds__(256, 1) void wgrad3_s2_dma_kernel(WS2Args a) {
 
 // ---- dispatch: the LDS-DMA kernel (16-wide tiles, two cout tiles per workgroup when Cout % 64 == 0) where W fits its
 // tiles, the register-staged kernel elsewhere
-static int s2_mode() { return 2; }
-static bool s2_dma(const WgradGeom& g) {
-    return s2_mode() >= 2 && (g.Wo % DW) == 0 &&
-           (int64_t)g.Di * g.Hi * g.Wi * g.ldx < (1ll << 30) && (int64_t)g.Do * g.Ho * g.Wo * g.lddy < (1ll << 30);
-}
-static int s2_nco(const WgradGeom& g) { return (s2_dma(g) && (g.Cout % 64) == 0) ? 2 : 1; }
-static int s2_tw(const WgradGeom& g) { return s2_dma(g) ? DW : TWO; }
+}  // namespace
 
-static int s2_groups(const WgradGeom& g, int64_t ntiles) {
-    const int pairs = (g.Cin / 32) * (g.Cout / (32 * s2_nco(g)));
+// fills p->dma / nco / tw / groups and the log names
+bool wgrad_s2_plan(const WgradGeom& g, WgradPlan* p) {
+    if (g.k != 3 || g.stride != 2 || g.pad != 1 || (g.Cin % 32) || (g.Cout % 32) || (g.ldx % 8) || (g.lddy % 8))
+        return false;
+    const bool dma = (g.Wo % DW) == 0 && (int64_t)g.Di * g.Hi * g.Wi * g.ldx < (1ll << 30) &&
+                     (int64_t)g.Do * g.Ho * g.Wo * g.lddy < (1ll << 30);
+    const int nco = (dma && (g.Cout % 64) == 0) ? 2 : 1, tw = dma ? DW : TWO;
+    if ((g.Wo % tw) || (g.Ho % THO) || (g.Do % TDO)) return false;
+    const int pairs = (g.Cin / 32) * (g.Cout / (32 * nco));
+    const int64_t ntiles = (int64_t)g.N * (g.Do / TDO) * (g.Ho / THO) * (g.Wo / tw);
+    if (pairs > 32 || ntiles * pairs < 192 || ntiles > 0x7fffffff) return false;
     int64_t G = ru3d_get_cu_budget() / pairs;            // one workgroup per CU (112-123 KB of LDS each)
     if (G < 1) G = 1;
     if (G > ntiles) G = ntiles;
-    return (int)G;
-}
-}  // namespace
-
-bool wgrad_s2_eligible(const WgradGeom& g) {
-    if (!s2_mode() || g.k != 3 || g.stride != 2 || g.pad != 1 || (g.Cin % 32) || (g.Cout % 32) || (g.ldx % 8) || (g.lddy % 8))
-        return false;
-    const int tw = s2_tw(g);
-    if ((g.Wo % tw) || (g.Ho % THO) || (g.Do % TDO)) return false;
-    const int pairs = (g.Cin / 32) * (g.Cout / (32 * s2_nco(g)));
-    const int64_t ntiles = (int64_t)g.N * (g.Do / TDO) * (g.Ho / THO) * (g.Wo / tw);
-    return pairs <= 32 && ntiles * pairs >= 192 && ntiles <= 0x7fffffff;
+    p->dma = dma; p->nco = nco; p->tw = tw;
+    p->groups = (int)G;
+    if (dma) {
+        snprintf(p->name, sizeof p->name, "wgrad3_s2_dma<%d>", nco);
+        snprintf(p->pair_name, sizeof p->pair_name, "wgrad3_s2_dma<%d,pair>", nco);
+    } else {
+        snprintf(p->name, sizeof p->name, "wgrad3_s2_tile");
+    }
+    return true;
 }
 
-size_t wgrad_s2_ws_bytes(const WgradGeom& g) {
-    if (!wgrad_s2_eligible(g)) return 0;
-    const int64_t ntiles = (int64_t)g.N * (g.Do / TDO) * (g.Ho / THO) * (g.Wo / s2_tw(g));
-    return (size_t)s2_groups(g, ntiles) * 27 * g.Cin * g.Cout * sizeof(float);
-}
-
-bool wgrad_s2_pair_eligible(const WgradGeom& g) { return wgrad_s2_eligible(g) && s2_dma(g) && !g.x_cseg; }
-
-size_t wgrad_s2_pair_ws_bytes(const WgradGeom& g) {
-    if (!wgrad_s2_pair_eligible(g)) return 0;
-    const int64_t ntiles = (int64_t)g.N * (g.Do / TDO) * (g.Ho / THO) * (g.Wo / s2_tw(g));
-    return (size_t)s2_groups(g, ntiles) * 28 * g.Cin * g.Cout * sizeof(float);
-}
-
-int wgrad_s2_launch(const void* x, const void* dy, float* dw, void* ws, const WgradGeom& g, hipStream_t st) {
-    return wgrad_s2_pair_launch(x, dy, nullptr, 0, dw, nullptr, ws, g, st);
-}
-
-// dy2 != nullptr: also dw2[co][ci] = sum_pos x[2 pos][ci] * dy2[pos][co] (the 1x1x1 stride-2 conv of the same x)
-int wgrad_s2_pair_launch(const void* x, const void* dy, const void* dy2, int lddy2, float* dw, float* dw2, void* ws,
-                         const WgradGeom& g, hipStream_t st) {
-    if (!wgrad_s2_eligible(g)) return ru3d_fail(-1, "wgrad_s2: shape not supported");
-    if (dy2 && !wgrad_s2_pair_eligible(g)) return ru3d_fail(-1, "wgrad_s2: no pair form for this shape");
-    const int tw = s2_tw(g), nco = s2_nco(g);
+// dy2 != nullptr: also dw2[co][ci] = sum_pos x[2 pos][ci] * dy2[pos][co] (the 1x1x1 stride-2 conv of the same x; DMA
+// kernel only: plan.can_pair)
+int wgrad_s2_launch(const void* x, const void* dy, const void* dy2, int lddy2, float* dw, float* dw2, void* ws,
+                    const WgradGeom& g, const WgradPlan& p, hipStream_t st) {
+    const int tw = p.tw, nco = p.nco;
     WS2Args a;
     a.x = (const bf16*)x;
     a.dy = (const bf16*)dy;
@@ -397,13 +378,12 @@ int wgrad_s2_pair_launch(const void* x, const void* dy, const void* dy2, int ldd
     a.Cin = g.Cin; a.Cout = g.Cout; a.ldx = g.ldx; a.lddy = g.lddy;
     a.tiles_d = g.Do / TDO; a.tiles_h = g.Ho / THO; a.tiles_w = g.Wo / tw;
     a.ntiles = g.N * a.tiles_d * a.tiles_h * a.tiles_w;
-    a.G = s2_groups(g, a.ntiles);
+    a.G = p.groups;
     a.dy2 = (const bf16*)dy2;
     a.lddy2 = lddy2;
     a.part2 = (float*)ws + (size_t)a.G * 27 * g.Cin * g.Cout;
     const dim3 grid(a.G, (g.Cin / 32) * (g.Cout / (32 * nco)));
-    if (s2_dma(g)) {
-        if ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dy2)) % 16) return ru3d_fail(-1, "wgrad_s2: x / dy must be 16-byte aligned");
+    if (p.dma) {
         if (dy2) {
             if (nco == 2) hipLaunchKernelGGL((wgrad3_s2_dma_kernel<2, true>), grid, dim3(256), 0, st, a);
             else hipLaunchKernelGGL((wgrad3_s2_dma_kernel<1, true>), grid, dim3(256), 0, st, a);
@@ -414,7 +394,7 @@ int wgrad_s2_pair_launch(const void* x, const void* dy, const void* dy2, int ldd
     } else {
         hipLaunchKernelGGL(wgrad3_s2_tile_kernel<1>, grid, dim3(256), 0, st, a);
     }
-    int rc = ru3d_check_launch("wgrad3_s2_tile");
+    int rc = ru3d_check_launch(dy2 ? p.pair_name : p.name);
     if (rc) return rc;
     rc = wgrad_reduce_launch((const float*)ws, dw, a.G, 27, g.Cin, g.Cout, g.s_o, g.s_i, st);
     if (rc || !dy2) return rc;

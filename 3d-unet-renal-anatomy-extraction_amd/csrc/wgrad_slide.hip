@@ -315,7 +315,7 @@ __global__ __launch_bounds__(256, 1) void wgrad3_s1_slide_kernel(WSlideArgs a) {
 }  // namespace
 
 // units per pair = N x dsplit x (H/8) x (W/32); G persistent workgroups per pair (= slabs), pairs on grid.y.
-bool wgrad_slide_plan(const WgradGeom& g, WgradSlidePlan* out) {
+bool wgrad_slide_plan(const WgradGeom& g, WgradPlan* p) {
     static const int mode = ru3d_env_int("RU3D_WGRAD_SLIDE", 1);
     if (!mode || g.k != 3 || g.stride != 1 || (g.Cin % 32) || (g.Cout % 32) || (g.Ho % TH) || (g.Wo % 8) || g.Wo < 16) return false;   // dy positions beyond W are masked one by one
     if (g.Do != g.Di || g.Ho != g.Hi || g.Wo != g.Wi || (g.ldx % 8) || (g.lddy % 8)) return false;
@@ -328,6 +328,7 @@ bool wgrad_slide_plan(const WgradGeom& g, WgradSlidePlan* out) {
     const bool light = (g.Wo % TW) != 0 && (g.Wo % TW) <= 16 && tw_n > 1;
     const int64_t cols = (int64_t)g.N * (g.Ho / TH) * tw_n;
     const int gmax = ru3d_get_cu_budget() / pairs;             // one workgroup per CU in total
+    if (gmax < 1) return false;                                // a CU budget below the pair count: not this kernel
     int64_t best_cost = -1;
     int best = 0;
     for (int ds = 1; ds <= g.Do / 8; ds++) {
@@ -351,38 +352,25 @@ bool wgrad_slide_plan(const WgradGeom& g, WgradSlidePlan* out) {
     const int64_t units = cols * best;
     const double ideal = (double)cols * pairs * g.Do / (double)ru3d_get_cu_budget();
     if (units * pairs < 192 || (double)best_cost > 1.5 * ideal + 8) return false;
-    out->dsplit = best;
-    out->DL = g.Do / best;
-    out->tiles_h = g.Ho / TH;
-    out->tiles_w = (g.Wo + TW - 1) / TW;
-    out->units = (int)units;
-    out->G = (int)(units < gmax ? units : gmax);
-    out->pairs = pairs;
+    WgradSlidePlan& sp = p->slide;
+    sp.dsplit = best;
+    sp.DL = g.Do / best;
+    sp.tiles_h = g.Ho / TH;
+    sp.tiles_w = tw_n;
+    sp.units = (int)units;
+    sp.G = p->groups = (int)(units < gmax ? units : gmax);
+    sp.pairs = pairs;
+    const bool edge = (g.Wo % TW) != 0;
+    snprintf(p->name, sizeof p->name, "wgrad3_s1_slide%s", edge ? "<edge>" : "");
+    snprintf(p->pair_name, sizeof p->pair_name, "wgrad3_s1_slide%s", edge ? "<edge,pair>" : "<pair>");
     return true;
 }
 
-size_t wgrad_slide_ws_bytes(const WgradGeom& g) {
-    WgradSlidePlan p;
-    if (!wgrad_slide_plan(g, &p)) return 0;
-    return (size_t)p.G * 27 * g.Cin * g.Cout * sizeof(float);
-}
-
-// the pair form's slabs: 27 + 1 taps
-size_t wgrad_slide_pair_ws_bytes(const WgradGeom& g) {
-    WgradSlidePlan p;
-    if (!wgrad_slide_plan(g, &p)) return 0;
-    return (size_t)p.G * 28 * g.Cin * g.Cout * sizeof(float);
-}
-
-int wgrad_slide_launch(const void* x, const void* dy, float* dw, void* ws, const WgradGeom& g, hipStream_t st) {
-    return wgrad_slide_pair_launch(x, dy, nullptr, 0, dw, nullptr, ws, g, st);
-}
-
-// dy2 != nullptr: also dw2[co][ci] = sum_pos x[pos][ci] * dy2[pos][co] (a 1x1x1 conv of the same x), PAIR kernel
-int wgrad_slide_pair_launch(const void* x, const void* dy, const void* dy2, int lddy2, float* dw, float* dw2, void* ws,
-                            const WgradGeom& g, hipStream_t st) {
-    WgradSlidePlan p;
-    if (!wgrad_slide_plan(g, &p)) return ru3d_fail(-1, "wgrad_slide: shape not supported");
+// dy2 != nullptr: also dw2[co][ci] = sum_pos x[pos][ci] * dy2[pos][co] (a 1x1x1 conv of the same x), PAIR kernel: its
+// slabs are 27 + 1 taps
+int wgrad_slide_launch(const void* x, const void* dy, const void* dy2, int lddy2, float* dw, float* dw2, void* ws,
+                       const WgradGeom& g, const WgradPlan& plan, hipStream_t st) {
+    const WgradSlidePlan& p = plan.slide;
     WSlideArgs a;
     a.x = (const bf16*)x;
     a.dy = (const bf16*)dy;
@@ -390,7 +378,6 @@ int wgrad_slide_pair_launch(const void* x, const void* dy, const void* dy2, int 
     a.N = g.N; a.D = g.Do; a.H = g.Ho; a.W = g.Wo;
     a.Cin = g.Cin; a.Cout = g.Cout; a.ldx = g.ldx; a.lddy = g.lddy;
     a.x_cseg = g.x_cseg; a.x_segstride = g.x_segstride;
-    if (g.x_cseg && (g.x_cseg % 32)) return ru3d_fail(-1, "wgrad_slide: split x needs segments of whole 32-channel tiles");
     a.tiles_h = p.tiles_h; a.tiles_w = p.tiles_w; a.dsplit = p.dsplit; a.DL = p.DL; a.units = p.units;
     a.light_last = (g.Wo % TW) != 0 && (g.Wo % TW) <= 16 && p.tiles_w > 1;
     a.dy2 = (const bf16*)dy2;
@@ -403,7 +390,7 @@ int wgrad_slide_pair_launch(const void* x, const void* dy, const void* dy2, int 
         if (g.Wo % TW) hipLaunchKernelGGL((wgrad3_s1_slide_kernel<true, false>), dim3(p.G, p.pairs), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((wgrad3_s1_slide_kernel<false, false>), dim3(p.G, p.pairs), dim3(256), 0, st, a);
     }
-    int rc = ru3d_check_launch("wgrad3_s1_slide");
+    int rc = ru3d_check_launch(dy2 ? plan.pair_name : plan.name);
     if (rc) return rc;
     rc = wgrad_reduce_launch((const float*)ws, dw, p.G, 27, g.Cin, g.Cout, g.s_o, g.s_i, st);
     if (rc || !dy2) return rc;
