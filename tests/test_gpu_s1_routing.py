@@ -3,6 +3,7 @@ kernel family and per launch-time fallback, at the smallest shape that reaches i
 case first asserts the launch log exactly - the names carry the instantiation - and then compares the result with torch
 CPU on operands rounded to the storage type (tests/test_gpu_pc4.py's tolerances).  The expected names were recorded
 from the dispatch as it stood before the plan was folded into one function.  Run with `-m gpu`."""
+import contextlib
 import ctypes
 
 import pytest
@@ -20,6 +21,13 @@ DEV = torch.device("cuda:0")
 F = torch.nn.functional
 EPS = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
 DT = torch.bfloat16
+DTYPES = [torch.bfloat16, torch.float16]
+
+
+def both_types(ids):
+    """(id, storage type) pairs and their test ids: every id in bf16 under its own name, then in fp16 as <id>-fp16"""
+    pairs = [(i, dt) for dt in DTYPES for i in ids]
+    return pairs, [i if dt == torch.bfloat16 else i + "-fp16" for i, dt in pairs]
 
 
 def _rt(t, dt=DT):
@@ -56,9 +64,25 @@ def _fwd_raw(x, pw, bias, y, res=None, with_ws=True):
                                  N.stream())
 
 
+@contextlib.contextmanager
+def scratch_short_by(nbytes):
+    """inside: the wrappers hand ru3d_conv3d_fwd / _dgrad their optional scratch `nbytes` short of what the query asks"""
+    def short(dsrc, ddst, k, stride, dtype, device):
+        need = N.lib.ru3d_conv3d_workspace_bytes(N.ref(dsrc), N.ref(ddst), k, stride, N.dtype_code(dtype))
+        assert need > nbytes, "the case has no scratch to shorten"
+        return N.ptr(N.workspace(need, device)), need - nbytes
+    real, ops._conv_ws = ops._conv_ws, short
+    try:
+        yield
+    finally:
+        ops._conv_ws = real
+
+
 # id: (n, cin, cout, dims, what, names).  what: "fwd" (bias), "res" (bias + residual), "stats" (ru3d_conv3d_fwd_in),
 # "dgrad" (input gradient of the module conv cin -> cout: the kernel sees cout -> cin channels, flipped taps),
-# "no_ws" (forward without the optional scratch), "y8" (forward into a y whose pointer is 8- but not 16-byte aligned)
+# "no_ws" (forward without the optional scratch), "y8" (forward into a y whose pointer is 8- but not 16-byte aligned),
+# "short:fwd" / "short:res" / "short:dgrad" (the form named, on a scratch 16 bytes under the query: the plan is a ladder,
+# and the launch takes the first kernel whose partials fit - on the deepest level conv_ws wants 8 slices, conv3_s1_sk 4)
 CASES = {
     "slide32": (2, 32, 64, (16, 32, 64), "fwd", ["conv3_s1_slide32"]),
     "slide32_res": (2, 32, 32, (16, 64, 64), "res", ["conv3_s1_slide32<res>"]),
@@ -76,9 +100,13 @@ CASES = {
     "conv_ws_res": (2, 256, 256, (10, 10, 5), "res", ["conv_ws", "conv_ksplit_reduce"]),
     "conv_ws_dgrad": (2, 256, 256, (10, 10, 5), "dgrad", ["conv_ws", "conv_ksplit_reduce"]),
     "conv_ws_no_ws": (2, 256, 256, (10, 10, 5), "no_ws", ["conv3_s1_mfma<2,8,8,1,1>"]),
+    "conv_ws_short": (2, 256, 256, (10, 10, 5), "short:fwd", ["conv3_s1_sk<8>", "conv_ksplit_reduce"]),
+    "conv_ws_short_res": (2, 256, 256, (10, 10, 5), "short:res", ["conv3_s1_sk<8>", "conv_ksplit_reduce"]),
+    "conv_ws_short_dgrad": (2, 256, 256, (10, 10, 5), "short:dgrad", ["conv3_s1_sk<8>", "conv_ksplit_reduce"]),
     "sk16": (2, 256, 256, (16, 16, 16), "fwd", ["conv3_s1_sk<16>"]),
     "sk16_dgrad": (2, 256, 256, (16, 16, 16), "dgrad", ["conv3_s1_sk<16>"]),
     "sk8_split": (3, 256, 128, (4, 8, 24), "res", ["conv3_s1_sk<8>", "conv_ksplit_reduce"]),
+    "sk8_split_short": (3, 256, 128, (4, 8, 24), "short:res", ["conv3_s1_sk<8>", "conv_ksplit_reduce"]),
     "sk16_split": (2, 256, 256, (8, 8, 32), "fwd", ["conv3_s1_sk<16>", "conv_ksplit_reduce"]),
     "sk16_split_no_ws": (2, 256, 256, (8, 8, 32), "no_ws", ["conv3_s1_mfma<1,4,32,1,1>"]),
     "sk8_split_no_ws": (2, 512, 512, (8, 8, 8), "no_ws", ["conv3_s1_mfma<2,8,8,1,1>"]),
@@ -97,30 +125,37 @@ CASES = {
     "tile_mt2_one_per_cu": (2, 96, 64, (18, 32, 32), "fwd", ["conv3_s1_mfma<2,4,32,2,1>"]),
     "tile_w8_splitk": (1, 64, 64, (8, 8, 8), "fwd", ["conv3_s1_mfma<4,8,8,2,1>", "conv_ksplit_reduce"]),
     "tile_w16_splitk": (1, 96, 32, (8, 8, 16), "fwd", ["conv3_s1_mfma<2,8,16,2,1>", "conv_ksplit_reduce"]),
+    "tile_w16_splitk_no_ws": (1, 96, 32, (8, 8, 16), "no_ws", ["conv3_s1_mfma<1,8,16,1,1>"]),
     "tile_w32_splitk": (1, 96, 32, (4, 8, 32), "res", ["conv3_s1_mfma<2,4,32,2,1>", "conv_ksplit_reduce"]),
     "tile_splitk_no_ws": (1, 128, 128, (8, 8, 8), "no_ws", ["conv3_s1_mfma<2,8,8,1,1>"]),
 }
 
 
-@pytest.mark.parametrize("case", sorted(CASES))
-def test_s1_routing(case):
+ROUTES, ROUTE_IDS = both_types(sorted(CASES))
+
+
+@pytest.mark.parametrize("case,DT", ROUTES, ids=ROUTE_IDS)
+def test_s1_routing(case, DT):
+    """the names are the same for both storage types: the fp16 build is a second compilation of the same dispatch"""
     n, cin, cout, dims, what, names = CASES[case]
     d, h, w = dims
     xv, wt, b, r, gy = _operands(n, cin, cout, dims, len(case) + n + cin + cout + sum(dims))
-    xr, wr = _rt(xv), _rt(wt)
+    xr, wr = _rt(xv, DT), _rt(wt, DT)
+    scratch = scratch_short_by(16) if what.startswith("short:") else contextlib.nullcontext()
+    what = what[6:] if what.startswith("short:") else what
     if what == "dgrad":
         pw = ops.pack_weight(wt.to(DEV), N.ROLE_CONV_DGRAD, DT, 1)
         gyd = ops.as_input(gy.to(DEV), DT)
-        with ops.launch_log() as log:
+        with scratch, ops.launch_log() as log:
             got = ops.conv_dgrad(gyd, pw, (n, cin, d, h, w), 3, 1)
-        want, tol = F.conv_transpose3d(_rt(gy), wr, None, padding=1), EPS[DT]
+        want, tol = F.conv_transpose3d(_rt(gy, DT), wr, None, padding=1), EPS[DT]
     else:
         pw = ops.pack_weight(wt.to(DEV), N.ROLE_CONV_FWD, DT, 1)
         x = ops.as_input(xv.to(DEV), DT)
         bias = b.to(DEV)
         want, tol = F.conv3d(xr, wr, b, padding=1), EPS[DT]
         res = ops.as_input(r.to(DEV), DT) if what == "res" else None
-        with ops.launch_log() as log:
+        with scratch, ops.launch_log() as log:
             if what == "fwd":
                 got = ops.conv_fwd(x, pw, bias, cout, 3, 1)
             elif what == "res":
@@ -136,8 +171,8 @@ def test_s1_routing(case):
                 assert got.data_ptr() % 16 == 8
                 N.check(_fwd_raw(x, pw, bias, got), "conv3d_fwd")
         if what == "res":       # two roundings: the conv's value, then the sum with the residual
-            want, tol = _rt(want) + _rt(r), 1.5 * EPS[DT]
-    print("ROUTE %s %s" % (case, log.names))
+            want, tol = _rt(want, DT) + _rt(r, DT), 1.5 * EPS[DT]
+    print("ROUTE %s %s %s" % (case, DT, log.names))
     assert log.names == names
     _close(got, want, tol, 1e-3, case)
     if what == "stats":
@@ -146,11 +181,15 @@ def test_s1_routing(case):
         _close(scale, 1.0 / (yd.var(dim=(2, 3, 4), unbiased=False).reshape(-1) + 1e-5).sqrt(), 2e-5, 1e-6, "scale")
 
 
-@pytest.mark.parametrize("n,cin,cout,dims", [(2, 32, 64, (16, 32, 64)), (2, 64, 64, (16, 32, 64))],
-                         ids=["slide32", "slide64"])
-def test_misaligned_y_with_statistics_is_refused(n, cin, cout, dims):
+MISALIGNED = {"slide32": (2, 32, 64, (16, 32, 64)), "slide64": (2, 64, 64, (16, 32, 64))}
+REFUSED, REFUSED_IDS = both_types(sorted(MISALIGNED))
+
+
+@pytest.mark.parametrize("shape,DT", REFUSED, ids=REFUSED_IDS)
+def test_misaligned_y_with_statistics_is_refused(shape, DT):
     """the slab was planned for the sliding kernel's grid: with a y that kernel cannot store to, ru3d_conv3d_fwd_in is an
     error (and launches nothing), not a run of another kernel into that slab"""
+    n, cin, cout, dims = MISALIGNED[shape]
     d, h, w = dims
     xv, wt, b, _, _ = _operands(n, cin, cout, dims, 5)
     x = ops.as_input(xv.to(DEV), DT)

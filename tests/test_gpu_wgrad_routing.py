@@ -22,6 +22,7 @@ import _ops as ops  # noqa: E402
 DEV = torch.device("cuda:0")
 F = torch.nn.functional
 BF, F32 = torch.bfloat16, torch.float32
+F16 = torch.float16
 RTOL, ATOL = 2e-3, 1e-3
 WIDE = 1024     # "wide": x is channels [0, cin) of a buffer this wide - a sample of 2^30 elements, past the LDS-DMA offsets
 
@@ -105,9 +106,14 @@ def _operands(what, dt, n, cin, cout, dims, k, stride):
     return xv, g1, g2, _wgrad_ref(xv, g1, k, stride), _wgrad_ref(xv, g2, 1, stride), g1.double().sum(dim=(0, 2, 3, 4))
 
 
-@pytest.mark.parametrize("case", sorted(CASES))
-def test_wgrad_routing(case):
-    what, dt, n, cin, cout, dims, k, stride, names = CASES[case]
+# every 16-bit case in both storage types (same names: the fp16 build is a second compilation of the same dispatch); the
+# fp32 stem case once
+ROUTES = [(case, CASES[case][1]) for case in sorted(CASES)] + [(case, F16) for case in sorted(CASES) if CASES[case][1] == BF]
+
+
+@pytest.mark.parametrize("case,dt", ROUTES, ids=[c + "-fp16" if t == F16 else c for c, t in ROUTES])
+def test_wgrad_routing(case, dt):
+    what, _, n, cin, cout, dims, k, stride, names = CASES[case]
     shared = what if what == "convt" else "conv"
     xv, g1, g2, ref, ref2, refb = _operands(shared, dt, n, cin, cout, dims, k, stride)
     if what == "split":        # [a | b] as two planes of one buffer
@@ -140,7 +146,7 @@ def test_wgrad_routing(case):
             assert dw.data_ptr() == buf.data_ptr() + 4 and dw.data_ptr() % 16 == 4
         else:
             dw = ops.conv_wgrad(x, dy, k, stride)
-    print("ROUTE %s %s" % (case, log.names))
+    print("ROUTE %s %s %s" % (case, dt, log.names))
     assert log.names == names
     _close(dw, ref, "%s dW" % case)
     if dw2 is not None:
