@@ -150,6 +150,24 @@ def test_maps_equal_the_twin(name):
         assert int(twin_squares(name, (1,))[0, 0, -1, -1, -1]) == (a - 1) ** 2 + (b - 1) ** 2 + (z - 1) ** 2
 
 
+@pytest.mark.parametrize("name", ["beyond", "long"])
+def test_maps_with_a_capped_grid(name):
+    """The pack kernel's grid is capped at 8 blocks a CU of the budget, the two scan kernels' at 4 (tiles of 32 KiB of
+    LDS).  "beyond" (129, 65, 5), two classes: 8385 words = 2097 pack blocks, 2 * 129 and 2 * 65 tiles at the least; "long"
+    (300, 2, 40): 600 words = 150 pack blocks, 2 * 300 tiles at the least in the first scan.  With the whole chip the scans
+    get up to 1024 blocks and only the pack of "beyond" meets its cap (2048); under a budget of 8 CUs the caps are 64 and
+    32, so these loops stride.  The same squares and maps as the twin, as in test_maps_equal_the_twin."""
+    import _native as N
+    y = map_case(name)
+    try:
+        assert N.lib.ru3d_set_cu_budget(8) == 0
+        for classes in ((1, 2), (2,)):
+            assert_maps(y.to(torch.uint8).to(DEV), classes, twin_squares(name, classes), "%s %s under 8 CUs" % (name, classes))
+    finally:
+        N.lib.ru3d_set_cu_budget(0)
+    assert N.lib.ru3d_get_cu_budget() == torch.cuda.get_device_properties(DEV).multi_processor_count
+
+
 def test_default_classes_int32_labels_and_a_strided_view():
     y = map_case("base")
     want = twin_squares("base", (1, 2))

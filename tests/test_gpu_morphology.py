@@ -259,3 +259,30 @@ def test_c_abi_refuses_bad_arguments_and_launches_nothing():
     assert lib.ru3d_binary_morph(p(src.bits), p(dst.bits), 6, 7, 70, N.MORPH_DILATE, rows, 1, 0, st) == 0
     assert torch.equal(dst.bits, src.bits)
     assert lib.ru3d_mask_bytes(6, 7, 70) == src.bits.numel() * 8
+
+
+# ------------------------------------------------------------------------------------------------ CU budget
+def test_confusion_counts_with_a_capped_grid():
+    """ru3d_confusion_counts caps its grid-stride grid at 8 blocks a CU of the budget.  1000003 voxels, both operands
+    16-byte aligned: 62500 vector trips + 3 tail voxels = 245 blocks of 256 threads uncapped, under the 2048 of the whole
+    chip; under a budget of 8 CUs the cap is 64 and every thread makes three or four trips.  The table is np.bincount's,
+    exactly (tests/test_gpu_evaluate.py's comparison), for an unaligned view (one voxel a trip: 3907 blocks uncapped) too."""
+    n, C = 1000003, 3
+    rng = np.random.RandomState(8)
+    pred = rng.randint(0, C + 3, size=n + 1).astype(np.uint8)                 # values above C in either operand
+    label = rng.randint(0, C + 2, size=n + 1).astype(np.uint8)
+
+    def want(p, g):
+        return np.bincount(np.minimum(g.astype(np.int64), C) * (C + 1) + np.minimum(p.astype(np.int64), C),
+                           minlength=(C + 1) ** 2).reshape(C + 1, C + 1)
+    dp, dl = _dev(pred), _dev(label)
+    full = morphology.confusion(dp[:n], dl[:n], C)
+    try:
+        assert N.lib.ru3d_set_cu_budget(8) == 0
+        got = morphology.confusion(dp[:n], dl[:n], C)
+        odd = morphology.confusion(dp[1:], dl[:n], C)                         # operands that never reach a boundary together
+    finally:
+        N.lib.ru3d_set_cu_budget(0)
+    assert N.lib.ru3d_get_cu_budget() == torch.cuda.get_device_properties(DEV).multi_processor_count
+    assert np.array_equal(got.cpu().numpy(), want(pred[:n], label[:n])) and torch.equal(got, full)
+    assert np.array_equal(odd.cpu().numpy(), want(pred[1:], label[:n]))

@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("no HIP device", allow_module_level=True)
 
+import _native as N  # noqa: E402
 import data  # noqa: E402
 import nifti  # noqa: E402
 import prepare  # noqa: E402
@@ -186,6 +187,31 @@ def test_intensity_statistics_against_numpy():
     _check_statistics((rng.randn(200_003) * 3 + 1).astype(np.float32), exact_quantiles=False)
     with pytest.raises(ValueError):
         prepare.intensity_statistics(_dev(np.array([1.0, np.nan], dtype=np.float32)))
+
+
+def test_streaming_passes_with_a_capped_grid():
+    """The streaming grids (box, radix-select passes, both moment passes) are capped at 8 blocks a CU of the budget, four
+    values a thread and trip.  The box of (37, 41, 67, 2): 101639 voxels = 100 blocks of 256 threads uncapped; the
+    statistics of 300001 values: 293 blocks - both under the 2048 of the whole chip, both over the 64 of a budget of 8 CUs,
+    where the loops make a second trip and more.  The comparisons are test_threshold_bbox_is_np_where's and
+    test_intensity_statistics_against_numpy's."""
+    rng = np.random.RandomState(3)
+    img = np.full((37, 41, 67, 2), -1000.0, dtype=np.float32)
+    img[9:28, 13:34, 13:47] = rng.rand(19, 21, 34, 2).astype(np.float32) * 600 - 300
+    img[36, 40, 66, 1] = 0.0                                              # the last voxel: the last trip of the last block
+    want, count = _np_box(img, -200)
+    ct = np.round(rng.randn(300_001) * 80 + 100).astype(np.float32)
+    full = prepare.intensity_statistics(_dev(ct))
+    try:
+        assert N.lib.ru3d_set_cu_budget(8) == 0
+        got, n = prepare.threshold_bbox(_dev(img), -200)
+        stats = _check_statistics(ct, exact_quantiles=True)
+    finally:
+        N.lib.ru3d_set_cu_budget(0)
+    assert N.lib.ru3d_get_cu_budget() == torch.cuda.get_device_properties(DEV).multi_processor_count
+    assert np.array_equal(got, want) and n == count
+    for key in ('median', 'min', 'max', 'pct_00_5', 'pct_99_5'):           # selected values: the same whatever the grid
+        assert stats[key] == full[key], key
 
 
 # ------------------------------------------------------------------------------------------------ data.py, case by case

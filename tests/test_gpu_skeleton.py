@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("no HIP device", allow_module_level=True)
 
+import _native as N  # noqa: E402
 import meshfile  # noqa: E402
 import morphology  # noqa: E402
 import nifti  # noqa: E402
@@ -131,6 +132,31 @@ def test_classify_length_overlap_radii(dev, name):
     empty = packed(np.zeros_like(volume), dev)
     assert skeleton.classify(empty)[2:] == (0, 0, 0) and skeleton.length(empty) == 0.0
     assert all(np.isnan(v) for v in skeleton.radii(empty, mask))
+
+
+def test_thin_classify_length_overlap_with_a_capped_grid(dev):
+    """The word loops (sk_mark of every thinning pass, classify, the pair counts of length, overlap) cap their grid at 8
+    blocks a CU of the budget.  (136, 128, 64): 136 * 128 * 1 = 17408 words = 68 blocks of 256 threads uncapped, under the
+    2048 of the whole chip; under a budget of 8 CUs the cap is 64, so 1024 words are done on the loop's second trip.  The
+    equalities are those of check_thin and test_classify_length_overlap_radii."""
+    volume = blob(11, (136, 128, 64))
+    want = transform._skeleton_numpy(volume)
+    try:
+        assert N.lib.ru3d_set_cu_budget(8) == 0
+        thin = check_thin(volume, dev, want)
+        mask = packed(volume, dev)
+        for m, v in ((thin, want[0]), (mask, volume)):
+            ends, junctions, n, n_ends, n_junctions = skeleton.classify(m)
+            ref = transform._skeleton_classify_numpy(v)
+            assert (n, n_ends, n_junctions) == ref[2:]
+            assert (volume_of(ends) == ref[0]).all() and (volume_of(junctions) == ref[1]).all()
+        other = np.roll(volume, 2, axis=2)
+        assert skeleton.overlap(thin, packed(other, dev)) == (int(want[0].sum()), int(other.sum()), int((want[0] & other).sum()))
+        for spacing in SPACINGS:
+            assert skeleton.length(thin, spacing) == transform._skeleton_length_numpy(want[0], spacing)
+    finally:
+        N.lib.ru3d_set_cu_budget(0)
+    assert N.lib.ru3d_get_cu_budget() == torch.cuda.get_device_properties(dev).multi_processor_count
 
 
 def test_complement_keeps_the_padding_clear(dev):

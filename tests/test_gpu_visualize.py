@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("no HIP device", allow_module_level=True)
 
+import _native as N  # noqa: E402
 import network  # noqa: E402
 import trainer as T  # noqa: E402
 import visualize as V  # noqa: E402
@@ -98,6 +99,30 @@ def test_case_sheet_and_render_case_equal_the_numpy_route(shape, spacing):
         assert got_depth.dtype == np.int32 and np.array_equal(got_depth, want_depth)
         assert got.dtype == np.uint8 and np.array_equal(got, want)
         assert (want_depth >= 0).any()
+
+
+def test_sheet_and_views_with_a_capped_grid():
+    """ru3d_render_tiles launches 8 blocks a CU of the budget and deals 256-pixel chunks of the tiles over them;
+    ru3d_render_surface_prepare caps its word loop at the same figure.  (96, 96, 96): 96 * 96 * 2 = 18432 words = 72 blocks
+    uncapped, and the tiles of the 772 x 1030 sheet are some 3000 chunks - under a budget of 8 CUs there are 64 blocks for
+    either (2048 with the whole chip), so the word loop makes a second trip and a block paints some 47 chunks.  The same
+    bits as the numpy route, as in test_case_sheet_and_render_case_equal_the_numpy_route."""
+    case = synthetic_case((96, 96, 96), (1.0, 1.0, 1.0), 4)
+    dev = on_device(case)
+    want_sheet = V.case_sheet(case, num_slices=4)
+    assert want_sheet.shape[0] * want_sheet.shape[1] > 64 * 256
+    views = ((33, 21), (200, -47))
+    want, want_depth = V.render_case(case, views=views, size=64, return_depth=True)
+    try:
+        assert N.lib.ru3d_set_cu_budget(8) == 0
+        sheet = V.case_sheet(dev, num_slices=4)
+        got, got_depth = V.render_case(dev, views=views, size=64, return_depth=True)
+    finally:
+        N.lib.ru3d_set_cu_budget(0)
+    assert N.lib.ru3d_get_cu_budget() == torch.cuda.get_device_properties(DEV).multi_processor_count
+    assert np.array_equal(sheet, want_sheet)
+    assert got_depth.dtype == np.int32 and np.array_equal(got_depth, want_depth) and np.array_equal(got, want)
+    assert (want_depth >= 0).any()
 
 
 @pytest.mark.parametrize("size", [15, 33, 65])
