@@ -100,7 +100,9 @@ ORDER_STATS_MAX_RANKS = 8
 EDT_MAX_AXIS = 4096             # RU3D_EDT_MAX_AXIS: x and y extents of the distance transform
 SPATIAL_MAX_YZ = 2560           # RU3D_SPATIAL_MAX_YZ: (ny + 4) * nz of an elastic lattice
 BOUNDARY_MAX_AXIS = 2048        # RU3D_BOUNDARY_MAX_AXIS: every extent of a patch of the signed distance maps
-DEGRADE_MAX_RADIUS = 16         # RU3D_DEGRADE_MAX_RADIUS: taps to either side of the Gaussian blur
+CLASS_INDEX_CLASSES = 32        # RU3D_CLASS_INDEX_CLASSES: label values 0 .. 31 are indexed
+CLASS_INDEX_MAX_PER_CLASS = 1 << 20     # RU3D_CLASS_INDEX_MAX_PER_CLASS: locations kept per class
+DEGRADE_MAX_RADIUS = 16       # RU3D_DEGRADE_MAX_RADIUS: taps to either side of the Gaussian blur
 PACK_MAX = 40
 _P = ctypes.POINTER(Tensor)
 _vp, _i, _i64, _f, _sz, _u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t,
@@ -291,6 +293,8 @@ SIGNATURES = {
                                _vp]),
     "ru3d_augment_patch_spatial": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(PatchParams),
                                        ctypes.POINTER(SpatialParams), _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_class_index_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_class_index": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_augment_degrade_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ru3d_augment_degrade": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(DegradeParams), _vp, _sz, _vp, _vp]),
     "ru3d_augment_intensity": (_i, [_vp, _i64, _vp, _i, ctypes.POINTER(PatchParams), _vp]),

@@ -23,6 +23,13 @@ the intensity chain (semantics, draw order and numpy twins: module `degrade`; ke
 which one of them applies takes three C calls - the resampling with the intensity flags cleared, ru3d_augment_degrade,
 ru3d_augment_intensity on the statistics of the degraded image; a patch on which none applies, and every patch when the
 three keywords are None, takes the one call it always took.
+
+`oversample_foreground` places the crop box, with that probability per patch, on a voxel drawn from the case's
+class-location index (`DeviceCase.class_index` -> `ClassIndex`, kernel: csrc/locations.hip; rule, draw order and numpy
+twin: module `locations`).  It replaces the rejection loop of `enforce_label_indices`, which launches the presence
+kernel and reads its mask back once per try: the index is built once per case, and from then on a forced patch is the C
+calls of any other patch with no transfer to the host.  `data.DeviceCaseDataset` keeps indexed cases resident for the
+Trainer.  Left at None it changes nothing.
 """
 import ctypes
 
@@ -31,6 +38,7 @@ import torch
 
 import _native as N
 import degrade
+import locations as fg
 import spatial
 from _native import check, ptr, stream
 
@@ -52,6 +60,7 @@ class DeviceCase:
             img = img[..., None]
         self.image = img.to(device=device, dtype=torch.float32).contiguous()
         self.label = None
+        self._index = None
         if label is not None:
             lab = torch.as_tensor(np.ascontiguousarray(label) if isinstance(label, np.ndarray) else label)
             if lab.dtype not in (torch.uint8, torch.int64):
@@ -64,11 +73,66 @@ class DeviceCase:
     def shape(self):
         return tuple(self.image.shape)
 
+    def class_index(self, max_per_class=10000):
+        """The ClassIndex of the label, built on first use and kept; another max_per_class builds it again."""
+        if self.label is None:
+            raise ValueError("class_index: the case has no label")
+        max_per_class = fg.check_max_locations(max_per_class)
+        if self._index is None or self._index.max_per_class != max_per_class:
+            self._index = ClassIndex(self.label, max_per_class)
+        return self._index
+
+
+class ClassIndex:
+    """Where the voxels of every class 0 .. 31 of a device label volume [X, Y, Z] are (ru3d_class_index; the contract
+    and its numpy twin: module `locations`).  counts: numpy int64 [32]; boxes: numpy int32 [32, 6], (x0, x1, y0, y1, z0,
+    z1) with the high end exclusive; device_locations: int32 device tensor [32, max_per_class], -1 behind the entries of a
+    row.  One call, then one download of counts and boxes and one of the rows of the classes >= 1 that are present (what
+    the sampler draws from); the row of class 0 comes down when it is first asked for."""
+
+    def __init__(self, label, max_per_class=10000):
+        self.max_per_class = m = fg.check_max_locations(max_per_class)
+        if label.dtype not in (torch.uint8, torch.int64) or label.dim() != 3 or not label.is_contiguous():
+            raise ValueError("ClassIndex: a contiguous uint8 or int64 device volume [X, Y, Z]")
+        N.require_device(label, "the label")
+        dev = label.device
+        x, y, z = (int(v) for v in label.shape)
+        classes = N.CLASS_INDEX_CLASSES
+        # counts and boxes share one buffer: one copy brings both to the host
+        head = torch.empty(classes * (2 + 6), dtype=torch.int32, device=dev)
+        self.device_locations = torch.empty((classes, m), dtype=torch.int32, device=dev)
+        ws = N.workspace(N.lib.ru3d_class_index_workspace_bytes(x, y, z), dev)
+        code = N.LABEL_U8 if label.dtype == torch.uint8 else N.LABEL_I64
+        N.note_device(dev)
+        check(N.lib.ru3d_class_index(ptr(label), code, x, y, z, m, ptr(head), ptr(head[2 * classes:]),
+                                     ptr(self.device_locations), ptr(ws), ws.numel(), stream()), "class_index")
+        host = head.cpu().numpy()
+        self.counts = host[:2 * classes].view(np.int64).copy()
+        self.boxes = host[2 * classes:].reshape(classes, 6).copy()
+        present = self.classes()
+        self._rows = {}
+        if present:
+            rows = self.device_locations[present].cpu().numpy()
+            for c, row in zip(present, rows):
+                self._rows[c] = row[:min(int(self.counts[c]), m)].copy()
+
+    def classes(self):
+        """The label values >= 1 present in the case, ascending."""
+        return [c for c in range(1, len(self.counts)) if self.counts[c] > 0]
+
+    def locations(self, c):
+        """numpy int32 [min(counts[c], max_per_class)]: linear indices (x * Y + y) * Z + z of voxels of class c."""
+        c = int(c)
+        if c not in self._rows:
+            self._rows[c] = self.device_locations[c, :min(int(self.counts[c]), self.max_per_class)].cpu().numpy()
+        return self._rows[c]
+
 
 class DeviceAugment:
     def __init__(self, scale=0.1, crop_size=128, crop_mode="random", crop_margin=0, enforce_label_indices=(),
                  image_pad_cval=0, label_pad_cval=0, mirror_p=(0.5, 0.5, 0.5), contrast=0.1, brightness=0.1,
-                 gamma=0.1, rng=None, rotation=None, elastic_spacing=None, elastic_magnitude=None, noise=None, blur=None,
+                 gamma=0.1, rng=None, rotation=None, elastic_spacing=None, elastic_magnitude=None,
+                 oversample_foreground=None, foreground_classes=None, max_locations=10000, noise=None, blur=None,
                  low_res=None):
         """Arguments as the reference classes take them; contrast / brightness / gamma = None switches the op off,
         mirror_p = None the mirror.  rng: an object with numpy's `uniform` / `randint` (default: numpy's global one).
@@ -84,7 +148,14 @@ class DeviceAugment:
         in [lo, hi], a Gaussian blur of a sigma (voxels, one for the three axes) uniform in [lo, hi], a round trip through
         a grid of zoom uniform in [lo, hi] (0 < lo <= hi <= 1) voxels per voxel.  The usual recipe is noise
         (0.1, (0, 0.1)), blur (0.2, (0.5, 1.0)), low_res (0.25, (0.5, 1.0)).  The blur reaches int(4 sigma + 0.5) voxels
-        to either side: at most 16 and at most the smallest patch extent."""
+        to either side: at most 16 and at most the smallest patch extent.
+
+        oversample_foreground: None | p in (0, 1] - with probability p per patch the crop box is placed on a voxel drawn
+        from the case's class-location index (DeviceCase.class_index(max_locations), built once per case) instead of
+        at random; foreground_classes: the label values (1 .. 31) to draw from, None = every value >= 1 the case holds;
+        values a case lacks are skipped for it, and a case with none of them gets the random box.  Rule and draw order:
+        module `locations`.  This is what replaces enforce_label_indices (the two exclude each other): no retry, no
+        readback - after the first patch of a case a forced patch is the C calls of any other patch."""
         assert crop_mode in ("center", "random"), "crop mode must be either center or random"
         self.scale = _range(scale)
         self.crop_size = crop_size
@@ -104,6 +175,8 @@ class DeviceAugment:
         self.blur = degrade.check_blur(blur, self._patch())
         self.low_res = degrade.check_low_res(low_res, self._patch())
         self.degrade = self.noise is not None or self.blur is not None or self.low_res is not None
+        self.oversample, self.foreground_classes, self.max_locations = fg.check_oversample(
+            oversample_foreground, foreground_classes, max_locations, crop_mode, self.enforce)
 
     def _patch(self):
         return [self.crop_size] * 3 if not isinstance(self.crop_size, (list, tuple, np.ndarray)) \
@@ -119,6 +192,10 @@ class DeviceAugment:
             else:
                 lo.append(int((shape[i] - before[i]) // 2))
         return lo
+
+    def _index(self, case):
+        index = case.class_index(self.max_locations)
+        return index.counts, index.locations
 
     def _presence(self, case, lo, before, mask):
         lo_a = (ctypes.c_int32 * 3)(*lo)
@@ -149,8 +226,12 @@ class DeviceAugment:
         s = self.rng.uniform(self.scale[0], self.scale[1])
         before = [int(v) for v in np.round(np.array(patch) / s).astype(int)]
         mask = torch.empty(1, dtype=torch.int32, device=dev)
+        placed = None
+        if self.oversample is not None:
+            placed = fg.draw_forced_box(self.rng, self.oversample, self.foreground_classes,
+                                        lambda: self._index(case), before, shape, margin)
         while True:
-            lo = self._bbox(before, shape, margin)
+            lo = placed if placed is not None else self._bbox(before, shape, margin)
             if case.label is None:
                 break
             self._presence(case, lo, before, mask)

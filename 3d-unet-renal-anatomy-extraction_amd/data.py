@@ -68,6 +68,40 @@ class CaseDataset(torch.utils.data.Dataset):
         return len(self.image_files)
 
 
+class DeviceCaseDataset(torch.utils.data.Dataset):
+    """CaseDataset's folder with the cases kept in HBM (not in the reference): a case is loaded and uploaded on first
+    access and its augment.DeviceCase kept - with its class-location index built, when max_locations is given -, so
+
+        Trainer(dataset=DeviceCaseDataset(folder, device, max_locations=10000),
+                train_transform=DeviceAugment(..., oversample_foreground=0.33),
+                dataloader_kwargs={'num_workers': 0})
+
+    uploads and indexes a case once, not once per sample.  Items: {'image': the DeviceCase (DeviceAugment cuts its
+    patches from it), 'label': its label tensor, 'case_id': ...}; with a transform, what the transform makes of that."""
+
+    def __init__(self, load_dir, device, max_locations=None, transform=None):
+        super().__init__()
+        files = CaseDataset(load_dir)
+        self.image_files, self.label_files, self.load_label = files.image_files, files.label_files, files.load_label
+        self.device, self.max_locations, self.transform = torch.device(device), max_locations, transform
+        self.cases = {}
+
+    def __getitem__(self, index):
+        index = range(len(self))[index]
+        if index not in self.cases:
+            from augment import DeviceCase            # augment imports nothing from here; transform imports augment
+            case = load_case(self.image_files[index], self.label_files[index] if self.load_label else None)
+            resident = DeviceCase(case['image'], case.get('label'), self.device)
+            if self.max_locations is not None and resident.label is not None:
+                resident.class_index(self.max_locations)
+            self.cases[index] = {'image': resident, 'label': resident.label, 'case_id': case['case_id']}
+        item = dict(self.cases[index])
+        return self.transform(item) if self.transform else item
+
+    def __len__(self):
+        return len(self.image_files)
+
+
 def load_case(image_file, label_file=None):
     image, affine, _ = nifti.load(image_file)
     case = {'case_id': _case_id(image_file), 'affine': affine, 'image': _with_channel(image.astype(np.float32))}

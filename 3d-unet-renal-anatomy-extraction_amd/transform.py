@@ -17,7 +17,9 @@ import torch
 
 from augment import DeviceAugment, DeviceCase  # noqa: F401  (the on-device replacement of the Random* chain)
 import degrade
+import locations
 import spatial
+from locations import class_locations  # noqa: F401  (the numpy twin of ru3d_class_index)
 from spatial import bspline_displacement, resample_at, rotation_matrix, spatial_coordinates  # noqa: F401
 
 
@@ -812,19 +814,38 @@ class RandomRescale(object):
 
 class Crop(object):
     """transform.py:440-511: crop image and label with one box; retry until every enforce_label_indices entry is in
-    the cropped label."""
+    the cropped label.
+
+    oversample_foreground = p in (0, 1] (not in the reference): with probability p the box is placed on a voxel drawn from
+    the label's class-location index instead (module `locations`: rule and draw order; foreground_classes: the values to
+    draw from, None = every value >= 1 present).  The index is class_locations(label, max_locations), computed per call
+    unless the case carries one under 'class_index'.  The numpy twin of DeviceAugment(oversample_foreground=...)."""
 
     def __init__(self, crop_size=128, crop_mode='center', crop_margin=0, enforce_label_indices=[],
-                 image_pad_mode='constant', image_pad_cval=0, label_pad_mode='constant', label_pad_cval=0):
+                 image_pad_mode='constant', image_pad_cval=0, label_pad_mode='constant', label_pad_cval=0,
+                 oversample_foreground=None, foreground_classes=None, max_locations=10000):
         self.crop_size, self.crop_mode, self.crop_margin = crop_size, crop_mode, crop_margin
         self.enforce_label_indices = ([enforce_label_indices] if isinstance(enforce_label_indices, int)
                                       else enforce_label_indices)
         self.image_pad_mode, self.image_pad_cval = image_pad_mode, image_pad_cval
         self.label_pad_mode, self.label_pad_cval = label_pad_mode, label_pad_cval
+        self.oversample, self.foreground_classes, self.max_locations = locations.check_oversample(
+            oversample_foreground, foreground_classes, max_locations, crop_mode, self.enforce_label_indices)
 
-    def _box(self, image, label, size):
+    def _placed(self, label, size, index):
+        """The oversampling draws: the box of a forced patch, or None for a box drawn the usual way."""
+        def rows():
+            counts, _, found = index if index is not None else class_locations(label, self.max_locations)
+            return counts, found.__getitem__
+        lo = locations.draw_forced_box(np.random, self.oversample, self.foreground_classes, rows, list(size)[:3],
+                                       label.shape, self.crop_margin)
+        return lo and [[lo[i], lo[i] + int(size[i])] for i in range(3)]
+
+    def _box(self, image, label, size, index=None):
+        placed = self._placed(label, size, index) if self.oversample is not None else None
         while True:
-            bbox = gen_bbox_for_crop(size, image.shape, self.crop_margin, self.crop_mode)
+            bbox = placed + [[0, image.shape[-1]]] if placed else \
+                gen_bbox_for_crop(size, image.shape, self.crop_margin, self.crop_mode)
             cropped = crop_pad_to_bbox(label, bbox[:-1], self.label_pad_mode, self.label_pad_cval)
             present = np.unique(cropped)
             if all(i in present for i in self.enforce_label_indices):
@@ -834,7 +855,7 @@ class Crop(object):
         dim = len(case['image'].shape) - 1
         self.crop_size = _per_axis(self.crop_size, dim)
         self.crop_margin = _per_axis(self.crop_margin, dim)
-        bbox, cropped_label = self._box(case['image'], case['label'], self.crop_size)
+        bbox, cropped_label = self._box(case['image'], case['label'], self.crop_size, case.get('class_index'))
         case['image'] = crop_pad_to_bbox(case['image'], bbox, self.image_pad_mode, self.image_pad_cval)
         case['label'] = cropped_label
         return case
@@ -842,10 +863,13 @@ class Crop(object):
 
 class RandomCrop(Crop):
     def __init__(self, crop_size=128, crop_margin=0, enforce_label_indices=[], image_pad_mode='constant',
-                 image_pad_cval=0, label_pad_mode='constant', label_pad_cval=0):
+                 image_pad_cval=0, label_pad_mode='constant', label_pad_cval=0, oversample_foreground=None,
+                 foreground_classes=None, max_locations=10000):
         super().__init__(crop_size, crop_mode='random', crop_margin=crop_margin,
                          enforce_label_indices=enforce_label_indices, image_pad_mode=image_pad_mode,
-                         image_pad_cval=image_pad_cval, label_pad_mode=label_pad_mode, label_pad_cval=label_pad_cval)
+                         image_pad_cval=image_pad_cval, label_pad_mode=label_pad_mode, label_pad_cval=label_pad_cval,
+                         oversample_foreground=oversample_foreground, foreground_classes=foreground_classes,
+                         max_locations=max_locations)
 
 
 class CenterCrop(Crop):
@@ -859,10 +883,13 @@ class RandomRescaleCrop(Crop):
     """transform.py:573-652: draw a scale, crop round(size / scale), resize the crop to `size`."""
 
     def __init__(self, scale, crop_size=128, crop_mode='center', crop_margin=0, enforce_label_indices=[],
-                 image_pad_mode='constant', image_pad_cval=0, label_pad_mode='constant', label_pad_cval=0):
+                 image_pad_mode='constant', image_pad_cval=0, label_pad_mode='constant', label_pad_cval=0,
+                 oversample_foreground=None, foreground_classes=None, max_locations=10000):
         super().__init__(crop_size, crop_mode=crop_mode, crop_margin=crop_margin,
                          enforce_label_indices=enforce_label_indices, image_pad_mode=image_pad_mode,
-                         image_pad_cval=image_pad_cval, label_pad_mode=label_pad_mode, label_pad_cval=label_pad_cval)
+                         image_pad_cval=image_pad_cval, label_pad_mode=label_pad_mode, label_pad_cval=label_pad_cval,
+                         oversample_foreground=oversample_foreground, foreground_classes=foreground_classes,
+                         max_locations=max_locations)
         self.scale = _as_range(scale)
 
     def __call__(self, case):
@@ -871,7 +898,7 @@ class RandomRescaleCrop(Crop):
         self.crop_margin = _per_axis(self.crop_margin, dim)
         s = np.random.uniform(self.scale[0], self.scale[1])
         before = np.round(np.array(self.crop_size) / s).astype(int)       # the reference's np.int (gone in numpy 1.24)
-        bbox, cropped_label = self._box(case['image'], case['label'], before)
+        bbox, cropped_label = self._box(case['image'], case['label'], before, case.get('class_index'))
         cropped_image = crop_pad_to_bbox(case['image'], bbox, self.image_pad_mode, self.image_pad_cval)
         case['image'] = resize(cropped_image, self.crop_size)
         case['label'] = resize(cropped_label, self.crop_size, is_label=True)
@@ -888,10 +915,11 @@ class RandomSpatialCrop(Crop):
 
     def __init__(self, scale, crop_size=128, rotation=None, elastic_spacing=None, elastic_magnitude=None,
                  crop_mode='center', crop_margin=0, enforce_label_indices=[], image_pad_cval=0, label_pad_cval=0,
-                 label_margin=False):
+                 label_margin=False, oversample_foreground=None, foreground_classes=None, max_locations=10000):
         super().__init__(crop_size, crop_mode=crop_mode, crop_margin=crop_margin,
                          enforce_label_indices=enforce_label_indices, image_pad_cval=image_pad_cval,
-                         label_pad_cval=label_pad_cval)
+                         label_pad_cval=label_pad_cval, oversample_foreground=oversample_foreground,
+                         foreground_classes=foreground_classes, max_locations=max_locations)
         self.scale = _as_range(scale)
         self.rotation = spatial.check_rotation(rotation)
         self.elastic = spatial.check_elastic(elastic_spacing, elastic_magnitude)
@@ -902,7 +930,7 @@ class RandomSpatialCrop(Crop):
         self.crop_margin = _per_axis(self.crop_margin, 3)
         s = np.random.uniform(self.scale[0], self.scale[1])
         before = np.round(np.array(self.crop_size) / s).astype(int)
-        bbox, cropped_label = self._box(case['image'], case['label'], before)
+        bbox, cropped_label = self._box(case['image'], case['label'], before, case.get('class_index'))
         angles, phi = spatial.draw_spatial(np.random, self.rotation, self.elastic, self.crop_size)
         centre, matrix = spatial.patch_geometry([b[0] for b in bbox[:3]], before, self.crop_size, angles)
         coords = spatial_coordinates(self.crop_size, centre, matrix, phi, self.elastic and self.elastic[0])

@@ -952,6 +952,27 @@ int ru3d_augment_patch_spatial(const float* image, const void* label, int label_
                                const uint32_t* presence_mask, float* out_image, int64_t* out_label, void* ws,
                                size_t ws_bytes, void* stream);
 
+/* The class-location index of a case, for foreground-oversampled patches: with probability p the sampler centres the
+ * crop box on a voxel drawn from this index instead of drawing boxes until the class happens to be inside one.  label:
+ * uint8 or int64 [X, Y, Z] (RU3D_LABEL_U8 / RU3D_LABEL_I64), linear index i = (x * Y + y) * Z + z < 2^31.  All outputs
+ * are device memory:
+ *   counts[c]        the number of voxels with value c, c in 0 .. 31; a value below 0 or above 31 is counted nowhere and
+ *                    appears nowhere;
+ *   boxes[c]         {x0, x1, y0, y1, z0, z1} of those voxels, low end inclusive, high end exclusive; zeros when
+ *                    counts[c] == 0;
+ *   locations[c][j]  for j < m = min(counts[c], max_per_class): the linear index of the voxel of class c whose rank among
+ *                    the class's voxels in raster order is (j * counts[c]) / m (64-bit integer division) - the complete
+ *                    raster-ordered list when the class has at most max_per_class voxels, an evenly rank-strided
+ *                    subsample otherwise: np.flatnonzero(label == c)[(np.arange(m) * n) // m].  Slots j >= m hold -1.
+ * 1 <= max_per_class <= RU3D_CLASS_INDEX_MAX_PER_CLASS.  Integer arithmetic only, and no atomic decides a position: the
+ * result is the same bits in every run.  Workspace: 32 ints per 2048 voxels.  The volume is read twice. */
+#define RU3D_CLASS_INDEX_CLASSES 32
+#define RU3D_CLASS_INDEX_MAX_PER_CLASS (1 << 20)
+size_t ru3d_class_index_workspace_bytes(int X, int Y, int Z); /* 0 when the shape is refused */
+int ru3d_class_index(const void* label, int label_dtype, int X, int Y, int Z, int max_per_class,
+                     int64_t* counts /* [32] */, int32_t* boxes /* [32][6] */,
+                     int32_t* locations /* [32][max_per_class] */, void* ws, size_t ws_bytes, void* stream);
+
 /* Image-quality augmentation of a sampled patch, between the resampling above and the intensity chain: Gaussian noise,
  * Gaussian blur, simulated low resolution, in that order, each on the image only and on all C channels of the patch
  * image[C][px][py][pz] (fp32, in place) with one parameter set.  The HOST draws the parameters; the kernels are

@@ -25,7 +25,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "3d-unet-renal-anatomy-extraction_amd", "csrc")
 SRCS = ["conv_slide32.hip", "conv_slide64.hip", "conv_s2.hip", "conv_ws.hip", "fused_skip.hip", "wgrad_slide.hip", "wgrad_s2.hip", "conv_mfma.hip", "small_convs.hip", "conv_generic.hip",
-        "norm.hip", "norm_small.hip", "loss.hip", "optim.hip", "predict.hip", "comm.hip", "components.hip", "morphology.hip", "augment.hip", "degrade.hip", "prepare.hip", "distance.hip", "mesh.hip", "render.hip"]
+        "norm.hip", "norm_small.hip", "loss.hip", "optim.hip", "predict.hip", "comm.hip", "components.hip", "morphology.hip", "augment.hip", "locations.hip", "degrade.hip", "prepare.hip", "distance.hip", "mesh.hip", "render.hip"]
 TWICE = {"conv_slide32.hip", "conv_slide64.hip", "conv_s2.hip", "conv_ws.hip", "fused_skip.hip", "wgrad_slide.hip", "wgrad_s2.hip", "conv_mfma.hip", "small_convs.hip", "conv_generic.hip",
          "norm.hip", "norm_small.hip"}
 # spilled VGPRs tolerated per kernel-name pattern (everything else: 0)
