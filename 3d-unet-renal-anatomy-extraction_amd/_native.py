@@ -178,6 +178,8 @@ SIGNATURES = {
     "ru3d_pointwise": (_i, [_i, _P, _P, _P, _P, _P, _f, _i, _vp]),
     "ru3d_copy_channels": (_i, [_P, _P, _i, _vp]),
     "ru3d_add": (_i, [_P, _P, _P, _i, _vp]),
+    "ru3d_maxpool3d_fwd": (_i, [_P, _P, _vp, _i, _vp]),
+    "ru3d_maxpool3d_bwd": (_i, [_P, _vp, _P, _i, _vp]),
     "ru3d_cast_f32": (_i, [_P, _P, _i, _vp]),
     "ru3d_ncdhw_to_ndhwc": (_i, [_vp, _P, _i, _vp]),
     "ru3d_ndhwc_to_ncdhw": (_i, [_P, _vp, _i, _vp]),

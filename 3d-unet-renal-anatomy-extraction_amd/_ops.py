@@ -1304,6 +1304,139 @@ class ResBlockFn(torch.autograd.Function):
         return gx, gw1, gb1, gw2, gb2, gws, gbs, None, None, None, None, None, None, None
 
 
+# --------------------------------------------------------------------------- autograd: ConvBlock stack, max pooling
+_TAPE = threading.local()
+
+
+class _TapeAware:
+    """torch runs Function.forward with grad mode off, and ctx.needs_input_grad is the inputs' requires_grad whatever the
+    caller's grad mode was: apply() notes the caller's mode, so that a forward under torch.no_grad() packs no
+    input-gradient weights, writes no pooling codes and saves nothing."""
+
+    @classmethod
+    def apply(cls, *args):
+        _TAPE.on = torch.is_grad_enabled()
+        return super().apply(*args)
+
+
+def _taped(ctx):
+    """needs_input_grad of the node being built, all False when the caller runs without a tape."""
+    on = getattr(_TAPE, "on", True)
+    return tuple(bool(g) and on for g in ctx.needs_input_grad)
+
+
+class ConvStackFn(_TapeAware, torch.autograd.Function):
+    """k >= 1 ConvBlocks in one node (reference network.py:153-199: conv -> dropout -> norm -> nonlin, repeated) - the
+    first half of ResBlockFn, k times:
+        a_i = lrelu(IN(dropout(conv_i(a_{i-1}))));  a_0 = x
+    weights_and_biases: w_1, b_1, ..., w_k, b_k.  drop_scales: None or one Dropout3d factor tensor (or None) per block.
+    shared: the weights are used more than once in a pass (RecBlock applies one ConvBlock t + 1 times): the weight
+    gradients then never go to the GRAD_ARENA slice of the parameter - a second use would overwrite the slice autograd
+    already adopted for the first.  pad_unused: where ResBlockFn takes `pad`; never read (plain blocks run unpadded:
+    network.Unet._configure_native)."""
+
+    @staticmethod
+    def forward(ctx, x, drop_scales, pad_unused, shared, *weights_and_biases):
+        sd = x.dtype
+        x = N.to_ndhwc(x)
+        ws, bs = weights_and_biases[0::2], weights_and_biases[1::2]
+        k = len(ws)
+        if k < 1 or len(bs) != k:
+            raise N.Ru3dError("ConvBlockStack: expected (weight, bias) pairs, got %d tensors" % len(weights_and_biases))
+        if x.shape[1] != ws[0].shape[1]:
+            raise N.Ru3dError("ConvBlock: input has %d channels, conv expects %d" % (x.shape[1], ws[0].shape[1]))
+        drops = list(drop_scales) if drop_scales is not None else [None] * k
+        needs = _taped(ctx)
+        need_gx = needs[0]
+        train = any(needs)
+        # every packed form the stack needs (forward now, input gradients later) in one launch
+        specs = [(w, N.ROLE_CONV_FWD, 1, 0, 0) for w in ws]
+        if train:
+            specs += [(w, N.ROLE_CONV_DGRAD, 1, 0, 0) for w in (ws if need_gx else ws[1:])]
+        packs = pack_weights(specs, sd)
+        a, acts, stats = x, [], []
+        y = None
+        for i in range(k):
+            y, mean, scale, a = conv_fwd_in_act(a, packs[i], bs[i], ws[i].shape[0], 3, 1, drops[i])
+            acts.append(a)
+            stats += [mean, scale]
+        if train:
+            dpacks = packs[k:] if need_gx else [None] + packs[k:]
+            ctx.save_for_backward(x, y, *(acts + stats + dpacks))
+            ctx.k = k
+            ctx.wkeys = [None if shared else w.data_ptr() for w in ws]
+        return a
+
+    @staticmethod
+    def backward(ctx, gz):
+        k = ctx.k
+        saved = ctx.saved_tensors
+        x, y = saved[0], saved[1]
+        acts, stats, pwd = saved[2:2 + k], saved[2 + k:2 + 3 * k], saved[2 + 3 * k:]
+        dev = x.device
+        gz = as_grad(gz, x.dtype)
+        # the last block's IN + LeakyReLU backward; the earlier ones ride behind the input-gradient convs
+        dy, _ = in_lrelu_bwd(gz, acts[k - 1], y, stats[2 * k - 2], stats[2 * k - 1])
+        del gz, y
+        nvox = dy.shape[0] * dy.shape[2] * dy.shape[3] * dy.shape[4]
+        gws = [None] * k
+        for i in range(k - 1, 0, -1):
+            with _OnSide(dev, nvox, (acts[i - 1], dy)):
+                gws[i] = conv_wgrad(acts[i - 1], dy, 3, 1, key=ctx.wkeys[i])
+            dy = conv_dgrad_in_bwd(dy, pwd[i], acts[i - 1], stats[2 * i - 2], stats[2 * i - 1])
+        with _OnSide(dev, nvox, (x, dy)):
+            gws[0] = conv_wgrad(x, dy, 3, 1, key=ctx.wkeys[0])
+        gx = conv_dgrad(dy, pwd[0], tuple(x.shape), 3, 1) if ctx.needs_input_grad[0] else None
+        _join(dev, *gws)
+        grads = [gx, None, None, None]
+        for gw in gws:      # a bias that feeds InstanceNorm has an identically zero gradient: reported as "no gradient"
+            grads += [gw, None]
+        return tuple(grads)
+
+
+def maxpool_fwd(x, want_idx=True):
+    """nn.MaxPool3d(2, 2) of an NDHWC tensor (ru3d_maxpool3d_fwd): (y, idx) - idx the uint8 winner codes, one per element
+    of y in NDHWC order, or None."""
+    n, c, d, h, w = x.shape
+    if min(d, h, w) < 2:      # (the library says the same; an empty result has no descriptor to hand it)
+        raise N.Ru3dError("maxpool3d_fwd: every spatial extent must be at least 2 (got %d x %d x %d)" % (d, h, w))
+    y = N.new_act(n, c, d // 2, h // 2, w // 2, x.dtype, x.device)
+    idx = torch.empty((n, d // 2, h // 2, w // 2, c), dtype=torch.uint8, device=x.device) if want_idx else None
+    dx, dyy = desc(x), desc(y)
+    check(N.lib.ru3d_maxpool3d_fwd(ref(dx), ref(dyy), ptr(idx), N.dtype_code(x.dtype), stream()), "maxpool3d_fwd")
+    return y, idx
+
+
+def maxpool_bwd(dy, idx, in_shape):
+    """Gradient of maxpool_fwd for an input of `in_shape`: every element of the result is written."""
+    n, c, d, h, w = in_shape
+    dx = N.new_act(n, c, d, h, w, dy.dtype, dy.device)
+    ddy, ddx = desc(dy), desc(dx)
+    check(N.lib.ru3d_maxpool3d_bwd(ref(ddy), ptr(idx), ref(ddx), N.dtype_code(dy.dtype), stream()), "maxpool3d_bwd")
+    return dx
+
+
+class MaxPoolFn(_TapeAware, torch.autograd.Function):
+    """reference network.py:452-463 (MaxPoolBlock with its defaults): nn.MaxPool3d(kernel_size=2, stride=2).  Backward
+    needs the winner codes and the input's shape, nothing else."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = N.to_ndhwc(x)
+        need = _taped(ctx)[0]
+        y, idx = maxpool_fwd(x, want_idx=need)
+        if need:
+            ctx.save_for_backward(idx)
+            ctx.in_shape = tuple(x.shape)
+            ctx.storage_dtype = x.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        idx, = ctx.saved_tensors
+        return maxpool_bwd(as_grad(gy, ctx.storage_dtype), idx, ctx.in_shape)
+
+
 # --------------------------------------------------------------------------- autograd: ConvTrans3D (+ concat)
 class UpFn(torch.autograd.Function):
     """reference network.py:311-317 (+ :346-350 when `skip` is given):

@@ -12,8 +12,13 @@ native path.
 Reference behaviour implemented (file:line in the reference repo):
   ResUnet3D 104-132, generate_paired_features 135-141, ConvTrans3D 298-320, UpConcat 323-350,
   ResBlock 374-416, ResBlockStack 419-449, Unet 470-565.
-Out-of-hot-path variants (ConvBlock*, RecBlock, ResRecBlock, AttBlock, MaxPoolBlock, BatchNorm /
-attention configurations: reference 153-295, 353-371, 452-463) are ordinary torch modules.
+The plain 3D U-Net - the assembler's own defaults, ConvBlockStack encoders / decoders and MaxPoolBlock pooling (reference
+153-199, 452-463) - runs on the same path: a ConvBlock or ConvBlockStack is one ops.ConvStackFn node (conv + Dropout3d
+factors + InstanceNorm + LeakyReLU per block), MaxPoolBlock is ops.MaxPoolFn (csrc/pool.hip), and any mix of them with
+ResBlocks counts as a native chain (16-bit storage applies).  They run unpadded and unlinked; RU3D_PLAIN_BLOCKS=torch
+(read per forward) keeps the three block types torch modules on the device, as a cross-check.  On CPU tensors they stay
+the torch composition.  RecBlock / ResRecBlock are torch compositions around native ConvBlocks; BatchNorm ConvBlocks,
+other pooling modules and AttBlock on its own (reference 200-295, 353-371) are ordinary torch modules.
 
 Precision: `set_compute_dtype(model, torch.bfloat16)` (or env RU3D_DTYPE=bf16) selects bf16 storage
 with fp32 accumulation, torch.float16 the reference's apex-O1 arithmetic (fp16 storage, fp32 accumulation; train it
@@ -132,9 +137,21 @@ def _is_plain_lrelu(act):
     return type(act) is nn.LeakyReLU and abs(act.negative_slope - ops.LRELU_SLOPE) < 1e-12
 
 
-# --------------------------------------------------------------------------- generic (torch) blocks
+def _plain_blocks_native():
+    """ConvBlock / ConvBlockStack / MaxPoolBlock run on the native kernels; RU3D_PLAIN_BLOCKS=torch (read per forward)
+    keeps them torch modules on the device (the behaviour before they were native, kept as a cross-check)."""
+    return os.environ.get("RU3D_PLAIN_BLOCKS", "native") != "torch"
+
+
+def _triple(v):
+    return (v, v, v) if isinstance(v, int) else tuple(v)
+
+
+# --------------------------------------------------------------------------- generic blocks
 class ConvBlock(nn.Module):
-    """conv -> dropout -> norm -> nonlin (out of the native hot path; plain torch ops)."""
+    """conv -> dropout -> norm -> nonlin.  With the reference's defaults (3x3x3 stride-1 conv, Dropout3d or none,
+    InstanceNorm3d, LeakyReLU) a CUDA tensor goes through ops.ConvStackFn; every other configuration, and any CPU
+    tensor, is the plain torch composition."""
 
     def __init__(self, in_channels, out_channels, conv_op=nn.Conv3d,
                  conv_kwargs={'kernel_size': 3, 'padding': 1},
@@ -148,8 +165,41 @@ class ConvBlock(nn.Module):
         self.dropout = dropout_op(**dropout_kwargs) if dropout_op else None
         self.norm = norm_op(out_channels, **norm_kwargs)
         self.nonlin = nonlin_op(**nonlin_kwargs)
+        self._native = (_is_plain_conv3(self.conv) and self.conv.stride == (1, 1, 1) and _is_plain_in(self.norm)
+                        and _is_plain_lrelu(self.nonlin)
+                        and (self.dropout is None or type(self.dropout) is nn.Dropout3d))
+        self._forced_keep = None   # tests: inject a recorded [N, C] keep mask instead of drawing one
+        self._shared = False       # set by RecBlock: the weights are used more than once in a pass
+
+    def _drop_scale(self, x):
+        """ResBlock._drop_scale for an unpadded block."""
+        if self.dropout is None or not self.training:
+            return None
+        p = float(self.dropout.p)
+        n, c = x.shape[0], self.out_channels
+        if self._forced_keep is not None:
+            keep = self._forced_keep.to(device=x.device, dtype=torch.float32).reshape(n, c)
+            return (keep.reshape(-1) / (1.0 - p)).contiguous()
+        if p == 0.0:
+            return None
+        pooled = ops.take_dropout(n, c, p)
+        return pooled if pooled is not None else ops.dropout_scale(n, c, p, x.device)
+
+    def _drop_spec(self, n):
+        """(n, c, p) of the draw this block will make in training mode, or None (same conditions as _drop_scale).
+        ResBlock's interface; no caller yet: only the linked route prefills the pass's draws (ops.prefill_dropout), and
+        a chain with plain blocks is never linked."""
+        if (not self._native or self.dropout is None or not self.training or self._forced_keep is not None
+                or float(self.dropout.p) == 0.0):
+            return None
+        return (n, self.out_channels, float(self.dropout.p))
+
+    def _on_device(self, x):
+        return self._native and x.is_cuda and _plain_blocks_native()
 
     def forward(self, x):
+        if self._on_device(x):
+            return ops.ConvStackFn.apply(x, (self._drop_scale(x),), False, self._shared, self.conv.weight, self.conv.bias)
         x = self.conv(x)
         if self.dropout:
             x = self.dropout(x)
@@ -170,13 +220,22 @@ class ConvBlockStack(nn.Module):
             ConvBlock(in_channels if i == 0 else out_channels, out_channels, **common) for i in range(num_stacks))
 
     def forward(self, x):
-        for blk in self.conv_blocks:
+        blocks = list(self.conv_blocks)
+        # one autograd node for the whole stack; a hook on an inner block expects that block's own call
+        if blocks and all(b._on_device(x) and not (b._forward_hooks or b._forward_pre_hooks) for b in blocks):
+            args = []
+            for b in blocks:
+                args += [b.conv.weight, b.conv.bias]
+            return ops.ConvStackFn.apply(x, tuple(b._drop_scale(x) for b in blocks), False,
+                                         any(b._shared for b in blocks), *args)
+        for blk in blocks:
             x = blk(x)
         return x
 
 
 class RecBlock(nn.Module):
-    """Recurrent conv block (R2U-Net style), torch ops."""
+    """Recurrent conv block (R2U-Net style): one ConvBlock applied t + 1 times (native on a CUDA tensor when it
+    qualifies), torch adds between the uses."""
 
     def __init__(self, out_channels, t=2, conv_op=nn.Conv3d, conv_kwargs={'kernel_size': 3, 'padding': 1},
                  dropout_op=nn.Dropout3d, dropout_kwargs={'p': 0.5, 'inplace': True},
@@ -188,6 +247,7 @@ class RecBlock(nn.Module):
         self.conv = ConvBlock(out_channels, out_channels, conv_op=conv_op, conv_kwargs=conv_kwargs,
                               dropout_op=dropout_op, dropout_kwargs=dropout_kwargs, norm_op=norm_op,
                               norm_kwargs=norm_kwargs, nonlin_op=nonlin_op, nonlin_kwargs=nonlin_kwargs)
+        self.conv._shared = True
 
     def forward(self, x):
         out = self.conv(x)
@@ -197,7 +257,7 @@ class RecBlock(nn.Module):
 
 
 class ResRecBlock(nn.Module):
-    """Residual recurrent block, torch ops."""
+    """Residual recurrent block: a torch composition around two RecBlocks."""
 
     def __init__(self, in_channels, out_channels, t=2, conv_op=nn.Conv3d,
                  conv_kwargs={'kernel_size': 3, 'padding': 1},
@@ -238,11 +298,21 @@ class AttBlock(nn.Module):
 
 
 class MaxPoolBlock(nn.Module):
+    """Pooling module of the plain U-Net.  The reference's default, nn.MaxPool3d(2, 2), runs as ops.MaxPoolFn on a CUDA
+    tensor; any other pooling is the torch module."""
+
     def __init__(self, in_channels, out_channels, pool_op=nn.MaxPool3d, pool_kwargs={'kernel_size': 2, 'stride': 2}):
         super().__init__()
         self.pool = pool_op(**pool_kwargs)
+        p = self.pool
+        self._native = (type(p) is nn.MaxPool3d and _triple(p.kernel_size) == (2, 2, 2)
+                        and _triple(p.stride if p.stride is not None else p.kernel_size) == (2, 2, 2)
+                        and _triple(p.padding) == (0, 0, 0) and _triple(p.dilation) == (1, 1, 1)
+                        and not p.ceil_mode and not p.return_indices)
 
     def forward(self, x):
+        if (self._native and x.is_cuda and x.dim() == 5 and x.dtype in _STORAGE_DTYPES and _plain_blocks_native()):
+            return ops.MaxPoolFn.apply(x)
         return self.pool(x)
 
 
@@ -576,6 +646,7 @@ class Unet(nn.Module):
         self._linked = False
         self._bn_blocks = None
         self._in_chain = False
+        self._plain_in_chain = False
         self._pad_bn = False
         self._configure_native()
 
@@ -586,10 +657,18 @@ class Unet(nn.Module):
         for blk in list(self.pool_blocks) + list(self.encode_blocks) + list(self.decode_blocks):
             if isinstance(blk, ResBlockStack):
                 blocks += list(blk.res_blocks)
+            elif isinstance(blk, ConvBlockStack):
+                blocks += list(blk.conv_blocks)
             else:
                 blocks.append(blk)
         kinds = set()
         for blk in blocks:
+            if isinstance(blk, (ConvBlock, MaxPoolBlock)):      # plain blocks: InstanceNorm chains only
+                if not blk._native or bn_ok:
+                    return None
+                if isinstance(blk, ConvBlock):
+                    kinds.add("in")
+                continue
             if not (isinstance(blk, ResBlock) and (blk._native or blk._bn_eval)):
                 return None
             kinds.add("in" if blk._native else "bn")
@@ -623,22 +702,30 @@ class Unet(nn.Module):
                             and all(ops.cpad(c) * 2 <= 3 * c for c in wb)
                             and os.environ.get("RU3D_PAD_CHANNELS", "1") != "0")
         widths = []
+        # ConvBlock / MaxPoolBlock chains run unpadded: under the channel plan that works with max pooling
+        # (generate_paired_features2) the decoder's concat is two unequal segments, which ops.seg_of does not hold
+        plain = chain is not None and any(isinstance(blk, (ConvBlock, MaxPoolBlock)) for blk in chain)
+        self._plain_in_chain = plain
         if chain is not None:
             for blk in chain:
-                widths += [blk.in_channels, blk.out_channels]
+                if not isinstance(blk, MaxPoolBlock):      # no channel attributes
+                    widths += [blk.in_channels, blk.out_channels]
         # worth it while the padding adds at most half again to every width (F >= 22); narrower toy models keep the
         # direct kernels rather than carry 2-4x the activation bytes
-        pad = (chain is not None and self.compute_dtype != torch.float32 and any(c % 32 for c in widths)
+        pad = (chain is not None and not plain and self.compute_dtype != torch.float32 and any(c % 32 for c in widths)
                and all(ops.cpad(c) * 2 <= 3 * c for c in widths)
                and os.environ.get("RU3D_PAD_CHANNELS", "1") != "0")
         self._pad = pad
-        # skip connections of an all-native net go through ops.SkipLink (no concat copy, no autograd add)
-        self._linked = (chain is not None and not any(getattr(up, "attention", False) for up in self.up_blocks)
+        # skip connections of an all-native net go through ops.SkipLink (no concat copy, no autograd add); the linked
+        # route (prepack, prefilled dropout, link arguments) is the ResBlocks': a chain with a plain block anywhere -
+        # the decoders are not among the conditions below - takes the unlinked one
+        self._linked = (chain is not None and not plain and not any(getattr(up, "attention", False) for up in self.up_blocks)
                         and all(isinstance(b, (ResBlock, ResBlockStack)) for b in self.encode_blocks)
                         and all(isinstance(b, ResBlock) and b.uses_skip_conv for b in self.pool_blocks)
                         and os.environ.get("RU3D_SKIP_LINK", "1") != "0")
         for blk in (chain or []):
-            blk._pad = pad
+            if not isinstance(blk, (ConvBlock, MaxPoolBlock)):
+                blk._pad = pad
         for blk in self.decode_blocks:      # their input is cat((up, skip)): two padded segments
             first = blk.res_blocks[0] if isinstance(blk, ResBlockStack) else blk
             if isinstance(first, ResBlock):
@@ -647,6 +734,8 @@ class Unet(nn.Module):
     def _storage_dtype(self):
         """16-bit storage only where the blocks behind the stem consume it: an all-native InstanceNorm chain, or a
         BatchNorm chain in inference mode; torch-module blocks (BatchNorm training, custom blocks) get fp32."""
+        if self._in_chain and self._plain_in_chain and not _plain_blocks_native():
+            return torch.float32      # RU3D_PLAIN_BLOCKS=torch: the plain blocks are torch modules in this forward
         if self._in_chain or (self._bn_blocks is not None and _bn_on_device(self)):
             return self.compute_dtype
         return torch.float32

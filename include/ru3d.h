@@ -303,6 +303,17 @@ int ru3d_pointwise(int op, const ru3d_tensor* a, const ru3d_tensor* b, const ru3
 int ru3d_copy_channels(const ru3d_tensor* src, const ru3d_tensor* dst, int dtype, void* stream);
 /* dst = src + add, same shape (gradient accumulation of the skip branch). */
 int ru3d_add(const ru3d_tensor* a, const ru3d_tensor* b, const ru3d_tensor* dst, int dtype, void* stream);
+/* 2x2x2 / stride-2 max pooling (MaxPoolBlock, network.py:452-463: nn.MaxPool3d(2, 2)); dtype: any of the three storage
+ * types (the values are copied, never rounded).  Any c; odd spatial extents are floored, an extent below 2 is an error;
+ * a split tensor is rejected.
+ * y[n,c,od,oh,ow] = max over the 2x2x2 window of x at (2od.., 2oh.., 2ow..), a bit copy of the element that wins by torch's
+ * rule: scan in (d, h, w) order, replace the running maximum when v > max || isnan(v) (first of equals, the last NaN).
+ * idx (may be NULL: inference) receives one byte per element of y, dense NDHWC in y's logical shape: code = dz*4 + dy*2 +
+ * dx of the element that won. */
+int ru3d_maxpool3d_fwd(const ru3d_tensor* x, const ru3d_tensor* y, uint8_t* idx, int dtype, void* stream);
+/* dx = the gradient of the above: dy at the winning element of each window, 0 elsewhere, 0 in the trailing planes of odd
+ * extents.  Writes EVERY element of dx. */
+int ru3d_maxpool3d_bwd(const ru3d_tensor* dy, const uint8_t* idx, const ru3d_tensor* dx, int dtype, void* stream);
 /* dst (dtype `dst_dtype`) = src (fp32), same shape: fp32 logits-gradient -> storage dtype. */
 int ru3d_cast_f32(const ru3d_tensor* src, const ru3d_tensor* dst, int dst_dtype, void* stream);
 /* NCDHW fp32 (reference tensor layout) -> NDHWC `dtype`, and back. */
