@@ -188,6 +188,9 @@ SIGNATURES = {
     "ru3d_loss_workspace_bytes": (_sz, [_i, _i64, _i]),
     "ru3d_loss_fwd": (_i, _LOSS_VIEW + [_i64, _i, _i, _f, _vp, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_loss_bwd": (_i, _LOSS_VIEW + [_i64, _i, _f, _vp, _vp, _vp, _i, _vp]),
+    # the same with (has_ignore, ignore_label) behind num_classes
+    "ru3d_loss_ignore_fwd": (_i, _LOSS_VIEW + [_i64, _i, _i, _i, _i, _f, _vp, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_loss_ignore_bwd": (_i, _LOSS_VIEW + [_i64, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "ru3d_tversky": (_i, [_vp, _vp, _i64, _f, _f, _f, _vp, _vp, _sz, _vp]),
     "ru3d_predict_accumulate": (_i, [_P, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ru3d_predict_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -208,6 +211,9 @@ SIGNATURES = {
     "ru3d_topk_loss_fwd_timed": (_i, _LOSS_VIEW + [_i64, _i, _i64, _i, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _sz,
                                                    _vp, _vp]),
     "ru3d_topk_loss_bwd": (_i, _LOSS_VIEW + [_i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ru3d_topk_loss_ignore_fwd": (_i, _LOSS_VIEW + [_i64, _i, _i, _i, _i64, _i, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp,
+                                                    _sz, _vp]),
+    "ru3d_topk_loss_ignore_bwd": (_i, _LOSS_VIEW + [_i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "ru3d_predict_accumulate_groups": (_i, [_P, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ru3d_predict_merge_groups": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ru3d_components_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -263,6 +269,10 @@ SIGNATURES = {
                               _vp, _vp, _sz, _vp]),
     "ru3d_ds_loss_bwd": (_i, [ctypes.POINTER(DsLevel), ctypes.POINTER(_vp), _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp,
                               _vp]),
+    "ru3d_ds_loss_ignore_fwd": (_i, [ctypes.POINTER(DsLevel), _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _f, _f,
+                                     _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_ds_loss_ignore_bwd": (_i, [ctypes.POINTER(DsLevel), ctypes.POINTER(_vp), _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
+                                     _f, _vp, _vp, _vp]),
     "ru3d_mesh_workspace_bytes": (_sz, [_i, _i, _i]),
     "ru3d_mesh_count": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ru3d_mesh_emit": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),

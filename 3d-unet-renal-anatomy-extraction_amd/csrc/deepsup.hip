@@ -76,8 +76,9 @@ __device__ __forceinline__ int64_t ds_label_index(const DsArgs& A, const DsLevel
     return ((ni * A.D + (a << Lv.shift)) * A.H + ((int64_t)b << Lv.shift)) * A.W + ((int64_t)c << Lv.shift);
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void ds_sums_kernel(DsArgs A, float gamma, double* __restrict__ part) {
+template <int C, bool IGN>
+__global__ __launch_bounds__(256) void ds_sums_kernel(DsArgs A, float gamma, int ignore_label,
+                                                      double* __restrict__ part) {
     const int l = ds_level_of(A, blockIdx.x);
     const DsLevelArg Lv = A.lev[l];
     const int first = Lv.block0;
@@ -89,9 +90,10 @@ __global__ __launch_bounds__(256) void ds_sums_kernel(DsArgs A, float gamma, dou
     const int64_t total = (int64_t)A.n * Lv.v;
     for (int64_t i = (int64_t)(blockIdx.x - first) * 256 + threadIdx.x; i < total; i += (int64_t)count * 256) {
         const int64_t ni = i / Lv.v, vi = i - ni * Lv.v;
+        const int t = load_label(A.labels, A.label_dtype, ds_label_index(A, Lv, ni, vi));
+        if (label_ignored<IGN>(t, ignore_label)) continue;      // the level ignores a voxel iff the label it reads is ignored
         float p[C], lp[C];
         voxel_probs<C>(Lv.logits + ni * Lv.stride_n + vi * Lv.stride_v, Lv.stride_c, p, lp);
-        const int t = load_label(A.labels, A.label_dtype, ds_label_index(A, Lv, ni, vi));
         region_add<C>(p, lp, t, gamma, tp, sp, sg, fo, bad);
     }
     region_write_row<C>(tp, sp, sg, fo, bad, part + (int64_t)blockIdx.x * REGION_Q);
@@ -100,6 +102,7 @@ __global__ __launch_bounds__(256) void ds_sums_kernel(DsArgs A, float gamma, dou
 // One workgroup of REGION_LF_THREADS, level after level: the fixed-order reduction of the level's partial rows, then
 // thread 0 turns the sums into the level's loss and backward coefficients.  block: float32 [0 .. 7] the level weights
 // (read), [8 .. 15] the levels' losses and [16] the total (written).
+template <bool IGN>
 __global__ __launch_bounds__(REGION_LF_THREADS) void ds_finalize_kernel(const double* __restrict__ part, DsParams P,
                                                                         float* __restrict__ block, DsState* __restrict__ st,
                                                                         float* __restrict__ loss_out) {
@@ -112,7 +115,8 @@ __global__ __launch_bounds__(REGION_LF_THREADS) void ds_finalize_kernel(const do
             DsLevelState* sl = &st->lev[l];
             // out-of-range labels are counted where every label is read once: on level 0
             const int bad = (l == 0) ? (int)tot[4 * RU3D_MAX_CLASSES] : 0;
-            const double loss = region_coefficients(P.kind, P.C, P.w, P.alpha, P.beta, P.smooth, P.nv[l], tot, bad, &sl->r);
+            const double nv = region_voxels<IGN>(P.nv[l], P.C, tot);      // with an ignore label: the level's own M_l
+            const double loss = region_coefficients(P.kind, P.C, P.w, P.alpha, P.beta, P.smooth, nv, tot, bad, &sl->r);
             const float wl = block[l];
             sl->weight = wl;
             sl->pad = 0;
@@ -128,8 +132,9 @@ __global__ __launch_bounds__(REGION_LF_THREADS) void ds_finalize_kernel(const do
     loss_out[0] = (float)total;
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void ds_bwd_kernel(DsArgs A, float gamma, const DsState* __restrict__ st,
+template <int C, bool IGN>
+__global__ __launch_bounds__(256) void ds_bwd_kernel(DsArgs A, float gamma, int ignore_label,
+                                                     const DsState* __restrict__ st,
                                                      const float* __restrict__ grad_out) {
     const int l = ds_level_of(A, blockIdx.x);
     const DsLevelArg Lv = A.lev[l];
@@ -142,9 +147,15 @@ __global__ __launch_bounds__(256) void ds_bwd_kernel(DsArgs A, float gamma, cons
     for (int64_t i = (int64_t)(blockIdx.x - first) * 256 + threadIdx.x; i < total; i += (int64_t)count * 256) {
         const int64_t ni = i / Lv.v, vi = i - ni * Lv.v;
         const int64_t base = ni * Lv.stride_n + vi * Lv.stride_v;
+        const int t = load_label(A.labels, A.label_dtype, ds_label_index(A, Lv, ni, vi));
+        if (label_ignored<IGN>(t, ignore_label)) {      // dlogits is uninitialised memory: the zeros are written
+#pragma unroll
+            for (int c = 0; c < C; c++) Lv.dlogits[base + c * Lv.stride_c] = 0.f;
+            continue;
+        }
         float p[C], lp[C], d[C];
         voxel_probs<C>(Lv.logits + base, Lv.stride_c, p, lp);
-        grad.voxel(p, lp, load_label(A.labels, A.label_dtype, ds_label_index(A, Lv, ni, vi)), gamma, d);
+        grad.voxel(p, lp, t, gamma, d);
 #pragma unroll
         for (int c = 0; c < C; c++) Lv.dlogits[base + c * Lv.stride_c] = d[c] * go;
     }
@@ -221,13 +232,16 @@ extern "C" size_t ru3d_ds_loss_workspace_bytes(const ru3d_ds_level* levels, int 
     return (size_t)ds_fwd_blocks(levels, num_levels, n) * REGION_Q * sizeof(double);
 }
 
-extern "C" int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, const void* labels, int label_dtype, int n,
-                                int D, int H, int W, int num_classes, int kind, float gamma, const float* weight_v,
-                                float alpha, float beta, float smooth, float* block, void* state, float* loss_out,
-                                void* ws, size_t ws_bytes, void* stream) {
+extern "C" int ru3d_ds_loss_ignore_fwd(const ru3d_ds_level* levels, int num_levels, const void* labels, int label_dtype,
+                                       int n, int D, int H, int W, int num_classes, int has_ignore, int ignore_label,
+                                       int kind, float gamma, const float* weight_v, float alpha, float beta, float smooth,
+                                       float* block, void* state, float* loss_out, void* ws, size_t ws_bytes,
+                                       void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
     int rc = loss_view_check("ds_loss_fwd", levels && labels && block && state && loss_out && ws,
                              n > 0 && D > 0 && H > 0 && W > 0, label_dtype, num_classes, 1);
+    if (rc) return rc;
+    rc = loss_ignore_check("ds_loss_fwd", has_ignore, ignore_label, label_dtype, num_classes);
     if (rc) return rc;
     RU3D_REQUIRE(kind == RU3D_LOSS_HYBIRD || kind == RU3D_LOSS_DICELOSS || kind == RU3D_LOSS_FOCAL,
                  "ds_loss_fwd: bad kind %d (HYBIRD, DICELOSS or FOCAL)", kind);
@@ -237,8 +251,9 @@ extern "C" int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, con
     RU3D_REQUIRE(ws_bytes >= (size_t)A.nblocks * REGION_Q * sizeof(double),
                  "ds_loss_fwd: workspace too small");
     hipStream_t st = as_stream(stream);
-#define CALL(CC) hipLaunchKernelGGL(ds_sums_kernel<CC>, dim3(A.nblocks), dim3(256), 0, st, A, gamma, (double*)ws)
-    RU3D_DISPATCH_C(1, num_classes, CALL)
+#define CALL(CC, IGN) \
+    hipLaunchKernelGGL((ds_sums_kernel<CC, IGN>), dim3(A.nblocks), dim3(256), 0, st, A, gamma, ignore_label, (double*)ws)
+    RU3D_DISPATCH_C_IGN(1, num_classes, has_ignore, CALL)
 #undef CALL
     rc = ru3d_check_launch("ds_loss_sums");
     if (rc) return rc;
@@ -253,25 +268,48 @@ extern "C" int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, con
     fill_class_weights(P.w, weight_v, num_classes);
     for (int l = 0; l <= RU3D_DS_MAX_LEVELS; l++) P.blocks[l] = (l < num_levels) ? A.lev[l].block0 : A.nblocks;
     for (int l = 0; l < RU3D_DS_MAX_LEVELS; l++) P.nv[l] = (l < num_levels) ? (double)n * (double)A.lev[l].v : 1.0;
-    hipLaunchKernelGGL(ds_finalize_kernel, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)ws, P, block,
-                       (DsState*)state, loss_out);
+    if (has_ignore)
+        hipLaunchKernelGGL(ds_finalize_kernel<true>, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)ws, P, block,
+                           (DsState*)state, loss_out);
+    else
+        hipLaunchKernelGGL(ds_finalize_kernel<false>, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)ws, P, block,
+                           (DsState*)state, loss_out);
     return ru3d_check_launch("ds_loss_finalize");
 }
 
-extern "C" int ru3d_ds_loss_bwd(const ru3d_ds_level* levels, void* const* dlogits, int num_levels, const void* labels,
-                                int label_dtype, int n, int D, int H, int W, int num_classes, float gamma,
-                                const void* state, const float* grad_out, void* stream) {
+extern "C" int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, const void* labels, int label_dtype, int n,
+                                int D, int H, int W, int num_classes, int kind, float gamma, const float* weight_v,
+                                float alpha, float beta, float smooth, float* block, void* state, float* loss_out,
+                                void* ws, size_t ws_bytes, void* stream) {
+    return ru3d_ds_loss_ignore_fwd(levels, num_levels, labels, label_dtype, n, D, H, W, num_classes, 0, 0, kind, gamma,
+                                   weight_v, alpha, beta, smooth, block, state, loss_out, ws, ws_bytes, stream);
+}
+
+extern "C" int ru3d_ds_loss_ignore_bwd(const ru3d_ds_level* levels, void* const* dlogits, int num_levels,
+                                       const void* labels, int label_dtype, int n, int D, int H, int W, int num_classes,
+                                       int has_ignore, int ignore_label, float gamma, const void* state,
+                                       const float* grad_out, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
     int rc = loss_view_check("ds_loss_bwd", levels && labels && state && dlogits, n > 0 && D > 0 && H > 0 && W > 0,
                              label_dtype, num_classes, 1);
+    if (rc) return rc;
+    rc = loss_ignore_check("ds_loss_bwd", has_ignore, ignore_label, label_dtype, num_classes);
     if (rc) return rc;
     DsArgs A;
     rc = ds_fill_args(A, levels, dlogits, num_levels, labels, label_dtype, n, D, H, W, ds_bwd_blocks, "ds_loss_bwd");
     if (rc) return rc;
     hipStream_t st = as_stream(stream);
-#define CALL(CC) \
-    hipLaunchKernelGGL(ds_bwd_kernel<CC>, dim3(A.nblocks), dim3(256), 0, st, A, gamma, (const DsState*)state, grad_out)
-    RU3D_DISPATCH_C(1, num_classes, CALL)
+#define CALL(CC, IGN)                                                                                            \
+    hipLaunchKernelGGL((ds_bwd_kernel<CC, IGN>), dim3(A.nblocks), dim3(256), 0, st, A, gamma, ignore_label, \
+                       (const DsState*)state, grad_out)
+    RU3D_DISPATCH_C_IGN(1, num_classes, has_ignore, CALL)
 #undef CALL
     return ru3d_check_launch("ds_loss_bwd");
+}
+
+extern "C" int ru3d_ds_loss_bwd(const ru3d_ds_level* levels, void* const* dlogits, int num_levels, const void* labels,
+                                int label_dtype, int n, int D, int H, int W, int num_classes, float gamma,
+                                const void* state, const float* grad_out, void* stream) {
+    return ru3d_ds_loss_ignore_bwd(levels, dlogits, num_levels, labels, label_dtype, n, D, H, W, num_classes, 0, 0, gamma,
+                                   state, grad_out, stream);
 }

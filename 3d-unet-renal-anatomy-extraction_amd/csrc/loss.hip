@@ -10,6 +10,9 @@
 //   w       = weight_v / |weight_v|_1   (weight_c and the presence mask are dead)   loss.py:69,155,237
 //   Hybird  = sum_c w_c (1 - dice_c + focal_c); DiceLoss = sum w (1 - dice); Focal = sum w focal;
 //   Dice    = sum w dice
+// With an ignore label (the IGN instantiations, ru3d_loss_ignore_fwd / _bwd) all of this is taken over the voxels whose
+// label is not the ignore label, M of them: tp, sp, sg over those only, focal_c = C * sum / max(M, 1) with M = sum_c sg_c,
+// and exact zeros written as the gradient of the others, whose logits are never read.
 #include "common.h"
 #include "loss_core.h"
 
@@ -30,11 +33,12 @@ extern "C" size_t ru3d_loss_workspace_bytes(int n, int64_t v, int num_classes) {
     return (size_t)region_fwd_blocks((int64_t)n * v) * REGION_Q * sizeof(double);
 }
 
-template <int C>
+template <int C, bool IGN>
 __global__ __launch_bounds__(256) void loss_sums_kernel(const float* __restrict__ logits, int64_t stride_n,
                                                         int64_t stride_c, int64_t stride_v,
                                                         const void* __restrict__ labels, int label_dtype, int n,
-                                                        int64_t v, float gamma, double* __restrict__ part) {
+                                                        int64_t v, float gamma, int ignore_label,
+                                                        double* __restrict__ part) {
     float tp[C], sp[C], sg[C], fo[C];
 #pragma unroll
     for (int c = 0; c < C; c++) tp[c] = sp[c] = sg[c] = fo[c] = 0.f;
@@ -42,9 +46,11 @@ __global__ __launch_bounds__(256) void loss_sums_kernel(const float* __restrict_
     const int64_t total = (int64_t)n * v;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t ni = i / v, vi = i - ni * v;
+        const int t = load_label(labels, label_dtype, i);
+        if (label_ignored<IGN>(t, ignore_label)) continue;
         float p[C], lp[C];
         voxel_probs<C>(logits + ni * stride_n + vi * stride_v, stride_c, p, lp);
-        region_add<C>(p, lp, load_label(labels, label_dtype, i), gamma, tp, sp, sg, fo, bad);
+        region_add<C>(p, lp, t, gamma, tp, sp, sg, fo, bad);
     }
     region_write_row<C>(tp, sp, sg, fo, bad, part + (int64_t)blockIdx.x * REGION_Q);
 }
@@ -56,6 +62,7 @@ struct LossParams {
     float w[RU3D_MAX_CLASSES];  // weight_v (un-normalised); all ones when the caller passed NULL
 };
 
+template <bool IGN>
 __global__ __launch_bounds__(REGION_LF_THREADS) void loss_finalize_kernel(const double* __restrict__ part, int blocks,
                                                                           LossParams P, LossState* __restrict__ st,
                                                                           float* __restrict__ loss_out) {
@@ -63,15 +70,17 @@ __global__ __launch_bounds__(REGION_LF_THREADS) void loss_finalize_kernel(const 
     __shared__ double tot[REGION_Q];
     region_reduce_rows(part, blocks, P.C, red, tot);
     if (threadIdx.x != 0) return;
-    loss_out[0] = (float)region_coefficients(P.kind, P.C, P.w, P.alpha, P.beta, P.smooth, (double)P.n * (double)P.v,
-                                             tot, (int)tot[4 * RU3D_MAX_CLASSES], &st->r);
+    const double nv = region_voxels<IGN>((double)P.n * (double)P.v, P.C, tot);
+    loss_out[0] = (float)region_coefficients(P.kind, P.C, P.w, P.alpha, P.beta, P.smooth, nv, tot,
+                                             (int)tot[4 * RU3D_MAX_CLASSES], &st->r);
 }
 
-template <int C, typename TG>
+template <int C, typename TG, bool IGN>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ logits, int64_t stride_n,
                                                        int64_t stride_c, int64_t stride_v,
                                                        const void* __restrict__ labels, int label_dtype, int n,
-                                                       int64_t v, float gamma, const LossState* __restrict__ st,
+                                                       int64_t v, float gamma, int ignore_label,
+                                                       const LossState* __restrict__ st,
                                                        const float* __restrict__ grad_out, TG* __restrict__ dz) {
     const RegionGrad<C> grad(&st->r);
     const float go = grad_out ? grad_out[0] : 1.f;
@@ -79,30 +88,39 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t ni = i / v, vi = i - ni * v;
         const int64_t base = ni * stride_n + vi * stride_v;
+        const int t = load_label(labels, label_dtype, i);
+        if (label_ignored<IGN>(t, ignore_label)) {      // dz is uninitialised memory: the zeros are written
+#pragma unroll
+            for (int c = 0; c < C; c++) dz[base + c * stride_c] = from_f32<TG>(0.f);
+            continue;
+        }
         float p[C], lp[C], d[C];
         voxel_probs<C>(logits + base, stride_c, p, lp);
-        grad.voxel(p, lp, load_label(labels, label_dtype, i), gamma, d);
+        grad.voxel(p, lp, t, gamma, d);
 #pragma unroll
         for (int c = 0; c < C; c++) dz[base + c * stride_c] = from_f32<TG>(d[c] * go);
     }
 }
 
-extern "C" int ru3d_loss_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
-                             const void* labels, int label_dtype, int n, int64_t v, int num_classes, int kind,
-                             float gamma, const float* weight_v, float alpha, float beta, float smooth, void* state,
-                             float* loss_out, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int ru3d_loss_ignore_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
+                                    const void* labels, int label_dtype, int n, int64_t v, int num_classes,
+                                    int has_ignore, int ignore_label, int kind, float gamma, const float* weight_v,
+                                    float alpha, float beta, float smooth, void* state, float* loss_out, void* ws,
+                                    size_t ws_bytes, void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
     int rc = loss_view_check("loss_fwd", logits && labels && state && loss_out && ws, n > 0 && v > 0, label_dtype,
                              num_classes, 1);
+    if (rc) return rc;
+    rc = loss_ignore_check("loss_fwd", has_ignore, ignore_label, label_dtype, num_classes);
     if (rc) return rc;
     RU3D_REQUIRE(kind >= 0 && kind <= 3, "loss_fwd: bad kind %d", kind);
     RU3D_REQUIRE(ws_bytes >= ru3d_loss_workspace_bytes(n, v, num_classes), "loss_fwd: workspace too small");
     hipStream_t st = as_stream(stream);
     const int blocks = region_fwd_blocks((int64_t)n * v);
-#define CALL(CC)                                                                                                    \
-    hipLaunchKernelGGL(loss_sums_kernel<CC>, dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, stride_v, \
-                       labels, label_dtype, n, v, gamma, (double*)ws)
-    RU3D_DISPATCH_C(1, num_classes, CALL)
+#define CALL(CC, IGN)                                                                                          \
+    hipLaunchKernelGGL((loss_sums_kernel<CC, IGN>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, \
+                       stride_v, labels, label_dtype, n, v, gamma, ignore_label, (double*)ws)
+    RU3D_DISPATCH_C_IGN(1, num_classes, has_ignore, CALL)
 #undef CALL
     rc = ru3d_check_launch("loss_sums");
     if (rc) return rc;
@@ -116,27 +134,50 @@ extern "C" int ru3d_loss_fwd(const float* logits, int64_t stride_n, int64_t stri
     P.beta = beta;
     P.smooth = smooth;
     fill_class_weights(P.w, weight_v, num_classes);
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)ws, blocks, P,
-                       (LossState*)state, loss_out);
+    if (has_ignore)
+        hipLaunchKernelGGL(loss_finalize_kernel<true>, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)ws, blocks,
+                           P, (LossState*)state, loss_out);
+    else
+        hipLaunchKernelGGL(loss_finalize_kernel<false>, dim3(1), dim3(REGION_LF_THREADS), 0, st, (const double*)ws, blocks,
+                           P, (LossState*)state, loss_out);
     return ru3d_check_launch("loss_finalize");
+}
+
+extern "C" int ru3d_loss_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
+                             const void* labels, int label_dtype, int n, int64_t v, int num_classes, int kind,
+                             float gamma, const float* weight_v, float alpha, float beta, float smooth, void* state,
+                             float* loss_out, void* ws, size_t ws_bytes, void* stream) {
+    return ru3d_loss_ignore_fwd(logits, stride_n, stride_c, stride_v, labels, label_dtype, n, v, num_classes, 0, 0, kind,
+                                gamma, weight_v, alpha, beta, smooth, state, loss_out, ws, ws_bytes, stream);
+}
+
+extern "C" int ru3d_loss_ignore_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
+                                    const void* labels, int label_dtype, int n, int64_t v, int num_classes,
+                                    int has_ignore, int ignore_label, float gamma, const void* state,
+                                    const float* grad_out, void* dlogits, int dlogits_dtype, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    int rc = loss_view_check("loss_bwd", logits && labels && state && dlogits, n > 0 && v > 0, label_dtype, num_classes, 1);
+    if (rc) return rc;
+    rc = loss_ignore_check("loss_bwd", has_ignore, ignore_label, label_dtype, num_classes);
+    if (rc) return rc;
+    RU3D_REQUIRE(dlogits_dtype == RU3D_F32 || dlogits_dtype == RU3D_BF16, "loss_bwd: bad dlogits dtype");
+    hipStream_t st = as_stream(stream);
+    const int blocks = flat_bwd_blocks((int64_t)n * v, 8192);
+#define CALL(CC, TG, IGN)                                                                                        \
+    hipLaunchKernelGGL((loss_bwd_kernel<CC, TG, IGN>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, \
+                       stride_v, labels, label_dtype, n, v, gamma, ignore_label, (const LossState*)state, grad_out,  \
+                       (TG*)dlogits)
+    RU3D_DISPATCH_C_DZ_IGN(1, num_classes, dlogits_dtype, has_ignore, CALL)
+#undef CALL
+    return ru3d_check_launch("loss_bwd");
 }
 
 extern "C" int ru3d_loss_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
                              const void* labels, int label_dtype, int n, int64_t v, int num_classes, float gamma,
                              const void* state, const float* grad_out, void* dlogits, int dlogits_dtype,
                              void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    int rc = loss_view_check("loss_bwd", logits && labels && state && dlogits, n > 0 && v > 0, label_dtype, num_classes, 1);
-    if (rc) return rc;
-    RU3D_REQUIRE(dlogits_dtype == RU3D_F32 || dlogits_dtype == RU3D_BF16, "loss_bwd: bad dlogits dtype");
-    hipStream_t st = as_stream(stream);
-    const int blocks = flat_bwd_blocks((int64_t)n * v, 8192);
-#define CALL(CC, TG)                                                                                                  \
-    hipLaunchKernelGGL((loss_bwd_kernel<CC, TG>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, stride_v, \
-                       labels, label_dtype, n, v, gamma, (const LossState*)state, grad_out, (TG*)dlogits)
-    RU3D_DISPATCH_C_DZ(1, num_classes, dlogits_dtype, CALL)
-#undef CALL
-    return ru3d_check_launch("loss_bwd");
+    return ru3d_loss_ignore_bwd(logits, stride_n, stride_c, stride_v, labels, label_dtype, n, v, num_classes, 0, 0, gamma,
+                                state, grad_out, dlogits, dlogits_dtype, stream);
 }
 
 // --------------------------------------------------------------------------- functional dice

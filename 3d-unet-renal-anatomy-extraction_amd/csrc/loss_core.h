@@ -39,6 +39,14 @@ __device__ __forceinline__ int load_label(const void* labels, int label_dtype, i
     return (int)((const uint8_t*)labels)[i];
 }
 
+// The ignore form of a loss kernel (template parameter IGN): a voxel whose label equals ignore_label is skipped before
+// its logits are read - it enters no sum, its ce is 0, its gradient is written as exact zeros - so what its logits hold
+// (NaN, Inf, padding) cannot reach anything.  Without IGN the test is compiled out.
+template <bool IGN>
+__device__ __forceinline__ bool label_ignored(int t, int ignore_label) {
+    return IGN && t == ignore_label;
+}
+
 __device__ __forceinline__ float pow_gamma(float base, float gamma) {
     if (gamma == 2.f) return base * base;
     if (gamma == 1.f) return base;
@@ -233,6 +241,16 @@ __device__ __forceinline__ double region_coefficients(int kind, int C, const flo
     return loss;
 }
 
+// The voxel count of the focal mean.  Without an ignore label it is the batch's N V; with one it is M, the counted
+// voxels: sum_c sg_c, float64 sums of exact small integers, floored at 1 (M = 0 leaves every sum 0: focal 0, dice 1).
+template <bool IGN>
+__device__ __forceinline__ double region_voxels(double NV, int C, const double* tot) {
+    if (!IGN) return NV;
+    double m = 0.0;
+    for (int c = 0; c < C; c++) m += tot[2 * RU3D_MAX_CLASSES + c];
+    return m < 1.0 ? 1.0 : m;
+}
+
 // the backward of one voxel: d[c] = d loss / d z_c from the coefficients a finalize left
 template <int C>
 struct RegionGrad {
@@ -306,6 +324,38 @@ static inline int loss_view_check(const char* who, bool pointers, bool nonempty,
                  min_count, RU3D_MAX_CLASSES);
     return 0;
 }
+
+// The ignore label of the softmax losses, checked after loss_view_check and before any launch: it must not be a class,
+// the single-channel (sigmoid) form has none, and uint8 labels can only carry 0 .. 255.
+static inline int loss_ignore_check(const char* who, int has_ignore, int ignore_label, int label_dtype, int num_classes) {
+    if (!has_ignore) return 0;
+    RU3D_REQUIRE(num_classes >= 2, "%s: an ignore label needs at least 2 classes (the group loss is the single-channel form)", who);
+    RU3D_REQUIRE(ignore_label < 0 || ignore_label >= num_classes, "%s: ignore_label %d is one of the %d classes", who,
+                 ignore_label, num_classes);
+    RU3D_REQUIRE(label_dtype != RU3D_LABEL_U8 || (ignore_label >= 0 && ignore_label <= 255),
+                 "%s: uint8 labels cannot carry ignore_label %d", who, ignore_label);
+    return 0;
+}
+
+// CALL(C, IGN, ...) for a run-time has_ignore: the ignore form is an instantiation of its own beside the plain one
+#define RU3D_DISPATCH_C_IGN(MIN, C, HAS_IGNORE, CALL)  \
+    if (HAS_IGNORE) {                                  \
+        RU3D_DISPATCH_C(2, C, CALL, true)              \
+    } else {                                           \
+        RU3D_DISPATCH_C(MIN, C, CALL, false)           \
+    }
+#define RU3D_DISPATCH_C_DZ_IGN(MIN, C, DTYPE, HAS_IGNORE, CALL) \
+    if ((DTYPE) == RU3D_F32) {                                   \
+        if (HAS_IGNORE) {                                        \
+            RU3D_DISPATCH_C(2, C, CALL, float, true)             \
+        } else {                                                 \
+            RU3D_DISPATCH_C(MIN, C, CALL, float, false)          \
+        }                                                        \
+    } else if (HAS_IGNORE) {                                     \
+        RU3D_DISPATCH_C(2, C, CALL, bf16, true)                  \
+    } else {                                                     \
+        RU3D_DISPATCH_C(MIN, C, CALL, bf16, false)               \
+    }
 
 // the classes a loss is restricted to (clDice, boundary); goes to kernels by value
 struct ClassList {

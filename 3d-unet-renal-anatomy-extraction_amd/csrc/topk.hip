@@ -16,6 +16,9 @@
 //   HybirdTopKLoss = sum_c w_c (1 - dice_c) + ce_weight * topk,  w = weight_v / sum|weight_v| and the Tversky dice_c
 //           exactly DiceLoss's (loss_core.h)
 //   k = 100 is the plain mean cross-entropy.
+//   With an ignore label (the IGN instantiations; nnU-Net's ignore_index rule): an ignored voxel has ce = 0 without its
+//   logits being read, is selected like any voxel whose cross-entropy is 0 - K stays relative to all M voxels - and gets
+//   a zero gradient whatever s_v the tie rule gives to ce == tau == 0; the Dice term sums over the counted voxels only.
 //
 // The select.  Radix select on select_key.h's order-preserving key, three digits of 11 / 11 / 10 bits, most significant
 // first; the two zeros are one value (the key is taken of x + 0, and a zero tau is +0).  A level counts the digit of the
@@ -346,10 +349,11 @@ extern "C" size_t ru3d_topk_loss_workspace_bytes(int n, int64_t v, int num_class
 // the first pass: logits and labels read once; ce[] written, the top digit of every ce counted, and - with_dice - the
 // region sums tp / sp / sg of the Tversky term.  part: one row of REGION_Q doubles per workgroup (the bad-label count
 // is its last entry, with or without the region sums).
-template <int C>
+template <int C, bool IGN>
 __global__ __launch_bounds__(256) void tk_ce_kernel(const float* __restrict__ logits, int64_t stride_n, int64_t stride_c,
                                                     int64_t stride_v, const void* __restrict__ labels, int label_dtype,
-                                                    int n, int64_t v, int with_dice, float* __restrict__ ce,
+                                                    int n, int64_t v, int with_dice, int ignore_label,
+                                                    float* __restrict__ ce,
                                                     tk_u64* __restrict__ hist, double* __restrict__ part) {
     __shared__ unsigned s_hist[TK_BINS];
     for (int i = threadIdx.x; i < TK_BINS; i += 256) s_hist[i] = 0;
@@ -361,19 +365,21 @@ __global__ __launch_bounds__(256) void tk_ce_kernel(const float* __restrict__ lo
     const int64_t total = (int64_t)n * v;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t ni = i / v, vi = i - ni * v;
-        float p[C], lp[C];
-        voxel_probs<C>(logits + ni * stride_n + vi * stride_v, stride_c, p, lp);
         const int t = load_label(labels, label_dtype, i);
-        float cev = 0.f;                     // a label out of range: ce = 0
+        float cev = 0.f;                     // a label out of range, or the ignore label: ce = 0
+        if (!label_ignored<IGN>(t, ignore_label)) {      // an ignored voxel enters the selection as a zero and no sum
+            float p[C], lp[C];
+            voxel_probs<C>(logits + ni * stride_n + vi * stride_v, stride_c, p, lp);
 #pragma unroll
-        for (int c = 0; c < C; c++)
-            if (c == t) cev = 0.f - lp[c];   // lp <= 0; 0 - (+0) is +0, never -0
+            for (int c = 0; c < C; c++)
+                if (c == t) cev = 0.f - lp[c];   // lp <= 0; 0 - (+0) is +0, never -0
+            if (with_dice)
+                region_add<C>(p, lp, t, 0.f, tp, sp, sg, fo, bad);
+            else
+                bad += (t < 0 || t >= C);
+        }
         ce[i] = cev;
         tk_lds_count(s_hist, tk_key(cev) >> tk_shift(0));
-        if (with_dice)
-            region_add<C>(p, lp, t, 0.f, tp, sp, sg, fo, bad);
-        else
-            bad += (t < 0 || t >= C);
     }
     region_write_row<C>(tp, sp, sg, fo, bad, part + (int64_t)blockIdx.x * REGION_Q);
     __syncthreads();
@@ -432,10 +438,11 @@ __global__ __launch_bounds__(REGION_LF_THREADS) void tk_loss_finalize_kernel(con
     loss_out[0] = (float)loss;
 }
 
-template <int C, typename TG>
+template <int C, typename TG, bool IGN>
 __global__ __launch_bounds__(256) void tk_bwd_kernel(const float* __restrict__ logits, int64_t stride_n, int64_t stride_c,
                                                      int64_t stride_v, const void* __restrict__ labels, int label_dtype,
-                                                     int n, int64_t v, int with_dice, const float* __restrict__ ce,
+                                                     int n, int64_t v, int with_dice, int ignore_label,
+                                                     const float* __restrict__ ce,
                                                      const TopKState* __restrict__ st, const float* __restrict__ grad_out,
                                                      TG* __restrict__ dz) {
     const RegionGrad<C> grad(&st->r);
@@ -445,9 +452,14 @@ __global__ __launch_bounds__(256) void tk_bwd_kernel(const float* __restrict__ l
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t ni = i / v, vi = i - ni * v;
         const int64_t base = ni * stride_n + vi * stride_v;
+        const int t = load_label(labels, label_dtype, i);
+        if (label_ignored<IGN>(t, ignore_label)) {      // zero whatever share the tie rule gives to ce == tau == 0
+#pragma unroll
+            for (int c = 0; c < C; c++) dz[base + c * stride_c] = from_f32<TG>(0.f);
+            continue;
+        }
         float p[C], lp[C], d[C];
         voxel_probs<C>(logits + base, stride_c, p, lp);
-        const int t = load_label(labels, label_dtype, i);
         if (with_dice) {
             grad.voxel(p, lp, t, 0.f, d);
         } else {
@@ -465,11 +477,14 @@ __global__ __launch_bounds__(256) void tk_bwd_kernel(const float* __restrict__ l
 #define TK_FWD_LAUNCHES (2 + 2 * (TK_LEVELS - 1) + 1)
 
 static int tk_loss_forward(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
-                           int label_dtype, int n, int64_t v, int num_classes, int64_t K, int with_dice,
+                           int label_dtype, int n, int64_t v, int num_classes, int has_ignore, int ignore_label,
+                           int64_t K, int with_dice,
                            const float* weight_v, float alpha, float beta, float smooth, float ce_weight, float* ce,
                            void* state, float* loss_out, void* ws, size_t ws_bytes, void* stream, hipEvent_t* ev) {
     int rc = loss_view_check("topk_loss_fwd", logits && labels && ce && state && loss_out && ws, n > 0 && v > 0,
                              label_dtype, num_classes, 2);
+    if (rc) return rc;
+    rc = loss_ignore_check("topk_loss_fwd", has_ignore, ignore_label, label_dtype, num_classes);
     if (rc) return rc;
     const int64_t m = (int64_t)n * v;
     RU3D_REQUIRE(K >= 1 && K <= m, "topk_loss_fwd: K = %lld of %lld voxels", (long long)K, (long long)m);
@@ -483,10 +498,10 @@ static int tk_loss_forward(const float* logits, int64_t stride_n, int64_t stride
     if (ev) (void)hipEventRecord(*ev++, st);
     tk_launch_zero(w, st);
     if (ev) (void)hipEventRecord(*ev++, st);
-#define CALL(CC)                                                                                                       \
-    hipLaunchKernelGGL(tk_ce_kernel<CC>, dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, stride_v, labels, \
-                       label_dtype, n, v, with_dice, ce, w.hist, part)
-    RU3D_DISPATCH_C(2, num_classes, CALL)
+#define CALL(CC, IGN)                                                                                               \
+    hipLaunchKernelGGL((tk_ce_kernel<CC, IGN>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, stride_v, \
+                       labels, label_dtype, n, v, with_dice, ignore_label, ce, w.hist, part)
+    RU3D_DISPATCH_C_IGN(2, num_classes, has_ignore, CALL)
 #undef CALL
     if (ev) (void)hipEventRecord(*ev++, st);
     rc = ru3d_check_launch("topk_loss_ce");
@@ -512,14 +527,26 @@ static int tk_loss_forward(const float* logits, int64_t stride_n, int64_t stride
     return ru3d_check_launch("topk_loss_finalize");
 }
 
+extern "C" int ru3d_topk_loss_ignore_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
+                                         const void* labels, int label_dtype, int n, int64_t v, int num_classes,
+                                         int has_ignore, int ignore_label, int64_t K, int with_dice,
+                                         const float* weight_v, float alpha, float beta, float smooth, float ce_weight,
+                                         float* ce, void* state, float* loss_out, void* ws, size_t ws_bytes,
+                                         void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    return tk_loss_forward(logits, stride_n, stride_c, stride_v, labels, label_dtype, n, v, num_classes, has_ignore,
+                           ignore_label, K, with_dice, weight_v, alpha, beta, smooth, ce_weight, ce, state, loss_out, ws,
+                           ws_bytes, stream, nullptr);
+}
+
 extern "C" int ru3d_topk_loss_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
                                   const void* labels, int label_dtype, int n, int64_t v, int num_classes, int64_t K,
                                   int with_dice, const float* weight_v, float alpha, float beta, float smooth,
                                   float ce_weight, float* ce, void* state, float* loss_out, void* ws, size_t ws_bytes,
                                   void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    return tk_loss_forward(logits, stride_n, stride_c, stride_v, labels, label_dtype, n, v, num_classes, K, with_dice,
-                           weight_v, alpha, beta, smooth, ce_weight, ce, state, loss_out, ws, ws_bytes, stream, nullptr);
+    return ru3d_topk_loss_ignore_fwd(logits, stride_n, stride_c, stride_v, labels, label_dtype, n, v, num_classes, 0, 0, K,
+                                     with_dice, weight_v, alpha, beta, smooth, ce_weight, ce, state, loss_out, ws,
+                                     ws_bytes, stream);
 }
 
 extern "C" int ru3d_topk_loss_fwd_launches(void) { return TK_FWD_LAUNCHES; }
@@ -540,7 +567,7 @@ extern "C" int ru3d_topk_loss_fwd_timed(const float* logits, int64_t stride_n, i
         if (hipEventCreate(&ev[made]) != hipSuccess) break;
     int rc = made == TK_FWD_LAUNCHES + 1 ? 0 : ru3d_fail(-1, "topk_loss_fwd_timed: hipEventCreate failed");
     if (!rc)
-        rc = tk_loss_forward(logits, stride_n, stride_c, stride_v, labels, label_dtype, n, v, num_classes, K, with_dice,
+        rc = tk_loss_forward(logits, stride_n, stride_c, stride_v, labels, label_dtype, n, v, num_classes, 0, 0, K, with_dice,
                              weight_v, alpha, beta, smooth, ce_weight, ce, state, loss_out, ws, ws_bytes, stream, ev);
     if (!rc && hipEventSynchronize(ev[TK_FWD_LAUNCHES]) != hipSuccess)
         rc = ru3d_fail(-1, "topk_loss_fwd_timed: hipEventSynchronize failed");
@@ -551,21 +578,33 @@ extern "C" int ru3d_topk_loss_fwd_timed(const float* logits, int64_t stride_n, i
     return rc;
 }
 
-extern "C" int ru3d_topk_loss_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
-                                  const void* labels, int label_dtype, int n, int64_t v, int num_classes, int with_dice,
-                                  const float* ce, const void* state, const float* grad_out, void* dlogits,
-                                  int dlogits_dtype, void* stream) {
+extern "C" int ru3d_topk_loss_ignore_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
+                                         const void* labels, int label_dtype, int n, int64_t v, int num_classes,
+                                         int has_ignore, int ignore_label, int with_dice, const float* ce,
+                                         const void* state, const float* grad_out, void* dlogits, int dlogits_dtype,
+                                         void* stream) {
     Ru3dDeviceGuard dev_guard(stream);
     int rc = loss_view_check("topk_loss_bwd", logits && labels && ce && state && dlogits, n > 0 && v > 0, label_dtype,
                              num_classes, 2);
     if (rc) return rc;
+    rc = loss_ignore_check("topk_loss_bwd", has_ignore, ignore_label, label_dtype, num_classes);
+    if (rc) return rc;
     RU3D_REQUIRE(dlogits_dtype == RU3D_F32 || dlogits_dtype == RU3D_BF16, "topk_loss_bwd: bad dlogits dtype");
     hipStream_t st = as_stream(stream);
     const int blocks = flat_bwd_blocks((int64_t)n * v, 8192);
-#define CALL(CC, TG)                                                                                                   \
-    hipLaunchKernelGGL((tk_bwd_kernel<CC, TG>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c, stride_v,   \
-                       labels, label_dtype, n, v, with_dice, ce, (const TopKState*)state, grad_out, (TG*)dlogits)
-    RU3D_DISPATCH_C_DZ(2, num_classes, dlogits_dtype, CALL)
+#define CALL(CC, TG, IGN)                                                                                           \
+    hipLaunchKernelGGL((tk_bwd_kernel<CC, TG, IGN>), dim3(blocks), dim3(256), 0, st, logits, stride_n, stride_c,        \
+                       stride_v, labels, label_dtype, n, v, with_dice, ignore_label, ce, (const TopKState*)state, grad_out, \
+                       (TG*)dlogits)
+    RU3D_DISPATCH_C_DZ_IGN(2, num_classes, dlogits_dtype, has_ignore, CALL)
 #undef CALL
     return ru3d_check_launch("topk_loss_bwd");
+}
+
+extern "C" int ru3d_topk_loss_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
+                                  const void* labels, int label_dtype, int n, int64_t v, int num_classes, int with_dice,
+                                  const float* ce, const void* state, const float* grad_out, void* dlogits,
+                                  int dlogits_dtype, void* stream) {
+    return ru3d_topk_loss_ignore_bwd(logits, stride_n, stride_c, stride_v, labels, label_dtype, n, v, num_classes, 0, 0,
+                                     with_dice, ce, state, grad_out, dlogits, dlogits_dtype, stream);
 }

@@ -28,6 +28,11 @@ Beyond the reference: nested or overlapping structures train one sigmoid channel
 `DC_and_topk_loss`: the cross-entropy averaged over the hardest k percent of the batch's voxels, selected on the device
 between the forward and the backward.  `DeepSupervisionLoss` does not take them as a base: top-k under deep supervision
 is not implemented.
+
+Partly annotated cases: `Dice`, `DiceLoss`, `FocalLoss`, `HybirdLoss`, `TopKLoss` and `HybirdTopKLoss` take
+`ignore_label=` (default None: nothing changes), `DeepSupervisionLoss` takes it over from its base.  The loss is then the
+loss of the voxels whose label is not `ignore_label`; those voxels count in no sum, their logits are never read and
+their gradient is exactly 0 (the section "ignore label" below).
 """
 import collections
 import os
@@ -152,6 +157,34 @@ def _flat_strides(x):
     return x.stride(0), x.stride(1), sv
 
 
+# --------------------------------------------------------------------------- ignore label
+# The loss with an ignore label is the loss applied to the counted voxels alone: gather the voxels whose label is not
+# ignore_label into one (1, C, M) batch and call the plain loss on it.  With S those voxels - over the whole batch - and
+# M = |S|: tp_c, sp_c, sg_c run over S only (an ignored voxel adds to no sum, not to sp either), the Tversky formula is
+# unchanged; focal_c = C * (sum over S of -(1-p_c)^gamma g_c log p_c) / max(M, 1); d loss / d logits is exactly 0.0 at an
+# ignored voxel, whose logits influence nothing (they may be NaN or Inf: padding).  M = 0 gives dice_c = 1: DiceLoss,
+# FocalLoss, HybirdLoss 0 and Dice sum w, gradient all zeros.  A label outside [0, C) that is not the ignore label is a
+# bad label as ever.  Deep supervision: a level's voxel is ignored iff the label it reads is, and every level divides by
+# its own max(M_l, 1).  Top-k follows nnU-Net (ignore_index in the cross-entropy, then top-k over ALL voxels): an ignored
+# voxel has ce = 0 and takes part in the selection like any voxel whose cross-entropy is 0; K = max(1, int(N V k / 100))
+# stays relative to all voxels - a K relative to M would have to be computed on the device, which is not implemented.
+def _checked_softmax_ignore(ignore_label, c, target):
+    """The ignore label of one call as an int (None: none), or ValueError - before anything is launched."""
+    if ignore_label is None:
+        return None
+    ig = int(ignore_label)
+    if c == 1:
+        raise ValueError("ignore_label: not with C == 1 (the sigmoid form); GroupHybirdLoss is the single-channel loss "
+                         "with an ignore label")
+    if 0 <= ig < c:
+        raise ValueError("ignore_label %d lies inside the class range [0, %d)" % (ig, c))
+    if target.dtype == torch.uint8 and not 0 <= ig <= 255:
+        raise ValueError("ignore_label %d cannot occur in uint8 labels" % ig)
+    if not -2 ** 31 <= ig < 2 ** 31:
+        raise ValueError("ignore_label %d is no int32 value" % ig)
+    return ig
+
+
 def _view(x, st, lab, lab_code):
     """How every entry point begins: logits, stride_n, stride_c, stride_v, labels, label_dtype."""
     return ptr(x), st[0], st[1], st[2], ptr(lab), lab_code
@@ -161,11 +194,12 @@ class _Operands:
     """What _loss_operands prepares.  x, st: the float32 logits and their flat strides (tuples of them, one per level,
     when a list of logits came in, and no view then); checked: the labels were range-checked before the launch.  A ctx
     keeps x and lab by save_for_backward and meta() beside them; its backward makes the _view of those again."""
-    __slots__ = ("x", "lab", "st", "lab_code", "n", "c", "v", "checked", "view")
+    __slots__ = ("x", "lab", "st", "lab_code", "n", "c", "v", "checked", "view", "ignore")
 
-    def __init__(self, x, lab, st, lab_code, n, c, v, checked):
+    def __init__(self, x, lab, st, lab_code, n, c, v, checked, ignore=None):
         self.x, self.lab, self.st, self.lab_code = x, lab, st, lab_code
         self.n, self.c, self.v, self.checked = n, c, v, checked
+        self.ignore = ignore      # the call's checked ignore label (None: the plain entry points)
         self.view = None if isinstance(x, tuple) else _view(x, st, lab, lab_code)
 
     def meta(self):
@@ -193,12 +227,13 @@ def _label_operand(target):
     return lab, (N.LABEL_U8 if lab.dtype == torch.uint8 else N.LABEL_I64)
 
 
-def _operand_parts(input, target, check_labels, one_hot):
+def _operand_parts(input, target, check_labels, one_hot, ignore=None):
     """What every fused loss does to its operands before it launches: float32 logits with a single spatial stride,
     contiguous int64 / uint8 labels, and the blocking label check where one is asked for.  input: one (N, C, d1, ..., dn)
     tensor, or - deep supervision - the list of the levels' tensors, finest first: the labels belong to the first, and x
     and st come back as tuples.  one_hot=False (the group losses): the labels are no class indices of the C channels, so
-    neither that check nor the C == 1 rule applies; check_labels then says that the caller has checked them itself."""
+    neither that check nor the C == 1 rule applies; check_labels then says that the caller has checked them itself.
+    ignore: the blocking check skips this value, as _GroupLossFn's does."""
     many = isinstance(input, (list, tuple))
     first = input[0] if many else input
     N.require_device(first, "loss input")
@@ -220,14 +255,20 @@ def _operand_parts(input, target, check_labels, one_hot):
     checked = bool(check_labels or (one_hot and c == 1))
     if one_hot and checked:
         # reference: F.one_hot(target, C) raises for labels >= C (always hit by C == 1 with labels {0,1})
-        if lab.numel() and (int(lab.max()) >= c or int(lab.min()) < 0):
+        seen = lab if ignore is None else lab[lab != ignore]
+        if seen.numel() and (int(seen.max()) >= c or int(seen.min()) < 0):
             raise RuntimeError(_BAD_LABELS)
     return x, lab, st, lab_code, n, c, v, checked
 
 
-def _loss_operands(input, target, check_labels, one_hot=True):
+def _loss_operands(input, target, check_labels, one_hot=True, ignore=None):
     """_operand_parts as the object the shared helpers take."""
-    return _Operands(*_operand_parts(input, target, check_labels, one_hot))
+    return _Operands(*_operand_parts(input, target, check_labels, one_hot, ignore), ignore)
+
+
+def _ignore_args(ignore):
+    """(has_ignore, ignore_label) as the ..._ignore_... entry points take them."""
+    return 1, ignore
 
 
 def _weight_array(weight_v, c):
@@ -297,54 +338,71 @@ def _hybird_forward(ops, kind, gamma, weight_v, alpha, beta, smooth):
     """ru3d_loss_fwd of `kind` on prepared operands -> (state, 0-dim loss)."""
     state, out, ws, wv = _forward_scaffold(ops.x.device, N.lib.ru3d_loss_state_bytes(ops.c),
                                            N.lib.ru3d_loss_workspace_bytes(ops.n, ops.v, ops.c), weight_v, ops.c)
-    check(N.lib.ru3d_loss_fwd(*ops.view, ops.n, ops.v, ops.c, kind, float(gamma), wv, float(alpha),
-                              float(beta), float(smooth), ptr(state), ptr(out), ptr(ws), ws.numel(), stream()),
-          "loss_fwd")
+    if ops.ignore is None:
+        check(N.lib.ru3d_loss_fwd(*ops.view, ops.n, ops.v, ops.c, kind, float(gamma), wv, float(alpha),
+                                  float(beta), float(smooth), ptr(state), ptr(out), ptr(ws), ws.numel(), stream()),
+              "loss_fwd")
+    else:
+        check(N.lib.ru3d_loss_ignore_fwd(*ops.view, ops.n, ops.v, ops.c, *_ignore_args(ops.ignore), kind, float(gamma),
+                                         wv, float(alpha), float(beta), float(smooth), ptr(state), ptr(out), ptr(ws),
+                                         ws.numel(), stream()), "loss_fwd")
     return state, out
 
 
-def _hybird_backward(view, n, v, c, gamma, state, g, dz):
+def _hybird_backward(view, n, v, c, gamma, state, g, dz, ignore=None):
     """ru3d_loss_bwd: dz = g * d loss / d logits from the state a _hybird_forward left."""
-    check(N.lib.ru3d_loss_bwd(*view, n, v, c, gamma, ptr(state), ptr(g), ptr(dz), N.F32, stream()), "loss_bwd")
+    if ignore is None:
+        check(N.lib.ru3d_loss_bwd(*view, n, v, c, gamma, ptr(state), ptr(g), ptr(dz), N.F32, stream()), "loss_bwd")
+    else:
+        check(N.lib.ru3d_loss_ignore_bwd(*view, n, v, c, *_ignore_args(ignore), gamma, ptr(state), ptr(g), ptr(dz),
+                                         N.F32, stream()), "loss_bwd")
 
 
 class _FusedLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, input, target, kind, gamma, weight_v, alpha, beta, smooth, check_labels):
-        ops = _loss_operands(input, target, check_labels)
+    def forward(ctx, input, target, kind, gamma, weight_v, alpha, beta, smooth, check_labels, ignore=None):
+        ops = _loss_operands(input, target, check_labels, ignore=ignore)
         state, out = _hybird_forward(ops, kind, gamma, weight_v, alpha, beta, smooth)
         _note_state(ops, state)
         ctx.save_for_backward(ops.x, ops.lab, state)
-        ctx.meta = (ops.meta(), float(gamma), input.dtype)
+        ctx.meta = (ops.meta(), float(gamma), input.dtype, ignore)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         x, lab, state = ctx.saved_tensors
-        (st, lab_code, n, v, c), gamma, in_dtype = ctx.meta
+        (st, lab_code, n, v, c), gamma, in_dtype, ignore = ctx.meta
         g, dz = _backward_prologue(gout, x)
-        _hybird_backward(_view(x, st, lab, lab_code), n, v, c, gamma, state, g, dz)
-        return _backward_epilogue(dz, in_dtype, 8)
+        _hybird_backward(_view(x, st, lab, lab_code), n, v, c, gamma, state, g, dz, ignore)
+        return _backward_epilogue(dz, in_dtype, 9)
 
 
 class _FusedLoss(nn.Module):
     _kind = None
 
+    def _ignore_for(self, input, target):
+        """This module's ignore_label, checked against the C and the label dtype of the call."""
+        ig = getattr(self, "ignore_label", None)
+        if ig is None or input.dim() < 2:
+            return None
+        return _checked_softmax_ignore(ig, input.shape[1], target)
+
     def _call(self, input, target, gamma, weight_v, alpha, beta, smooth):
         return _FusedLossFn.apply(input, target, self._kind, gamma, weight_v, alpha, beta, smooth,
-                                  getattr(self, "check_labels", _CHECK_LABELS))
+                                  getattr(self, "check_labels", _CHECK_LABELS), self._ignore_for(input, target))
 
 
 class Dice(_FusedLoss):
     """Weighted mean Tversky/Dice *score* (a metric: higher is better)."""
     _kind = N.LOSS_DICE
 
-    def __init__(self, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7):
+    def __init__(self, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7, ignore_label=None):
         super().__init__()
         self.weight_v = weight_v
         self.alpha = alpha
         self.beta = beta
         self.smooth = smooth
+        self.ignore_label = ignore_label
 
     def forward(self, input, target):
         return self._call(input, target, 2.0, self.weight_v, self.alpha, self.beta, self.smooth)
@@ -354,13 +412,14 @@ class DiceLoss(_FusedLoss):
     """sum_c w_c (1 - dice_c)."""
     _kind = N.LOSS_DICELOSS
 
-    def __init__(self, weight_c=None, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7):
+    def __init__(self, weight_c=None, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7, ignore_label=None):
         super().__init__()
         self.weight_c = weight_c      # accepted, no effect (reference behaviour)
         self.weight_v = weight_v
         self.alpha = alpha
         self.beta = beta
         self.smooth = smooth
+        self.ignore_label = ignore_label
 
     def forward(self, input, target):
         return self._call(input, target, 2.0, self.weight_v, self.alpha, self.beta, self.smooth)
@@ -370,11 +429,12 @@ class FocalLoss(_FusedLoss):
     """sum_c w_c * C * mean_v(-(1 - p_c)^gamma * onehot_c * log p_c)."""
     _kind = N.LOSS_FOCAL
 
-    def __init__(self, gamma=2, weight_c=None, weight_v=None):
+    def __init__(self, gamma=2, weight_c=None, weight_v=None, ignore_label=None):
         super().__init__()
         self.gamma = gamma
         self.weight_c = weight_c      # accepted, no effect (reference behaviour)
         self.weight_v = weight_v
+        self.ignore_label = ignore_label
 
     def forward(self, input, target):
         return self._call(input, target, self.gamma, self.weight_v, 0.5, 0.5, 1e-7)
@@ -384,7 +444,7 @@ class HybirdLoss(_FusedLoss):
     """sum_c w_c (1 - dice_c + focal_c): the training loss of the nb_train_* scripts."""
     _kind = N.LOSS_HYBIRD
 
-    def __init__(self, gamma=2, weight_c=None, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7):
+    def __init__(self, gamma=2, weight_c=None, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7, ignore_label=None):
         super().__init__()
         self.weight_c = weight_c      # accepted, no effect (reference behaviour)
         self.weight_v = weight_v
@@ -392,6 +452,7 @@ class HybirdLoss(_FusedLoss):
         self.beta = beta
         self.smooth = smooth
         self.gamma = gamma
+        self.ignore_label = ignore_label
 
     def forward(self, input, target):
         return self._call(input, target, self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)
@@ -892,9 +953,19 @@ def main_output(y):
     return y[0] if isinstance(y, (list, tuple)) else y
 
 
-def _region_loss_host(kind, input, target, gamma, weight_v, alpha, beta, smooth):
-    """HybirdLoss / DiceLoss / FocalLoss on host tensors with torch ops, in the logits' dtype: the formulas of the header
-    comment of csrc/loss.hip (what the device path is tested against)."""
+def _counted_operands(z, t, c, ignore_label):
+    """What the host twins do to (n, C, V) logits and (n, V) labels under an ignore label: the checked label, the mask of
+    the counted voxels, and logits and labels with zeros at the ignored voxels (torch.where: whatever those logits hold,
+    NaN included, reaches no value, and their gradient is exactly 0)."""
+    ig = _checked_softmax_ignore(ignore_label, c, t)
+    counted = t != ig
+    return counted, torch.where(counted[:, None], z, torch.zeros((), dtype=z.dtype)), torch.where(counted, t, torch.zeros_like(t))
+
+
+def _region_loss_host(kind, input, target, gamma, weight_v, alpha, beta, smooth, ignore_label=None):
+    """HybirdLoss / DiceLoss / FocalLoss / Dice on host tensors with torch ops, in the logits' dtype: the formulas of the
+    header comment of csrc/loss.hip (what the device path is tested against).  ignore_label: the section "ignore label"
+    above - the sums run over the counted voxels and the focal mean divides by max(M, 1)."""
     n, c = input.shape[0], input.shape[1]
     if tuple(target.shape) != (n,) + tuple(input.shape[2:]):
         raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape), tuple(input.shape)))
@@ -902,22 +973,32 @@ def _region_loss_host(kind, input, target, gamma, weight_v, alpha, beta, smooth)
         raise RuntimeError("weight_v has %d entries for %d classes" % (len(weight_v), c))
     z = input.reshape(n, c, -1)
     t = target.long().reshape(n, -1)
+    counted = None
+    if ignore_label is not None:
+        counted, z, t = _counted_operands(z, target.reshape(n, -1), c, ignore_label)
+        t = t.long()
     if t.numel() and (int(t.max()) >= c or int(t.min()) < 0):
         raise RuntimeError(_BAD_LABELS)
     logp = torch.log_softmax(z, dim=1) if c > 1 else F.logsigmoid(z)
     p = logp.exp()
     g = F.one_hot(t, num_classes=c).movedim(-1, 1).to(z.dtype)
+    voxels = n * z.shape[2]
+    if counted is not None:
+        cm = counted[:, None].to(z.dtype)
+        g, p = g * cm, p * cm       # p is used in the sums only
+        voxels = max(int(counted.sum()), 1)
     w = torch.tensor([1.0] * c if weight_v is None else [float(a) for a in weight_v], dtype=z.dtype)
     w = w / w.abs().sum().clamp_min(1e-12)
     term = torch.zeros(c, dtype=z.dtype)
     if kind != N.LOSS_FOCAL:
         tp, sp, sg = (p * g).sum((0, 2)), p.sum((0, 2)), g.sum((0, 2))
-        term = term + 1.0 - (tp + smooth) / (tp + alpha * (sg - tp) + beta * (sp - tp) + smooth)
-    if kind != N.LOSS_DICELOSS:
+        d = (tp + smooth) / (tp + alpha * (sg - tp) + beta * (sp - tp) + smooth)
+        term = term + (d if kind == N.LOSS_DICE else 1.0 - d)
+    if kind in (N.LOSS_HYBIRD, N.LOSS_FOCAL):
         # only the target class of a voxel contributes: gathered, so that log p = -inf of another class never meets a 0
         lt = logp.gather(1, t[:, None]) if c > 1 else logp
         per_voxel = -((1.0 - lt.exp()) ** gamma) * lt if gamma != 0 else -lt
-        term = term + (g * per_voxel).sum((0, 2)) * c / (n * z.shape[2])
+        term = term + (g * per_voxel).sum((0, 2)) * c / voxels
     return (w * term).sum()
 
 
@@ -953,31 +1034,41 @@ class _DeepSupFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, target, hyper, block, check_labels, *outputs):
-        kind, gamma, weight_v, alpha, beta, smooth = hyper
-        ops = _loss_operands(outputs, target, check_labels)
+        kind, gamma, weight_v, alpha, beta, smooth, ignore = hyper
+        ops = _loss_operands(outputs, target, check_labels, ignore=ignore)
         table = (N.DsLevel * len(outputs))()
         for l, (x, st) in enumerate(zip(ops.x, ops.st)):
             table[l] = N.DsLevel(x.data_ptr(), *st, *x.shape[2:], l)
         n, c, full = ops.n, ops.c, tuple(outputs[0].shape[2:])
         state, out, ws, wv = _forward_scaffold(ops.lab.device, N.lib.ru3d_ds_state_bytes(),
                                                N.lib.ru3d_ds_loss_workspace_bytes(table, len(outputs), n), weight_v, c)
-        check(N.lib.ru3d_ds_loss_fwd(table, len(outputs), ptr(ops.lab), ops.lab_code, n, *full, c, kind, float(gamma),
-                                     wv, float(alpha), float(beta), float(smooth), ptr(block), ptr(state), ptr(out),
-                                     ptr(ws), ws.numel(), stream()), "ds_loss_fwd")
+        if ignore is None:
+            check(N.lib.ru3d_ds_loss_fwd(table, len(outputs), ptr(ops.lab), ops.lab_code, n, *full, c, kind, float(gamma),
+                                         wv, float(alpha), float(beta), float(smooth), ptr(block), ptr(state), ptr(out),
+                                         ptr(ws), ws.numel(), stream()), "ds_loss_fwd")
+        else:
+            check(N.lib.ru3d_ds_loss_ignore_fwd(table, len(outputs), ptr(ops.lab), ops.lab_code, n, *full, c,
+                                                *_ignore_args(ignore), kind, float(gamma), wv, float(alpha), float(beta),
+                                                float(smooth), ptr(block), ptr(state), ptr(out), ptr(ws), ws.numel(),
+                                                stream()), "ds_loss_fwd")
         _note_state(ops, state, offset=_DS_BAD_OFF[0])
         ctx.save_for_backward(ops.lab, state, *ops.x)
-        ctx.meta = (table, ops.lab_code, n, full, c, float(gamma), [x.dtype for x in outputs])
+        ctx.meta = (table, ops.lab_code, n, full, c, float(gamma), [x.dtype for x in outputs], ignore)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         lab, state = ctx.saved_tensors[:2]
         xs = ctx.saved_tensors[2:]
-        table, lab_code, n, full, c, gamma, in_dtypes = ctx.meta
+        table, lab_code, n, full, c, gamma, in_dtypes, ignore = ctx.meta
         g, dzs = _upstream(gout, lab.device), [_empty_grad(x) for x in xs]
         dptr = (N.ctypes.c_void_p * len(dzs))(*[dz.data_ptr() for dz in dzs])
-        check(N.lib.ru3d_ds_loss_bwd(table, dptr, len(xs), ptr(lab), lab_code, n, *full, c, gamma, ptr(state), ptr(g),
-                                     stream()), "ds_loss_bwd")
+        if ignore is None:
+            check(N.lib.ru3d_ds_loss_bwd(table, dptr, len(xs), ptr(lab), lab_code, n, *full, c, gamma, ptr(state), ptr(g),
+                                         stream()), "ds_loss_bwd")
+        else:
+            check(N.lib.ru3d_ds_loss_ignore_bwd(table, dptr, len(xs), ptr(lab), lab_code, n, *full, c,
+                                                *_ignore_args(ignore), gamma, ptr(state), ptr(g), stream()), "ds_loss_bwd")
         return (None, None, None, None) + tuple(_backward_epilogue(dz, dt) for dz, dt in zip(dzs, in_dtypes))
 
 
@@ -988,8 +1079,9 @@ assert _DS_BAD_OFF[0] >= _BAD_OFF[0]
 class DeepSupervisionLoss(_FusedLoss):
     """sum_l w_l base(outputs[l], downsample_labels(target, l)) over the list a deep-supervision net returns in training
     mode (finest first; level l has the extents ceil(full / 2**l)), against the full-resolution labels.  `base` is a
-    HybirdLoss, DiceLoss or FocalLoss instance whose hyper-parameters (gamma, weight_v, alpha, beta, smooth) are taken
-    over when this module is built.  weights: one per level (default deep_supervision_weights(len(outputs))).  A single
+    HybirdLoss, DiceLoss or FocalLoss instance whose hyper-parameters (gamma, weight_v, alpha, beta, smooth, ignore_label)
+    are taken over when this module is built; with an ignore label a level's voxel is ignored iff the label it reads is
+    the ignore label, and every level divides its focal sum by its own max(M_l, 1).  weights: one per level (default deep_supervision_weights(len(outputs))).  A single
     tensor instead of a list is one level with weight 1 - the plain base loss - so the same criterion object serves
     validation in eval mode.
 
@@ -1008,6 +1100,7 @@ class DeepSupervisionLoss(_FusedLoss):
         self.alpha = getattr(base, "alpha", 0.5)
         self.beta = getattr(base, "beta", 0.5)
         self.smooth = getattr(base, "smooth", 1e-7)
+        self.ignore_label = getattr(base, "ignore_label", None)
         if hasattr(base, "check_labels"):
             self.check_labels = base.check_labels
         self._weights = None
@@ -1074,12 +1167,13 @@ class DeepSupervisionLoss(_FusedLoss):
         if not outputs[0].is_cuda:
             ws = self._weights_for(levels)
             per = [_region_loss_host(self._kind, x, downsample_labels(target, l), self.gamma, self.weight_v, self.alpha,
-                                     self.beta, self.smooth) for l, x in enumerate(outputs)]
+                                     self.beta, self.smooth, self.ignore_label) for l, x in enumerate(outputs)]
             self._last = (torch.cat([torch.zeros(N.DS_MAX_LEVELS)] + [v.detach().float().reshape(1) for v in per]), levels)
             return sum(w * v for w, v in zip(ws, per))
         block = self._block(outputs[0].device, levels)
         self._last = (block, levels)
-        hyper = (self._kind, self.gamma, self.weight_v, self.alpha, self.beta, self.smooth)
+        hyper = (self._kind, self.gamma, self.weight_v, self.alpha, self.beta, self.smooth,
+                 self._ignore_for(outputs[0], target))
         return _DeepSupFn.apply(target, hyper, block, getattr(self, "check_labels", _CHECK_LABELS), *outputs)
 
 
@@ -1341,18 +1435,26 @@ def _topk_checks(input, weight_v):
         raise ValueError("weight_v has %d entries for %d classes" % (len(weight_v), c))
 
 
-def _topk_loss_host(input, target, k, with_dice=False, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7, ce_weight=1.0):
+def _topk_loss_host(input, target, k, with_dice=False, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7, ce_weight=1.0,
+                    ignore_label=None):
     """The definitions above on host tensors with torch ops, differentiable, in the logits' dtype, the tie rule included:
-    the twin the kernels are held to."""
+    the twin the kernels are held to.  ignore_label: an ignored voxel has ce = 0 and is selected like any voxel whose
+    cross-entropy is 0; K counts all voxels."""
     _topk_checks(input, weight_v)
     n, c = input.shape[0], input.shape[1]
     if tuple(target.shape) != (n,) + tuple(input.shape[2:]):
         raise N.Ru3dError("loss: target shape %s does not match input %s" % (tuple(target.shape), tuple(input.shape)))
     z = input.reshape(n, c, -1)
     t = target.long().reshape(n, -1)
+    counted = None
+    if ignore_label is not None:
+        counted, z, t = _counted_operands(z, target.reshape(n, -1), c, ignore_label)
+        t = t.long()
     if t.numel() and (int(t.max()) >= c or int(t.min()) < 0):
         raise RuntimeError(_BAD_LABELS)
     ce = -torch.log_softmax(z, dim=1).gather(1, t[:, None]).reshape(-1)
+    if counted is not None:
+        ce = torch.where(counted.reshape(-1), ce, torch.zeros((), dtype=ce.dtype))
     kk = topk_count(ce.numel(), _checked_k(k))
     held = ce.detach()
     tau = torch.topk(held, kk).values[-1]
@@ -1361,36 +1463,46 @@ def _topk_loss_host(input, target, k, with_dice=False, weight_v=None, alpha=0.5,
     s = above.to(ce.dtype) + tied.to(ce.dtype) * share
     value = (s * ce).sum() / kk * ce_weight
     if with_dice:
-        value = value + _region_loss_host(N.LOSS_DICELOSS, input, target, 2.0, weight_v, alpha, beta, smooth)
+        value = value + _region_loss_host(N.LOSS_DICELOSS, input, target, 2.0, weight_v, alpha, beta, smooth,
+                                          ignore_label)
     return value
 
 
 class _TopKLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, input, target, kk, with_dice, weight_v, alpha, beta, smooth, ce_weight, check_labels):
-        ops = _loss_operands(input, target, check_labels)
+    def forward(ctx, input, target, kk, with_dice, weight_v, alpha, beta, smooth, ce_weight, check_labels, ignore=None):
+        ops = _loss_operands(input, target, check_labels, ignore=ignore)
         n, v, c = ops.n, ops.v, ops.c
         state, out, ws, wv = _forward_scaffold(ops.x.device, N.lib.ru3d_topk_loss_state_bytes(),
                                                N.lib.ru3d_topk_loss_workspace_bytes(n, v, c), weight_v, c)
         # the backward compares these stored values with tau: a tensor of this call, not a slice of the shared workspace,
         # which other calls reuse between a forward and its backward
         ce = torch.empty(n * v, dtype=torch.float32, device=ops.x.device)
-        check(N.lib.ru3d_topk_loss_fwd(*ops.view, n, v, c, kk, int(with_dice), wv, float(alpha),
-                                       float(beta), float(smooth), float(ce_weight), ptr(ce), ptr(state), ptr(out),
-                                       ptr(ws), ws.numel(), stream()), "topk_loss_fwd")
+        if ignore is None:
+            check(N.lib.ru3d_topk_loss_fwd(*ops.view, n, v, c, kk, int(with_dice), wv, float(alpha),
+                                           float(beta), float(smooth), float(ce_weight), ptr(ce), ptr(state), ptr(out),
+                                           ptr(ws), ws.numel(), stream()), "topk_loss_fwd")
+        else:
+            check(N.lib.ru3d_topk_loss_ignore_fwd(*ops.view, n, v, c, *_ignore_args(ignore), kk, int(with_dice), wv,
+                                                  float(alpha), float(beta), float(smooth), float(ce_weight), ptr(ce),
+                                                  ptr(state), ptr(out), ptr(ws), ws.numel(), stream()), "topk_loss_fwd")
         _note_state(ops, state)
         ctx.save_for_backward(ops.x, ops.lab, ce, state)
-        ctx.meta = (ops.meta(), int(with_dice), input.dtype)
+        ctx.meta = (ops.meta(), int(with_dice), input.dtype, ignore)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         x, lab, ce, state = ctx.saved_tensors
-        (st, lab_code, n, v, c), with_dice, in_dtype = ctx.meta
+        (st, lab_code, n, v, c), with_dice, in_dtype, ignore = ctx.meta
         g, dz = _backward_prologue(gout, x)
-        check(N.lib.ru3d_topk_loss_bwd(*_view(x, st, lab, lab_code), n, v, c, with_dice, ptr(ce), ptr(state),
-                                       ptr(g), ptr(dz), N.F32, stream()), "topk_loss_bwd")
-        return _backward_epilogue(dz, in_dtype, 9)
+        if ignore is None:
+            check(N.lib.ru3d_topk_loss_bwd(*_view(x, st, lab, lab_code), n, v, c, with_dice, ptr(ce), ptr(state),
+                                           ptr(g), ptr(dz), N.F32, stream()), "topk_loss_bwd")
+        else:
+            check(N.lib.ru3d_topk_loss_ignore_bwd(*_view(x, st, lab, lab_code), n, v, c, *_ignore_args(ignore), with_dice,
+                                                  ptr(ce), ptr(state), ptr(g), ptr(dz), N.F32, stream()), "topk_loss_bwd")
+        return _backward_epilogue(dz, in_dtype, 10)
 
 
 class _TopKLoss(_FusedLoss):
@@ -1399,13 +1511,15 @@ class _TopKLoss(_FusedLoss):
 
     def _call_topk(self, input, target, weight_v, alpha, beta, smooth, ce_weight):
         _topk_checks(input, weight_v)
+        ignore = self._ignore_for(input, target)
         if not input.is_cuda:
-            return _topk_loss_host(input, target, self.k, self._with_dice, weight_v, alpha, beta, smooth, ce_weight)
+            return _topk_loss_host(input, target, self.k, self._with_dice, weight_v, alpha, beta, smooth, ce_weight,
+                                   ignore)
         voxels = input.shape[0]
         for s in input.shape[2:]:
             voxels *= s
         return _TopKLossFn.apply(input, target, topk_count(voxels, self.k), self._with_dice, weight_v, alpha, beta,
-                                 smooth, ce_weight, getattr(self, "check_labels", _CHECK_LABELS))
+                                 smooth, ce_weight, getattr(self, "check_labels", _CHECK_LABELS), ignore)
 
 
 class TopKLoss(_TopKLoss):
@@ -1414,11 +1528,15 @@ class TopKLoss(_TopKLoss):
     tied at the threshold share the weight that is left equally (the section comment above).  k is fixed at construction,
     0 < k <= 100; K is a launch argument of a captured step (graph.GraphedTrainStep), so another k - or another batch
     shape - means a recapture.  C >= 2.  HIP tensors run the kernels of csrc/topk.hip (no sort, no host round trip
-    between the forward and the backward), host tensors the torch twin of the definitions."""
+    between the forward and the backward), host tensors the torch twin of the definitions.  ignore_label (nnU-Net's
+    ignore_index rule): an ignored voxel has ce = 0, takes part in the selection like any voxel whose cross-entropy is 0
+    and gets a zero gradient; K stays relative to ALL N * V voxels - a K relative to the counted voxels would have to be
+    computed on the device and is not implemented."""
 
-    def __init__(self, k=10):
+    def __init__(self, k=10, ignore_label=None):
         super().__init__()
         self.k = _checked_k(k)
+        self.ignore_label = ignore_label
 
     def forward(self, input, target):
         return self._call_topk(input, target, None, 0.5, 0.5, 1e-7, 1.0)
@@ -1428,11 +1546,14 @@ class HybirdTopKLoss(_TopKLoss):
     """sum_c w_c (1 - dice_c) + ce_weight * topk: DiceLoss(weight_v, alpha, beta, smooth) plus TopKLoss(k), nnU-Net's
     DC_and_topk_loss, in one forward pass over logits and labels and one backward pass.  k is fixed at construction,
     0 < k <= 100; K = max(1, int(N * V * k / 100)) is a launch argument of a captured step, so another k - or another
-    batch shape - means a recapture.  C >= 2.  HIP tensors run the kernels of csrc/topk.hip, host tensors the torch twin."""
+    batch shape - means a recapture.  C >= 2.  HIP tensors run the kernels of csrc/topk.hip, host tensors the torch twin.
+    ignore_label: as TopKLoss's for the cross-entropy leg (K relative to all voxels; a K relative to the counted voxels
+    is not implemented), and the Dice leg sums over the counted voxels only."""
     _with_dice = True
 
-    def __init__(self, k=10, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7, ce_weight=1.0):
+    def __init__(self, k=10, weight_v=None, alpha=0.5, beta=0.5, smooth=1e-7, ce_weight=1.0, ignore_label=None):
         super().__init__()
+        self.ignore_label = ignore_label
         self.k = _checked_k(k)
         self.weight_v = weight_v
         self.alpha = alpha

@@ -752,16 +752,45 @@ def _device_bytes(v, device):
     return torch.from_numpy(np.ascontiguousarray(v)).to(device)
 
 
-def _confusion_table(case):
+def _ignore_to_row(label, ig):
+    """(label volume for _device_bytes, count of its ignore voxels, table row that collects them) for an ignore label
+    ig.  A value in 0 .. 31 has its own row; any other is mapped to 255 BEFORE _device_bytes clamps - a negative value
+    must not be clamped to background - and lands in row 32.  The count of a HIP volume stays on the device."""
+    if torch.is_tensor(label):
+        hit = label == ig
+        count = hit.sum()
+        if not 0 <= ig < _EVAL_CLASSES and ig != 255:
+            label = torch.where(hit, torch.full((), 255, dtype=torch.int64, device=label.device), label.long())
+    else:
+        label = np.asarray(label)
+        hit = label == ig
+        count = int(hit.sum())
+        if not 0 <= ig < _EVAL_CLASSES and ig != 255:
+            label = np.where(hit, 255, label.astype(np.int64))
+    return label, count, (ig if 0 <= ig < _EVAL_CLASSES else _EVAL_CLASSES)
+
+
+def _confusion_table(case, ignore_label=None):
     """(int64 numpy table [K, K] with entry [l][p] = voxels of label l predicted as p, highest label present).
     HIP operands: one launch of the confusion kernel (the other operand is uploaded if needed) and one download of the
-    33 x 33 table; numpy operands: one np.bincount."""
+    33 x 33 table; numpy operands: one np.bincount.  ignore_label: voxels whose LABEL has this value count in no cell
+    (numpy: masked before the bincount; HIP: their row is dropped, and their count comes down with the table)."""
     pred, label = case['pred'], case['label']
     if _is_hip(pred) or _is_hip(label):
         import morphology
         device = pred.device if _is_hip(pred) else label.device
+        row = None
+        if ignore_label is not None:
+            label, ignored, row = _ignore_to_row(label, int(ignore_label))
         table = morphology.confusion(_device_bytes(pred, device), _device_bytes(label, device), _EVAL_CLASSES)
-        table = table.cpu().numpy()
+        if row is not None and torch.is_tensor(ignored):      # one download: the table, then the count
+            both = torch.cat([table.reshape(-1), ignored.to(table.device).reshape(1).to(table.dtype)]).cpu().numpy()
+            table, ignored = both[:-1].reshape(tuple(table.shape)).copy(), int(both[-1])
+        else:
+            table = table.cpu().numpy()
+        if row is not None:
+            if row < _EVAL_CLASSES or int(table[row].sum()) <= ignored:      # else: a class above 31 beside the ignored
+                table[row, :] = 0
         present = np.flatnonzero(table.sum(axis=1))
         top = int(present.max()) if present.size else 0
         if top >= _EVAL_CLASSES:
@@ -770,6 +799,11 @@ def _confusion_table(case):
         return table, top
     pred = np.asarray(pred.cpu() if torch.is_tensor(pred) else pred).astype(np.int64).ravel()
     label = np.asarray(label.cpu() if torch.is_tensor(label) else label).astype(np.int64).ravel()
+    if ignore_label is not None:
+        keep = label != int(ignore_label)
+        pred, label = pred[keep], label[keep]
+        if label.size == 0:
+            return np.zeros((1, 1), dtype=np.int64), 0
     top = int(label.max())
     k = max(top, int(pred.max())) + 1
     return np.bincount(label * k + pred, minlength=k * k).reshape(k, k), top
@@ -783,18 +817,24 @@ def _class_counts(table, c):
     return tp, fn, fp, int(table.sum()) - tp - fn - fp
 
 
-def evaluate_case(case):
+def evaluate_case(case, ignore_label=None):
     """trainer.py:348-356: Dice (loss.dice, alpha = beta = 0.5) of every foreground class of label vs pred.  When the
     prediction or the label is a HIP tensor the Dice values come from the integer confusion table of the two volumes
-    (one kernel launch, csrc/morphology.hip) in Python floats."""
+    (one kernel launch, csrc/morphology.hip) in Python floats.  ignore_label: voxels whose label has this value count
+    nowhere - not in tp, fn, fp or tn - and the classes run up to the highest label among the others."""
     if _is_hip(case['pred']) or _is_hip(case['label']):
-        table, top = _confusion_table(case)
+        table, top = _confusion_table(case, ignore_label)
         out = []
         for c in range(1, top + 1):
             tp, fn, fp, _ = _class_counts(table, c)
             out.append((tp + 1e-7) / (tp + 0.5 * fn + 0.5 * fp + 1e-7))
         return out
     out = []
+    if ignore_label is not None:
+        keep = np.asarray(case['label']) != int(ignore_label)
+        case = {'pred': np.asarray(case['pred'])[keep], 'label': np.asarray(case['label'])[keep]}
+        if case['label'].size == 0:
+            return out
     for c in range(int(case['label'].max())):
         p = np.array(case['pred'] == c + 1).astype(np.float32)
         g = np.array(case['label'] == c + 1).astype(np.float32)
@@ -802,11 +842,12 @@ def evaluate_case(case):
     return out
 
 
-def evaluate_metrics(case, smooth=1e-7):
+def evaluate_metrics(case, smooth=1e-7, ignore_label=None):
     """Dice, sensitivity, specificity and accuracy (the formulas of the reference's nb.py:11-25) of every foreground
     class 1 .. label.max(): a list of dicts with the keys dsc / sen / spe / acc.  All four are functions of one table
-    of integer counts - np.bincount on numpy volumes, the confusion kernel when either volume is a HIP tensor."""
-    table, top = _confusion_table(case)
+    of integer counts - np.bincount on numpy volumes, the confusion kernel when either volume is a HIP tensor.
+    ignore_label: voxels whose label has this value count in no cell of that table."""
+    table, top = _confusion_table(case, ignore_label)
     out = []
     for c in range(1, top + 1):
         tp, fn, fp, tn = _class_counts(table, c)

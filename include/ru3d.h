@@ -340,6 +340,37 @@ int ru3d_loss_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64
 int ru3d_loss_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
                   int label_dtype, int n, int64_t v, int num_classes, float gamma, const void* state,
                   const float* grad_out, void* dlogits, int dlogits_dtype, void* stream);
+/* Ignore label of the softmax losses: train on partly annotated cases.  ru3d_loss_ignore_fwd / _bwd,
+ * ru3d_ds_loss_ignore_fwd / _bwd and ru3d_topk_loss_ignore_fwd / _bwd are their namesakes with (has_ignore, ignore_label)
+ * behind num_classes, as ru3d_group_loss_fwd takes them; the plain entry points are calls of these with has_ignore = 0,
+ * which launch the same kernels on the same arithmetic as before.  State sizes, workspace sizes and the bad-label offset
+ * functions are shared.  has_ignore != 0 selects kernels instantiated for it (no run-time branch in the plain ones).
+ * The loss with an ignore label is the loss of the counted voxels alone.  Let S be the voxels with
+ * t_v != ignore_label - over the whole batch, as all sums of these losses are - and M = |S|:
+ *   tp_c, sp_c, sg_c run over S only (an ignored voxel adds to no sum, not to sp either); the Tversky formula is unchanged.
+ *   focal_c = C * (sum over S of -(1-p_c)^gamma g_c log p_c) / max(M, 1): the "C * mean over all rows" of the rows that
+ *     remain.  M is sum_c sg_c, float64 sums of exact small integers: the state keeps its layout.
+ *   d loss / d logits is exactly 0.0 at every ignored voxel, in every class channel: the backward writes these zeros.
+ *   The label is loaded first and an ignored voxel's logits are never read: NaN or Inf there leaves the loss finite and
+ *     every other gradient unchanged.
+ *   M = 0 gives dice_c = (0 + s) / (0 + s) = 1: DiceLoss 0, FocalLoss 0, HybirdLoss 0, Dice sum w; gradient all zeros.
+ *   A label outside [0, C) that is not the ignore label is a bad label as before: counted, loss NaN.
+ *   Deep supervision: a level's voxel is ignored iff the label it reads is the ignore label; every level has its own
+ *     M_l and its own max(M_l, 1).
+ *   Top-k (nnU-Net's ignore_index rule): an ignored voxel has ce = 0 and takes part in the selection like any voxel whose
+ *     cross-entropy is 0; K stays the caller's launch argument, relative to all n * v voxels; the ignored voxels get a zero
+ *     gradient whatever share the tie rule gives to voxels at ce == tau == 0; the Dice leg follows the rule above.
+ * Refused before any launch, like every argument error: an ignore_label inside [0, C); C == 1 (the sigmoid form has the
+ * all-ones one-hot quirk; the group loss is the single-channel loss with an ignore label); uint8 labels with an
+ * ignore_label outside 0 .. 255.  With int64 labels any int value outside [0, C) is legal, e.g. -1 or 255. */
+int ru3d_loss_ignore_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
+                         int label_dtype, int n, int64_t v, int num_classes, int has_ignore, int ignore_label, int kind,
+                         float gamma, const float* weight_v, float alpha, float beta, float smooth, void* state,
+                         float* loss_out, void* ws, size_t ws_bytes, void* stream);
+int ru3d_loss_ignore_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
+                         int label_dtype, int n, int64_t v, int num_classes, int has_ignore, int ignore_label,
+                         float gamma, const void* state, const float* grad_out, void* dlogits, int dlogits_dtype,
+                         void* stream);
 /* functional `dice` of loss.py:32-48 on two flat fp32 vectors (used by trainer.evaluate_case). */
 int ru3d_tversky(const float* p, const float* g, int64_t count, float alpha, float beta, float smooth,
                  float* out, void* ws, size_t ws_bytes, void* stream);
@@ -451,6 +482,16 @@ int ru3d_topk_loss_fwd_timed(const float* logits, int64_t stride_n, int64_t stri
 int ru3d_topk_loss_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v, const void* labels,
                        int label_dtype, int n, int64_t v, int num_classes, int with_dice, const float* ce,
                        const void* state, const float* grad_out, void* dlogits, int dlogits_dtype, void* stream);
+/* the same with an ignore label (semantics: the comment of ru3d_loss_ignore_fwd) */
+int ru3d_topk_loss_ignore_fwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
+                              const void* labels, int label_dtype, int n, int64_t v, int num_classes, int has_ignore,
+                              int ignore_label, int64_t K, int with_dice, const float* weight_v, float alpha, float beta,
+                              float smooth, float ce_weight, float* ce, void* state, float* loss_out, void* ws,
+                              size_t ws_bytes, void* stream);
+int ru3d_topk_loss_ignore_bwd(const float* logits, int64_t stride_n, int64_t stride_c, int64_t stride_v,
+                              const void* labels, int label_dtype, int n, int64_t v, int num_classes, int has_ignore,
+                              int ignore_label, int with_dice, const float* ce, const void* state, const float* grad_out,
+                              void* dlogits, int dlogits_dtype, void* stream);
 /* accumulate_groups: signature and contract of ru3d_predict_accumulate_weighted (flip, three device tables that may all
  * be NULL, one thread per window voxel, sums in launch order) with an independent sigmoid per channel in place of the
  * softmax; f32 or bf16 logits of 1..8 channels.  With flip 0 and NULL tables it serves the reference placement too. */
@@ -763,6 +804,14 @@ int ru3d_ds_loss_fwd(const ru3d_ds_level* levels, int num_levels, const void* la
 int ru3d_ds_loss_bwd(const ru3d_ds_level* levels, void* const* dlogits, int num_levels, const void* labels,
                      int label_dtype, int n, int D, int H, int W, int num_classes, float gamma, const void* state,
                      const float* grad_out, void* stream);
+/* the same with an ignore label (semantics: the comment of ru3d_loss_ignore_fwd) */
+int ru3d_ds_loss_ignore_fwd(const ru3d_ds_level* levels, int num_levels, const void* labels, int label_dtype, int n, int D,
+                            int H, int W, int num_classes, int has_ignore, int ignore_label, int kind, float gamma,
+                            const float* weight_v, float alpha, float beta, float smooth, float* block, void* state,
+                            float* loss_out, void* ws, size_t ws_bytes, void* stream);
+int ru3d_ds_loss_ignore_bwd(const ru3d_ds_level* levels, void* const* dlogits, int num_levels, const void* labels,
+                            int label_dtype, int n, int D, int H, int W, int num_classes, int has_ignore,
+                            int ignore_label, float gamma, const void* state, const float* grad_out, void* stream);
 
 /* ------------------------------------------------------------------ surface meshes */
 /* The anatomy as closed triangle meshes: the faces between a set voxel and an unset one of a packed mask (the
