@@ -124,6 +124,7 @@ SIGNATURES = {
     "ru3d_unpad_weight_grad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ru3d_conv3d_workspace_bytes": (_sz, [_P, _P, _i, _i, _i]),
     "ru3d_conv3d_fwd": (_i, [_P, _vp, _vp, _P, _P, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "ru3d_conv3d_plan_names": (_i, [_P, _P, _i, _i, _i, _i, ctypes.c_char_p, _sz]),
     "ru3d_conv3d_fwd_in_workspace_bytes": (_sz, [_P, _P, _i, _i, _i]),
     "ru3d_conv3d_fwd_in": (_i, [_P, _vp, _vp, _P, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _f, _vp]),
     "ru3d_conv3d_fwd_in_lrelu_workspace_bytes": (_sz, [_P, _P, _i, _i, _i]),

@@ -267,6 +267,30 @@ extern "C" size_t ru3d_conv3d_workspace_bytes(const ru3d_tensor* x, const ru3d_t
     return s1_plan_for(fwd_geom(x, y, k, stride), dtype).ws_bytes;
 }
 
+// Which kernels a conv of this geometry runs on, in the order of preference, joined by '|': run_conv's routing for dense
+// tensors of one dtype without a residual, then the MFMA family's plan.  Pure host code; no pointer is dereferenced.
+extern "C" int ru3d_conv3d_plan_names(const ru3d_tensor* x, const ru3d_tensor* y, int k, int stride, int transposed,
+                                      int dtype, char* buf, size_t cap) {
+    RU3D_FWD_F16(dtype, ru3d_conv3d_plan_names_f16(x, y, k, stride, transposed, dtype, buf, cap));
+    RU3D_REQUIRE(tensor_ok(x) && tensor_ok(y) && x->n == y->n && buf && cap > 0, "conv3d_plan_names: bad argument");
+    RU3D_REQUIRE((k == 1 || k == 3) && (stride == 1 || stride == 2) && dtype_ok(dtype) && (!transposed || stride == 2),
+                 "conv3d_plan_names: k=%d stride=%d transposed=%d dtype=%d unsupported", k, stride, transposed, dtype);
+    const ConvGeom g = conv_geom(x, y, nullptr, k, stride, transposed ? 1 : 0);
+    std::string s;
+    if (stem_fwd_eligible(g, dtype, dtype, nullptr)) s = "stem";
+    else if (head_fwd_eligible(g, dtype, nullptr) || head_dgrad_eligible(g, dtype, dtype, nullptr)) s = "head";
+    else if (!mfma_conv_eligible(g.Cin, g.Cout, k, dtype, dtype)) s = "generic";
+    else if (const Conv3S1Plan p = conv3_s1_plan(g); p.count) {
+        for (int i = 0; i < p.count; i++) s += std::string(i ? "|" : "") + p.choice[i].name;
+    } else {
+        const ConvDirectPlan d = conv_direct_plan(g);
+        RU3D_REQUIRE(d.family, "%s", d.refusal);
+        s = d.tile ? std::string(d.tile_name) + "|" + d.name : std::string(d.name);
+    }
+    snprintf(buf, cap, "%s", s.c_str());
+    return 0;
+}
+
 extern "C" int ru3d_conv3d_fwd(const ru3d_tensor* x, const void* w_packed, const float* bias, const ru3d_tensor* res,
                                const ru3d_tensor* y, int k, int stride, int dtype, int y_dtype, void* ws,
                                size_t ws_bytes, void* stream) {
@@ -488,20 +512,27 @@ extern "C" int ru3d_skip1x1_in_lrelu_head_fwd(const ru3d_tensor* x, const void* 
 }
 
 // ---- the two stride-2 convs of a pooling ResBlock: forward of both + InstanceNorm sums in one launch (conv_s2.hip, G form)
+// the conditions on the three tensors, then the plan's tile kernel and its launch-time conditions; *g / *p: for the caller
+static bool s2_pair_fwd_ok(const ru3d_tensor* x, const ru3d_tensor* y3, const ru3d_tensor* y1, int dtype, ConvGeom* g,
+                           ConvDirectPlan* p) {
+    if (dtype != RU3D_BF16 || !tensor_ok(x) || !tensor_ok(y3) || !tensor_ok(y1)) return false;
+    if (y3->n != x->n || y3->d != conv_out(x->d, 3, 2) || y3->h != conv_out(x->h, 3, 2) || y3->w != conv_out(x->w, 3, 2)) return false;
+    if (y1->n != y3->n || y1->d != y3->d || y1->h != y3->h || y1->w != y3->w || y1->c != y3->c) return false;
+    *g = fwd_geom(x, y3, 3, 2);
+    *p = conv_direct_plan(*g);
+    return p->tile == S2_TILE_G && conv_direct_tile_ok(*p, *g, x->ptr, nullptr, y3->ptr, y1->ptr, y1->ld);
+}
+
 extern "C" int ru3d_conv3d_s2_pair_fwd_in_supported(const ru3d_tensor* x, const ru3d_tensor* y3, const ru3d_tensor* y1, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_s2_pair_fwd_in_supported_f16(x, y3, y1, dtype));
-    if (dtype != RU3D_BF16 || !tensor_ok(x) || !tensor_ok(y3) || !tensor_ok(y1)) return 0;
-    if (y3->n != x->n || y3->d != conv_out(x->d, 3, 2) || y3->h != conv_out(x->h, 3, 2) || y3->w != conv_out(x->w, 3, 2)) return 0;
-    if (y1->n != y3->n || y1->d != y3->d || y1->h != y3->h || y1->w != y3->w || y1->c != y3->c) return 0;
-    if ((y1->ld % 4) || (int64_t)y1->d * y1->h * y1->w * y1->ld >= (1ll << 30)) return 0;
-    if ((((uintptr_t)x->ptr) % 16) || ((((uintptr_t)y3->ptr) | ((uintptr_t)y1->ptr)) % 8)) return 0;
-    return conv_s2_tile_eligible(fwd_geom(x, y3, 3, 2)) ? 1 : 0;
+    ConvGeom g; ConvDirectPlan p;
+    return s2_pair_fwd_ok(x, y3, y1, dtype, &g, &p) ? 1 : 0;
 }
 
 extern "C" size_t ru3d_conv3d_s2_pair_fwd_in_workspace_bytes(const ru3d_tensor* x, const ru3d_tensor* y3, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_s2_pair_fwd_in_workspace_bytes_f16(x, y3, dtype));
     if (!tensor_ok(x) || !tensor_ok(y3)) return 0;
-    return conv_s2_tile_slab_bytes(fwd_geom(x, y3, 3, 2));
+    return conv_direct_plan(fwd_geom(x, y3, 3, 2)).slab_bytes;
 }
 
 extern "C" int ru3d_conv3d_s2_pair_fwd_in(const ru3d_tensor* x, const void* w3_packed, const float* b3, const ru3d_tensor* y3,
@@ -511,16 +542,13 @@ extern "C" int ru3d_conv3d_s2_pair_fwd_in(const ru3d_tensor* x, const void* w3_p
     RU3D_FWD_F16(dtype, ru3d_conv3d_s2_pair_fwd_in_f16(x, w3_packed, b3, y3, w1_packed, b1, y1, drop_scale, mean, scale, ws, ws_bytes, eps, dtype, stream));
     Ru3dDeviceGuard dev_guard(stream);
     RU3D_REQUIRE(w3_packed && w1_packed && mean && scale && ws, "conv3d_s2_pair_fwd_in: null argument");
-    RU3D_REQUIRE(ru3d_conv3d_s2_pair_fwd_in_supported(x, y3, y1, dtype),
+    ConvGeom g; ConvDirectPlan p;
+    RU3D_REQUIRE(s2_pair_fwd_ok(x, y3, y1, dtype, &g, &p),
                  "conv3d_s2_pair_fwd_in: shapes have no fused kernel (ask ru3d_conv3d_s2_pair_fwd_in_supported first)");
-    const ConvGeom g = fwd_geom(x, y3, 3, 2);
-    const size_t slab = conv_s2_tile_slab_bytes(g);
-    RU3D_REQUIRE(ws_bytes >= slab, "conv3d_s2_pair_fwd_in: workspace too small");
-    int rc = conv_s2_tile_launch(x->ptr, w3_packed, b3, y3->ptr, g, (float*)ws, w1_packed, b1, y1->ptr, y1->ld, as_stream(stream));
+    RU3D_REQUIRE(ws_bytes >= p.slab_bytes, "conv3d_s2_pair_fwd_in: workspace too small");
+    int rc = conv_s2_tile_launch(p, x->ptr, w3_packed, b3, y3->ptr, g, (float*)ws, w1_packed, b1, y1->ptr, y1->ld, as_stream(stream));
     if (rc) return rc;
-    int gx, cb;
-    if (conv_s2_tile_slab_geom(g, &gx, &cb)) return ru3d_fail(-1, "conv3d_s2_pair_fwd_in: no slab geometry");
-    return stats_slab_finalize_launch((const float*)ws, gx, cb, g.N, g.Cout, 1.0 / ((double)g.Do * g.Ho * g.Wo), drop_scale, eps,
+    return stats_slab_finalize_launch((const float*)ws, p.gx, p.cb, g.N, g.Cout, 1.0 / ((double)g.Do * g.Ho * g.Wo), drop_scale, eps,
                                       mean, scale, as_stream(stream));
 }
 
@@ -529,16 +557,22 @@ static ConvGeom s2_dgrad_geom(const ru3d_tensor* dy, const ru3d_tensor* res, con
     return conv_geom(dy, dx, res, 3, 2, 1);
 }
 
+static bool s2_dgrad_pair_ok(const ru3d_tensor* dy, const ru3d_tensor* dy2, const ru3d_tensor* res, const ru3d_tensor* dx,
+                             int dtype, ConvGeom* g, ConvDirectPlan* p) {
+    if (dtype != RU3D_BF16 || !tensor_ok(dy) || !tensor_ok(dy2) || !tensor_ok(dx) || !res_ok(res, dx)) return false;
+    if (dy2->n != dy->n || dy2->d != dy->d || dy2->h != dy->h || dy2->w != dy->w || dy2->c != dy->c) return false;
+    if (dx->n != dy->n || dy->d != conv_out(dx->d, 3, 2) || dy->h != conv_out(dx->h, 3, 2) || dy->w != conv_out(dx->w, 3, 2))
+        return false;
+    *g = s2_dgrad_geom(dy, res, dx);
+    *p = conv_direct_plan(*g);
+    return p->tile == S2_TILE_T && conv_direct_tile_ok(*p, *g, dy->ptr, res ? res->ptr : nullptr, dx->ptr, dy2->ptr, dy2->ld);
+}
+
 extern "C" int ru3d_conv3d_s2_dgrad_pair_supported(const ru3d_tensor* dy, const ru3d_tensor* dy2, const ru3d_tensor* res,
                                                    const ru3d_tensor* dx, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_conv3d_s2_dgrad_pair_supported_f16(dy, dy2, res, dx, dtype));
-    if (dtype != RU3D_BF16 || !tensor_ok(dy) || !tensor_ok(dy2) || !tensor_ok(dx) || !res_ok(res, dx)) return 0;
-    if (dy2->n != dy->n || dy2->d != dy->d || dy2->h != dy->h || dy2->w != dy->w || dy2->c != dy->c) return 0;
-    if (dx->n != dy->n || dy->d != conv_out(dx->d, 3, 2) || dy->h != conv_out(dx->h, 3, 2) || dy->w != conv_out(dx->w, 3, 2))
-        return 0;
-    if ((dy2->ld % 8) || (int64_t)dy2->d * dy2->h * dy2->w * dy2->ld >= (1ll << 30)) return 0;
-    if ((((uintptr_t)dy->ptr) | ((uintptr_t)dy2->ptr) | ((uintptr_t)dx->ptr) | (res ? (uintptr_t)res->ptr : 0)) % 16) return 0;
-    return convt_s2_tile_eligible(s2_dgrad_geom(dy, res, dx)) ? 1 : 0;
+    ConvGeom g; ConvDirectPlan p;
+    return s2_dgrad_pair_ok(dy, dy2, res, dx, dtype, &g, &p) ? 1 : 0;
 }
 
 extern "C" int ru3d_conv3d_s2_dgrad_pair(const ru3d_tensor* dy, const void* w3_packed, const ru3d_tensor* dy2,
@@ -547,10 +581,10 @@ extern "C" int ru3d_conv3d_s2_dgrad_pair(const ru3d_tensor* dy, const void* w3_p
     RU3D_FWD_F16(dtype, ru3d_conv3d_s2_dgrad_pair_f16(dy, w3_packed, dy2, w1_packed, res, dx, dtype, stream));
     Ru3dDeviceGuard dev_guard(stream);
     RU3D_REQUIRE(w3_packed && w1_packed, "conv3d_s2_dgrad_pair: null weight");
-    RU3D_REQUIRE(ru3d_conv3d_s2_dgrad_pair_supported(dy, dy2, res, dx, dtype),
+    ConvGeom g; ConvDirectPlan p;
+    RU3D_REQUIRE(s2_dgrad_pair_ok(dy, dy2, res, dx, dtype, &g, &p),
                  "conv3d_s2_dgrad_pair: shapes have no fused kernel (ask ru3d_conv3d_s2_dgrad_pair_supported first)");
-    const ConvGeom g = s2_dgrad_geom(dy, res, dx);
-    return convt_s2_tile_launch(dy->ptr, w3_packed, nullptr, res ? res->ptr : nullptr, dx->ptr, g, nullptr, dy2->ptr,
+    return convt_s2_tile_launch(p, dy->ptr, w3_packed, nullptr, res ? res->ptr : nullptr, dx->ptr, g, nullptr, dy2->ptr,
                                 dy2->ld, w1_packed, as_stream(stream));
 }
 
@@ -764,20 +798,24 @@ static ConvGeom convt_fwd_geom(const ru3d_tensor* x, const ru3d_tensor* y) {
     return conv_geom(x, y, nullptr, 3, 2, 1, 0, 1);
 }
 
-static bool convt_fwd_in_fused(const ru3d_tensor* x, const ru3d_tensor* y, int dtype) {
-    return dtype == RU3D_BF16 && convt_shapes_ok(x, y) && mfma_conv_eligible(x->c, y->c, 3, dtype, dtype) &&
-           ((((uintptr_t)x->ptr) | ((uintptr_t)y->ptr)) % 16) == 0 && convt_s2_tile_eligible(convt_fwd_geom(x, y));
+// the tile kernel sums the InstanceNorm statistics in its epilogue; *g / *p: the geometry and its plan for the caller
+static bool convt_fwd_in_fused(const ru3d_tensor* x, const ru3d_tensor* y, int dtype, ConvGeom* g, ConvDirectPlan* p) {
+    if (dtype != RU3D_BF16 || !convt_shapes_ok(x, y) || !mfma_conv_eligible(x->c, y->c, 3, dtype, dtype)) return false;
+    *g = convt_fwd_geom(x, y);
+    *p = conv_direct_plan(*g);
+    return p->tile == S2_TILE_T && conv_direct_tile_ok(*p, *g, x->ptr, nullptr, y->ptr);
+}
+
+static size_t convt_fwd_in_ws_bytes(const ru3d_tensor* y, bool fused, const ConvDirectPlan& p) {
+    const size_t need = ru3d_reduce_workspace_bytes(y);
+    return fused && p.slab_bytes > need ? p.slab_bytes : need;
 }
 
 extern "C" size_t ru3d_convtranspose3d_k3s2p1_fwd_in_workspace_bytes(const ru3d_tensor* x, const ru3d_tensor* y, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_convtranspose3d_k3s2p1_fwd_in_workspace_bytes_f16(x, y, dtype));
     if (!tensor_ok(x) || !tensor_ok(y)) return 0;
-    size_t need = ru3d_reduce_workspace_bytes(y);
-    if (convt_fwd_in_fused(x, y, dtype)) {
-        const size_t slab = convt_s2_tile_slab_bytes(convt_fwd_geom(x, y));
-        if (slab > need) need = slab;
-    }
-    return need;
+    ConvGeom g; ConvDirectPlan p;
+    return convt_fwd_in_ws_bytes(y, convt_fwd_in_fused(x, y, dtype, &g, &p), p);
 }
 
 extern "C" int ru3d_convtranspose3d_k3s2p1_fwd_in(const ru3d_tensor* x, const void* w_packed, const float* bias,
@@ -786,15 +824,13 @@ extern "C" int ru3d_convtranspose3d_k3s2p1_fwd_in(const ru3d_tensor* x, const vo
     RU3D_FWD_F16(dtype, ru3d_convtranspose3d_k3s2p1_fwd_in_f16(x, w_packed, bias, y, mean, scale, ws, ws_bytes, eps, dtype, stream));
     Ru3dDeviceGuard dev_guard(stream);
     RU3D_REQUIRE(convt_shapes_ok(x, y) && w_packed && mean && scale && ws, "convtranspose3d_fwd_in: bad argument");
-    RU3D_REQUIRE(ws_bytes >= ru3d_convtranspose3d_k3s2p1_fwd_in_workspace_bytes(x, y, dtype),
-                 "convtranspose3d_fwd_in: workspace too small");
-    if (convt_fwd_in_fused(x, y, dtype)) {
-        const ConvGeom g = convt_fwd_geom(x, y);
-        int rc = convt_s2_tile_launch(x->ptr, w_packed, bias, nullptr, y->ptr, g, (float*)ws, nullptr, 0, nullptr, as_stream(stream));
+    ConvGeom g; ConvDirectPlan p;
+    const bool fused = convt_fwd_in_fused(x, y, dtype, &g, &p);
+    RU3D_REQUIRE(ws_bytes >= convt_fwd_in_ws_bytes(y, fused, p), "convtranspose3d_fwd_in: workspace too small");
+    if (fused) {
+        int rc = convt_s2_tile_launch(p, x->ptr, w_packed, bias, nullptr, y->ptr, g, (float*)ws, nullptr, 0, nullptr, as_stream(stream));
         if (rc) return rc;
-        int gx, cb;
-        if (convt_s2_tile_slab_geom(g, &gx, &cb)) return ru3d_fail(-1, "convtranspose3d_fwd_in: no slab geometry");
-        return stats_slab_finalize_launch((const float*)ws, gx, cb, g.N, g.Cout, 1.0 / ((double)g.Do * g.Ho * g.Wo), nullptr, eps,
+        return stats_slab_finalize_launch((const float*)ws, p.gx, p.cb, g.N, g.Cout, 1.0 / ((double)g.Do * g.Ho * g.Wo), nullptr, eps,
                                           mean, scale, as_stream(stream));
     }
     int rc = ru3d_convtranspose3d_k3s2p1_fwd(x, w_packed, bias, y, dtype, stream);

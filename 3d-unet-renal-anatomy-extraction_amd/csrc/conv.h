@@ -175,18 +175,44 @@ int conv_ws_launch(const void* x, const void* w, float* part, int N, int D, int 
 int conv_slide64_launch(const void* x, const void* w, const float* bias, const void* res, void* y, const ConvGeom& g,
                         const SlidePlan& p, float* stat_slab, hipStream_t st);
 
-// conv_s2.hip (the stride-2 forms of the large levels: LDS-DMA plane ring, producer wave, weights in registers)
-bool convt_s2_tile_eligible(const ConvGeom& g);
-size_t convt_s2_tile_slab_bytes(const ConvGeom& g);
-int convt_s2_tile_slab_geom(const ConvGeom& g, int* gx, int* cb);
-int convt_s2_tile_launch(const void* x, const void* w, const float* bias, const void* res, void* y, const ConvGeom& g,
-                         float* stat_slab, const void* x2, int ldx2, const void* w2, hipStream_t st);
+// conv_direct.hip.  The MFMA forms conv3_s1_plan leaves (count == 0): 3x3x3 stride-2 gather, transposed, 1x1x1.  ONE plan
+// per geometry, made by conv_direct_plan and read by the launcher, the slab queries and the fused entry points with their
+// "supported" predicates.  At most two choices: the LDS-DMA tile kernel of conv_s2.hip where the geometry is eligible
+// (tile != 0; what only a launch knows about it is asked of conv_direct_tile_ok, by the launcher and the predicates
+// alike), then exactly one fallback without launch-time conditions, its template parameters stored as data.
+enum { S2_TILE_T = 1, S2_TILE_G };      // transposed / gather form
+enum { DIRECT_KSPLIT = 1, DIRECT_CONVT_TILE, DIRECT_GATHER, DIRECT_T };
+struct ConvDirectPlan {
+    int tile = 0;             // S2_TILE_*; 0: no tile kernel for this geometry
+    SlidePlan slide = {};     // its decomposition
+    int tile_tw = 0;          // tile width (T form)
+    char tile_name[40] = "";  // what the launch log reports
+    // the tile kernel's statistics slab[(y * gx + workgroup) * 4 + wave][n][cb][2].  Set wherever the decomposition exists,
+    // for a pitch or an extent the kernel refuses too: the workspace queries report it and predate the plan
+    int gx = 0, cb = 0;
+    size_t slab_bytes = 0;
+    int family = 0;           // DIRECT_*; 0: nothing takes this geometry (refusal says why) and nothing is launched
+    const char* refusal = nullptr;
+    int nt = 0;               // 32-cout tiles per workgroup
+    int rd = 0;               // K-split / gather: prefetch depth
+    int td = 0, th = 0, tw = 0;   // DIRECT_CONVT_TILE: the half-resolution tile
+    char name[40] = "";
+};
+ConvDirectPlan conv_direct_plan(const ConvGeom& g);
+// may this launch run the plan's tile kernel?  partner: a fused pair's second gradient (T form) / second output (G form)
+bool conv_direct_tile_ok(const ConvDirectPlan& p, const ConvGeom& g, const void* x, const void* res, const void* y,
+                         const void* partner = nullptr, int ld_partner = 0);
+int conv_direct_launch(const ConvDirectPlan& p, const void* x, const void* w, const float* bias, const void* res, void* y,
+                       const ConvGeom& g, hipStream_t st);
 
-bool conv_s2_tile_eligible(const ConvGeom& g);
-size_t conv_s2_tile_slab_bytes(const ConvGeom& g);
-int conv_s2_tile_slab_geom(const ConvGeom& g, int* gx, int* cb);
-int conv_s2_tile_launch(const void* x, const void* w, const float* bias, void* y, const ConvGeom& g, float* stat_slab,
-                        const void* w2, const float* bias2, void* y2, int ldy2, hipStream_t st);
+// conv_s2.hip (the stride-2 forms of the large levels: LDS-DMA plane ring, producer wave, weights in registers): the tile
+// halves of conv_direct_plan and the launches that read them back.  x2 / ldx2 / w2 and w2 / bias2 / y2 / ldy2: the fused pairs
+bool convt_s2_tile_plan(const ConvGeom& g, ConvDirectPlan* p);
+int convt_s2_tile_launch(const ConvDirectPlan& p, const void* x, const void* w, const float* bias, const void* res, void* y,
+                         const ConvGeom& g, float* stat_slab, const void* x2, int ldx2, const void* w2, hipStream_t st);
+bool conv_s2_tile_plan(const ConvGeom& g, ConvDirectPlan* p);
+int conv_s2_tile_launch(const ConvDirectPlan& p, const void* x, const void* w, const float* bias, void* y, const ConvGeom& g,
+                        float* stat_slab, const void* w2, const float* bias2, void* y2, int ldy2, hipStream_t st);
 
 // fused_skip.hip (decoder ResBlock tail: 1x1x1 skip conv + InstanceNorm apply + sum + LeakyReLU in one pass)
 bool skip1x1_fused_eligible(const ru3d_tensor* x, const ru3d_tensor* y2, const ru3d_tensor* out, int dtype);

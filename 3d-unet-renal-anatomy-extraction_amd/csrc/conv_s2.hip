@@ -745,8 +745,7 @@ __global__ __launch_bounds__(320) void conv3_s2_tile_kernel(S2Args a) {
 // --------------------------------------------------------------------------------------------------- host: T form
 // Work decomposition: units = N x dsplit x ceil(Hi / 4) x ceil(Wi / TW) columns of DL input planes each.
 static bool t_plan(int N, int Di, int Hi, int Wi, int Cin, int Cout, int* tw_out, SlidePlan* out) {
-    static const int mode = ru3d_env_int("RU3D_CONV_S2", 1);
-    if (!mode || Cin != 64 || (Cout % 32) || Cout > 64 || Di < 2) return false;
+    if (Cin != 64 || (Cout % 32) || Cout > 64 || Di < 2) return false;
     const int ny = Cout / 32;
     int64_t best_cost = -1;
     int best_ds = 0, best_tw = 0;
@@ -786,37 +785,26 @@ static bool t_plan(int N, int Di, int Hi, int Wi, int Cin, int Cout, int* tw_out
     return true;
 }
 
-bool convt_s2_tile_eligible(const ConvGeom& g) {
-    SlidePlan sp;
-    int tw;
+// The T half of conv_direct_plan: the decomposition and the slab it implies, then whether the kernel takes the geometry
+bool convt_s2_tile_plan(const ConvGeom& g, ConvDirectPlan* p) {
     if (!(g.transposed && g.k == 3 && g.stride == 2 && g.pad == 1)) return false;
+    if (!t_plan(g.N, g.Di, g.Hi, g.Wi, g.Cin, g.Cout, &p->tile_tw, &p->slide)) return false;
+    p->gx = p->slide.grid; p->cb = 32;
+    p->slab_bytes = (size_t)p->slide.grid * p->slide.ny * 4 * g.N * 32 * 2 * sizeof(float);
     if ((g.ldx % 8) || (g.ldy % 8) || (g.ldr % 8)) return false;
     // 32-bit byte offsets inside a sample, top bit = "outside"
     if ((int64_t)g.Di * g.Hi * g.Wi * g.ldx >= (1ll << 30) || (int64_t)g.Do * g.Ho * g.Wo * g.ldy >= (1ll << 30) ||
         (int64_t)g.Do * g.Ho * g.Wo * g.ldr >= (1ll << 30))
         return false;
     if ((g.Do + 1) / 2 != g.Di || (g.Ho + 1) / 2 != g.Hi || (g.Wo + 1) / 2 != g.Wi) return false;
-    return t_plan(g.N, g.Di, g.Hi, g.Wi, g.Cin, g.Cout, &tw, &sp);
-}
-
-size_t convt_s2_tile_slab_bytes(const ConvGeom& g) {
-    SlidePlan sp;
-    int tw;
-    if (!t_plan(g.N, g.Di, g.Hi, g.Wi, g.Cin, g.Cout, &tw, &sp)) return 0;
-    return (size_t)sp.grid * sp.ny * 4 * g.N * 32 * 2 * sizeof(float);
-}
-
-int convt_s2_tile_slab_geom(const ConvGeom& g, int* gx, int* cb) {
-    SlidePlan sp;
-    int tw;
-    if (!t_plan(g.N, g.Di, g.Hi, g.Wi, g.Cin, g.Cout, &tw, &sp)) return -1;
-    *gx = sp.grid;
-    *cb = 32;
-    return 0;
+    p->tile = S2_TILE_T;
+    snprintf(p->tile_name, sizeof(p->tile_name), "convt3_s2_tile");
+    return true;
 }
 
 template <int CIN, int TW>
-static int t_launch(const S2Args& a, const SlidePlan& p, bool has_res, bool has_stats, bool has_x2, hipStream_t st) {
+static int t_launch(const S2Args& a, const SlidePlan& p, bool has_res, bool has_stats, bool has_x2, hipStream_t st,
+                    const char* name) {
     const dim3 grid(p.grid, p.ny), block(320);
     const size_t lds = t_lds_bytes<CIN, TW>(has_x2);
 #define RU3D_T_LAUNCH(R, S, X)                                                                                    \
@@ -842,22 +830,19 @@ static int t_launch(const S2Args& a, const SlidePlan& p, bool has_res, bool has_
         RU3D_T_LAUNCH(false, false, false);
     }
 #undef RU3D_T_LAUNCH
-    return ru3d_check_launch("convt3_s2_tile");
+    return ru3d_check_launch(name);
 }
 
 // x2 / w2: the 1x1x1 stride-2 partner's gradient operand (on the input grid, Cin channels, pitch ldx2) and its packed
 // input-gradient weight; stat_slab: InstanceNorm sums of the output (no residual then)
-int convt_s2_tile_launch(const void* x, const void* w, const float* bias, const void* res, void* y, const ConvGeom& g,
-                         float* stat_slab, const void* x2, int ldx2, const void* w2, hipStream_t st) {
-    SlidePlan p;
-    int tw;
-    if (!convt_s2_tile_eligible(g) || !t_plan(g.N, g.Di, g.Hi, g.Wi, g.Cin, g.Cout, &tw, &p))
-        return ru3d_fail(-1, "convt_s2_tile: shape not supported");
-    if ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)res) | ((uintptr_t)x2) | ((uintptr_t)w) | ((uintptr_t)w2)) % 16)
-        return ru3d_fail(-1, "convt_s2_tile: operands must be 16-byte aligned");
+int convt_s2_tile_launch(const ConvDirectPlan& plan, const void* x, const void* w, const float* bias, const void* res,
+                         void* y, const ConvGeom& g, float* stat_slab, const void* x2, int ldx2, const void* w2,
+                         hipStream_t st) {
+    const SlidePlan& p = plan.slide;
+    if (plan.tile != S2_TILE_T) return ru3d_fail(-1, "convt_s2_tile: shape not supported");
+    if (!conv_direct_tile_ok(plan, g, x, res, y, x2, ldx2) || (((uintptr_t)w) | ((uintptr_t)w2)) % 16 || (x2 && !w2))
+        return ru3d_fail(-1, "convt_s2_tile: operands must be 16-byte aligned, a partner within the 30-bit range");
     if (stat_slab && (res || x2)) return ru3d_fail(-1, "convt_s2_tile: statistics and residual / partner cannot be combined");
-    if (x2 && ((ldx2 % 8) || !w2 || (int64_t)g.Di * g.Hi * g.Wi * ldx2 >= (1ll << 30)))
-        return ru3d_fail(-1, "convt_s2_tile: bad partner operand");
     S2Args a;
     a.x = (const bf16*)x; a.w = (const bf16x8*)w; a.bias = bias; a.res = (const bf16*)res; a.y = (bf16*)y;
     a.stat_slab = stat_slab;
@@ -868,14 +853,12 @@ int convt_s2_tile_launch(const void* x, const void* w, const float* bias, const 
     a.tiles_h = p.tiles_h; a.tiles_w = p.tiles_w; a.dsplit = p.dsplit; a.DL = p.DL; a.units = p.units;
     static const int dbg = ru3d_env_int("RU3D_S2_DBG", 0);
     a.dbg = dbg;
-    (void)tw;
-    return t_launch<64, 16>(a, p, res != nullptr, stat_slab != nullptr, x2 != nullptr, st);
+    return t_launch<64, 16>(a, p, res != nullptr, stat_slab != nullptr, x2 != nullptr, st, plan.tile_name);
 }
 
 // --------------------------------------------------------------------------------------------------- host: G form
 static bool g_plan(int N, int Do, int Ho, int Wo, int Cin, int Cout, SlidePlan* out) {
-    static const int mode = ru3d_env_int("RU3D_CONV_S2", 1);
-    if (!mode || Cin != 32 || (Cout % 64) || Cout > 128 || Do < 2) return false;
+    if (Cin != 32 || (Cout % 64) || Cout > 128 || Do < 2) return false;
     const int ny = Cout / 64;
     const int64_t cols = (int64_t)N * ((Ho + TH - 1) / TH) * ((Wo + GW - 1) / GW);
     int64_t best_cost = -1;
@@ -907,39 +890,29 @@ static bool g_plan(int N, int Do, int Ho, int Wo, int Cin, int Cout, SlidePlan* 
     return true;
 }
 
-bool conv_s2_tile_eligible(const ConvGeom& g) {
-    SlidePlan sp;
+// The G half of conv_direct_plan
+bool conv_s2_tile_plan(const ConvGeom& g, ConvDirectPlan* p) {
     if (g.transposed || g.k != 3 || g.stride != 2 || g.pad != 1) return false;
+    if (!g_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &p->slide)) return false;
+    p->tile_tw = GW; p->gx = p->slide.grid; p->cb = 64;
+    p->slab_bytes = (size_t)p->slide.grid * p->slide.ny * 4 * g.N * 64 * 2 * sizeof(float);
     if ((g.ldx % 8) || (g.ldy % 4)) return false;
     if ((int64_t)g.Di * g.Hi * g.Wi * g.ldx >= (1ll << 30) || (int64_t)g.Do * g.Ho * g.Wo * g.ldy >= (1ll << 30)) return false;
     if (g.Do != (g.Di - 1) / 2 + 1 || g.Ho != (g.Hi - 1) / 2 + 1 || g.Wo != (g.Wi - 1) / 2 + 1) return false;
-    return g_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp);
-}
-
-size_t conv_s2_tile_slab_bytes(const ConvGeom& g) {
-    SlidePlan sp;
-    if (!g_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp)) return 0;
-    return (size_t)sp.grid * sp.ny * 4 * g.N * 64 * 2 * sizeof(float);
-}
-
-int conv_s2_tile_slab_geom(const ConvGeom& g, int* gx, int* cb) {
-    SlidePlan sp;
-    if (!g_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &sp)) return -1;
-    *gx = sp.grid;
-    *cb = 64;
-    return 0;
+    p->tile = S2_TILE_G;
+    snprintf(p->tile_name, sizeof(p->tile_name), "conv3_s2_tile");
+    return true;
 }
 
 // w2 / bias2 / y2 (pitch ldy2): the 1x1x1 stride-2 conv of the same input as a second output; stat_slab: sums of y
-int conv_s2_tile_launch(const void* x, const void* w, const float* bias, void* y, const ConvGeom& g, float* stat_slab,
-                        const void* w2, const float* bias2, void* y2, int ldy2, hipStream_t st) {
-    SlidePlan p;
-    if (!conv_s2_tile_eligible(g) || !g_plan(g.N, g.Do, g.Ho, g.Wo, g.Cin, g.Cout, &p))
-        return ru3d_fail(-1, "conv_s2_tile: shape not supported");
-    if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)w2)) % 16 || (((uintptr_t)y) | ((uintptr_t)y2)) % 8)
-        return ru3d_fail(-1, "conv_s2_tile: operands must be 16-byte (x, w) / 8-byte (y) aligned");
-    if (y2 && (!w2 || (ldy2 % 4) || (int64_t)g.Do * g.Ho * g.Wo * ldy2 >= (1ll << 30)))
-        return ru3d_fail(-1, "conv_s2_tile: bad second output");
+int conv_s2_tile_launch(const ConvDirectPlan& plan, const void* x, const void* w, const float* bias, void* y,
+                        const ConvGeom& g, float* stat_slab, const void* w2, const float* bias2, void* y2, int ldy2,
+                        hipStream_t st) {
+    const SlidePlan& p = plan.slide;
+    if (plan.tile != S2_TILE_G) return ru3d_fail(-1, "conv_s2_tile: shape not supported");
+    if (!conv_direct_tile_ok(plan, g, x, nullptr, y, y2, ldy2) || (((uintptr_t)w) | ((uintptr_t)w2)) % 16 || (y2 && !w2))
+        return ru3d_fail(-1, "conv_s2_tile: operands must be 16-byte (x, w) / 8-byte (y) aligned, a second output within "
+                             "the 30-bit range");
     S2Args a;
     a.x = (const bf16*)x; a.w = (const bf16x8*)w; a.bias = bias; a.res = nullptr; a.y = (bf16*)y;
     a.stat_slab = stat_slab;
@@ -969,7 +942,7 @@ int conv_s2_tile_launch(const void* x, const void* w, const float* bias, void* y
     else if (y2) RU3D_G_LAUNCH(false, true);
     else RU3D_G_LAUNCH(false, false);
 #undef RU3D_G_LAUNCH
-    return ru3d_check_launch("conv3_s2_tile");
+    return ru3d_check_launch(plan.tile_name);
 }
 
 }  // namespace RU3D_NS

@@ -8,6 +8,7 @@
     X(ru3d_pack_weights) \
     X(ru3d_conv3d_workspace_bytes) \
     X(ru3d_conv3d_fwd) \
+    X(ru3d_conv3d_plan_names) \
     X(ru3d_conv3d_fwd_in_workspace_bytes) \
     X(ru3d_conv3d_fwd_in) \
     X(ru3d_conv3d_fwd_in_lrelu) \
@@ -67,6 +68,7 @@
 #define ru3d_pack_weights ru3d_pack_weights_f16
 #define ru3d_conv3d_workspace_bytes ru3d_conv3d_workspace_bytes_f16
 #define ru3d_conv3d_fwd ru3d_conv3d_fwd_f16
+#define ru3d_conv3d_plan_names ru3d_conv3d_plan_names_f16
 #define ru3d_conv3d_fwd_in_workspace_bytes ru3d_conv3d_fwd_in_workspace_bytes_f16
 #define ru3d_conv3d_fwd_in ru3d_conv3d_fwd_in_f16
 #define ru3d_conv3d_fwd_in_lrelu ru3d_conv3d_fwd_in_lrelu_f16

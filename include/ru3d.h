@@ -124,6 +124,13 @@ size_t ru3d_conv3d_workspace_bytes(const ru3d_tensor* x, const ru3d_tensor* y, i
 int ru3d_conv3d_fwd(const ru3d_tensor* x, const void* w_packed, const float* bias, const ru3d_tensor* res,
                     const ru3d_tensor* y, int k, int stride, int dtype, int y_dtype, void* ws,
                     size_t ws_bytes, void* stream);
+/* Which kernels the conv that gathers from x and writes y (dense tensors of one dtype, no residual; transposed: the
+ * fractionally strided form of ConvTranspose3d forward and the stride-2 input gradient) runs on: the launch-log names in
+ * the order of preference, joined by '|', written to buf (cap bytes).  A launch runs the first whose launch-time
+ * conditions (operand alignment, scratch) hold.  "stem" / "head": the small-channel kernels; "generic": no MFMA kernel
+ * takes the shape.  Pure host code: no pointer is dereferenced.  < 0: bad argument or no kernel. */
+int ru3d_conv3d_plan_names(const ru3d_tensor* x, const ru3d_tensor* y, int k, int stride, int transposed, int dtype,
+                           char* buf, size_t cap);
 /* The same forward conv FOLLOWED by the InstanceNorm statistics of its output (ResBlock: conv -> dropout ->
  * norm, network.py:411-414): y = conv(x) + bias, then mean / scale exactly as ru3d_instnorm_stats(y, ...)
  * would produce.  On the producer/consumer MFMA kernel the sums are accumulated in the conv epilogue (no
