@@ -123,10 +123,7 @@ template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16 from_f32<bf16>(float v) { return (bf16)v; }
 
-// vector of VEC elements of T, loaded/stored as one access when aligned
-template <typename T, int VEC> struct vec_t {
-    T v[VEC];
-};
+// VEC elements of T, loaded/stored as one access when aligned
 template <typename T, int VEC>
 __device__ __forceinline__ void load_vec(const T* p, float (&out)[VEC]) {
     typedef __attribute__((ext_vector_type(VEC))) T VT;

@@ -5,10 +5,13 @@
 // Work decomposition shared by every kernel here ("channel loop"): a tensor is [N][V][C] with pitch
 // ld.  Channels are cut into groups of VEC elements (one 16-byte access for bf16x8 / f32x4); a block
 // of 256 threads owns Gb <= 256 channel groups x vpb = 256/Gb voxel lanes and walks a span of voxels.
-// grid = (chunks, N, group blocks).
+// grid = (chunks, N, group blocks).  On the host that decomposition is chan_launch: it alone picks the vector width, makes
+// the ChanLoop and the grid, switches on the width and checks the launch; every entry point hands it a callable that
+// spells out one kernel launch.  ReduceWs is the one layout of the reductions' workspace.
 #include "common.h"
 #include "conv.h"
 #include <initializer_list>
+#include <type_traits>
 
 namespace RU3D_NS {
 
@@ -469,53 +472,141 @@ __global__ __launch_bounds__(256) void copy_add_kernel(const T* __restrict__ a, 
     }
 }
 
-// --------------------------------------------------------------------------- dispatch helpers
-#define DISPATCH_VEC(T, vec, CALL)                 \
-    switch (vec) {                                 \
-        case 8: if constexpr (sizeof(T) == 2) { CALL(T, 8); } break; \
-        case 4: CALL(T, 4); break;                 \
-        case 2: CALL(T, 2); break;                 \
-        default: CALL(T, 1); break;                \
-    }
-
+// --------------------------------------------------------------------------- launch helpers
 static bool same_shape(const ru3d_tensor* a, const ru3d_tensor* b) {
     return a->n == b->n && a->d == b->d && a->h == b->h && a->w == b->w && a->c == b->c;
 }
 
+// a kernel operand from a descriptor; a null descriptor is an operand the launched form does not read
+template <typename T> static T* tptr(const ru3d_tensor* t) { return t ? (T*)t->ptr : nullptr; }
+static int tld(const ru3d_tensor* t) { return t ? t->ld : 0; }
+
+template <int I> using int_c = std::integral_constant<int, I>;
+
+// f(std::true_type) or f(std::false_type): a runtime flag as a template argument
+template <typename F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// The tail of an entry point: the bound of the kernels' int voxel index, then f(T{}) with this build's element type.
+template <typename F>
+static int by_dtype(const char* name, const ru3d_tensor* t, int dtype, F&& f) {
+    if ((int64_t)t->d * t->h * t->w >= (1ll << 31)) return ru3d_fail(-1, "%s: sample too large", name);
+    if (dtype == RU3D_F32) return f(float{});
+    if (dtype == RU3D_BF16) return f(bf16{});
+    return ru3d_fail(-1, "%s: bad dtype %d", name, dtype);
+}
+
+// One channel-loop launch.  ts: every tensor the launch touches, and those of the launches that must run at its width;
+// the first one is never null and gives the shape.  launch(int_c<VEC>, grid, cl) spells out the kernel; the width 8 exists
+// for the 2-byte types only.  *used receives the geometry (the reductions' finalizes and workspace offsets need chunks).
+template <typename T, typename F>
+static int chan_launch(const char* name, std::initializer_list<const ru3d_tensor*> ts, int max_iters, F&& launch,
+                       ChanLoop* used = nullptr) {
+    const ru3d_tensor* t = *ts.begin();
+    const int vec = pick_vec<T>(t->c, ts);
+    const ChanLoop cl = make_chanloop((int64_t)t->d * t->h * t->w, t->c, vec, max_iters, t->n);
+    const dim3 grid(cl.chunks, t->n, (cl.G + cl.Gb - 1) / cl.Gb);
+    switch (vec) {
+        case 8: if constexpr (sizeof(T) == 2) launch(int_c<8>{}, grid, cl); break;
+        case 4: launch(int_c<4>{}, grid, cl); break;
+        case 2: launch(int_c<2>{}, grid, cl); break;
+        default: launch(int_c<1>{}, grid, cl); break;
+    }
+    if (used) *used = cl;
+    return ru3d_check_launch(name);
+}
+
+// The reductions' workspace for a tensor [n][V][c] whose reduction ran on `chunks` blocks along V, in the order of use:
+//   part   n * chunks * c pairs of doubles: reduce2's per-block partials
+//   m12    n * c pairs of floats: the backward's two means, padded to a multiple of 256 bytes
+//   dpart  n * chunks' * c pairs of doubles: the apply pass's dy-sum partials (ru3d_in_lrelu_bwd with dy_sum; chunks' is
+//          that pass's own, shorter-span geometry); part and m12 are still in use while it runs
+struct ReduceWs {
+    double* part;
+    float* m12;
+    double* dpart;
+    ReduceWs(void* ws, int n, int c, int chunks)
+        : part((double*)ws), m12((float*)((char*)ws + (size_t)n * chunks * c * 2 * sizeof(double))),
+          dpart((double*)((char*)m12 + (((size_t)n * c * 2 * sizeof(float) + 255) / 256) * 256)) {}
+};
+
+// The bound Python allocates by, for every width pick_vec may choose.  make_chanloop gives a span of at least one voxel
+// and at most 4096 chunks, so chunks and chunks' are both <= min(V, 4096): part and dpart end within 2 * n * min(V, 4096)
+// * c * 16 bytes, m12 adds n * c * 8, and its padding to 256 bytes at most 255 of the + 512 (the rest is slack that callers
+// have allocated since the first version).
 static size_t reduce_ws_bytes(const ru3d_tensor* t) {
-    // upper bound over the VEC choices: chunks is largest when vpb is smallest
     int64_t V = (int64_t)t->d * t->h * t->w;
     int64_t chunks = V < 4096 ? V : 4096;
     if (chunks < 1) chunks = 1;
-    // reduction partials + m12 + (in_lrelu_bwd with dy_sum) the apply pass's dy-sum partials
     return 2 * (size_t)t->n * chunks * t->c * 2 * sizeof(double) + (size_t)t->n * t->c * 2 * sizeof(float) + 512;
 }
+
+// ru3d_head_in_bwd: the ReduceWs regions, then the head's dW / db partials
+static size_t head_in_red_bytes(const ru3d_tensor* z) { return ((reduce_ws_bytes(z) + 255) / 256) * 256; }
 
 #ifndef RU3D_STORAGE_F16
 extern "C" size_t ru3d_reduce_workspace_bytes(const ru3d_tensor* t) { return t ? reduce_ws_bytes(t) : 0; }
 #endif
 
-template <typename T>
-static int stats_impl(const ru3d_tensor* y, const float* drop, float* mean, float* scale, void* ws, float eps,
-                      hipStream_t st) {
-    const int64_t V = (int64_t)y->d * y->h * y->w;
-    const int vec = pick_vec<T>(y->c, {y});
-    ChanLoop cl = make_chanloop(V, y->c, vec, 64, y->n);
-    dim3 grid(cl.chunks, y->n, (cl.G + cl.Gb - 1) / cl.Gb);
-    double* part = (double*)ws;
-#define CALL(TT, VV)                                                                                              \
-    hipLaunchKernelGGL((reduce2_kernel<TT, VV, 0>), grid, dim3(256), 0, st, (const TT*)y->ptr, y->ld, (const TT*)0, \
-                       0, (const TT*)0, 0, (const float*)0, (const float*)0, 0.f, part, cl, y->c)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    int rc = ru3d_check_launch("instnorm_stats");
-    if (rc) return rc;
-    const int NC = y->n * y->c;
-    hipLaunchKernelGGL(stats_finalize_kernel, dim3((NC + FIN_CX - 1) / FIN_CX), dim3(256), 0, st, (const double*)part, cl.chunks,
-                       y->c, NC, 1.0 / (double)V, drop, eps, mean, scale);
-    return ru3d_check_launch("instnorm_stats_finalize");
+// reduce2_kernel<T, VEC, MODE> into ReduceWs::part; each caller follows it with its own finalize.  ts as for chan_launch.
+template <typename T, int MODE>
+static int reduce2_launch(const char* name, std::initializer_list<const ru3d_tensor*> ts, void* ws, ChanLoop* used,
+                          hipStream_t st, const ru3d_tensor* a, const ru3d_tensor* b = nullptr,
+                          const ru3d_tensor* c3 = nullptr, const float* mean = nullptr, const float* scale = nullptr,
+                          float slope = 0.f, const ru3d_tensor* gp_out = nullptr, const float* shift = nullptr) {
+    return chan_launch<T>(name, ts, 64, [&](auto vec, dim3 grid, const ChanLoop& cl) {
+        hipLaunchKernelGGL((reduce2_kernel<T, decltype(vec)::value, MODE>), grid, dim3(256), 0, st, tptr<const T>(a),
+                           tld(a), tptr<const T>(b), tld(b), tptr<const T>(c3), tld(c3), mean, scale, slope,
+                           ReduceWs(ws, a->n, a->c, cl.chunks).part, cl, a->c, tptr<T>(gp_out), tld(gp_out), shift);
+    }, used);
 }
 
+// in_lrelu_bwd_kernel<T, VEC, GPRE, GPRE, AFFINE>.  GPRE: the pre-activation gradient is read from `gpre` (gout and out may be
+// null); otherwise xhat comes from `out` and y only gives the extents.  ts as for chan_launch.
+template <typename T, bool GPRE, bool AFFINE = false>
+static int bwd_apply_launch(const char* name, std::initializer_list<const ru3d_tensor*> ts, hipStream_t st,
+                            const ru3d_tensor* gout, const ru3d_tensor* out, const ru3d_tensor* y, const float* mean,
+                            const float* scale, const float* m12, const ru3d_tensor* dy, const ru3d_tensor* gpre,
+                            float slope, int zero_far, const float* shift = nullptr, const float* oscale = nullptr,
+                            double* dpart = nullptr, ChanLoop* used = nullptr) {
+    return chan_launch<T>(name, ts, 16, [&](auto vec, dim3 grid, const ChanLoop& ca) {
+        hipLaunchKernelGGL((in_lrelu_bwd_kernel<T, decltype(vec)::value, GPRE, GPRE, AFFINE>), grid, dim3(256), 0, st,
+                           tptr<const T>(gout), tld(gout), tptr<const T>(out), tld(out), tptr<const T>(y), tld(y), mean,
+                           scale, m12, tptr<T>(dy), tld(dy), tptr<T>(gpre), tld(gpre), slope, zero_far, y->d, y->h, y->w,
+                           ca, y->c, shift, oscale, dpart);
+    }, used);
+}
+
+// The InstanceNorm + LeakyReLU backward behind its reduction (`cl`: that launch's geometry): the two means and the skip
+// conv's bias gradient from the partials, the apply pass, the optional sum of dy from the apply pass's own partials.
+template <typename T>
+static int in_bwd_tail(const char* finalize_name, const char* apply_name, std::initializer_list<const ru3d_tensor*> ts,
+                       void* ws, const ChanLoop& cl, const ru3d_tensor* gout, const ru3d_tensor* out,
+                       const ru3d_tensor* y, const float* mean, const float* scale, const ru3d_tensor* dy,
+                       const ru3d_tensor* gpre, float slope, int zero_far, float* gpre_sum, float* dy_sum,
+                       hipStream_t st) {
+    const ReduceWs w(ws, y->n, y->c, cl.chunks);
+    const dim3 fin_grid((y->c + FIN_CX - 1) / FIN_CX);
+    hipLaunchKernelGGL(bwd_finalize_kernel, fin_grid, dim3(256), 0, st, (const double*)w.part, cl.chunks, y->c, y->n,
+                       1.0 / (double)cl.V, w.m12, (double)cl.V, gpre_sum);
+    int rc = ru3d_check_launch(finalize_name);
+    if (rc) return rc;
+    double* dpart = dy_sum ? w.dpart : nullptr;
+    ChanLoop ca;
+    with_bool(gpre != nullptr, [&](auto has_gpre) {
+        rc = bwd_apply_launch<T, decltype(has_gpre)::value>(apply_name, ts, st, gout, out, y, mean, scale, w.m12, dy, gpre,
+                                                            slope, zero_far, nullptr, nullptr, dpart, &ca);
+    });
+    if (rc || !dy_sum) return rc;
+    hipLaunchKernelGGL(chansum_finalize_kernel, fin_grid, dim3(256), 0, st, (const double*)dpart, ca.chunks, y->c, y->n,
+                       dy_sum);
+    return ru3d_check_launch("in_lrelu_bwd_dysum_finalize");
+}
+
+// --------------------------------------------------------------------------- InstanceNorm entry points
 extern "C" int ru3d_instnorm_stats(const ru3d_tensor* y, const float* drop_scale, float* mean, float* scale, void* ws,
                                    size_t ws_bytes, float eps, int dtype, void* stream) {
     RU3D_FWD_F16(dtype, ru3d_instnorm_stats_f16(y, drop_scale, mean, scale, ws, ws_bytes, eps, dtype, stream));
@@ -524,29 +615,31 @@ extern "C" int ru3d_instnorm_stats(const ru3d_tensor* y, const float* drop_scale
     RU3D_REQUIRE(mean && scale && ws, "instnorm_stats: null output/workspace");
     RU3D_REQUIRE(ws_bytes >= reduce_ws_bytes(y), "instnorm_stats: workspace too small (%zu < %zu)", ws_bytes,
                  reduce_ws_bytes(y));
-    RU3D_REQUIRE((int64_t)y->d * y->h * y->w < (1ll << 31), "instnorm_stats: sample too large");
-    if (dtype == RU3D_F32) return stats_impl<float>(y, drop_scale, mean, scale, ws, eps, as_stream(stream));
-    if (dtype == RU3D_BF16) return stats_impl<bf16>(y, drop_scale, mean, scale, ws, eps, as_stream(stream));
-    return ru3d_fail(-1, "instnorm_stats: bad dtype %d", dtype);
+    return by_dtype("instnorm_stats", y, dtype, [&](auto tag) {
+        hipStream_t st = as_stream(stream);
+        ChanLoop cl;
+        int rc = reduce2_launch<decltype(tag), 0>("instnorm_stats", {y}, ws, &cl, st, y);
+        if (rc) return rc;
+        const int NC = y->n * y->c;
+        hipLaunchKernelGGL(stats_finalize_kernel, dim3((NC + FIN_CX - 1) / FIN_CX), dim3(256), 0, st,
+                           (const double*)ReduceWs(ws, y->n, y->c, cl.chunks).part, cl.chunks, y->c, NC,
+                           1.0 / (double)cl.V, drop_scale, eps, mean, scale);
+        return ru3d_check_launch("instnorm_stats_finalize");
+    });
 }
 
-template <typename T>
-static int in_fwd_impl(const ru3d_tensor* y, const float* mean, const float* scale, const ru3d_tensor* res,
-                       const ru3d_tensor* out, float slope, hipStream_t st) {
-    const int64_t V = (int64_t)y->d * y->h * y->w;
-    const int vec = pick_vec<T>(y->c, {y, res, out});
-    ChanLoop cl = make_chanloop(V, y->c, vec, 16, y->n);
-    dim3 grid(cl.chunks, y->n, (cl.G + cl.Gb - 1) / cl.Gb);
-#define CALL(TT, VV)                                                                                               \
-    if (res)                                                                                                       \
-        hipLaunchKernelGGL((in_lrelu_fwd_kernel<TT, VV, true>), grid, dim3(256), 0, st, (const TT*)y->ptr, y->ld,   \
-                           mean, scale, (const TT*)res->ptr, res->ld, (TT*)out->ptr, out->ld, slope, cl, y->c);    \
-    else                                                                                                           \
-        hipLaunchKernelGGL((in_lrelu_fwd_kernel<TT, VV, false>), grid, dim3(256), 0, st, (const TT*)y->ptr, y->ld,  \
-                           mean, scale, (const TT*)0, 0, (TT*)out->ptr, out->ld, slope, cl, y->c)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    return ru3d_check_launch("in_lrelu_fwd");
+// out = lrelu((y - mean) * scale (+ res)); AFFINE (BatchNorm): out = lrelu(y * scale[n][c] + shift[n][c] (+ res))
+template <typename T, bool AFFINE>
+static int lrelu_fwd_launch(const char* name, const ru3d_tensor* y, const float* mean, const float* scale,
+                            const float* shift, const ru3d_tensor* res, const ru3d_tensor* out, float slope,
+                            hipStream_t st) {
+    return chan_launch<T>(name, {y, res, out}, 16, [&](auto vec, dim3 grid, const ChanLoop& cl) {
+        with_bool(res != nullptr, [&](auto has_res) {
+            hipLaunchKernelGGL((in_lrelu_fwd_kernel<T, decltype(vec)::value, decltype(has_res)::value, AFFINE>), grid,
+                               dim3(256), 0, st, tptr<const T>(y), y->ld, mean, scale, tptr<const T>(res), tld(res),
+                               tptr<T>(out), out->ld, slope, cl, y->c, shift);
+        });
+    });
 }
 
 extern "C" int ru3d_in_lrelu_fwd(const ru3d_tensor* y, const float* mean, const float* scale, const ru3d_tensor* res,
@@ -556,61 +649,10 @@ extern "C" int ru3d_in_lrelu_fwd(const ru3d_tensor* y, const float* mean, const 
     RU3D_REQUIRE(tensor_ok(y) && tensor_ok(out) && same_shape(y, out), "in_lrelu_fwd: bad y/out");
     RU3D_REQUIRE(!res || (tensor_ok(res) && same_shape(y, res)), "in_lrelu_fwd: bad residual");
     RU3D_REQUIRE(mean && scale, "in_lrelu_fwd: null stats");
-    RU3D_REQUIRE((int64_t)y->d * y->h * y->w < (1ll << 31), "in_lrelu_fwd: sample too large");
-    if (dtype == RU3D_F32) return in_fwd_impl<float>(y, mean, scale, res, out, slope, as_stream(stream));
-    if (dtype == RU3D_BF16) return in_fwd_impl<bf16>(y, mean, scale, res, out, slope, as_stream(stream));
-    return ru3d_fail(-1, "in_lrelu_fwd: bad dtype %d", dtype);
-}
-
-template <typename T>
-static int in_bwd_impl(const ru3d_tensor* gout, const ru3d_tensor* out, const ru3d_tensor* y, const float* mean,
-                       const float* scale, const ru3d_tensor* dy, const ru3d_tensor* gpre, void* ws, float slope,
-                       int zero_far, float* gpre_sum, float* dy_sum, hipStream_t st) {
-    const int64_t V = (int64_t)y->d * y->h * y->w;
-    const int vec = pick_vec<T>(y->c, {gout, out, y, dy, gpre});
-    ChanLoop cl = make_chanloop(V, y->c, vec, 64, y->n);
-    dim3 grid(cl.chunks, y->n, (cl.G + cl.Gb - 1) / cl.Gb);
-    double* part = (double*)ws;
-    float* m12 = (float*)((char*)ws + (size_t)y->n * cl.chunks * y->c * 2 * sizeof(double));
-#define CALL(TT, VV)                                                                                                  \
-    if (gpre)                                                                                                         \
-        hipLaunchKernelGGL((reduce2_kernel<TT, VV, 4>), grid, dim3(256), 0, st, (const TT*)gout->ptr, gout->ld,       \
-                           (const TT*)out->ptr, out->ld, (const TT*)y->ptr, y->ld, mean, scale, slope, part, cl,      \
-                           y->c, (TT*)gpre->ptr, gpre->ld);                                                           \
-    else                                                                                                              \
-        hipLaunchKernelGGL((reduce2_kernel<TT, VV, 3>), grid, dim3(256), 0, st, (const TT*)gout->ptr, gout->ld,       \
-                           (const TT*)out->ptr, out->ld, (const TT*)0, 0, mean, scale, slope, part, cl, y->c)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    int rc = ru3d_check_launch("in_lrelu_bwd_reduce");
-    if (rc) return rc;
-    hipLaunchKernelGGL(bwd_finalize_kernel, dim3((y->c + FIN_CX - 1) / FIN_CX), dim3(256), 0, st, (const double*)part,
-                       cl.chunks, y->c, y->n, 1.0 / (double)V, m12, (double)V, gpre_sum);
-    rc = ru3d_check_launch("in_lrelu_bwd_finalize");
-    if (rc) return rc;
-    ChanLoop ca = make_chanloop(V, y->c, vec, 16, y->n);
-    dim3 grida(ca.chunks, y->n, (ca.G + ca.Gb - 1) / ca.Gb);
-    // dy-sum partials of the apply pass: behind the reduction partials and m12 (both still in use while it runs)
-    double* dpart =
-        dy_sum ? (double*)((char*)m12 + (((size_t)y->n * y->c * 2 * sizeof(float) + 255) / 256) * 256) : nullptr;
-#define CALL(TT, VV)                                                                                                  \
-    if (gpre)                                                                                                         \
-        hipLaunchKernelGGL((in_lrelu_bwd_kernel<TT, VV, true, true>), grida, dim3(256), 0, st, (const TT*)gout->ptr,  \
-                           gout->ld, (const TT*)out->ptr, out->ld, (const TT*)y->ptr, y->ld, mean, scale,            \
-                           (const float*)m12, (TT*)dy->ptr, dy->ld, (TT*)gpre->ptr, gpre->ld, slope, zero_far, y->d,  \
-                           y->h, y->w, ca, y->c, (const float*)nullptr, (const float*)nullptr, dpart);               \
-    else                                                                                                              \
-        hipLaunchKernelGGL((in_lrelu_bwd_kernel<TT, VV, false>), grida, dim3(256), 0, st, (const TT*)gout->ptr,       \
-                           gout->ld, (const TT*)out->ptr, out->ld, (const TT*)y->ptr, y->ld, mean, scale,            \
-                           (const float*)m12, (TT*)dy->ptr, dy->ld, (TT*)0, 0, slope, zero_far, y->d, y->h, y->w, ca, \
-                           y->c, (const float*)nullptr, (const float*)nullptr, dpart)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    rc = ru3d_check_launch("in_lrelu_bwd_apply");
-    if (rc || !dy_sum) return rc;
-    hipLaunchKernelGGL(chansum_finalize_kernel, dim3((y->c + FIN_CX - 1) / FIN_CX), dim3(256), 0, st,
-                       (const double*)dpart, ca.chunks, y->c, y->n, dy_sum);
-    return ru3d_check_launch("in_lrelu_bwd_dysum_finalize");
+    return by_dtype("in_lrelu_fwd", y, dtype, [&](auto tag) {
+        return lrelu_fwd_launch<decltype(tag), false>("in_lrelu_fwd", y, mean, scale, nullptr, res, out, slope,
+                                                      as_stream(stream));
+    });
 }
 
 extern "C" int ru3d_in_lrelu_bwd(const ru3d_tensor* gout, const ru3d_tensor* out, const ru3d_tensor* y,
@@ -626,22 +668,29 @@ extern "C" int ru3d_in_lrelu_bwd(const ru3d_tensor* gout, const ru3d_tensor* out
     RU3D_REQUIRE(mean && scale && ws, "in_lrelu_bwd: null stats/workspace");
     RU3D_REQUIRE(ws_bytes >= reduce_ws_bytes(y), "in_lrelu_bwd: workspace too small (%zu < %zu)", ws_bytes,
                  reduce_ws_bytes(y));
-    RU3D_REQUIRE((int64_t)y->d * y->h * y->w < (1ll << 31), "in_lrelu_bwd: sample too large");
-    // the small levels: one launch instead of three (norm_small.hip)
-    if (dtype == RU3D_BF16 && in_small_mode(out, gpre_sum != nullptr, gout, y, dy, gpre)) {
-        int rc = in_small_bwd_launch(gout, nullptr, 0, out, y, mean, scale, dy, gpre, ws, slope, zero_far, gpre_sum, as_stream(stream));
-        if (rc || !dy_sum) return rc;
-        return ru3d_channel_sum(dy, dy_sum, ws, ws_bytes, dtype, stream);      // small tensors: a pass of its own
-    }
-    if (dtype == RU3D_F32)
-        return in_bwd_impl<float>(gout, out, y, mean, scale, dy, gpre, ws, slope, zero_far, gpre_sum, dy_sum, as_stream(stream));
-    if (dtype == RU3D_BF16)
-        return in_bwd_impl<bf16>(gout, out, y, mean, scale, dy, gpre, ws, slope, zero_far, gpre_sum, dy_sum, as_stream(stream));
-    return ru3d_fail(-1, "in_lrelu_bwd: bad dtype %d", dtype);
+    return by_dtype("in_lrelu_bwd", y, dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipStream_t st = as_stream(stream);
+        // the small levels: one launch instead of three (norm_small.hip)
+        if (dtype == RU3D_BF16 && in_small_mode(out, gpre_sum != nullptr, gout, y, dy, gpre)) {
+            int rc = in_small_bwd_launch(gout, nullptr, 0, out, y, mean, scale, dy, gpre, ws, slope, zero_far, gpre_sum, st);
+            if (rc || !dy_sum) return rc;
+            return ru3d_channel_sum(dy, dy_sum, ws, ws_bytes, dtype, stream);      // small tensors: a pass of its own
+        }
+        // with a residual (gpre) the reduction also stores g' = gout * lrelu'(out), which the apply pass reads back
+        ChanLoop cl;
+        int rc = gpre ? reduce2_launch<T, 4>("in_lrelu_bwd_reduce", {gout, out, y, dy, gpre}, ws, &cl, st, gout, out, y,
+                                             mean, scale, slope, gpre)
+                      : reduce2_launch<T, 3>("in_lrelu_bwd_reduce", {gout, out, y, dy, gpre}, ws, &cl, st, gout, out,
+                                             nullptr, mean, scale, slope);
+        if (rc) return rc;
+        return in_bwd_tail<T>("in_lrelu_bwd_finalize", "in_lrelu_bwd_apply", {gout, out, y, dy, gpre}, ws, cl, gout, out,
+                              y, mean, scale, dy, gpre, slope, zero_far, gpre_sum, dy_sum, st);
+    });
 }
 
 // ---- the head's backward and the InstanceNorm + LeakyReLU backward of the residual block in front of it
-// (reference network.py:547 fc behind :414-416).  ru3d_head_bwd stored dz (the head's input gradient) and in_bwd_impl's
+// (reference network.py:547 fc behind :414-416).  ru3d_head_bwd stored dz (the head's input gradient) and ru3d_in_lrelu_bwd's
 // reduction read it straight back with z and y.  Here dz exists in registers only: head_bwd_wgrad_kernel (small_convs.hip)
 // takes dW and db from (z, dlogits) in ru3d_head_bwd's order, and head_dz_reduce2_kernel is reduce2_kernel MODE 4 - same
 // grid, same voxel order, same sums, same partial layout - with its first operand formed from dlogits and the head's
@@ -731,9 +780,6 @@ __global__ __launch_bounds__(256) void head_dz_reduce2_kernel(const float* __res
     }
 }
 
-// workspace: in_bwd_impl's (partials, m12) followed by the head's dW / db partials
-static size_t head_in_red_bytes(const ru3d_tensor* z) { return ((reduce_ws_bytes(z) + 255) / 256) * 256; }
-
 extern "C" int ru3d_head_in_bwd_supported(const ru3d_tensor* z, const ru3d_tensor* dlogits, const ru3d_tensor* y,
                                           const ru3d_tensor* gpre, const ru3d_tensor* dy, int dtype) {
     RU3D_FWD_F16(dtype, ru3d_head_in_bwd_supported_f16(z, dlogits, y, gpre, dy, dtype));
@@ -765,51 +811,25 @@ extern "C" int ru3d_head_in_bwd(const ru3d_tensor* z, const ru3d_tensor* dlogits
     RU3D_REQUIRE(weight && dw && mean && scale && ws && cin_real > 0 && cin_real <= z->c, "head_in_bwd: bad argument");
     RU3D_REQUIRE(ws_bytes >= ru3d_head_in_bwd_workspace_bytes(z, dtype), "head_in_bwd: workspace too small");
     hipStream_t st = as_stream(stream);
-    const int64_t V = (int64_t)z->d * z->h * z->w;
     // the head's dW and db: ru3d_head_bwd's pass over (z, dlogits) without its store
     int rc = head_bwd_launch(z->ptr, z->ld, (const float*)dlogits->ptr, dlogits->ld, weight, cin_real, z->c, dlogits->c,
                              nullptr, 0, dw, db, (char*)ws + head_in_red_bytes(z), nvox(z), st);
     if (rc) return rc;
-    // in_bwd_impl's three launches, the first with dz from registers
-    ChanLoop cl = make_chanloop(V, y->c, 8, 64, y->n);
-    dim3 grid(cl.chunks, y->n, (cl.G + cl.Gb - 1) / cl.Gb);
-    double* part = (double*)ws;
-    float* m12 = (float*)((char*)ws + (size_t)y->n * cl.chunks * y->c * 2 * sizeof(double));
-    hipLaunchKernelGGL((head_dz_reduce2_kernel<8>), grid, dim3(256), 0, st, (const float*)dlogits->ptr, dlogits->ld, weight,
-                       cin_real, dlogits->c, (const bf16*)z->ptr, z->ld, (const bf16*)y->ptr, y->ld, mean, scale, slope, part,
-                       cl, y->c, (bf16*)gpre->ptr, gpre->ld);
-    rc = ru3d_check_launch("head_in_bwd_reduce");
+    // ru3d_in_lrelu_bwd's launches, the first with dz from registers; `supported` has seen to the width of 8
+    ChanLoop cl;
+    rc = chan_launch<bf16>("head_in_bwd_reduce", {z, y, gpre, dy}, 64, [&](auto vec, dim3 grid, const ChanLoop& c8) {
+        if constexpr (decltype(vec)::value == 8)
+            hipLaunchKernelGGL((head_dz_reduce2_kernel<8>), grid, dim3(256), 0, st, (const float*)dlogits->ptr,
+                               dlogits->ld, weight, cin_real, dlogits->c, (const bf16*)z->ptr, z->ld,
+                               (const bf16*)y->ptr, y->ld, mean, scale, slope, ReduceWs(ws, y->n, y->c, c8.chunks).part,
+                               c8, y->c, (bf16*)gpre->ptr, gpre->ld);
+    }, &cl);
     if (rc) return rc;
-    hipLaunchKernelGGL(bwd_finalize_kernel, dim3((y->c + FIN_CX - 1) / FIN_CX), dim3(256), 0, st, (const double*)part,
-                       cl.chunks, y->c, y->n, 1.0 / (double)V, m12, (double)V, gpre_sum);
-    rc = ru3d_check_launch("head_in_bwd_finalize");
-    if (rc) return rc;
-    ChanLoop ca = make_chanloop(V, y->c, 8, 16, y->n);
-    dim3 grida(ca.chunks, y->n, (ca.G + ca.Gb - 1) / ca.Gb);
-    hipLaunchKernelGGL((in_lrelu_bwd_kernel<bf16, 8, true, true>), grida, dim3(256), 0, st, (const bf16*)nullptr, 0,
-                       (const bf16*)nullptr, 0, (const bf16*)y->ptr, y->ld, mean, scale, (const float*)m12, (bf16*)dy->ptr,
-                       dy->ld, (bf16*)gpre->ptr, gpre->ld, slope, 0, y->d, y->h, y->w, ca, y->c, (const float*)nullptr,
-                       (const float*)nullptr, (double*)nullptr);
-    return ru3d_check_launch("head_in_bwd_apply");
+    return in_bwd_tail<bf16>("head_in_bwd_finalize", "head_in_bwd_apply", {z, y, gpre, dy}, ws, cl, nullptr, nullptr, y,
+                             mean, scale, dy, gpre, slope, 0, gpre_sum, nullptr, st);
 }
 
 // the apply pass alone, with the two means given (ru3d_conv3d_dgrad_in_bwd: they come out of the conv's epilogue)
-template <typename T>
-static int in_bwd_apply_impl(const ru3d_tensor* gout, const ru3d_tensor* out, const float* mean, const float* scale,
-                             const float* m12, const ru3d_tensor* dy, float slope, int zero_far, hipStream_t st) {
-    const int64_t V = (int64_t)out->d * out->h * out->w;
-    const int vec = pick_vec<T>(out->c, {gout, out, dy});
-    ChanLoop ca = make_chanloop(V, out->c, vec, 16, out->n);
-    dim3 grida(ca.chunks, out->n, (ca.G + ca.Gb - 1) / ca.Gb);
-#define CALL(TT, VV)                                                                                                  \
-    hipLaunchKernelGGL((in_lrelu_bwd_kernel<TT, VV, false>), grida, dim3(256), 0, st, (const TT*)gout->ptr, gout->ld, \
-                       (const TT*)out->ptr, out->ld, (const TT*)out->ptr, out->ld, mean, scale, m12, (TT*)dy->ptr,    \
-                       dy->ld, (TT*)0, 0, slope, zero_far, out->d, out->h, out->w, ca, out->c)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    return ru3d_check_launch("in_lrelu_bwd_apply");
-}
-
 extern "C" int ru3d_in_lrelu_bwd_apply(const ru3d_tensor* gout, const ru3d_tensor* out, const float* mean,
                                        const float* scale, const float* m12, const ru3d_tensor* dy, float slope,
                                        int zero_far, int dtype, void* stream) {
@@ -818,10 +838,10 @@ extern "C" int ru3d_in_lrelu_bwd_apply(const ru3d_tensor* gout, const ru3d_tenso
     RU3D_REQUIRE(tensor_ok(gout) && tensor_ok(out) && tensor_ok(dy), "in_lrelu_bwd_apply: bad tensor");
     RU3D_REQUIRE(same_shape(out, gout) && same_shape(out, dy), "in_lrelu_bwd_apply: shape mismatch");
     RU3D_REQUIRE(mean && scale && m12, "in_lrelu_bwd_apply: null stats");
-    RU3D_REQUIRE((int64_t)out->d * out->h * out->w < (1ll << 31), "in_lrelu_bwd_apply: sample too large");
-    if (dtype == RU3D_F32) return in_bwd_apply_impl<float>(gout, out, mean, scale, m12, dy, slope, zero_far, as_stream(stream));
-    if (dtype == RU3D_BF16) return in_bwd_apply_impl<bf16>(gout, out, mean, scale, m12, dy, slope, zero_far, as_stream(stream));
-    return ru3d_fail(-1, "in_lrelu_bwd_apply: bad dtype %d", dtype);
+    return by_dtype("in_lrelu_bwd_apply", out, dtype, [&](auto tag) {
+        return bwd_apply_launch<decltype(tag), false>("in_lrelu_bwd_apply", {gout, out, dy}, as_stream(stream), gout, out,
+                                                      out, mean, scale, m12, dy, nullptr, slope, zero_far);
+    });
 }
 
 // --------------------------------------------------------------------------- BatchNorm3d, training mode
@@ -908,23 +928,12 @@ extern "C" int ru3d_batchnorm_stats_finalize(const double* pooled, int n, int c,
 }
 #endif
 
-template <typename T>
-static int bn_pool_impl(const ru3d_tensor* y, const float* drop, double* pooled, void* ws, hipStream_t st) {
-    const int64_t V = (int64_t)y->d * y->h * y->w;
-    const int vec = pick_vec<T>(y->c, {y});
-    ChanLoop cl = make_chanloop(V, y->c, vec, 64, y->n);
-    dim3 grid(cl.chunks, y->n, (cl.G + cl.Gb - 1) / cl.Gb);
-    double* part = (double*)ws;
-#define CALL(TT, VV)                                                                                              \
-    hipLaunchKernelGGL((reduce2_kernel<TT, VV, 0>), grid, dim3(256), 0, st, (const TT*)y->ptr, y->ld, (const TT*)0, \
-                       0, (const TT*)0, 0, (const float*)0, (const float*)0, 0.f, part, cl, y->c)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    int rc = ru3d_check_launch("batchnorm_stats_reduce");
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_pool_kernel, dim3((y->c + FIN_CX - 1) / FIN_CX), dim3(256), 0, st, (const double*)part, cl.chunks,
-                       y->c, y->n, drop, pooled);
-    return ru3d_check_launch("batchnorm_stats_pool");
+// pooled = (sum_n d S1, sum_n d^2 S2) of the partials a reduction left in the workspace
+static int bn_pool_launch(const char* name, void* ws, const ChanLoop& cl, const ru3d_tensor* y, const float* drop,
+                          double* pooled, hipStream_t st) {
+    hipLaunchKernelGGL(bn_pool_kernel, dim3((y->c + FIN_CX - 1) / FIN_CX), dim3(256), 0, st,
+                       (const double*)ReduceWs(ws, y->n, y->c, cl.chunks).part, cl.chunks, y->c, y->n, drop, pooled);
+    return ru3d_check_launch(name);
 }
 
 extern "C" int ru3d_batchnorm_stats_pool(const ru3d_tensor* y, const float* drop_scale, double* pooled, void* ws,
@@ -935,32 +944,12 @@ extern "C" int ru3d_batchnorm_stats_pool(const ru3d_tensor* y, const float* drop
     RU3D_REQUIRE(pooled && ws, "batchnorm_stats_pool: null output/workspace");
     RU3D_REQUIRE(ws_bytes >= reduce_ws_bytes(y), "batchnorm_stats_pool: workspace too small (%zu < %zu)", ws_bytes,
                  reduce_ws_bytes(y));
-    RU3D_REQUIRE((int64_t)y->d * y->h * y->w < (1ll << 31), "batchnorm_stats_pool: sample too large");
-    if (dtype == RU3D_F32) return bn_pool_impl<float>(y, drop_scale, pooled, ws, as_stream(stream));
-    if (dtype == RU3D_BF16) return bn_pool_impl<bf16>(y, drop_scale, pooled, ws, as_stream(stream));
-    return ru3d_fail(-1, "batchnorm_stats_pool: bad dtype %d", dtype);
-}
-
-// out = lrelu(y * scale[n][c] + shift[n][c] (+ res))
-template <typename T>
-static int affine_fwd_impl(const ru3d_tensor* y, const float* scale, const float* shift, const ru3d_tensor* res,
-                           const ru3d_tensor* out, float slope, hipStream_t st) {
-    const int64_t V = (int64_t)y->d * y->h * y->w;
-    const int vec = pick_vec<T>(y->c, {y, res, out});
-    ChanLoop cl = make_chanloop(V, y->c, vec, 16, y->n);
-    dim3 grid(cl.chunks, y->n, (cl.G + cl.Gb - 1) / cl.Gb);
-#define CALL(TT, VV)                                                                                               \
-    if (res)                                                                                                       \
-        hipLaunchKernelGGL((in_lrelu_fwd_kernel<TT, VV, true, true>), grid, dim3(256), 0, st, (const TT*)y->ptr,    \
-                           y->ld, (const float*)0, scale, (const TT*)res->ptr, res->ld, (TT*)out->ptr, out->ld,    \
-                           slope, cl, y->c, shift);                                                                \
-    else                                                                                                           \
-        hipLaunchKernelGGL((in_lrelu_fwd_kernel<TT, VV, false, true>), grid, dim3(256), 0, st, (const TT*)y->ptr,   \
-                           y->ld, (const float*)0, scale, (const TT*)0, 0, (TT*)out->ptr, out->ld, slope, cl, y->c, \
-                           shift)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    return ru3d_check_launch("affine_lrelu_fwd");
+    return by_dtype("batchnorm_stats_pool", y, dtype, [&](auto tag) {
+        ChanLoop cl;
+        int rc = reduce2_launch<decltype(tag), 0>("batchnorm_stats_reduce", {y}, ws, &cl, as_stream(stream), y);
+        if (rc) return rc;
+        return bn_pool_launch("batchnorm_stats_pool", ws, cl, y, drop_scale, pooled, as_stream(stream));
+    });
 }
 
 extern "C" int ru3d_affine_lrelu_fwd(const ru3d_tensor* y, const float* scale, const float* shift, const ru3d_tensor* res,
@@ -970,35 +959,13 @@ extern "C" int ru3d_affine_lrelu_fwd(const ru3d_tensor* y, const float* scale, c
     RU3D_REQUIRE(tensor_ok(y) && tensor_ok(out) && same_shape(y, out), "affine_lrelu_fwd: bad y/out");
     RU3D_REQUIRE(!res || (tensor_ok(res) && same_shape(y, res)), "affine_lrelu_fwd: bad residual");
     RU3D_REQUIRE(scale && shift, "affine_lrelu_fwd: null scale/shift");
-    RU3D_REQUIRE((int64_t)y->d * y->h * y->w < (1ll << 31), "affine_lrelu_fwd: sample too large");
-    if (dtype == RU3D_F32) return affine_fwd_impl<float>(y, scale, shift, res, out, slope, as_stream(stream));
-    if (dtype == RU3D_BF16) return affine_fwd_impl<bf16>(y, scale, shift, res, out, slope, as_stream(stream));
-    return ru3d_fail(-1, "affine_lrelu_fwd: bad dtype %d", dtype);
+    return by_dtype("affine_lrelu_fwd", y, dtype, [&](auto tag) {
+        return lrelu_fwd_launch<decltype(tag), true>("affine_lrelu_fwd", y, nullptr, scale, shift, res, out, slope,
+                                                     as_stream(stream));
+    });
 }
 
 // backward, first half: gpre = gout * lrelu'(out) stored, pooled = (sum gpre, sum gpre * xhat) over n and voxels
-template <typename T>
-static int bn_bwd_pool_impl(const ru3d_tensor* gout, const ru3d_tensor* out, const ru3d_tensor* y, const float* a,
-                            const float* b, const ru3d_tensor* gpre, double* pooled, void* ws, float slope,
-                            hipStream_t st) {
-    const int64_t V = (int64_t)y->d * y->h * y->w;
-    const int vec = pick_vec<T>(y->c, {gout, out, y, gpre});
-    ChanLoop cl = make_chanloop(V, y->c, vec, 64, y->n);
-    dim3 grid(cl.chunks, y->n, (cl.G + cl.Gb - 1) / cl.Gb);
-    double* part = (double*)ws;
-#define CALL(TT, VV)                                                                                                  \
-    hipLaunchKernelGGL((reduce2_kernel<TT, VV, 5>), grid, dim3(256), 0, st, (const TT*)gout->ptr, gout->ld,           \
-                       (const TT*)out->ptr, out->ld, (const TT*)y->ptr, y->ld, (const float*)0, a, slope, part, cl,   \
-                       y->c, (TT*)gpre->ptr, gpre->ld, b)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    int rc = ru3d_check_launch("batchnorm_bwd_reduce");
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_pool_kernel, dim3((y->c + FIN_CX - 1) / FIN_CX), dim3(256), 0, st, (const double*)part, cl.chunks,
-                       y->c, y->n, (const float*)0, pooled);
-    return ru3d_check_launch("batchnorm_bwd_pool");
-}
-
 extern "C" int ru3d_batchnorm_bwd_pool(const ru3d_tensor* gout, const ru3d_tensor* out, const ru3d_tensor* y,
                                        const float* a, const float* b, const ru3d_tensor* gpre, double* pooled, void* ws,
                                        size_t ws_bytes, float slope, int dtype, void* stream) {
@@ -1009,33 +976,16 @@ extern "C" int ru3d_batchnorm_bwd_pool(const ru3d_tensor* gout, const ru3d_tenso
     RU3D_REQUIRE(a && b && pooled && ws, "batchnorm_bwd_pool: null pointer");
     RU3D_REQUIRE(ws_bytes >= reduce_ws_bytes(y), "batchnorm_bwd_pool: workspace too small (%zu < %zu)", ws_bytes,
                  reduce_ws_bytes(y));
-    RU3D_REQUIRE((int64_t)y->d * y->h * y->w < (1ll << 31), "batchnorm_bwd_pool: sample too large");
-    if (dtype == RU3D_F32) return bn_bwd_pool_impl<float>(gout, out, y, a, b, gpre, pooled, ws, slope, as_stream(stream));
-    if (dtype == RU3D_BF16) return bn_bwd_pool_impl<bf16>(gout, out, y, a, b, gpre, pooled, ws, slope, as_stream(stream));
-    return ru3d_fail(-1, "batchnorm_bwd_pool: bad dtype %d", dtype);
+    return by_dtype("batchnorm_bwd_pool", y, dtype, [&](auto tag) {
+        ChanLoop cl;
+        int rc = reduce2_launch<decltype(tag), 5>("batchnorm_bwd_reduce", {gout, out, y, gpre}, ws, &cl, as_stream(stream),
+                                                  gout, out, y, nullptr, a, slope, gpre, b);
+        if (rc) return rc;
+        return bn_pool_launch("batchnorm_bwd_pool", ws, cl, y, nullptr, pooled, as_stream(stream));
+    });
 }
 
 // backward, second half: dy = fscale * (gpre - M1 - xhat * M2) with M = pooled / count
-static void bn_m12_launch(const double* pooled, int n, int c, double count, float* m12, hipStream_t st) {
-    hipLaunchKernelGGL(bn_m12_kernel, dim3((n * c + 255) / 256), dim3(256), 0, st, pooled, n, c, 1.0 / count, m12);
-}
-
-template <typename T>
-static int bn_bwd_apply_impl(const ru3d_tensor* gpre, const ru3d_tensor* y, const float* a, const float* b,
-                             const float* fscale, const float* m12, const ru3d_tensor* dy, int zero_far, hipStream_t st) {
-    const int64_t V = (int64_t)y->d * y->h * y->w;
-    const int vec = pick_vec<T>(y->c, {gpre, y, dy});
-    ChanLoop ca = make_chanloop(V, y->c, vec, 16, y->n);
-    dim3 grida(ca.chunks, y->n, (ca.G + ca.Gb - 1) / ca.Gb);
-#define CALL(TT, VV)                                                                                                  \
-    hipLaunchKernelGGL((in_lrelu_bwd_kernel<TT, VV, true, true, true>), grida, dim3(256), 0, st, (const TT*)0, 0,      \
-                       (const TT*)0, 0, (const TT*)y->ptr, y->ld, (const float*)0, a, m12, (TT*)dy->ptr, dy->ld,      \
-                       (TT*)gpre->ptr, gpre->ld, 0.f, zero_far, y->d, y->h, y->w, ca, y->c, b, fscale)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    return ru3d_check_launch("batchnorm_bwd_apply");
-}
-
 extern "C" int ru3d_batchnorm_bwd_apply(const ru3d_tensor* gpre, const ru3d_tensor* y, const float* a, const float* b,
                                         const float* fscale, const double* pooled, double count, const ru3d_tensor* dy,
                                         void* ws, size_t ws_bytes, int zero_far, int dtype, void* stream) {
@@ -1045,33 +995,15 @@ extern "C" int ru3d_batchnorm_bwd_apply(const ru3d_tensor* gpre, const ru3d_tens
     RU3D_REQUIRE(same_shape(y, gpre) && same_shape(y, dy), "batchnorm_bwd_apply: shape mismatch");
     RU3D_REQUIRE(a && b && fscale && pooled && ws && count > 0.0, "batchnorm_bwd_apply: null pointer / bad count");
     RU3D_REQUIRE(ws_bytes >= (size_t)y->n * y->c * 2 * sizeof(float), "batchnorm_bwd_apply: workspace too small");
-    RU3D_REQUIRE((int64_t)y->d * y->h * y->w < (1ll << 31), "batchnorm_bwd_apply: sample too large");
-    float* m12 = (float*)ws;
-    bn_m12_launch(pooled, y->n, y->c, count, m12, as_stream(stream));
-    int rc = ru3d_check_launch("batchnorm_bwd_means");
-    if (rc) return rc;
-    if (dtype == RU3D_F32) return bn_bwd_apply_impl<float>(gpre, y, a, b, fscale, m12, dy, zero_far, as_stream(stream));
-    if (dtype == RU3D_BF16) return bn_bwd_apply_impl<bf16>(gpre, y, a, b, fscale, m12, dy, zero_far, as_stream(stream));
-    return ru3d_fail(-1, "batchnorm_bwd_apply: bad dtype %d", dtype);
-}
-
-template <typename T>
-static int chansum_impl(const ru3d_tensor* t, float* out, void* ws, hipStream_t st) {
-    const int64_t V = (int64_t)t->d * t->h * t->w;
-    const int vec = pick_vec<T>(t->c, {t});
-    ChanLoop cl = make_chanloop(V, t->c, vec, 64, t->n);
-    dim3 grid(cl.chunks, t->n, (cl.G + cl.Gb - 1) / cl.Gb);
-    double* part = (double*)ws;
-#define CALL(TT, VV)                                                                                              \
-    hipLaunchKernelGGL((reduce2_kernel<TT, VV, 2>), grid, dim3(256), 0, st, (const TT*)t->ptr, t->ld, (const TT*)0, \
-                       0, (const TT*)0, 0, (const float*)0, (const float*)0, 0.f, part, cl, t->c)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    int rc = ru3d_check_launch("channel_sum");
-    if (rc) return rc;
-    hipLaunchKernelGGL(chansum_finalize_kernel, dim3((t->c + FIN_CX - 1) / FIN_CX), dim3(256), 0, st, (const double*)part,
-                       cl.chunks, t->c, t->n, out);
-    return ru3d_check_launch("channel_sum_finalize");
+    return by_dtype("batchnorm_bwd_apply", y, dtype, [&](auto tag) {
+        float* m12 = (float*)ws;      // the whole workspace of this call: no partials in front of the means
+        hipLaunchKernelGGL(bn_m12_kernel, dim3((y->n * y->c + 255) / 256), dim3(256), 0, as_stream(stream), pooled, y->n,
+                           y->c, 1.0 / count, m12);
+        int rc = ru3d_check_launch("batchnorm_bwd_means");
+        if (rc) return rc;
+        return bwd_apply_launch<decltype(tag), true, true>("batchnorm_bwd_apply", {gpre, y, dy}, as_stream(stream), nullptr,
+                                                           nullptr, y, nullptr, a, m12, dy, gpre, 0.f, zero_far, b, fscale);
+    });
 }
 
 extern "C" int ru3d_channel_sum(const ru3d_tensor* t, float* out, void* ws, size_t ws_bytes, int dtype,
@@ -1080,50 +1012,14 @@ extern "C" int ru3d_channel_sum(const ru3d_tensor* t, float* out, void* ws, size
     Ru3dDeviceGuard dev_guard(stream);
     RU3D_REQUIRE(tensor_ok(t) && out && ws, "channel_sum: bad argument");
     RU3D_REQUIRE(ws_bytes >= reduce_ws_bytes(t), "channel_sum: workspace too small");
-    RU3D_REQUIRE((int64_t)t->d * t->h * t->w < (1ll << 31), "channel_sum: sample too large");
-    if (dtype == RU3D_F32) return chansum_impl<float>(t, out, ws, as_stream(stream));
-    if (dtype == RU3D_BF16) return chansum_impl<bf16>(t, out, ws, as_stream(stream));
-    return ru3d_fail(-1, "channel_sum: bad dtype %d", dtype);
-}
-
-template <typename T>
-static int copy_add_impl(const ru3d_tensor* a, const ru3d_tensor* b, const ru3d_tensor* dst, hipStream_t st) {
-    const int64_t V = (int64_t)a->d * a->h * a->w;
-    const int vec = pick_vec<T>(a->c, {a, b, dst});
-    ChanLoop cl = make_chanloop(V, a->c, vec, 16, a->n);
-    dim3 grid(cl.chunks, a->n, (cl.G + cl.Gb - 1) / cl.Gb);
-#define CALL(TT, VV)                                                                                                 \
-    if (b)                                                                                                           \
-        hipLaunchKernelGGL((copy_add_kernel<TT, VV, true>), grid, dim3(256), 0, st, (const TT*)a->ptr, a->ld,         \
-                           (const TT*)b->ptr, b->ld, (TT*)dst->ptr, dst->ld, cl);                                    \
-    else                                                                                                             \
-        hipLaunchKernelGGL((copy_add_kernel<TT, VV, false>), grid, dim3(256), 0, st, (const TT*)a->ptr, a->ld,        \
-                           (const TT*)0, 0, (TT*)dst->ptr, dst->ld, cl)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-    return ru3d_check_launch("copy_add");
-}
-
-template <typename T>
-static int pointwise_impl(int op, const ru3d_tensor* a, const ru3d_tensor* b, const ru3d_tensor* c, const ru3d_tensor* o1,
-                          const ru3d_tensor* o2, float slope, hipStream_t st) {
-    const int64_t V = (int64_t)a->d * a->h * a->w;
-    const int vec = pick_vec<T>(a->c, {a, b, c, o1, o2});
-    ChanLoop cl = make_chanloop(V, a->c, vec, 16, a->n);
-    dim3 grid(cl.chunks, a->n, (cl.G + cl.Gb - 1) / cl.Gb);
-#define PW(TT, VV, OPV)                                                                                                \
-    hipLaunchKernelGGL((pointwise_kernel<TT, VV, OPV>), grid, dim3(256), 0, st, (const TT*)a->ptr, a->ld,                \
-                       (const TT*)(b ? b->ptr : nullptr), b ? b->ld : 0, (const TT*)(c ? c->ptr : nullptr),              \
-                       c ? c->ld : 0, (TT*)o1->ptr, o1->ld, (TT*)(o2 ? o2->ptr : nullptr), o2 ? o2->ld : 0, slope, cl)
-#define CALL(TT, VV)              \
-    if (op == 0) PW(TT, VV, 0);   \
-    else if (op == 1) PW(TT, VV, 1); \
-    else if (op == 2) PW(TT, VV, 2); \
-    else PW(TT, VV, 3)
-    DISPATCH_VEC(T, vec, CALL)
-#undef CALL
-#undef PW
-    return ru3d_check_launch("pointwise");
+    return by_dtype("channel_sum", t, dtype, [&](auto tag) {
+        ChanLoop cl;
+        int rc = reduce2_launch<decltype(tag), 2>("channel_sum", {t}, ws, &cl, as_stream(stream), t);
+        if (rc) return rc;
+        hipLaunchKernelGGL(chansum_finalize_kernel, dim3((t->c + FIN_CX - 1) / FIN_CX), dim3(256), 0, as_stream(stream),
+                           (const double*)ReduceWs(ws, t->n, t->c, cl.chunks).part, cl.chunks, t->c, t->n, out);
+        return ru3d_check_launch("channel_sum_finalize");
+    });
 }
 
 extern "C" int ru3d_pointwise(int op, const ru3d_tensor* a, const ru3d_tensor* b, const ru3d_tensor* c,
@@ -1135,20 +1031,44 @@ extern "C" int ru3d_pointwise(int op, const ru3d_tensor* a, const ru3d_tensor* b
     RU3D_REQUIRE(op < 1 || (tensor_ok(b) && same_shape(a, b)), "pointwise: op %d needs b", op);
     RU3D_REQUIRE(op < 2 || (tensor_ok(c) && same_shape(a, c) && tensor_ok(o2) && same_shape(a, o2)),
                  "pointwise: op %d needs c and o2", op);
-    RU3D_REQUIRE((int64_t)a->d * a->h * a->w < (1ll << 31), "pointwise: sample too large");
-    if (dtype == RU3D_F32) return pointwise_impl<float>(op, a, b, c, o1, o2, slope, as_stream(stream));
-    if (dtype == RU3D_BF16) return pointwise_impl<bf16>(op, a, b, c, o1, o2, slope, as_stream(stream));
-    return ru3d_fail(-1, "pointwise: bad dtype %d", dtype);
+    return by_dtype("pointwise", a, dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return chan_launch<T>("pointwise", {a, b, c, o1, o2}, 16, [&](auto vec, dim3 grid, const ChanLoop& cl) {
+            auto pw = [&](auto opc) {
+                hipLaunchKernelGGL((pointwise_kernel<T, decltype(vec)::value, decltype(opc)::value>), grid, dim3(256), 0,
+                                   as_stream(stream), tptr<const T>(a), a->ld, tptr<const T>(b), tld(b), tptr<const T>(c),
+                                   tld(c), tptr<T>(o1), o1->ld, tptr<T>(o2), tld(o2), slope, cl);
+            };
+            switch (op) {
+                case 0: pw(int_c<0>{}); break;
+                case 1: pw(int_c<1>{}); break;
+                case 2: pw(int_c<2>{}); break;
+                default: pw(int_c<3>{}); break;
+            }
+        });
+    });
+}
+
+// dst = a (+ b)
+static int copy_add(const char* name, const ru3d_tensor* a, const ru3d_tensor* b, const ru3d_tensor* dst, int dtype,
+                    void* stream) {
+    return by_dtype(name, a, dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return chan_launch<T>("copy_add", {a, b, dst}, 16, [&](auto vec, dim3 grid, const ChanLoop& cl) {
+            with_bool(b != nullptr, [&](auto add) {
+                hipLaunchKernelGGL((copy_add_kernel<T, decltype(vec)::value, decltype(add)::value>), grid, dim3(256), 0,
+                                   as_stream(stream), tptr<const T>(a), a->ld, tptr<const T>(b), tld(b), tptr<T>(dst),
+                                   dst->ld, cl);
+            });
+        });
+    });
 }
 
 extern "C" int ru3d_copy_channels(const ru3d_tensor* src, const ru3d_tensor* dst, int dtype, void* stream) {
     RU3D_FWD_F16(dtype, ru3d_copy_channels_f16(src, dst, dtype, stream));
     Ru3dDeviceGuard dev_guard(stream);
     RU3D_REQUIRE(tensor_ok(src) && tensor_ok(dst) && same_shape(src, dst), "copy_channels: bad tensors");
-    RU3D_REQUIRE((int64_t)src->d * src->h * src->w < (1ll << 31), "copy_channels: sample too large");
-    if (dtype == RU3D_F32) return copy_add_impl<float>(src, nullptr, dst, as_stream(stream));
-    if (dtype == RU3D_BF16) return copy_add_impl<bf16>(src, nullptr, dst, as_stream(stream));
-    return ru3d_fail(-1, "copy_channels: bad dtype %d", dtype);
+    return copy_add("copy_channels", src, nullptr, dst, dtype, stream);
 }
 
 extern "C" int ru3d_add(const ru3d_tensor* a, const ru3d_tensor* b, const ru3d_tensor* dst, int dtype,
@@ -1157,11 +1077,9 @@ extern "C" int ru3d_add(const ru3d_tensor* a, const ru3d_tensor* b, const ru3d_t
     Ru3dDeviceGuard dev_guard(stream);
     RU3D_REQUIRE(tensor_ok(a) && tensor_ok(b) && tensor_ok(dst) && same_shape(a, b) && same_shape(a, dst),
                  "add: bad tensors");
-    RU3D_REQUIRE((int64_t)a->d * a->h * a->w < (1ll << 31), "add: sample too large");
-    if (dtype == RU3D_F32) return copy_add_impl<float>(a, b, dst, as_stream(stream));
-    if (dtype == RU3D_BF16) return copy_add_impl<bf16>(a, b, dst, as_stream(stream));
-    return ru3d_fail(-1, "add: bad dtype %d", dtype);
+    return copy_add("add", a, b, dst, dtype, stream);
 }
+
 
 // fp32 -> storage dtype (small tensors: the 2..4-channel logits gradient)
 template <typename T>

@@ -24,6 +24,8 @@ if not torch.cuda.is_available():
 
 import _native as N  # noqa: E402
 import _ops as ops  # noqa: E402
+# make_chanloop and the workspace layout restated: what the launches write, maximised over the widths pick_vec may choose
+from test_host_norm_ws import chanloop as _chanloop, ws_need as _ws_need  # noqa: E402
 
 DEV = torch.device("cuda:0")
 BF16, FP16, FP32 = torch.bfloat16, torch.float16, torch.float32
@@ -76,23 +78,6 @@ def _vec(dt, c, *slabs):
             break
         vec //= 2
     return vec
-
-
-def _chanloop(V, c, vec, max_iters, n):
-    """make_chanloop restated -> (G, Gb, vpb, span, chunks)"""
-    G = c // vec
-    Gb = min(G, 256)
-    vpb = 256 // Gb
-    gz = -(-G // Gb)
-    iters = -(-(V * n * gz) // (vpb * 2048))
-    iters = min(max(iters, 4), max_iters)
-    span = vpb * iters
-    chunks = -(-V // span)
-    if chunks > 4096:
-        span = -(-V // 4096)
-        span = -(-span // vpb) * vpb
-        chunks = -(-V // span)
-    return G, Gb, vpb, span, chunks
 
 
 def _geom(dt, n, c, dims, vec, max_iters=64):
@@ -414,22 +399,6 @@ class GuardedWs:
         assert bool((self.buf[hi:] == 0xA5).all()), "%s wrote behind its %d bytes of workspace" % (what, self.nbytes)
 
 
-def _ws_need(n, c, V, itemsize):
-    """What the launches write, from make_chanloop, maximised over the widths pick_vec may choose: the reduction partials
-    (n * chunks * C pairs of doubles, 64 iterations at most), m12 rounded up to 256 bytes and, with dy_sum, the apply pass's
-    partials (16 iterations at most)."""
-    need = 0
-    vec = 16 // itemsize
-    while vec >= 1:
-        if c % vec == 0:
-            chunks = _chanloop(V, c, vec, 64, n)[4]
-            chunks_a = _chanloop(V, c, vec, 16, n)[4]
-            m12 = -(-(n * c * 8) // 256) * 256
-            need = max(need, n * chunks * c * 16 + m12 + n * chunks_a * c * 16)
-        vec //= 2
-    return need
-
-
 # Few voxels, where chunks equals the bound of reduce_ws_bytes and only its + 512 covers the rounding of m12 to 256 bytes.
 # V = 1 and 2 run in the 16-bit types only: there y^2 is exact in a float, so the kernel's statistics are exact sums and
 # scale keeps its 2e-6 bound even where a channel's voxels coincide (V = 1: var = 0; V = 2: var = ((a - b) / 2)^2 falls to
@@ -745,3 +714,126 @@ def test_repack_pitched(c, v, dt):
     back = torch.full((n, c) + dims, float("nan"), dtype=torch.float32, device=DEV)
     N.check(N.lib.ru3d_ndhwc_to_ncdhw(N.ref(dd), N.ptr(back), code, N.stream(DEV)), "ndhwc_to_ncdhw")
     assert back.is_contiguous() and torch.equal(back.cpu(), xv.to(dt).float()), "ndhwc_to_ncdhw != stored values"
+
+
+# --------------------------------------------------------------------------- 6. launch sequences
+# What every entry point of the family launches, in order, as the launch log reports it.  n = 2, C = 12, (3, 5, 7) at dense
+# pitch: width 4 in every type, and C % 8 != 0 keeps the backward on norm.hip's launches.
+LOG_SHAPE = (2, 12, (3, 5, 7))
+_IN_BWD = "in_lrelu_bwd_reduce;in_lrelu_bwd_finalize;in_lrelu_bwd_apply"
+
+
+def _call_stats(o):
+    return N.lib.ru3d_instnorm_stats(o["y"], None, o["mean"], o["scale"], o["ws"], o["nbytes"], IN_EPS, o["code"], o["st"])
+
+
+def _call_in_fwd(o):
+    return N.lib.ru3d_in_lrelu_fwd(o["y"], o["mean"], o["scale"], o["res"], o["out"], SLOPE, o["code"], o["st"])
+
+
+def _call_in_bwd(o, gpre, dsum):
+    return N.lib.ru3d_in_lrelu_bwd(o["gout"], o["act"], o["y"], o["mean"], o["scale"], o["dy"], o["gpre"] if gpre else None,
+                                   o["ws"], o["nbytes"], SLOPE, 0, None, o["dsum"] if dsum else None, o["code"], o["st"])
+
+
+def _call_in_bwd_apply(o):
+    return N.lib.ru3d_in_lrelu_bwd_apply(o["gout"], o["act"], o["mean"], o["scale"], o["m12"], o["dy"], SLOPE, 0, o["code"],
+                                         o["st"])
+
+
+def _call_bn_stats_pool(o):
+    return N.lib.ru3d_batchnorm_stats_pool(o["y"], None, o["pooled"], o["ws"], o["nbytes"], o["code"], o["st"])
+
+
+def _call_affine_fwd(o):
+    return N.lib.ru3d_affine_lrelu_fwd(o["y"], o["scale"], o["mean"], o["res"], o["out"], SLOPE, o["code"], o["st"])
+
+
+def _call_bn_bwd_pool(o):
+    return N.lib.ru3d_batchnorm_bwd_pool(o["gout"], o["act"], o["y"], o["scale"], o["mean"], o["gpre"], o["pooled"], o["ws"],
+                                         o["nbytes"], SLOPE, o["code"], o["st"])
+
+
+def _call_bn_bwd_apply(o):
+    return N.lib.ru3d_batchnorm_bwd_apply(o["gout"], o["y"], o["scale"], o["mean"], o["scale"], o["pooled"], 210.0, o["dy"],
+                                          o["ws"], o["nbytes"], 0, o["code"], o["st"])
+
+
+def _call_pointwise(o, op):
+    return N.lib.ru3d_pointwise(op, o["act"], o["y"] if op else None, o["gout"] if op else None, o["out"],
+                                o["dy"] if op else None, SLOPE, o["code"], o["st"])
+
+
+LAUNCHES = [
+    ("instnorm_stats", _call_stats, "instnorm_stats;instnorm_stats_finalize"),
+    ("in_lrelu_fwd", _call_in_fwd, "in_lrelu_fwd"),
+    ("in_lrelu_bwd", lambda o: _call_in_bwd(o, False, False), _IN_BWD),
+    ("in_lrelu_bwd_gpre", lambda o: _call_in_bwd(o, True, False), _IN_BWD),
+    ("in_lrelu_bwd_dysum", lambda o: _call_in_bwd(o, False, True), _IN_BWD + ";in_lrelu_bwd_dysum_finalize"),
+    ("in_lrelu_bwd_gpre_dysum", lambda o: _call_in_bwd(o, True, True), _IN_BWD + ";in_lrelu_bwd_dysum_finalize"),
+    ("in_lrelu_bwd_apply", _call_in_bwd_apply, "in_lrelu_bwd_apply"),
+    ("batchnorm_stats_pool", _call_bn_stats_pool, "batchnorm_stats_reduce;batchnorm_stats_pool"),
+    ("affine_lrelu_fwd", _call_affine_fwd, "affine_lrelu_fwd"),
+    ("batchnorm_bwd_pool", _call_bn_bwd_pool, "batchnorm_bwd_reduce;batchnorm_bwd_pool"),
+    ("batchnorm_bwd_apply", _call_bn_bwd_apply, "batchnorm_bwd_means;batchnorm_bwd_apply"),
+    ("channel_sum", lambda o: N.lib.ru3d_channel_sum(o["y"], o["dsum"], o["ws"], o["nbytes"], o["code"], o["st"]),
+     "channel_sum;channel_sum_finalize"),
+    ("copy_channels", lambda o: N.lib.ru3d_copy_channels(o["y"], o["out"], o["code"], o["st"]), "copy_add"),
+    ("add", lambda o: N.lib.ru3d_add(o["y"], o["res"], o["out"], o["code"], o["st"]), "copy_add"),
+    ("pointwise_op0", lambda o: _call_pointwise(o, 0), "pointwise"),
+    ("pointwise_op3", lambda o: _call_pointwise(o, 3), "pointwise"),
+]
+
+
+def _log_operands(dt):
+    """descriptors and pointers of one set of dense operands, built once per dtype; the inputs are never modified"""
+    key = ("launch log", dt)
+    if key not in _INPUTS:
+        n, c, dims = LOG_SHAPE
+        g = torch.Generator().manual_seed(12)
+        rnd = lambda: torch.randn((n, c) + dims, generator=g)   # noqa: E731
+        slabs = {"y": Slab(n, c, dims, None, dt, rnd() * 1.5 + 0.2), "res": Slab(n, c, dims, None, dt, rnd() * 0.5),
+                 "gout": Slab(n, c, dims, None, dt, rnd()), "act": Slab(n, c, dims, None, dt, rnd()),
+                 "out": Slab(n, c, dims, None, dt), "dy": Slab(n, c, dims, None, dt), "gpre": Slab(n, c, dims, None, dt)}
+        assert _vec(dt, c, *slabs.values()) == 4
+        assert _not_small(dt, c, dims, *slabs.values())
+        descs = {k: s.desc() for k, s in slabs.items()}
+        nbytes = N.lib.ru3d_reduce_workspace_bytes(N.ref(descs["y"]))
+        tens = {"mean": torch.randn(n * c, generator=g).to(DEV), "scale": (torch.rand(n * c, generator=g) + 0.5).to(DEV),
+                "m12": torch.randn(n * c * 2, generator=g).to(DEV), "dsum": torch.empty(c, dtype=torch.float32, device=DEV),
+                "pooled": torch.randn(2 * c, generator=g).double().to(DEV), "ws": _ws(nbytes)}
+        o = {k: N.ref(d) for k, d in descs.items()}
+        o.update({k: N.ptr(t) for k, t in tens.items()})
+        o.update(code=N.dtype_code(dt), st=N.stream(DEV), nbytes=nbytes)
+        _INPUTS[key] = (o, slabs, descs, tens)          # the descriptors and tensors stay alive with their pointers
+    return _INPUTS[key][0]
+
+
+@pytest.mark.parametrize("dt", [BF16, FP32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("name,call,want", LAUNCHES, ids=[case[0] for case in LAUNCHES])
+def test_launch_sequence(name, call, want, dt):
+    o = _log_operands(dt)
+    N.lib.ru3d_launch_log_begin()
+    rc = call(o)
+    got = N.lib.ru3d_launch_log_end().decode()
+    N.check(rc, name)
+    torch.cuda.synchronize()
+    assert got == want
+
+
+def test_launch_sequence_head_in_bwd():
+    """ru3d_head_in_bwd on the smallest shape it takes and in_small_mode refuses (C = 32, 3 classes, V = 8400 > 8192):
+    head_bwd_launch's two names, then the head's own three."""
+    n, c, hc, dims = 1, 32, 3, (21, 20, 20)
+    g = torch.Generator().manual_seed(32)
+    z = ops.as_input((torch.randn((n, c) + dims, generator=g)).to(DEV), BF16)
+    y = ops.as_input((torch.randn((n, c) + dims, generator=g) * 1.5 + 0.2).to(DEV), BF16)
+    gy = N.to_ndhwc((torch.randn((n, hc) + dims, generator=g) * 1e-2).to(DEV))
+    hw = (torch.randn(hc, c, 1, 1, 1, generator=g) * 0.3).to(DEV)
+    mean, scale = ops.in_stats(y)
+    N.lib.ru3d_launch_log_begin()
+    out = ops.head_in_bwd(z, gy, hw, True, y, mean, scale)
+    got = N.lib.ru3d_launch_log_end().decode()
+    torch.cuda.synchronize()
+    assert out is not None, "no fused kernel"
+    assert got == "head_bwd_wgrad;head_bwd_finalize;head_in_bwd_reduce;head_in_bwd_finalize;head_in_bwd_apply"
