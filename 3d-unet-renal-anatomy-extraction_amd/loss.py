@@ -69,7 +69,8 @@ def dice(input, target, alpha=0.5, beta=0.5, smooth=1e-7):
         g = target.detach().reshape(-1).float().contiguous()
         out = torch.empty((), dtype=torch.float32, device=p.device)
         N.note_device(p.device)
-        ws = N.workspace(1024 * 3 * 8, p.device)
+        # ru3d_tversky's layout: one row of three float64 sums per block of 2048 elements, at most 1024 blocks
+        ws = N.workspace(min((p.numel() + 2047) // 2048, 1024) * 3 * 8, p.device)
         check(N.lib.ru3d_tversky(ptr(p), ptr(g), p.numel(), alpha, beta, smooth, ptr(out), ptr(ws), ws.numel(),
                                  stream()), "tversky")
         return out

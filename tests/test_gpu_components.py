@@ -181,7 +181,7 @@ def test_bad_arguments_are_refused_before_any_launch():
     mask = torch.zeros((8, 8, 8), dtype=torch.uint8, device=DEV)
     labels = torch.full((8, 8, 8), 77, dtype=torch.int32, device=DEV)
     count = torch.full((1,), 77, dtype=torch.int32, device=DEV)
-    ws = torch.zeros(1 << 16, dtype=torch.uint8, device=DEV)
+    ws = torch.empty(1 << 16, dtype=torch.uint8, device=DEV).fill_(0xFF)
     st = N.stream(DEV)
     p = lambda t: ctypes.c_void_p(t.data_ptr())
     calls = [lib.ru3d_label_components(p(mask), 2048, 1024, 1024, p(labels), p(count), p(ws), ws.numel(), st),

@@ -263,9 +263,10 @@ def c_abi(x, y, groups, kind=N.LOSS_HYBIRD, gamma=2.0, dz_dtypes=(N.F32,), ignor
     table = L.group_table(groups)
     st = L._flat_strides(x)
     N.note_device(x.device)
-    state = torch.zeros(N.lib.ru3d_group_loss_state_bytes(), dtype=torch.uint8, device=DEV)
+    # what production hands over is torch.empty: the forward initialises the state block and its scratch itself
+    state = torch.empty(N.lib.ru3d_group_loss_state_bytes(), dtype=torch.uint8, device=DEV).fill_(0xFF)
     out = torch.empty((), device=DEV)
-    ws = torch.empty(N.lib.ru3d_group_loss_workspace_bytes(n, v, k), dtype=torch.uint8, device=DEV)
+    ws = torch.empty(N.lib.ru3d_group_loss_workspace_bytes(n, v, k), dtype=torch.uint8, device=DEV).fill_(0xFF)
     code = N.LABEL_I64 if y.dtype == torch.int64 else N.LABEL_U8
     group = (k, table, len(table), 0 if ignore is None else 1, 0 if ignore is None else ignore)
     N.check(N.lib.ru3d_group_loss_fwd(N.ptr(x), st[0], st[1], st[2], N.ptr(y), code, n, v, *group, kind, gamma, None,

@@ -379,9 +379,10 @@ def test_same_input_same_bits():
 def _abi_fwd_bwd(x, y, c, kind, gamma, out_dtype, upstream=None):
     n, v = x.shape[0], x[0, 0].numel()
     st = L._flat_strides(x)
-    state = torch.zeros(N.lib.ru3d_loss_state_bytes(c), dtype=torch.uint8, device=DEV)
-    out = torch.zeros((), dtype=torch.float32, device=DEV)
-    ws = torch.zeros(N.lib.ru3d_loss_workspace_bytes(n, v, c), dtype=torch.uint8, device=DEV)
+    # what production hands over is torch.empty: the forward initialises state, output and scratch itself
+    state = torch.empty(N.lib.ru3d_loss_state_bytes(c), dtype=torch.uint8, device=DEV).fill_(0xFF)
+    out = torch.full((), float("nan"), dtype=torch.float32, device=DEV)
+    ws = torch.empty(N.lib.ru3d_loss_workspace_bytes(n, v, c), dtype=torch.uint8, device=DEV).fill_(0xFF)
     N.note_device(DEV)
     N.check(N.lib.ru3d_loss_fwd(N.ptr(x), st[0], st[1], st[2], N.ptr(y), N.LABEL_I64, n, v, c, KIND_CODE[kind],
                                 float(gamma), None, 0.5, 0.5, 1e-7, N.ptr(state), N.ptr(out), N.ptr(ws), ws.numel(),

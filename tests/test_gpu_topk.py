@@ -424,10 +424,11 @@ def test_state_block():
     n, c, v = 2, 3, 2049
     kk = L.topk_count(n * v, 10)
     N.note_device(DEV)
-    state = torch.zeros(N.lib.ru3d_topk_loss_state_bytes(), dtype=torch.uint8, device=DEV)
+    # what production hands over is torch.empty: the forward initialises the state block and its scratch itself
+    state = torch.empty(N.lib.ru3d_topk_loss_state_bytes(), dtype=torch.uint8, device=DEV).fill_(0xFF)
     out = torch.empty((), device=DEV)
     ce = torch.full((n * v,), -1.0, device=DEV)
-    ws = torch.empty(N.lib.ru3d_topk_loss_workspace_bytes(n, v, c), dtype=torch.uint8, device=DEV)
+    ws = torch.empty(N.lib.ru3d_topk_loss_workspace_bytes(n, v, c), dtype=torch.uint8, device=DEV).fill_(0xFF)
     N.check(N.lib.ru3d_topk_loss_fwd(N.ptr(dx), c * v, v, 1, N.ptr(dy), N.LABEL_I64, n, v, c, kk, 1, None, 0.5, 0.5, 1e-7,
                                      0.5, N.ptr(ce), N.ptr(state), N.ptr(out), N.ptr(ws), ws.numel(), N.stream()), "fwd")
     off = N.lib.ru3d_loss_state_bad_labels_offset()
