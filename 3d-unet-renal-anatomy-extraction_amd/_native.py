@@ -224,6 +224,13 @@ SIGNATURES = {
     "ru3d_filter_components": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_region_accumulate": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     "ru3d_cascade_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ru3d_label_moments": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ru3d_label_faces": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ru3d_label_extents": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ru3d_label_feret_count": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ru3d_label_feret_fill": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ru3d_label_feret": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, ctypes.POINTER(_dbl), _vp, _vp, _vp, _vp,
+                              _vp]),
     "ru3d_mask_bytes": (_sz, [_i, _i, _i]),
     "ru3d_mask_pack": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ru3d_mask_unpack": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),

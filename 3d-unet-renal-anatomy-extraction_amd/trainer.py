@@ -1166,6 +1166,135 @@ def batch_extract_mesh(pred_dir, save_dir, data_range=None, fmt='stl', device=No
             for i in (data_range if data_range is not None else range(len(pred_files)))]
 
 
+# ------------------------------------------------------------------ morphometry: the numbers of a report
+def _entry_mask(volume, values):
+    """uint8 0 / 1 volume of the voxels of `volume` (numpy or HIP, uint8) that carry one of `values`."""
+    if torch.is_tensor(volume):
+        mask = volume == values[0]
+        for v in values[1:]:
+            mask |= volume == v
+        return mask.view(torch.uint8)
+    return np.isin(volume, values).view(np.uint8)
+
+
+def _entry_components(mask, min_voxels):
+    """(int32 labels, K) of the 6-connected components of `mask` with at least `min_voxels` voxels, numbered in the
+    order of their first voxel among the survivors (scipy's numbering when nothing is dropped)."""
+    import transform
+    labels, count = transform.label_components(mask)
+    if count == 0 or min_voxels <= 1:
+        return labels, count
+    if torch.is_tensor(labels):
+        import components
+        sizes, _ = components.stats(labels, count)
+        return components.filter_small(labels, count, sizes, min_voxels, relabel=True)
+    keep = np.bincount(labels.ravel(), minlength=count + 1)[1:] >= min_voxels
+    remap = np.r_[0, np.where(keep, np.cumsum(keep), 0)].astype(labels.dtype)
+    return remap[labels], int(keep.sum())
+
+
+def measure_case(case, key='pred', labels=None, components=False, min_voxels=0, gaps=(), return_device=False):
+    """The morphometry of the label volume `case[key]` (csrc/morphometry.hip, morphometry.describe): a dict with
+      case_id     the case's, when it has one,
+      structures  one dict per measured structure: `label` (the value, or the tuple of values of a union) and the fields
+                  of morphometry.describe - voxels, volume_mm3, centroid, principal axes and their extents, the longest
+                  diameter with its end points, surface, contact area per class and exposed fraction - in the world
+                  coordinates of `case['affine']` (voxel units without one),
+      gaps        one dict per pair of `gaps`: a, b (two label entries) and gap_mm, their smallest distance in mm.
+    labels: entries as in extract_mesh_case, None = every non-zero value the volume holds.  components=True splits every entry into its
+    6-connected components, drops those below min_voxels and measures each one (`component` = its number in scipy's
+    order).  Contact is counted against the class volume itself.  A numpy volume takes the numpy route; a HIP volume -
+    for instance `cascade_predict_case(..., return_device=True)['pred']` - never leaves the device: the kernels fill
+    small tables and only those are downloaded.  return_device=True downloads nothing: every structure is `label`,
+    `count` and the raw tables `moments`, `faces`, `feret_d2`, `feret_pair` where the volume lives."""
+    import morphometry
+    volume = case[key]
+    affine = np.asarray(case['affine'], dtype=np.float64) if case.get('affine') is not None else None
+    hip = _is_hip(volume)
+    if hip:
+        volume = _device_bytes(volume, volume.device)
+    else:
+        volume = np.asarray(volume.cpu() if torch.is_tensor(volume) else volume)
+        if volume.dtype != np.uint8:
+            volume = np.clip(volume, 0, 255).astype(np.uint8)
+    ndim = volume.dim() if hip else volume.ndim
+    if ndim < 1 or ndim > 3:
+        raise ValueError("measure_case: case[%r] has shape %s (1 to 3 axes)" % (key, tuple(volume.shape)))
+    top = int(volume.max()) if volume.shape and min(volume.shape) > 0 else 0
+    if labels is None:                          # every value the volume holds, not every value up to a stray 255
+        labels = [v for v in (torch.unique(volume) if hip else np.unique(volume)).tolist() if v >= 1]
+    masks = {}
+
+    def mask_of(values):
+        if values not in masks:
+            masks[values] = _entry_mask(volume, values)
+        return masks[values]
+
+    structures = []
+    for name, values in _mesh_labels(labels, top):
+        ids, count = mask_of(values), 1
+        if components:
+            ids, count = _entry_components(ids, min_voxels)
+        if return_device:
+            d2, pair = morphometry.feret(ids, count, morphometry.gram(affine))
+            structures.append({'label': name, 'count': count, 'moments': morphometry.moments(ids, count),
+                               'faces': morphometry.faces(ids, count, volume, top + 1), 'feret_d2': d2, 'feret_pair': pair})
+            continue
+        for d in morphometry.describe(ids, count, affine=affine, other=volume, num_other=top + 1):
+            d['label'] = name
+            if components:
+                d['component'] = d['id']
+            del d['id']
+            structures.append(d)
+    A = affine[:3, :3] if affine is not None else np.eye(3)
+    sampling = tuple(float(s) for s in np.linalg.norm(A, axis=0)[3 - ndim:])
+    found = []
+    for a, b in gaps:
+        (name_a, values_a), (name_b, values_b) = _mesh_labels((a, b), top)
+        found.append({'a': name_a, 'b': name_b, 'gap_mm': morphometry.gap_mm(mask_of(values_a), mask_of(values_b), sampling)})
+    result = {'structures': structures, 'gaps': found}
+    if 'case_id' in case:
+        result['case_id'] = case['case_id']
+    return result
+
+
+def measure(pred_file, save_dir=None, device=None, **options):
+    """measure_case of a NIfTI label volume (a `*.pred.nii.gz` of save_pred, or a ground-truth segmentation) with the
+    file's affine.  save_dir: the result is written as `<case_id>.json`.  device: a HIP device uploads the volume (as
+    bytes) and measures there.  options: labels, components, min_voxels, gaps.  Prints one line per structure."""
+    import nifti
+    from pathlib import Path
+    from utils import json_save
+    pred_file = Path(pred_file)
+    case_id = pred_file.name
+    for suffix in ('.gz', '.nii', '.pred'):
+        if case_id.endswith(suffix):
+            case_id = case_id[:-len(suffix)]
+    pred, affine, _ = nifti.load(pred_file)
+    pred = np.ascontiguousarray(np.clip(pred, 0, 255).astype(np.uint8))
+    case = {'case_id': case_id, 'affine': affine, 'pred': pred if device is None else torch.from_numpy(pred).to(device)}
+    result = measure_case(case, 'pred', **options)
+    for d in result['structures']:
+        if d['voxels']:
+            print("%s label_%s%s: %.3f ml, longest diameter %.1f mm, surface %.1f mm^2, %.0f %% exposed"
+                  % (case_id, _label_name(d['label']), ' #%d' % d['component'] if 'component' in d else '',
+                     d['volume_mm3'] / 1000.0, d['feret_mm'], d['surface_mm2'], 100.0 * d['exposed_fraction']))
+    if save_dir is not None:
+        save_dir = Path(save_dir)
+        save_dir.mkdir(parents=True, exist_ok=True)
+        result['file'] = str(save_dir / ('%s.json' % case_id))
+        json_save(result['file'], result)
+    return result
+
+
+def batch_measure(pred_dir, save_dir, data_range=None, device=None, **options):
+    """measure over the sorted *.nii.gz files of `pred_dir`; returns the per-file results."""
+    from pathlib import Path
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    return [measure(pred_files[i], save_dir, device, **options)
+            for i in (data_range if data_range is not None else range(len(pred_files)))]
+
+
 # ------------------------------------------------------------------ centrelines of the tubular structures
 def _ratio(num, den):
     return num / den if den else math.nan

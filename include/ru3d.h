@@ -546,6 +546,45 @@ int ru3d_region_accumulate(const float* prob, int rx, int ry, int rz, int num_cl
 int ru3d_cascade_merge(const double* total, const int32_t* hits, int X, int Y, int Z, int num_classes, uint8_t* out,
                        void* stream);
 
+/* ------------------------------------------------------------------ morphometry of a label volume */
+/* What a report says about every structure (csrc/morphometry.hip).  ids: a uint8 class volume (id_bytes = 1) or an
+ * int32 component-label volume (id_bytes = 4), [X, Y, Z] with Z contiguous, X*Y*Z < 2^31, any alignment.  Ids
+ * 1 .. count are measured; 0 and every value above `count` (a stray 255 ignore label) is skipped silently.  Every
+ * output is written in full by the call, whatever it held before, and nothing but the outputs is written; no entry
+ * point needs scratch.  Integer atomics and 64-bit min / max only: exact, and the same bytes in every run.  count = 0
+ * launches nothing.  The grids are sized by ru3d_get_cu_budget().
+ *
+ * moments: table (int64 [count][10]) = n, Sx, Sy, Sz, Sxx, Syy, Szz, Sxy, Sxz, Syz over the voxel indices of each id.
+ * Refused when X*Y*Z * (largest extent - 1)^2 reaches 2^63. */
+int ru3d_label_moments(const void* ids, int id_bytes, int X, int Y, int Z, int count, int64_t* table, void* stream);
+/* faces: other is a uint8 volume over the same grid with classes 0 .. num_other - 1 (num_other <= 256).  table (int64
+ * [count][num_other + 1][3]): for every voxel p of id k and each of its six neighbours q, a q outside the volume counts
+ * in column num_other, a q inside with ids[q] != k counts in column other[q]; the last index is the axis of the shared
+ * face.  A value of other[q] at or above num_other counts nowhere.  other may be `ids` itself (class mode). */
+int ru3d_label_faces(const void* ids, int id_bytes, const uint8_t* other, int num_other, int X, int Y, int Z, int count,
+                     int64_t* table, void* stream);
+/* extents: frames (device float64 [count][3][4]) holds three rows (ax, ay, az, b) per id; out (float64 [count][3][2]) =
+ * the minimum and the maximum of t = ax x + ay y + az z + b over the id's voxels, (+inf, -inf) for an id without one. */
+int ru3d_label_extents(const void* ids, int id_bytes, int X, int Y, int Z, int count, const double* frames, double* out,
+                       void* stream);
+/* The longest centre-to-centre distance inside each id under the metric d^2 = D^T G D.  Candidates are the first and the
+ * last voxel of the id in every (x, y) row along Z: no other voxel is an extreme point of the id's voxel set.
+ * count: counts (int64 [count]) = candidates per id.
+ * fill: starts (int64 [count]) = where each id's group begins in `candidates` (int32 [capacity], linear voxel indices;
+ * the exclusive prefix sums of counts, made by the caller); filled (int64 [count]) leaves equal to counts.  Inside a
+ * group the order is not defined; nothing is written at or beyond `capacity`, and only the groups are written.
+ * feret: total = the filled prefix of `candidates`; gram: HOST float64 [6] = G00, G11, G22, G01, G02, G12.  row_d2
+ * (float64 [total]) and row_partner (int32 [total]) receive, per candidate, its largest squared distance to a candidate
+ * of its id and the linear index that reaches it.  out_d2 (float64 [count]) = the largest of them, out_pair (int32
+ * [count][6]) = (x, y, z) of its two voxels; ties go to the smallest pair of linear indices.  An id of one voxel gives 0
+ * and the voxel twice, an id without a voxel -1 and six times -1. */
+int ru3d_label_feret_count(const void* ids, int id_bytes, int X, int Y, int Z, int count, int64_t* counts, void* stream);
+int ru3d_label_feret_fill(const void* ids, int id_bytes, int X, int Y, int Z, int count, const int64_t* starts,
+                          int64_t* filled, int32_t* candidates, int64_t capacity, void* stream);
+int ru3d_label_feret(const void* ids, int id_bytes, int X, int Y, int Z, int count, const int32_t* candidates,
+                     int64_t total, const int64_t* starts, const int64_t* counts, const double* gram, double* row_d2,
+                     int32_t* row_partner, double* out_d2, int32_t* out_pair, void* stream);
+
 /* ------------------------------------------------------------------ binary morphology on packed masks + confusion table */
 /* The clean-up and the evaluation of a prediction (nb_post.py:88-112, nb.py:11-37) on volumes that stay in HBM.
  * A packed mask holds 64 voxels of the contiguous Z axis per 64-bit word: bit b of word w of row (x, y) is voxel
