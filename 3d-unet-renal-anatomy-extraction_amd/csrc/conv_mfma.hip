@@ -1291,10 +1291,27 @@ __global__ __launch_bounds__(256) void stats_slab_finalize_kernel(const float* _
     if (c < C) {
         const int y = c / cb, cl = c % cb;
         const int parts = gx * 4;   // (workgroup x, wave) pairs that hold channel c
-        for (int p = lane; p < parts; p += 64) {
-            const float* e = slab + ((((int64_t)(y * gx + (p >> 2)) * 4 + (p & 3)) * N + n) * cb + cl) * 2;
-            a1 += (double)e[0];
-            a2 += (double)e[1];
+        // the lane's chain over p = lane, lane + 64, ... ascending, SLAB_BATCH pairs loaded before the first add (one
+        // round trip for up to 256 workgroups per row, where every pair used to wait for the one before); a pair past
+        // the end is loaded from the batch's first and not added
+        constexpr int SLAB_BATCH = 16;
+        for (int p0 = lane; p0 < parts; p0 += 64 * SLAB_BATCH) {
+            float e0[SLAB_BATCH], e1[SLAB_BATCH];
+#pragma unroll
+            for (int j = 0; j < SLAB_BATCH; j++) {
+                const int p = p0 + 64 * j < parts ? p0 + 64 * j : p0;
+                const float* e = slab + ((((int64_t)(y * gx + (p >> 2)) * 4 + (p & 3)) * N + n) * cb + cl) * 2;
+                e0[j] = e[0];
+                e1[j] = e[1];
+            }
+            __builtin_amdgcn_sched_barrier(0);      // or the scheduler pairs every load with its add to save registers
+#pragma unroll
+            for (int j = 0; j < SLAB_BATCH; j++) {
+                if (p0 + 64 * j < parts) {
+                    a1 += (double)e0[j];
+                    a2 += (double)e1[j];
+                }
+            }
         }
     }
     const double t1 = wave_sum_d(a1), t2 = wave_sum_d(a2);   // xor-butterfly: fixed order

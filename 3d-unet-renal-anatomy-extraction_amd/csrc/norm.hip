@@ -69,6 +69,25 @@ static int pick_vec(int c, std::initializer_list<const ru3d_tensor*> ts) {
 // MODE 2: (sum t, 0)                                       bias gradient
 // MODE 3: as MODE 1 with xhat recovered from the activation (no residual in the forward: out = lrelu(xhat))
 // Partials: part[((n*chunks + chunk)*C + c)*2 + {0,1}] as double.
+//
+// The cross-lane tail of a first stage.  sh[s][tid][i] holds the block's per-thread sums (tid = vl * Gb + cgl); every
+// (channel, sum) pair is one chain over the voxel lanes l = 0 .. vpb-1 ascending, and every chain has a thread of its own
+// (chain = (cgl * HV + i) * 2 + s: neighbouring threads write neighbouring doubles), where Gb threads used to run HV * 2
+// chains each, one after the other, with the rest of the block waiting.  row: this block's row of the partials.
+template <int HV>
+__device__ __forceinline__ void lane_tail(const double (&sh)[2][256][HV], const ChanLoop& cl, int vec, int c_off,
+                                          double* __restrict__ row) {
+    for (int ch = threadIdx.x; ch < cl.Gb * HV * 2; ch += 256) {
+        const int s = ch & 1, i = (ch >> 1) % HV, cgl = ch / (2 * HV);
+        const int cg = blockIdx.z * cl.Gb + cgl;
+        if (cg >= cl.G) continue;
+        double t = 0.0;
+#pragma unroll 8
+        for (int l = 0; l < cl.vpb; l++) t += sh[s][l * cl.Gb + cgl][i];
+        row[(int64_t)(cg * vec + c_off + i) * 2 + s] = t;
+    }
+}
+
 template <typename T, int VEC, int MODE>
 __global__ __launch_bounds__(256) void reduce2_kernel(const T* __restrict__ a, int lda, const T* __restrict__ b,
                                                       int ldb, const T* __restrict__ c3, int ldc,
@@ -152,27 +171,46 @@ __global__ __launch_bounds__(256) void reduce2_kernel(const T* __restrict__ a, i
             sh[1][tid][i] = active ? (double)s2[half * HV + i] : 0.0;
         }
         __syncthreads();
-        if (vl == 0 && cg < cl.G) {
-#pragma unroll
-            for (int i = 0; i < HV; i++) {
-                double t1 = 0.0, t2 = 0.0;
-                for (int l = 0; l < cl.vpb; l++) {
-                    t1 += sh[0][l * cl.Gb + cgl][i];
-                    t2 += sh[1][l * cl.Gb + cgl][i];
-                }
-                const int c = cg * VEC + half * HV + i;
-                double* pp = part + (((int64_t)n * cl.chunks + blockIdx.x) * C + c) * 2;
-                pp[0] = t1;
-                pp[1] = t2;
-            }
-        }
+        lane_tail<HV>(sh, cl, VEC, half * HV, part + ((int64_t)n * cl.chunks + blockIdx.x) * C * 2);
     }
 }
 
 // Finalize kernels: 16 channel lanes x 16 chunk lanes per block; every lane sums a strided subset of the
 // per-block partials in double, the 16 subsets are combined in a fixed order through LDS (deterministic).
+//
+// Contract of every second stage of a fixed-order reduction (here, stats_slab_finalize_kernel, head_bwd_finalize_kernel,
+// the wgrad_reduce kernels, and the cross-lane tails of reduce2_kernel and its kin): the value an output receives is one
+// fixed sequence of floating-point operations on fixed operands.  A lane's chain a += p[r] runs over r ascending, the
+// combine order of the lanes is fixed, a float-to-double conversion stays where it is.  What is free is when the loads
+// are issued and which thread runs a chain: the loads of a whole batch are in flight before the first add, so a kernel
+// pays one memory round trip per batch, not one per row.
 #define FIN_CX 16
 #define FIN_KY 16
+#define FIN_BATCH 32
+// B rows of a lane's chain, rows r0, r0 + FIN_KY, ...: every load is issued, then the adds run in row order.  GUARD: a row
+// past the end is loaded from row r0 (the same cache line again) and not added.
+template <int B, bool GUARD>
+__device__ __forceinline__ void finalize_batch(const double* __restrict__ base, int rows, int64_t row_stride, int r0,
+                                               double& a1, double& a2) {
+    double u1[B], u2[B];
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+        const int r = r0 + j * FIN_KY;
+        const double* pp = base + (int64_t)((!GUARD || r < rows) ? r : r0) * row_stride;
+        u1[j] = pp[0];
+        u2[j] = pp[1];
+    }
+    // nothing crosses: left alone, the scheduler pairs every load with its add to save registers - one round trip per row
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+        if (!GUARD || r0 + j * FIN_KY < rows) {
+            a1 += u1[j];
+            a2 += u2[j];
+        }
+    }
+}
+
 __device__ __forceinline__ void finalize_sums(const double* __restrict__ part, int rows, int64_t row_stride, int c,
                                               bool ok, double& t1, double& t2) {
     // rows = number of partial rows for this (n) (or N*chunks for channel sums); row r at part + r*row_stride + c*2
@@ -180,29 +218,14 @@ __device__ __forceinline__ void finalize_sums(const double* __restrict__ part, i
     const int cx = threadIdx.x % FIN_CX, ky = threadIdx.x / FIN_CX;
     double a1 = 0.0, a2 = 0.0;
     if (ok) {
-        // eight independent partial rows in flight per lane (a serial chain of dependent loads cost ~10 us on the
-        // 512-chunk tensors); the order of the additions is fixed, so the result is still deterministic
+        // the lane's chain over rows ky, ky + FIN_KY, ... ascending: whole batches of FIN_BATCH rows, then what is left in
+        // one guarded batch (a short one where eight rows or fewer are left)
         const double* base = part + (int64_t)c * 2;
-        int r = ky;
-        for (; r + 7 * FIN_KY < rows; r += 8 * FIN_KY) {
-            double u1[8], u2[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const double* pp = base + (int64_t)(r + j * FIN_KY) * row_stride;
-                u1[j] = pp[0];
-                u2[j] = pp[1];
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                a1 += u1[j];
-                a2 += u2[j];
-            }
-        }
-        for (; r < rows; r += FIN_KY) {
-            const double* pp = base + (int64_t)r * row_stride;
-            a1 += pp[0];
-            a2 += pp[1];
-        }
+        int r0 = ky;
+        for (; r0 + (FIN_BATCH - 1) * FIN_KY < rows; r0 += FIN_BATCH * FIN_KY)
+            finalize_batch<FIN_BATCH, false>(base, rows, row_stride, r0, a1, a2);
+        if (r0 + 8 * FIN_KY < rows) finalize_batch<FIN_BATCH, true>(base, rows, row_stride, r0, a1, a2);
+        else if (r0 < rows) finalize_batch<8, true>(base, rows, row_stride, r0, a1, a2);
     }
     sh[0][ky][cx] = a1;
     sh[1][ky][cx] = a2;
@@ -392,15 +415,17 @@ __global__ __launch_bounds__(256) void in_lrelu_bwd_kernel(const T* __restrict__
 #pragma unroll
     for (int i = 0; i < VEC; i++) dsh[tid][i] = active ? dsum[i] : 0.f;
     __syncthreads();
-    if (vl == 0 && cg < cl.G) {
-#pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            double t = 0.0;
-            for (int l = 0; l < cl.vpb; l++) t += (double)dsh[l * cl.Gb + cgl][i];      // fixed order
-            double* pp = dysum_part + (((int64_t)n * cl.chunks + blockIdx.x) * C + cg * VEC + i) * 2;
-            pp[0] = t;
-            pp[1] = 0.0;
-        }
+    // one chain per channel over the voxel lanes ascending, each on a thread of its own (see lane_tail)
+    for (int ch = tid; ch < cl.Gb * VEC; ch += 256) {
+        const int i = ch % VEC, gl = ch / VEC;
+        const int g = blockIdx.z * cl.Gb + gl;
+        if (g >= cl.G) continue;
+        double t = 0.0;
+#pragma unroll 8
+        for (int l = 0; l < cl.vpb; l++) t += (double)dsh[l * cl.Gb + gl][i];      // fixed order
+        double* pp = dysum_part + (((int64_t)n * cl.chunks + blockIdx.x) * C + g * VEC + i) * 2;
+        pp[0] = t;
+        pp[1] = 0.0;
     }
 }
 
@@ -763,20 +788,7 @@ __global__ __launch_bounds__(256) void head_dz_reduce2_kernel(const float* __res
             sh[1][tid][i] = active ? (double)s2[half * 4 + i] : 0.0;
         }
         __syncthreads();
-        if (vl == 0 && cg < cl.G) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                double t1 = 0.0, t2 = 0.0;
-                for (int l = 0; l < cl.vpb; l++) {
-                    t1 += sh[0][l * cl.Gb + cgl][i];
-                    t2 += sh[1][l * cl.Gb + cgl][i];
-                }
-                const int c = cg * VEC + half * 4 + i;
-                double* pp = part + (((int64_t)n * cl.chunks + blockIdx.x) * C + c) * 2;
-                pp[0] = t1;
-                pp[1] = t2;
-            }
-        }
+        lane_tail<4>(sh, cl, VEC, half * 4, part + ((int64_t)n * cl.chunks + blockIdx.x) * C * 2);
     }
 }
 

@@ -718,7 +718,18 @@ __global__ __launch_bounds__(256) void head_bwd_finalize_kernel(const float* __r
     const int row = 4 * Cin + 4;
     if (e >= row) return;
     double acc = 0.0;
-    for (int b = lane; b < blocks; b += 64) acc += (double)part[(int64_t)b * row + e];
+    // the lane's chain over b = lane, lane + 64, ... ascending; the loads of a batch (all of them at the 2048 blocks a
+    // launch has at most) are in flight before the first add; a row past the end is loaded from the batch's first
+    constexpr int HB_BATCH = 32;
+    for (int b0 = lane; b0 < blocks; b0 += 64 * HB_BATCH) {
+        float u[HB_BATCH];
+#pragma unroll
+        for (int j = 0; j < HB_BATCH; j++) u[j] = part[(int64_t)(b0 + 64 * j < blocks ? b0 + 64 * j : b0) * row + e];
+        __builtin_amdgcn_sched_barrier(0);      // or the scheduler pairs every load with its add to save registers
+#pragma unroll
+        for (int j = 0; j < HB_BATCH; j++)
+            if (b0 + 64 * j < blocks) acc += (double)u[j];
+    }
     acc = wave_sum_d(acc);
     if (lane) return;
     if (e < 4 * Cin) {
