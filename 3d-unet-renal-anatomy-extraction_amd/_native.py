@@ -95,6 +95,8 @@ OVERLAY_FILL, OVERLAY_OUTLINE = 0, 1
 RENDER_MAX_TILES = 256
 MORPH_ERODE, MORPH_DILATE = 0, 1
 MORPH_MAX_EXTENT, MORPH_MAX_ROWS = 15, 225
+KEEP_LARGEST_MAX = 8
+PROPAGATE_MAX_ROUNDS = 64
 CONFUSION_MAX_CLASSES = 32
 ORDER_STATS_MAX_RANKS = 8
 EDT_MAX_AXIS = 4096             # RU3D_EDT_MAX_AXIS: x and y extents of the distance transform
@@ -222,6 +224,7 @@ SIGNATURES = {
     "ru3d_component_stats": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ru3d_filter_components_workspace_bytes": (_sz, [_i]),
     "ru3d_filter_components": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_keep_largest_components": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_region_accumulate": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     "ru3d_cascade_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ru3d_label_moments": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -235,6 +238,8 @@ SIGNATURES = {
     "ru3d_mask_pack": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ru3d_mask_unpack": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ru3d_binary_morph": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.POINTER(MorphRow), _i, _i, _vp]),
+    "ru3d_binary_propagate": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ru3d_mask_fill_result": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "ru3d_confusion_counts": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "ru3d_threshold_bbox": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "ru3d_masked_sample_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -85,18 +85,55 @@ def filter_small(labels, count, sizes, threshold, mask=None, relabel=False):
     return (out.reshape(labels.shape) if out is not None else None), int(kept.item())
 
 
-def remove_small_region(input, threshold):
-    """transform.remove_small_region for a HIP tensor: label -> sizes -> filter, `input` modified in place."""
+def keep_largest(labels, count, sizes, k=1, mask=None, relabel=False):
+    """Zero `mask` (uint8 HIP tensor, in place) outside the `k` largest components (1 <= k <= 8; among equal sizes the
+    smaller number wins, `np.argsort(-sizes, kind='stable')[:k]`); with `relabel` also return the label volume of the
+    survivors, renumbered in their old order.  The choice is made on the device.  Returns (labels or None, kept)."""
+    lab = _volume3(labels, "keep_largest")
+    X, Y, Z = (int(s) for s in lab.shape)
+    if int(k) != k or not 1 <= k <= N.KEEP_LARGEST_MAX:
+        raise ValueError("keep_largest: k=%r (1 .. %d)" % (k, N.KEEP_LARGEST_MAX))
+    if mask is None and not relabel:
+        raise ValueError("keep_largest: nothing to write (no mask, relabel=False)")
+    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != lab.numel()):
+        raise ValueError("keep_largest: the mask must be a contiguous uint8 tensor of the labels' shape")
+    if count and (sizes is None or sizes.dtype != torch.int32 or sizes.numel() != int(count)):
+        raise ValueError("keep_largest: sizes must be the int32 tensor of %d sizes that `stats` returns" % int(count))
+    out = torch.empty_like(lab) if relabel else None
+    kept = torch.zeros(1, dtype=torch.int32, device=lab.device)
+    nbytes = N.lib.ru3d_filter_components_workspace_bytes(int(count))    # the same layout
+    ws = N.workspace(nbytes, lab.device)
+    N.note_device(lab.device)
+    check(N.lib.ru3d_keep_largest_components(ptr(lab), X, Y, Z, int(count), ptr(sizes) if count else None, int(k),
+                                             ptr(mask), ptr(out), ptr(kept), ptr(ws), ws.numel(), stream()),
+          "keep_largest_components")
+    return (out.reshape(labels.shape) if out is not None else None), int(kept.item())
+
+
+def _in_place(input, edit):
+    """Run edit(labels, count, sizes, mask) on the uint8 mask of `input` and zero `input` where the mask was cleared."""
     labels, count = label(input)
     if count == 0:
         return input
     sizes, _ = stats(labels, count)
     direct = input.dtype in (torch.uint8, torch.bool) and input.is_contiguous()
     mask = input.view(torch.uint8) if direct else as_mask(input)
-    filter_small(labels, count, sizes, threshold, mask=mask.reshape(labels.shape))
+    edit(labels, count, sizes, mask.reshape(labels.shape))
     if not direct:
         input.masked_fill_(mask.reshape(input.shape) == 0, 0)
     return input
+
+
+def keep_largest_region(input, k=1):
+    """transform.keep_largest_region for a HIP tensor: label -> sizes -> pick -> filter, `input` modified in place."""
+    if int(k) != k or not 1 <= k <= N.KEEP_LARGEST_MAX:
+        raise ValueError("keep_largest_region: k=%r (1 .. %d)" % (k, N.KEEP_LARGEST_MAX))
+    return _in_place(input, lambda labels, count, sizes, mask: keep_largest(labels, count, sizes, k, mask=mask))
+
+
+def remove_small_region(input, threshold):
+    """transform.remove_small_region for a HIP tensor: label -> sizes -> filter, `input` modified in place."""
+    return _in_place(input, lambda labels, count, sizes, mask: filter_small(labels, count, sizes, threshold, mask=mask))
 
 
 def region_boxes(mask, threshold):

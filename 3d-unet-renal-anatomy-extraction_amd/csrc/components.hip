@@ -34,6 +34,7 @@
 #define CC_HASH 256                         // per-tile statistics table (entries)
 #define CC_PROBES 8
 #define CC_MAX_CLASSES 8
+#define CC_MAX_KEEP RU3D_KEEP_LARGEST_MAX   // the k of ru3d_keep_largest_components: one selection pass each
 
 typedef unsigned long long cc_u64;
 
@@ -302,6 +303,51 @@ __global__ __launch_bounds__(256) void cc_keep_count_kernel(const int* __restric
     bv_chunk_sum(kept, counts);
 }
 
+// The renumbering table of "keep the k largest": remap[i] = 1 .. kept in index order for the k largest of
+// sizes[0 .. count), 0 for the others; among equal sizes the smaller index wins (np.argsort(-sizes, kind='stable')[:k]).
+// *kept = min(k, count).  One workgroup and k selection passes over the table, in which remap marks what is picked.
+__global__ __launch_bounds__(BV_SCAN_THREADS) void cc_pick_largest_kernel(const int* __restrict__ sizes, int count, int k,
+                                                                          int* remap, int* kept) {
+    __shared__ cc_u64 s_best[BV_SCAN_THREADS / RU3D_WAVE];
+    __shared__ int s_pick[CC_MAX_KEEP];
+    for (int i = threadIdx.x; i < count; i += BV_SCAN_THREADS) remap[i] = k >= count ? i + 1 : 0;
+    if (k >= count) {                                        // everything stays, under its old number
+        if (threadIdx.x == 0) *kept = count;
+        return;
+    }
+    __syncthreads();
+    for (int pass = 0; pass < k; pass++) {
+        cc_u64 best = 0;                                     // (size, ~index): the maximum is the largest, first one
+        for (int i = threadIdx.x; i < count; i += BV_SCAN_THREADS) {
+            if (remap[i]) continue;
+            const cc_u64 key = (cc_u64)(unsigned)max(sizes[i], 0) << 32 | (0xffffffffu - (unsigned)i);
+            best = key > best ? key : best;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const cc_u64 other = bv_shfl_xor(best, o);
+            best = other > best ? other : best;
+        }
+        if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < BV_SCAN_THREADS / RU3D_WAVE; w++) best = s_best[w] > best ? s_best[w] : best;
+            const int pick = (int)(0xffffffffu - (unsigned)best);       // k < count: every pass finds one
+            s_pick[pass] = pick;
+            remap[pick] = 1;
+        }
+        __syncthreads();                                     // the pick is visible to the next pass, s_best is free
+    }
+    if (threadIdx.x == 0) {
+        for (int a = 0; a < k; a++) {                        // the picks get their numbers in index order
+            int number = 1;
+            for (int b = 0; b < k; b++) number += s_pick[b] < s_pick[a] ? 1 : 0;
+            remap[s_pick[a]] = number;
+        }
+        *kept = k;
+    }
+}
+
 __global__ __launch_bounds__(256) void cc_filter_apply_kernel(const int* __restrict__ labels, int64_t n, int count,
                                                               const int* __restrict__ remap, uint8_t* mask,
                                                               int* labels_out) {
@@ -532,6 +578,22 @@ extern "C" size_t ru3d_filter_components_workspace_bytes(int count) {
     return bv_align((size_t)count * sizeof(int)) + bv_align((size_t)cc_chunks(count) * sizeof(int));
 }
 
+// The pass that ru3d_filter_components and ru3d_keep_largest_components share: remap[k] (made on `st` by the caller,
+// count > 0) is the new number of component k + 1, 0 to drop it.  Without a component nothing is removed or kept.
+static int cc_filter_apply(const char* what, const int32_t* labels, int64_t n, int count, const int* remap,
+                           uint8_t* mask_inout, int32_t* labels_out, int32_t* kept_dev, hipStream_t st) {
+    if (count == 0) {
+        if (hipMemsetAsync(kept_dev, 0, sizeof(int), st) != hipSuccess) return ru3d_check_launch(what);
+        if (labels_out && labels_out != labels)
+            hipLaunchKernelGGL(cc_filter_apply_kernel, dim3(cc_stream_blocks(n)), dim3(256), 0, st, labels, n, 0,
+                               (const int*)nullptr, (uint8_t*)nullptr, labels_out);
+        return ru3d_check_launch(what);
+    }
+    hipLaunchKernelGGL(cc_filter_apply_kernel, dim3(cc_stream_blocks(n)), dim3(256), 0, st, labels, n, count, remap,
+                       mask_inout, labels_out);
+    return ru3d_check_launch(what);
+}
+
 extern "C" int ru3d_filter_components(const int32_t* labels, int X, int Y, int Z, int count, const int32_t* sizes,
                                       int threshold, uint8_t* mask_inout, int32_t* labels_out, int32_t* kept_dev, void* ws,
                                       size_t ws_bytes, void* stream) {
@@ -544,24 +606,37 @@ extern "C" int ru3d_filter_components(const int32_t* labels, int X, int Y, int Z
                  "filter_components: workspace of %zu bytes, %zu needed", ws_bytes,
                  ru3d_filter_components_workspace_bytes(count));
     hipStream_t st = as_stream(stream);
-    const int64_t n = (int64_t)X * Y * Z;
-    if (count == 0) {                                     // no component: nothing to remove, nothing kept
-        if (hipMemsetAsync(kept_dev, 0, sizeof(int), st) != hipSuccess) return ru3d_check_launch("filter_components");
-        if (labels_out && labels_out != labels)
-            hipLaunchKernelGGL(cc_filter_apply_kernel, dim3(cc_stream_blocks(n)), dim3(256), 0, st, labels, n, 0,
-                               (const int*)nullptr, (uint8_t*)nullptr, labels_out);
-        return ru3d_check_launch("filter_components");
-    }
     int* remap = (int*)ws;
-    int* counts = (int*)((char*)ws + bv_align((size_t)count * sizeof(int)));
-    const int chunks = (int)cc_chunks(count);
-    hipLaunchKernelGGL(cc_keep_count_kernel, dim3(chunks), dim3(256), 0, st, sizes, threshold, (int64_t)count, counts);
-    hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(BV_SCAN_THREADS), 0, st, counts, chunks, kept_dev);
-    hipLaunchKernelGGL((cc_rank_kernel<CC_RANK_KEEP>), dim3(chunks), dim3(256), 0, st, remap, sizes, threshold,
-                       (int64_t)count, counts);
-    hipLaunchKernelGGL(cc_filter_apply_kernel, dim3(cc_stream_blocks(n)), dim3(256), 0, st, labels, n, count, remap,
-                       mask_inout, labels_out);
-    return ru3d_check_launch("filter_components");
+    if (count > 0) {
+        int* counts = (int*)((char*)ws + bv_align((size_t)count * sizeof(int)));
+        const int chunks = (int)cc_chunks(count);
+        hipLaunchKernelGGL(cc_keep_count_kernel, dim3(chunks), dim3(256), 0, st, sizes, threshold, (int64_t)count, counts);
+        hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(BV_SCAN_THREADS), 0, st, counts, chunks, kept_dev);
+        hipLaunchKernelGGL((cc_rank_kernel<CC_RANK_KEEP>), dim3(chunks), dim3(256), 0, st, remap, sizes, threshold,
+                           (int64_t)count, counts);
+    }
+    return cc_filter_apply("filter_components", labels, (int64_t)X * Y * Z, count, remap, mask_inout, labels_out, kept_dev, st);
+}
+
+// the workspace is the one of ru3d_filter_components (its renumbering table; the chunk counts stay unused)
+extern "C" int ru3d_keep_largest_components(const int32_t* labels, int X, int Y, int Z, int count, const int32_t* sizes, int k,
+                                            uint8_t* mask_inout, int32_t* labels_out, int32_t* kept_dev, void* ws,
+                                            size_t ws_bytes, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    BV_REQUIRE_SHAPE("keep_largest_components");
+    RU3D_REQUIRE(count >= 0, "keep_largest_components: count %d", count);
+    RU3D_REQUIRE(k >= 1 && k <= CC_MAX_KEEP, "keep_largest_components: k = %d (1 .. %d)", k, CC_MAX_KEEP);
+    RU3D_REQUIRE(labels && kept_dev && (count == 0 || sizes), "keep_largest_components: bad argument (null pointer)");
+    RU3D_REQUIRE(mask_inout || labels_out, "keep_largest_components: neither a mask nor a label output");
+    RU3D_REQUIRE(count == 0 || (ws && ws_bytes >= ru3d_filter_components_workspace_bytes(count)),
+                 "keep_largest_components: workspace of %zu bytes, %zu needed", ws_bytes,
+                 ru3d_filter_components_workspace_bytes(count));
+    hipStream_t st = as_stream(stream);
+    int* remap = (int*)ws;
+    if (count > 0)
+        hipLaunchKernelGGL(cc_pick_largest_kernel, dim3(1), dim3(BV_SCAN_THREADS), 0, st, sizes, count, k, remap, kept_dev);
+    return cc_filter_apply("keep_largest_components", labels, (int64_t)X * Y * Z, count, remap, mask_inout, labels_out,
+                           kept_dev, st);
 }
 
 extern "C" int ru3d_region_accumulate(const float* prob, int rx, int ry, int rz, int num_classes, int bx, int by, int bz,

@@ -6,7 +6,9 @@ _closing` of the reference's clean-up (nb_post.py:88-112) and the per-class floa
 (trainer.py:348-356, nb.py:11-37).  A mask is held as a `PackedMask`: 64 voxels of the contiguous Z axis per 64-bit
 word, so `pred == 2` is formed straight from the uint8 prediction and a 512x512x256 mask is 8 MB.  The results are
 scipy's, voxel for voxel, including its border rule (voxels outside the volume read as `border_value`) and the
-reflection of the structure in a dilation.  There is no host fallback in here: every function wants HIP tensors.
+reflection of the structure in a dilation.  `propagate` and `fill_holes` (csrc/propagate.hip) are
+`scipy.ndimage.binary_propagation` and `binary_fill_holes` on the same masks: a flood by rounds that never builds a
+label volume.  There is no host fallback in here: every function wants HIP tensors.
 """
 import functools
 
@@ -218,3 +220,90 @@ def confusion(pred, label, num_classes):
     N.note_device(pred.device)
     check(N.lib.ru3d_confusion_counts(ptr(pred), ptr(label), pred.numel(), C, ptr(table), stream()), "confusion_counts")
     return table
+
+
+# ------------------------------------------------------------------------------------------------ propagation, hole filling
+# rounds of the last flood (propagate / fill_holes) of this process, the overshoot of the last batch included
+last_rounds = 0
+
+
+def _connectivity(structure, ndim, what):
+    """1 for the centre and its 2 * ndim face neighbours (None), 3 for the full 3 ** ndim cube; nothing else."""
+    if structure is None:
+        return 1
+    if torch.is_tensor(structure):
+        structure = structure.cpu().numpy()
+    s = np.asarray(structure) != 0
+    if s.shape == (3,) * ndim:
+        if s.all():
+            return 3
+        if np.array_equal(s, default_structure()[(1,) * (3 - ndim)]):
+            return 1
+    raise ValueError("%s: structure must be None (the face neighbours) or the full 3 x 3 x 3 cube, in the form of the "
+                     "mask's %d axes" % (what, ndim))
+
+
+def _flood(allowed, invert, reach, connectivity, border_value):
+    """Grow reach.bits to the fixpoint: batches of 8, 16, 32, 64, 64, .. rounds, one download of the batch's counters of
+    changed tiles after each; a batch whose last round changed nothing has converged."""
+    global last_rounds
+    N.require_device(allowed.bits, "the packed mask")
+    X, Y, Z = allowed.shape3
+    ndim = len(allowed.shape)
+    border_axes = (7 & ~((1 << (3 - ndim)) - 1)) if border_value else 0       # only the axes the mask really has
+    changed = torch.empty(N.PROPAGATE_MAX_ROUNDS, dtype=torch.int32, device=allowed.device)
+    N.note_device(allowed.device)
+    rounds, total = 8, 0
+    while True:
+        check(N.lib.ru3d_binary_propagate(ptr(allowed.bits), 1 if invert else 0, ptr(reach.bits), X, Y, Z, connectivity,
+                                          border_axes, rounds, ptr(changed), stream()), "binary_propagate")
+        total += rounds
+        if int(changed[:rounds].cpu()[-1]) == 0:
+            break
+        rounds = min(2 * rounds, N.PROPAGATE_MAX_ROUNDS)
+    last_rounds = total
+    return reach
+
+
+def _packed(mask, what):
+    if not isinstance(mask, PackedMask):
+        raise ValueError("%s: expected a PackedMask (morphology.pack), got %s" % (what, type(mask).__name__))
+    return mask
+
+
+def propagate(seed, allowed, structure=None, border_value=0):
+    """scipy.ndimage.binary_propagation(seed, structure, mask=allowed, border_value=border_value) of PackedMasks: the
+    seed and every voxel of `allowed` that a chain of allowed neighbours connects to it (and, with border_value 1, to
+    the outside of the volume).  As in scipy, a seed voxel outside `allowed` stays set and spreads into its allowed
+    neighbours.  seed=None is the empty seed, allowed=None the whole volume (one of the two is needed for the shape).
+    structure: None (face neighbours) or the full cube.  A new PackedMask; the operands are left as they are."""
+    if seed is None and allowed is None:
+        raise ValueError("propagate: neither a seed nor an allowed mask")
+    like = _packed(allowed, "propagate: allowed") if allowed is not None else _packed(seed, "propagate: seed")
+    if border_value not in (0, 1, False, True):
+        raise ValueError("propagate: border_value=%r (0 or 1)" % (border_value,))
+    connectivity = _connectivity(structure, len(like.shape), "propagate")
+    if seed is None:
+        reach = PackedMask(torch.zeros_like(like.bits), like.shape)
+    else:
+        _packed(seed, "propagate: seed")
+        if seed.shape != like.shape or seed.device != like.device:
+            raise ValueError("propagate: seed of shape %s on %s, allowed of shape %s on %s"
+                             % (seed.shape, seed.device, like.shape, like.device))
+        reach = PackedMask(seed.bits.clone(), seed.shape)
+    if allowed is None:                                     # everywhere: the complement of an empty mask, formed on load
+        return _flood(PackedMask(torch.zeros_like(like.bits), like.shape), True, reach, connectivity, border_value)
+    return _flood(allowed, False, reach, connectivity, border_value)
+
+
+def fill_holes(mask, structure=None):
+    """scipy.ndimage.binary_fill_holes of a PackedMask: the mask plus every voxel of its complement that the outside of
+    the volume does not reach through the complement (structure: the neighbourhood of that flood, None or the cube).
+    The complement is formed on load, so the flood needs one packed volume beside the result."""
+    _packed(mask, "fill_holes: mask")
+    connectivity = _connectivity(structure, len(mask.shape), "fill_holes")
+    reach = _flood(mask, True, PackedMask(torch.zeros_like(mask.bits), mask.shape), connectivity, 1)
+    out = mask.new()
+    X, Y, Z = mask.shape3
+    check(N.lib.ru3d_mask_fill_result(ptr(mask.bits), ptr(reach.bits), ptr(out.bits), X, Y, Z, stream()), "mask_fill_result")
+    return out

@@ -1295,6 +1295,134 @@ def batch_measure(pred_dir, save_dir, data_range=None, device=None, **options):
             for i in (data_range if data_range is not None else range(len(pred_files)))]
 
 
+# ------------------------------------------------------------------ the clean-up recipe of a validation set
+def _label_bytes(path, device):
+    """A NIfTI label volume as contiguous uint8, numpy or uploaded to `device`."""
+    import nifti
+    volume, affine, _ = nifti.load(path)
+    volume = np.ascontiguousarray(np.clip(volume, 0, 255).astype(np.uint8))
+    return (volume if device is None else torch.from_numpy(volume).to(device)), affine
+
+
+def _class_dice_means(cases, recipe, num_classes):
+    """Mean over the cases of the Dice 2TP / (2TP + FP + FN) of every class 1 .. num_classes - 1 between the label and
+    the prediction cleaned by `recipe`, as float64 from the integer confusion tables; a case in which a class is absent
+    from both volumes does not count for that class, and a class that no case counts for has the mean None."""
+    import transform
+    sums = [[] for _ in range(num_classes)]
+    for label, pred in cases:
+        table, _ = _confusion_table({'label': label, 'pred': transform.clean_labels(pred, **recipe)})
+        full = np.zeros((max(num_classes, table.shape[0]),) * 2, dtype=np.int64)
+        full[:table.shape[0], :table.shape[1]] = table
+        for c in range(1, num_classes):
+            tp, fn, fp, _ = _class_counts(full, c)
+            if tp + fn + fp:
+                sums[c].append(2.0 * tp / (2.0 * tp + fp + fn))
+    return [float(np.mean(np.asarray(s, dtype=np.float64))) if s else None for s in sums]
+
+
+def _with_step(recipe, target, k):
+    """`recipe` with the k largest components kept of `target`: 'foreground' or a class."""
+    out = {key: (dict(v) if isinstance(v, dict) else v) for key, v in recipe.items()}
+    if target == 'foreground':
+        out['foreground'] = k
+    else:
+        out.setdefault('keep_largest', {})[target] = k
+    return out
+
+
+def determine_postprocessing(label_dir, pred_dir, num_classes=3, max_components=2, fill_holes=(), save_file=None,
+                             data_range=None, device=None):
+    """Which keep-the-largest-components steps help on a validation set (the rule of nnU-Net's post-processing search,
+    fixed here).  The sorted *.nii.gz of `label_dir` and `pred_dir` pair up.  The targets are 'foreground' first, then
+    each class 1 .. num_classes - 1 ascending, each judged on the predictions as the steps adopted so far (and the given
+    `fill_holes` labels, which are applied and not searched) clean them.  For a target, k = 1 .. max_components is
+    tried; a candidate's score is the mean over the affected classes (all for foreground, else the one) of the
+    mean-over-cases Dice; the smallest k with the best score is adopted if that score is strictly above the score
+    without the step and, for foreground, no class's mean falls below its mean without it.  Scores are float64 from
+    integer tables, so device=None (scipy) and a HIP device (the kernels; only the tables come down) return the same.
+    Returns {'recipe': keywords of transform.clean_labels, 'table': one entry per target}; save_file: written as JSON
+    (json_save; label keys become strings there, which clean_labels accepts)."""
+    from pathlib import Path
+    from utils import json_save
+    if num_classes < 2:
+        raise ValueError("determine_postprocessing: num_classes=%r (background and at least one class)" % (num_classes,))
+    if int(max_components) != max_components or not 1 <= max_components <= 8:
+        raise ValueError("determine_postprocessing: max_components=%r (1 .. 8)" % (max_components,))
+    label_files = sorted(Path(label_dir).glob('*.nii.gz'))
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    if len(label_files) != len(pred_files):
+        raise ValueError("determine_postprocessing: %d label files, %d prediction files" % (len(label_files), len(pred_files)))
+    cases = [(_label_bytes(label_files[i], device)[0], _label_bytes(pred_files[i], device)[0])
+             for i in (data_range if data_range is not None else range(len(label_files)))]
+    if not cases:
+        raise ValueError("determine_postprocessing: no case in %s" % (label_dir,))
+    recipe = {'fill_holes': [int(v) for v in fill_holes]} if len(fill_holes) else {}
+    table = []
+    for target in ['foreground'] + list(range(1, num_classes)):
+        affected = list(range(1, num_classes)) if target == 'foreground' else [target]
+        base = _class_dice_means(cases, recipe, num_classes)
+        scored = [c for c in affected if base[c] is not None]
+        entry = {'target': target, 'class_means': base[1:], 'score': None, 'candidates': {}, 'adopted': None}
+        table.append(entry)
+        if not scored:                                       # no case holds an affected class: nothing to judge by
+            continue
+        entry['score'] = float(np.mean(np.asarray([base[c] for c in scored], dtype=np.float64)))
+        best = None
+        for k in range(1, int(max_components) + 1):
+            means = _class_dice_means(cases, _with_step(recipe, target, k), num_classes)
+            # a class that no case counts for any more (only false positives before, all removed) keeps its old mean
+            after = [base[c] if means[c] is None else means[c] for c in scored]
+            score = float(np.mean(np.asarray(after, dtype=np.float64)))
+            harmless = all(a >= base[c] for a, c in zip(after, scored))
+            entry['candidates'][k] = {'score': score, 'class_means': means[1:]}
+            if best is None or score > best[1]:              # the smallest k with the best score
+                best = (k, score, harmless)
+        if best[1] > entry['score'] and (target != 'foreground' or best[2]):
+            entry['adopted'] = best[0]
+            recipe = _with_step(recipe, target, best[0])
+    result = {'recipe': recipe, 'table': table}
+    if save_file is not None:
+        json_save(save_file, result)
+    return result
+
+
+def postprocess_case(case, recipe, key='pred'):
+    """case[key] replaced by transform.clean_labels(case[key], **recipe), for numpy cases and cases on the device."""
+    import transform
+    case[key] = transform.clean_labels(case[key], **recipe)
+    return case
+
+
+def postprocess(pred_file, save_dir, recipe, device=None):
+    """clean_labels of a NIfTI label volume (a `*.pred.nii.gz` of save_pred), written to `save_dir` as
+    `<case_id>.pred.nii.gz` with the file's affine.  device: a HIP device uploads the volume and cleans it there.
+    Returns the written path."""
+    import nifti
+    from pathlib import Path
+    pred_file = Path(pred_file)
+    case_id = pred_file.name
+    for suffix in ('.gz', '.nii', '.pred'):
+        if case_id.endswith(suffix):
+            case_id = case_id[:-len(suffix)]
+    pred, affine = _label_bytes(pred_file, device)
+    case = postprocess_case({'case_id': case_id, 'affine': affine, 'pred': pred}, recipe)
+    cleaned = case['pred'].cpu().numpy() if torch.is_tensor(case['pred']) else case['pred']
+    save_dir = Path(save_dir)
+    save_dir.mkdir(parents=True, exist_ok=True)
+    path = save_dir / ('%s.pred.nii.gz' % case_id)
+    nifti.save(cleaned.astype(np.uint8), affine, path)
+    return str(path)
+
+
+def batch_postprocess(pred_dir, save_dir, recipe, data_range=None, device=None):
+    """postprocess over the sorted *.nii.gz files of `pred_dir`; returns the written paths."""
+    from pathlib import Path
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    return [postprocess(pred_files[i], save_dir, recipe, device)
+            for i in (data_range if data_range is not None else range(len(pred_files)))]
+
+
 # ------------------------------------------------------------------ centrelines of the tubular structures
 def _ratio(num, den):
     return num / den if den else math.nan

@@ -196,6 +196,122 @@ def binary_closing(input, structure=None, iterations=1, border_value=0):
     return _binary_morphology('binary_closing', input, structure, iterations, border_value)
 
 
+def binary_propagation(input, structure=None, mask=None, border_value=0):
+    """scipy.ndimage.binary_propagation: `input` spread through `mask` (None: everywhere) until nothing changes.
+    structure: None (the face neighbours) or the full cube.  numpy in -> scipy, boolean numpy out; HIP tensor in -> pack
+    (!= 0), the flood of csrc/propagate.hip, unpack: a torch.bool HIP tensor of the input's shape."""
+    if torch.is_tensor(input):
+        import components
+        import morphology
+        if mask is not None and (not torch.is_tensor(mask) or tuple(mask.shape) != tuple(input.shape)):
+            raise ValueError("binary_propagation: mask must be a HIP tensor of the input's shape %s" % (tuple(input.shape),))
+        seed = morphology.pack(components.as_mask(input))
+        allowed = morphology.pack(components.as_mask(mask)) if mask is not None else None
+        result = morphology.propagate(seed, allowed, structure, border_value)
+        return morphology.unpack(result, 1, out=torch.empty(input.shape, dtype=torch.bool, device=input.device))
+    return ndi.binary_propagation(input, structure=structure, mask=mask, border_value=border_value)
+
+
+def binary_fill_holes(input, structure=None):
+    """scipy.ndimage.binary_fill_holes: the non-zero voxels plus what the outside of the volume cannot reach through
+    their complement.  numpy in -> scipy; HIP tensor in -> the flood of csrc/propagate.hip, a torch.bool HIP tensor out."""
+    if torch.is_tensor(input):
+        import components
+        import morphology
+        result = morphology.fill_holes(morphology.pack(components.as_mask(input)), structure)
+        return morphology.unpack(result, 1, out=torch.empty(input.shape, dtype=torch.bool, device=input.device))
+    return ndi.binary_fill_holes(input, structure=structure)
+
+
+def _check_k(what, k, limit=8):
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= limit:
+        raise ValueError("%s: k=%r (1 .. %d)" % (what, k, limit))
+    return int(k)
+
+
+def keep_largest_region(input, k=1):
+    """Zero everything but the `k` largest components (6-connectivity) of the non-zero voxels, 1 <= k <= 8; among equal
+    sizes the component met first wins.  Like remove_small_region, `input` is modified in place and returned.  numpy ->
+    scipy.ndimage.label; a HIP tensor is labelled, measured, picked and filtered on the device."""
+    k = _check_k("keep_largest_region", k)
+    if torch.is_tensor(input):
+        import components
+        return components.keep_largest_region(input, k)
+    labels, _ = ndi.label(input)
+    sizes = np.bincount(labels.ravel())[1:]
+    keep = np.zeros(sizes.size + 1, dtype=bool)
+    keep[np.argsort(-sizes, kind='stable')[:k] + 1] = True
+    input[~keep[labels]] = 0
+    return input
+
+
+def _label_table(what, table):
+    """{label: value} with integer keys (a recipe read back from JSON has them as strings), ascending."""
+    out = {}
+    for key, value in dict(table or {}).items():
+        label = int(key)
+        if not 1 <= label <= 255:
+            raise ValueError("clean_labels: %s names the label %r (1 .. 255)" % (what, key))
+        out[label] = value
+    return dict(sorted(out.items()))
+
+
+def clean_labels(input, foreground=None, keep_largest=None, min_voxels=None, fill_holes=(), structure=None):
+    """The clean-up of a predicted label map, a new uint8 volume; `input` is left as it is.
+      1. foreground=k: only the k largest components of `input > 0` survive.
+      2. for each label, ascending, named in min_voxels ({label: t}) or keep_largest ({label: k}): the components of
+         `== label` with fewer than t voxels become 0, then all but the k largest.
+      3. for each label of fill_holes, in the given order: the holes of `== label` (binary_fill_holes, `structure`)
+         are painted with the label where the volume is 0; another label enclosed in it stays.
+    numpy in -> scipy; a uint8 HIP tensor in -> csrc/components.hip and csrc/propagate.hip, a uint8 HIP tensor out with
+    the same voxels."""
+    keep_largest = {label: _check_k("clean_labels: keep_largest", k) for label, k in
+                    _label_table("keep_largest", keep_largest).items()}
+    min_voxels = _label_table("min_voxels", min_voxels)
+    fill = [int(label) for label in fill_holes]
+    if any(not 1 <= label <= 255 for label in fill):
+        raise ValueError("clean_labels: fill_holes=%r (labels 1 .. 255)" % (fill_holes,))
+    if foreground is not None:
+        foreground = _check_k("clean_labels: foreground", foreground)
+    device = torch.is_tensor(input)
+    if device:
+        import morphology
+        if input.dtype != torch.uint8:
+            raise ValueError("clean_labels: expected a uint8 label volume on the device, got %s" % input.dtype)
+        output = input.clone(memory_format=torch.contiguous_format)
+    else:
+        output = np.array(input, dtype=np.uint8)
+    if foreground is not None:
+        if device:
+            keep_largest_region(output, foreground)                  # non-zero bytes are the mask: dropped ones are zeroed
+        else:
+            output[~keep_largest_region(output > 0, foreground)] = 0
+    for label in sorted(set(min_voxels) | set(keep_largest)):
+        if device:
+            before = morphology.pack(output, 'eq', label)
+            kept = morphology.unpack(before, 1)
+        else:
+            before = output == label
+            kept = before.copy()
+        if label in min_voxels:
+            remove_small_region(kept, min_voxels[label])
+        if label in keep_largest:
+            keep_largest_region(kept, keep_largest[label])
+        if device:
+            morphology.unpack(before, 0, out=output, paint=True)
+            morphology.unpack(morphology.pack(kept), label, out=output, paint=True)
+        else:
+            output[before & ~kept] = 0
+    for label in fill:
+        if device:
+            filled = morphology.fill_holes(morphology.pack(output, 'eq', label), structure)
+            filled.bits &= morphology.pack(output, 'eq', 0).bits      # paint only where the volume is 0
+            morphology.unpack(filled, label, out=output, paint=True)
+        else:
+            output[ndi.binary_fill_holes(output == label, structure=structure) & (output == 0)] = label
+    return output
+
+
 def distance_transform_edt(input, sampling=None, squared=False):
     """scipy.ndimage.distance_transform_edt: the Euclidean distance, in `sampling` units, of every non-zero voxel to the
     nearest zero voxel (zero voxels get 0), or its square with `squared=True`.  numpy in -> scipy, float64 numpy out; a
@@ -761,6 +877,29 @@ class RemoveSmallRegion(object):
 
     def __call__(self, case):
         case['label'] = remove_small_region(case['label'], self.threshold)
+        return case
+
+
+class KeepLargestRegion(object):
+    """keep_largest_region on case[key] (the label by default, like RemoveSmallRegion)."""
+
+    def __init__(self, k=1, key='label'):
+        self.k, self.key = k, key
+
+    def __call__(self, case):
+        case[self.key] = keep_largest_region(case[self.key], self.k)
+        return case
+
+
+class CleanLabels(object):
+    """clean_labels on case['pred'] with the keywords of a recipe (trainer.determine_postprocessing), for numpy cases
+    and cases that live on the device."""
+
+    def __init__(self, **recipe):
+        self.recipe = recipe
+
+    def __call__(self, case):
+        case['pred'] = clean_labels(case['pred'], **self.recipe)
         return case
 
 

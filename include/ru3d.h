@@ -534,6 +534,16 @@ size_t ru3d_filter_components_workspace_bytes(int count);
 int ru3d_filter_components(const int32_t* labels, int X, int Y, int Z, int count, const int32_t* sizes, int threshold,
                            uint8_t* mask_inout, int32_t* labels_out, int32_t* kept_dev, void* ws, size_t ws_bytes,
                            void* stream);
+/* Keep the k largest components (1 <= k <= RU3D_KEEP_LARGEST_MAX): one workgroup picks them from sizes[0 .. count) on
+ * the device - among equal sizes the smaller component number wins, np.argsort(-sizes, kind='stable')[:k] - and the
+ * pass of ru3d_filter_components zeroes the others in mask_inout and / or renumbers the survivors in their old order
+ * into labels_out, with the same rules for NULL and for labels_out == labels.  k >= count keeps everything.  No size
+ * crosses to the host.  *kept_dev (device int32) = min(k, count).  `ws`: as for ru3d_filter_components, sized by
+ * ru3d_filter_components_workspace_bytes(count) - the call uses its renumbering table. */
+#define RU3D_KEEP_LARGEST_MAX 8
+int ru3d_keep_largest_components(const int32_t* labels, int X, int Y, int Z, int count, const int32_t* sizes, int k,
+                                 uint8_t* mask_inout, int32_t* labels_out, int32_t* kept_dev, void* ws, size_t ws_bytes,
+                                 void* stream);
 /* cascade_predict_case (trainer.py:203-240).  total: zero-initialised float64 [X, Y, Z, C], hits: zero-initialised
  * int32 [X, Y, Z] (the reference's C copies of `hits` are equal).  accumulate: prob is one region's float32
  * [rx, ry, rz, C] map whose box starts at (bx, by, bz) in volume coordinates (negative where the padded box leaves the
@@ -614,6 +624,21 @@ int ru3d_mask_unpack(const uint64_t* bits, int X, int Y, int Z, int value, int p
  * binary_dilation is the reflected set {centre - s}. */
 int ru3d_binary_morph(const uint64_t* src, uint64_t* dst, int X, int Y, int Z, int op, const ru3d_morph_row* rows,
                       int num_rows, int border_value, void* stream);
+/* scipy.ndimage.binary_propagation on packed volumes (csrc/propagate.hip).  `reach` holds the seed on entry and is
+ * grown in place: a voxel of `allowed` (of its complement inside the volume with invert_allowed = 1) is set once one of
+ * its neighbours is - the 6 face neighbours for connectivity 1, all 26 for connectivity 3.  A seed voxel outside
+ * `allowed` stays set and spreads like any other, as in scipy.  A voxel outside the volume reads as set when every
+ * axis along which it is outside (0 = X, 1 = Y, 2 = Z) has its bit in border_axes, else as clear; a volume of fewer
+ * axes names only the axes it has.  The call clears changed_dev[0 .. rounds) (device int32, 1 <= rounds <= 64) and
+ * runs `rounds` rounds as `rounds` launches; changed_dev[r] = the tiles that grew in round r.  A round that counts 0 is
+ * the fixpoint, and later rounds only read.  Convergence is the caller's loop: download the counters, stop when the
+ * last is 0, else call again.  The fixpoint is unique, so the result is the same bytes in every run.  `allowed` is
+ * only read and may carry set bits at z >= Z; `reach` must not. */
+int ru3d_binary_propagate(const uint64_t* allowed, int invert_allowed, uint64_t* reach, int X, int Y, int Z,
+                          int connectivity, int border_axes, int rounds, int32_t* changed_dev, void* stream);
+/* out = mask | ~reach inside the volume (binary_fill_holes: reach = what the outside floods of the complement of mask),
+ * zeros at z >= Z; three buffers, not in place. */
+int ru3d_mask_fill_result(const uint64_t* mask, const uint64_t* reach, uint64_t* out, int X, int Y, int Z, void* stream);
 /* table (device int64 [(C + 1)][(C + 1)], C = num_classes <= 32; zeroed by the call, on `stream`):
  * table[min(label[i], C)][min(pred[i], C)] += 1 over n < 2^31 voxels of two uint8 volumes of any alignment.  Integer
  * atomics only: exact, and the same in every run.  The grid is sized by ru3d_get_cu_budget(). */
