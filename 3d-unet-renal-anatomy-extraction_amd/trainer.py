@@ -1634,6 +1634,99 @@ def batch_extract_centerline(pred_dir, save_dir, data_range=None, device=None, l
             for i in (data_range if data_range is not None else range(len(pred_files)))]
 
 
+# ------------------------------------------------------------------ vessel trees: nodes and branches of a centreline
+def _vessel_graph_dict(name, g, rounds, affine):
+    """The graph `g` (skeleton.graph or its numpy twin, with radii) of one structure as plain Python numbers and lists."""
+    import transform
+    nodes, branches = g['node_table'], g['branch_table']
+    centroids = nodes[:, 2:5].astype(np.float64) / nodes[:, 0:1].astype(np.float64)
+    world = transform._to_world_numpy(centroids, np.zeros((0, 3), np.int32), affine)[0]
+    segments = []
+    for b in range(g['branches']):
+        segments.append({'id': b + 1, 'nodes': [int(branches[b, 3]), int(branches[b, 4])], 'voxels': int(branches[b, 0]),
+                         'length': float(g['length'][b]), 'chord': float(g['chord'][b]),
+                         'tortuosity': float(g['tortuosity'][b]), 'radius_min': float(g['radius_min'][b]),
+                         'radius_mean': float(g['radius_mean'][b]), 'radius_max': float(g['radius_max'][b])})
+    return {'label': name, 'nodes': g['nodes'], 'branches': g['branches'],
+            'bifurcations': int((nodes[:, 1] >= 3).sum()), 'endpoints': int((nodes[:, 1] == 1).sum()),
+            'loops': int((branches[:, 3] < 0).sum()), 'pruned_rounds': rounds, 'segments': segments,
+            'node_centroids': [[float(v) for v in p] for p in world]}
+
+
+def vessel_graph_case(case, labels=None, key='pred', min_branch_mm=0.0):
+    """The vessel tree of every structure of the label volume `case[key]` as a graph: the structure is thinned
+    (transform.skeletonize), spurs shorter than min_branch_mm are pruned (skeleton.prune; 0 prunes nothing), and the
+    skeleton's voxel graph is read as nodes and branches (skeleton.graph, include/ru3d.h "skeleton graph").  A list of
+    dicts of plain numbers and lists, ready for json:
+      label           the value (or the tuple of values whose union was thinned),
+      nodes, branches   their numbers; bifurcations (nodes of valence >= 3), endpoints (valence 1), loops (closed
+                      branches without a node), pruned_rounds (rounds of pruning run, 0 without pruning),
+      segments        per branch: id, nodes (the two it hangs on, -1 -1 for a loop), voxels, length, chord and radius_min /
+                      radius_mean / radius_max in millimetres, tortuosity = length / chord,
+      node_centroids  per node, world coordinates (`case['affine']`; voxel coordinates without one).
+    The voxel spacing is that of the affine.  A numpy volume takes the numpy route (the twins in transform.py); a HIP
+    volume is packed, thinned, pruned and labelled on the device (csrc/skeleton.hip, csrc/skeleton_graph.hip) and only
+    the tables come down.  Both routes give the same numbers."""
+    from data import get_spacing
+    import transform
+    (volume,), ndim, hip = _centerline_operands(case, (key,), "vessel_graph_case")
+    if not float(min_branch_mm) >= 0:
+        raise ValueError("vessel_graph_case: min_branch_mm=%r (>= 0)" % (min_branch_mm,))
+    affine = np.asarray(case['affine'], dtype=np.float64) if case.get('affine') is not None else np.eye(4)
+    spacing = get_spacing(affine)
+    top = 0
+    if labels is None:
+        top = (int(volume.max().item()) if volume.numel() else 0) if hip else (int(volume.max()) if volume.size else 0)
+    results = []
+    for name, values in _mesh_labels(labels, top):
+        rounds = 0
+        if hip:
+            import skeleton
+            mask = _packed_union(volume, values)
+            skel = skeleton.thin(mask)
+            if min_branch_mm > 0:
+                skel, rounds = skeleton.prune(skel, min_branch_mm, spacing[3 - ndim:])
+            g = skeleton.graph(skel, mask, spacing[3 - ndim:])
+        else:
+            mask = np.isin(volume, values)
+            skel = transform._skeleton_numpy(mask)[0]
+            if min_branch_mm > 0:
+                skel, rounds = transform._skeleton_prune_numpy(skel, min_branch_mm, spacing)
+            g = transform._skeleton_graph_numpy(skel, _radii_squared_numpy(skel, mask, spacing), spacing)
+        results.append(_vessel_graph_dict(name, g, rounds, affine))
+    return results
+
+
+def extract_vessel_graph(pred_file, save_dir=None, device=None, labels=None, min_branch_mm=0.0):
+    """vessel_graph_case of a NIfTI label volume with the file's affine.  save_dir: every structure's graph is written as
+    `<case_id>.label_<n>.graph.json` (utils.json_save) and its dict gains 'file'.  device: a HIP device uploads the volume
+    (as bytes) and works there.  Prints one line per structure; returns the list of dicts."""
+    import nifti
+    from pathlib import Path
+    from utils import json_save
+    pred_file = Path(pred_file)
+    case_id = pred_file.name
+    for suffix in ('.gz', '.nii', '.pred'):
+        if case_id.endswith(suffix):
+            case_id = case_id[:-len(suffix)]
+    pred, affine, _ = nifti.load(pred_file)
+    pred = np.ascontiguousarray(np.clip(pred, 0, 255).astype(np.uint8))
+    case = {'case_id': case_id, 'affine': affine, 'pred': pred if device is None else torch.from_numpy(pred).to(device)}
+    results = vessel_graph_case(case, labels, 'pred', min_branch_mm)
+    if save_dir is not None:
+        save_dir = Path(save_dir)
+        save_dir.mkdir(parents=True, exist_ok=True)
+    for r in results:
+        print("%s label_%s: %d nodes (%d bifurcations, %d endpoints), %d branches (%d loops), %.1f mm of branches, "
+              "%d pruning rounds" % (case_id, _label_name(r['label']), r['nodes'], r['bifurcations'], r['endpoints'],
+                                     r['branches'], r['loops'], sum(s['length'] for s in r['segments']), r['pruned_rounds']))
+        if save_dir is not None:
+            path = save_dir / ('%s.label_%s.graph.json' % (case_id, _label_name(r['label'])))
+            json_save(path, r)
+            r['file'] = path
+    return results
+
+
 def preview_case(case, key='pred', axes=(0, 1, 2), num_slices=8, views=((30, 20), (120, 20), (210, -20)), size=256,
                  alpha=None, labels=None, colours=None, window=None, pixel_mm=None):
     """One picture of a case to leaf through, uint8 [H, W, 3]: `visualize.case_sheet` (slices of the image under the

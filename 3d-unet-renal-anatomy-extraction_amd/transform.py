@@ -579,6 +579,119 @@ def _skeleton_length_numpy(skel, spacing):
     return total
 
 
+def _skeleton_components_numpy(kind, lin):
+    """(labels int64 [X, Y, Z], count, first voxel of each) of the 26-connected components of a boolean volume, numbered
+    in the order of their first voxel (linear index `lin`)."""
+    lab, count = ndi.label(kind, np.ones((3, 3, 3), dtype=bool))
+    lab = lab.astype(np.int64)
+    if not count:
+        return lab, 0, np.zeros(0, dtype=np.int64)
+    first = np.atleast_1d(ndi.minimum(lin, lab, np.arange(1, count + 1))).astype(np.int64)
+    order = np.argsort(first, kind='stable')
+    remap = np.zeros(count + 1, dtype=np.int64)
+    remap[order + 1] = np.arange(1, count + 1)
+    return remap[lab], count, first[order]
+
+
+def _skeleton_graph_numpy(skel, sq=None, spacing=(1, 1, 1)):
+    """skeleton.graph on the host, and the definition the device is held to (include/ru3d.h, "skeleton graph"): a
+    boolean volume [X, Y, Z] as nodes (the 26-connected components of the voxels that do not have exactly two set
+    neighbours) and branches (those of the voxels that do).  The same dict as skeleton.graph with `ids` a numpy int32
+    vector.  sq: the squared radii, as a float64 volume of skel's shape or as the vector over skel's voxels in element
+    order; with it the dict has radius_min, radius_mean, radius_max per branch."""
+    skel = np.asarray(skel, dtype=bool)
+    X, Y, Z = skel.shape
+    path = skel & (_skeleton_neighbours_numpy(skel) == 2)
+    node = skel & ~path
+    lin = np.arange(X * Y * Z, dtype=np.int64).reshape(X, Y, Z)
+    node_label, M, node_first = _skeleton_components_numpy(node, lin)
+    branch_label, B, _ = _skeleton_components_numpy(path, lin)
+    signed = branch_label - node_label                                      # +b on a path voxel, -m on a node voxel
+    node_table = np.zeros((M, 6), dtype=np.int64)
+    branch_table = np.zeros((B, 18), dtype=np.int64)
+    m = node_label[node] - 1
+    node_table[:, 0] = np.bincount(m, minlength=M)
+    for column, coordinate in zip((2, 3, 4), np.nonzero(node)):
+        np.add.at(node_table[:, column], m, coordinate)
+    node_table[:, 5] = node_first
+    branch_table[:, 0] = np.bincount(branch_label[path] - 1, minlength=B)
+    branch_table[:, 1:5] = -1
+    padded = np.zeros((X + 2, Y + 2, Z + 2), dtype=np.int64)
+    padded[1:-1, 1:-1, 1:-1] = signed
+    attachments = [np.zeros((0, 3), dtype=np.int64)]
+    for cell in range(27):
+        if cell == 13:
+            continue
+        dx, dy, dz = cell // 9 - 1, (cell // 3) % 3 - 1, cell % 3 - 1
+        other = padded[1 + dx:X + 1 + dx, 1 + dy:Y + 1 + dy, 1 + dz:Z + 1 + dz]
+        touch = (signed > 0) & (other < 0)                                  # a path voxel p and the node voxel p + o
+        np.add.at(node_table[:, 1], -other[touch] - 1, 1)
+        attachments.append(np.stack((signed[touch], lin[touch], -other[touch]), axis=1))
+        if cell > 13:                                                       # every unordered pair once
+            edge = (signed != 0) & (other != 0) & ((signed > 0) | (other > 0))
+            np.add.at(branch_table[:, 5 + cell - 14], np.where(signed > 0, signed, other)[edge] - 1, 1)
+    attachments = np.concatenate(attachments)
+    attachments = attachments[np.lexsort((attachments[:, 2], attachments[:, 1], attachments[:, 0]))]
+    per_branch = np.bincount(attachments[:, 0] - 1, minlength=B)
+    assert ((per_branch == 0) | (per_branch == 2)).all()                    # a simple path or a closed loop
+    open_ = per_branch == 2
+    branch_table[open_, 1], branch_table[open_, 2] = attachments[0::2, 1], attachments[1::2, 1]
+    branch_table[open_, 3], branch_table[open_, 4] = attachments[0::2, 2], attachments[1::2, 2]
+    out = {'ids': signed[skel].astype(np.int32), 'n': int(skel.sum()), 'nodes': M, 'branches': B,
+           'node_table': node_table, 'branch_table': branch_table}
+
+    sx, sy, sz = (float(s) for s in spacing)
+    length = np.zeros(B, dtype=np.float64)
+    for k, step in enumerate(_skeleton_step_lengths(spacing)):
+        length = length + branch_table[:, 5 + k].astype(np.float64) * step
+    x0, y0, z0 = np.unravel_index(np.where(open_, branch_table[:, 1], 0), (X, Y, Z))
+    x1, y1, z1 = np.unravel_index(np.where(open_, branch_table[:, 2], 0), (X, Y, Z))
+    ax, ay, az = sx * (x1 - x0).astype(np.float64), sy * (y1 - y0).astype(np.float64), sz * (z1 - z0).astype(np.float64)
+    chord = np.where(open_, np.sqrt(ax * ax + (ay * ay + az * az)), np.nan)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        out.update(length=length, chord=chord, tortuosity=np.where(chord > 0, length / chord, np.nan))
+    if sq is not None:
+        sq = np.asarray(sq, dtype=np.float64)
+        values = sq[path] if sq.shape == skel.shape else sq[path[skel]]
+        b = branch_label[path] - 1
+        rmin_sq, rmax_sq, rsum_q = np.full(B, np.inf), np.zeros(B), np.zeros(B, dtype=np.int64)
+        np.minimum.at(rmin_sq, b, values)
+        np.maximum.at(rmax_sq, b, values)
+        finite = np.isfinite(values)
+        np.add.at(rsum_q, b[finite], np.rint(np.sqrt(values[finite]) * float(1 << 24)).astype(np.int64))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            mean = rsum_q.astype(np.float64) / float(1 << 24) / branch_table[:, 0].astype(np.float64)
+        out.update(radius_min=np.sqrt(rmin_sq), radius_mean=np.where(np.isinf(rmax_sq), np.inf, mean),
+                   radius_max=np.sqrt(rmax_sq))
+    return out
+
+
+def _skeleton_prune_numpy(skel, min_length, spacing=(1, 1, 1), max_rounds=None):
+    """skeleton.prune on the host: (pruned boolean volume, rounds).  A spur is a branch shorter than min_length with
+    exactly one end on a node of valence 1 made of a single voxel and the other end on a node of valence >= 3; a round
+    erases the path voxels and the end voxel of every spur of the graph as it is when the round begins.  Rounds repeat
+    until one finds no spur (that round is counted) or max_rounds."""
+    out = np.array(skel, dtype=bool)
+    rounds = 0
+    while max_rounds is None or rounds < max_rounds:
+        g = _skeleton_graph_numpy(out, None, spacing)
+        rounds += 1
+        nodes, gone = g['node_table'], []
+        for b, row in enumerate(g['branch_table']):
+            n0, n1 = int(row[3]), int(row[4])
+            if n0 < 1 or not g['length'][b] < min_length:
+                continue
+            for tip, far in ((n0, n1), (n1, n0)):
+                if nodes[tip - 1, 0] == 1 and nodes[tip - 1, 1] == 1 and nodes[far - 1, 1] >= 3:
+                    gone += [b + 1, -tip]
+        if not gone:
+            break
+        signed = np.zeros(out.shape, dtype=np.int64)
+        signed[out] = g['ids']
+        out &= ~np.isin(signed, gone)
+    return out, rounds
+
+
 def skeletonize(input, max_iterations=None):
     """The curve skeleton of the non-zero voxels of a bool / uint8 volume of 1 to 3 axes: a topology-preserving thinning
     (objects 26-connected, background 6-connected, outside the volume is background) that deletes simple voxels

@@ -755,6 +755,52 @@ int ru3d_skeleton_overlap(const uint64_t* a, const uint64_t* b, int X, int Y, in
  * elements t, t + 256, .. in order starting from 0, then seven halving steps s[t] = fl(s[t] + s[t + h]), h = 128 .. 1. */
 int ru3d_skeleton_radius_stats(const double* sq, int64_t n, double* out, void* stream);
 
+/* ------------------------------------------------------------------ skeleton graph */
+/* The voxel graph of a packed mask S as nodes and branches: how many segments a vessel tree has, which segment hangs on
+ * which branch point, how long and how thick each one is.  S is any packed mask, thin or not, X*Y*Z < 2^31; bits at
+ * z >= Z are ignored.  Adjacency is the 26-neighbourhood, deg(p) the number of set voxels in N26*(p).  Every order
+ * below is element order (x slowest, z fastest), a linear index is (x Y + y) Z + z.
+ *
+ *   Voxel kinds.  A path voxel has deg(p) == 2; every other set voxel (deg 0, 1 or >= 3) is a node voxel.
+ *   Nodes.        The 26-connected components of the node voxels.  An end voxel that touches a junction clique belongs
+ *                 to that node (a one-voxel spur is absorbed); two node voxels that touch are never two nodes.
+ *   Branches.     The 26-connected components of the path voxels.  Each of a path voxel's two neighbours is a path voxel
+ *                 of the same branch or a node voxel, so a branch is a simple path with exactly two attachments to nodes
+ *                 (possibly to the same node; a path of one voxel attaches with both its neighbours) or a closed loop
+ *                 with none.  Every edge of the voxel graph lies in exactly one branch or inside exactly one node.
+ *   Numbering.    Nodes 1 .. M and branches 1 .. B, each in the order of their first voxel (ru3d_label_components).
+ *   ids           int32, one per set voxel in element order (the order of ru3d_edt_gather): +b on a voxel of branch b,
+ *                 -m on a voxel of node m.
+ *   nodes         int64 [M, 6]: voxels, valence (the number of attachments; a branch attached twice counts twice),
+ *                 sum_x, sum_y, sum_z (integer coordinate sums), first (the linear index of its first voxel).
+ *   branches      int64 [B, 18]: voxels; t0, t1, the linear indices of the two terminal path voxels, t0 <= t1; n0, n1,
+ *                 the nodes attached at t0 and at t1, n0 <= n1 when t0 == t1 (all four -1 for a loop); pairs[13], per
+ *                 offset o of cells 14 .. 26 (the indexing of ru3d_skeleton_length) the unordered pairs {p, q} of
+ *                 adjacent set voxels that differ by +-o with at least one of them a path voxel of this branch, each
+ *                 pair once, the attachment edges included.  A length is not computed here: a caller folds pairs with
+ *                 the expression of ru3d_skeleton_length and gets the numpy route's bits.
+ *   branch_radii  [B, 3] of 8 bytes, with sq (float64 [X, Y, Z], squared radii >= 0, radius < 2^15 units): float64
+ *                 rmin_sq and rmax_sq, exact over the branch's path voxels, and int64 rsum_q = the sum over its path
+ *                 voxels with finite v of llrint(sqrt(v) 2^24) - the square root is correctly rounded and the scaling
+ *                 exact, so this is an integer sum without an order.  +inf shows in rmax_sq and adds nothing to the sum.
+ * Integer atomics only: the same bytes in every run and under every CU budget.
+ *
+ * ru3d_skeleton_graph_label: counts (device int64 [3]) = (set voxels n, M, B); nothing is written at or beyond
+ * ids[capacity].  When n > capacity nothing is labelled, ids is left alone and M = B = 0: the caller compares
+ * counts[0] with its capacity.  ids == NULL with capacity == 0 counts the voxels only.  No host read.
+ * ru3d_skeleton_graph_measure fills the tables from the ids of the same mask (n, M, B: what label counted); sq and
+ * branch_radii are both given or both NULL.  ru3d_skeleton_graph_erase clears, in place, the voxels of the branches b
+ * with flags_branch[b - 1] != 0 and of the nodes m with flags_node[m - 1] != 0 (device bytes [B] and [M]).
+ * Workspace, all three: 3 * ru3d_skeleton_workspace_bytes(X, Y, Z) - the prefix sums of the ranks, the path voxels and
+ * the first voxels of the nodes and branches, a 64-bit plane of the packed words or less each. */
+int ru3d_skeleton_graph_label(const uint64_t* skel, int X, int Y, int Z, int32_t* ids, int64_t capacity, int64_t* counts,
+                              void* ws, size_t ws_bytes, void* stream);
+int ru3d_skeleton_graph_measure(const uint64_t* skel, int X, int Y, int Z, const int32_t* ids, int64_t n, int64_t M, int64_t B,
+                                const double* sq, int64_t* nodes, int64_t* branches, void* branch_radii, void* ws,
+                                size_t ws_bytes, void* stream);
+int ru3d_skeleton_graph_erase(uint64_t* skel, int X, int Y, int Z, const int32_t* ids, int64_t n, int64_t M, int64_t B,
+                              const uint8_t* flags_branch, const uint8_t* flags_node, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ soft skeletons, soft-clDice loss */
 /* The soft skeleton of Shit et al. (clDice, CVPR 2021) on float32 volumes x[A][B][Z] (Z fastest), `nvol` of them behind
  * one another; nothing outside a volume takes part and nothing crosses from one volume into the next.
