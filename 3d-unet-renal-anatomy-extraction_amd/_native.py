@@ -264,6 +264,9 @@ SIGNATURES = {
     "ru3d_skeleton_graph_label": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ru3d_skeleton_graph_measure": (_i, [_vp, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru3d_skeleton_graph_erase": (_i, [_vp, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_nearest_site": (_i, [_vp, _i, _i, _i, ctypes.POINTER(_dbl), _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_site_assign": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ru3d_territory_tally": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ru3d_cldice_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ru3d_cldice_state_bytes": (_sz, []),
     "ru3d_soft_skeleton_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1727,6 +1727,141 @@ def extract_vessel_graph(pred_file, save_dir=None, device=None, labels=None, min
     return results
 
 
+# ------------------------------------------------------------------ vessel territories: an organ by nearest branch
+def _label_values(entry, what):
+    values = tuple(int(v) for v in entry) if isinstance(entry, (tuple, list)) else (int(entry),)
+    if not values or any(v < 1 or v > 255 for v in values):
+        raise ValueError("vessel_territories_case: %s=%r (a value 1 .. 255, or a tuple of them)" % (what, entry))
+    return values
+
+
+def vessel_territories_case(case, vessel, organ, other=None, key='pred', min_branch_mm=0.0, root=None,
+                            return_labels=False):
+    """Which part of an organ every branch of a vessel tree feeds: the structure `vessel` of the label volume
+    `case[key]` is thinned, pruned and read as a graph exactly as vessel_graph_case does, and the voxels of `organ` -
+    together with those of `other` (a tumour is part of the organ it grows in, though it has a label of its own) - are
+    partitioned by their nearest centreline voxel under the affine's spacing (territory.nearest: the exact Euclidean
+    feature transform, ties by the rule of include/ru3d.h).  vessel, organ, other: a label value or a tuple of values.
+    With organ == vessel every vessel voxel gets its branch: the vessel mask coloured by branch, and the territories are
+    the branches' vessel volumes.  Returns the dict of vessel_graph_case for the vessel, with, per segment,
+      territory_voxels, territory_ml   the voxels nearest to the branch's own path voxels, and their volume,
+      downstream_voxels, downstream_ml   the same for the branch, the node it leads to and everything beyond it in the
+                      tree rooted at `root` (territory.rooted: None picks the end node whose branch is thickest, the
+                      ostium; else a node number),
+      parent, depth, order, reachable, chord   the branch's place in that tree (order: Strahler's),
+      other_voxels, downstream_other_voxels, downstream_other_fraction   with `other`: its voxels in the territory, in
+                      everything downstream, and the share of all of `other` that the branch and its subtree supply,
+    and root, organ_voxels (the partitioned voxels), unassigned_voxels (those of a case without any centreline),
+    node_territory_voxels (per node; they go downstream with the branch that reaches the node) and, with `other`,
+    other_voxels.  return_labels=True adds 'labels', the int32 volume of territories (branch b -> b, node m ->
+    branches + m, 0 outside the organ), a HIP tensor on the device route.  numpy volumes take the twins of transform.py;
+    a HIP volume stays on the device (csrc/skeleton.hip, csrc/skeleton_graph.hip, csrc/territory.hip) and only the
+    graph's tables and the tally come down.  Both routes give the same numbers."""
+    from data import get_spacing
+    import territory
+    import transform
+    (volume,), ndim, hip = _centerline_operands(case, (key,), "vessel_territories_case")
+    if not float(min_branch_mm) >= 0:
+        raise ValueError("vessel_territories_case: min_branch_mm=%r (>= 0)" % (min_branch_mm,))
+    vessel_values, organ_values = _label_values(vessel, 'vessel'), _label_values(organ, 'organ')
+    other_values = _label_values(other, 'other') if other is not None else ()
+    region_values = tuple(sorted(set(organ_values) | set(other_values)))
+    affine = np.asarray(case['affine'], dtype=np.float64) if case.get('affine') is not None else np.eye(4)
+    spacing = get_spacing(affine)
+    rounds = 0
+    if hip:
+        import morphology
+        import skeleton
+        mask = _packed_union(volume, vessel_values)
+        skel = skeleton.thin(mask)
+        if min_branch_mm > 0:
+            skel, rounds = skeleton.prune(skel, min_branch_mm, spacing[3 - ndim:])
+        g = skeleton.graph(skel, mask, spacing[3 - ndim:])
+        tumour = morphology.unpack(_packed_union(volume, other_values)) if other_values else None
+        table, labels = territory.partition(skel, g, _packed_union(volume, region_values), spacing[3 - ndim:], tumour,
+                                            1 if other_values else 0)
+    else:
+        mask = np.isin(volume, vessel_values)
+        skel = transform._skeleton_numpy(mask)[0]
+        if min_branch_mm > 0:
+            skel, rounds = transform._skeleton_prune_numpy(skel, min_branch_mm, spacing)
+        g = transform._skeleton_graph_numpy(skel, _radii_squared_numpy(skel, mask, spacing), spacing)
+        region = np.isin(volume, region_values)
+        tumour = np.isin(volume, other_values).astype(np.uint8) if other_values else None
+        site_ids, K = territory.branch_sites(g)
+        index, _ = transform._nearest_site_numpy(skel, spacing)
+        labels = transform._site_assign_numpy(skel, site_ids, index, region)
+        table = transform._territory_tally_numpy(labels, K, tumour, 1 if other_values else 0, region)
+        labels = labels.reshape(tuple(case[key].shape))
+    B = g['branches']
+    tree = territory.rooted(g['node_table'], g['branch_table'], g['radius_mean'], root)
+    down = territory.downstream(table, tree, B)
+    voxel_ml = float(spacing[0] * spacing[1] * spacing[2]) / 1000.0
+    other_total = int(table[:, 1].sum()) if other_values else 0
+    result = _vessel_graph_dict(vessel_values if isinstance(vessel, (tuple, list)) else int(vessel), g, rounds, affine)
+    for b, s in enumerate(result['segments']):
+        own, below = int(table[b + 1].sum()), int(down[b].sum())
+        s.update(territory_voxels=own, territory_ml=own * voxel_ml, downstream_voxels=below, downstream_ml=below * voxel_ml,
+                 parent=int(tree['parent'][b]), depth=int(tree['depth'][b]), order=int(tree['order'][b]),
+                 reachable=bool(tree['reachable'][b]), chord=bool(tree['chord'][b]))
+        if other_values:
+            s.update(other_voxels=int(table[b + 1, 1]), downstream_other_voxels=int(down[b, 1]),
+                     downstream_other_fraction=_ratio(int(down[b, 1]), other_total))
+    result.update(root=int(tree['root']), organ_voxels=int(table.sum()), unassigned_voxels=int(table[0].sum()),
+                  node_territory_voxels=[int(v) for v in table[B + 1:].sum(axis=1)])
+    if other_values:
+        result['other_voxels'] = other_total
+    if return_labels:
+        result['labels'] = labels
+    return result
+
+
+def extract_vessel_territories(pred_file, save_dir=None, device=None, vessel=None, organ=None, other=None,
+                               min_branch_mm=0.0, root=None):
+    """vessel_territories_case of a NIfTI label volume with the file's affine (vessel and organ are required; organ ==
+    vessel colours the vessel mask by branch).  save_dir: the dict is written as `<case_id>.label_<n>.territories.json`
+    (n names the vessel; utils.json_save) and the int32 volume of territories as `<case_id>.label_<n>.territories.nii.gz`
+    with the file's affine; the dict gains 'file' and 'labels_file'.  device: a HIP device uploads the volume (as bytes)
+    and works there; the label volume is the one download beside the tables.  Prints one line; returns the dict."""
+    import nifti
+    from pathlib import Path
+    from utils import json_save
+    if vessel is None or organ is None:
+        raise ValueError("extract_vessel_territories: vessel and organ are required (label values or tuples of values)")
+    pred_file = Path(pred_file)
+    case_id = pred_file.name
+    for suffix in ('.gz', '.nii', '.pred'):
+        if case_id.endswith(suffix):
+            case_id = case_id[:-len(suffix)]
+    pred, affine, _ = nifti.load(pred_file)
+    pred = np.ascontiguousarray(np.clip(pred, 0, 255).astype(np.uint8))
+    case = {'case_id': case_id, 'affine': affine, 'pred': pred if device is None else torch.from_numpy(pred).to(device)}
+    r = vessel_territories_case(case, vessel, organ, other, 'pred', min_branch_mm, root, return_labels=True)
+    labels = r.pop('labels')
+    fed = [s['downstream_ml'] for s in r['segments'] if s['reachable'] and not s['chord'] and s['parent'] == 0]
+    print("%s label_%s: %d branches from node %d, %d organ voxels in territories (%d unassigned), %.1f ml below the root"
+          % (case_id, _label_name(r['label']), r['branches'], r['root'], r['organ_voxels'] - r['unassigned_voxels'],
+             r['unassigned_voxels'], sum(fed))
+          + (", %d voxels of label_%s" % (r['other_voxels'], '_'.join(str(v) for v in _label_values(other, 'other')))
+             if other is not None else ""))
+    if save_dir is not None:
+        save_dir = Path(save_dir)
+        save_dir.mkdir(parents=True, exist_ok=True)
+        stem = '%s.label_%s.territories' % (case_id, _label_name(r['label']))
+        json_save(save_dir / (stem + '.json'), r)
+        nifti.save(labels.cpu().numpy() if torch.is_tensor(labels) else labels, affine, save_dir / (stem + '.nii.gz'))
+        r['file'], r['labels_file'] = save_dir / (stem + '.json'), save_dir / (stem + '.nii.gz')
+    return r
+
+
+def batch_extract_vessel_territories(pred_dir, save_dir, data_range=None, device=None, **options):
+    """extract_vessel_territories over the sorted *.nii.gz files of `pred_dir`; returns the per-file dicts."""
+    from pathlib import Path
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    return [extract_vessel_territories(pred_files[i], save_dir, device, **options)
+            for i in (data_range if data_range is not None else range(len(pred_files)))]
+
+
 def preview_case(case, key='pred', axes=(0, 1, 2), num_slices=8, views=((30, 20), (120, 20), (210, -20)), size=256,
                  alpha=None, labels=None, colours=None, window=None, pixel_mm=None):
     """One picture of a case to leaf through, uint8 [H, W, 3]: `visualize.case_sheet` (slices of the image under the

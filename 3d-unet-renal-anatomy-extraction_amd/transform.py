@@ -1193,3 +1193,89 @@ class RandomSpatialCrop(Crop):
             label, case['label_margin'] = label
         case['label'] = label
         return case
+
+
+# ------------------------------------------------------------------ nearest site / territories (contract: include/ru3d.h)
+def _nearest_pass_numpy(value, step, axis):
+    """One pass of the separable feature transform along `axis` of a float64 volume: (least fl(fl(fl(step (l - l'))^2) +
+    value[l']) over l', the smallest l' that attains it).  argmin takes the first of equal candidates."""
+    v = np.moveaxis(value, axis, -1)
+    L = v.shape[-1]
+    rows = v.reshape(-1, L)
+    t = step * (np.arange(L)[:, None] - np.arange(L)[None, :]).astype(np.float64)
+    sq = t * t                                                              # [l, l']
+    best = np.empty(rows.shape, dtype=np.float64)
+    arg = np.empty(rows.shape, dtype=np.int64)
+    chunk = max(1, (1 << 22) // (L * L))
+    for r in range(0, len(rows), chunk):
+        cand = sq[None, :, :] + rows[r:r + chunk, None, :]
+        a = cand.argmin(axis=-1)
+        arg[r:r + chunk] = a
+        best[r:r + chunk] = np.take_along_axis(cand, a[..., None], axis=-1)[..., 0]
+    return np.moveaxis(best.reshape(v.shape), -1, axis), np.moveaxis(arg.reshape(v.shape), -1, axis)
+
+
+def _nearest_site_numpy(sites, spacing=(1, 1, 1)):
+    """The definition ru3d_nearest_site is held to (include/ru3d.h, "nearest site / territories"): (index int32, sq
+    float64) of a bool volume [X, Y, Z] of sites - the linear index of the nearest site of every voxel, chosen pass by
+    pass (z, then y, then x) by value with the smaller coordinate winning a tie, and the squared distance
+    fl(A + fl(B + C)) to it.  No site: -1 and inf."""
+    sites = np.asarray(sites, dtype=bool)
+    X, Y, Z = sites.shape
+    sx, sy, sz = (float(s) for s in spacing)
+    value, at_z = _nearest_pass_numpy(np.where(sites, 0.0, np.inf), sz, 2)
+    value, at_y = _nearest_pass_numpy(value, sy, 1)
+    site = at_y * Z + np.take_along_axis(at_z, at_y, axis=1)
+    value, at_x = _nearest_pass_numpy(value, sx, 0)
+    site = at_x * (Y * Z) + np.take_along_axis(site, at_x, axis=0)
+    return np.where(np.isinf(value), -1, site).astype(np.int32), value
+
+
+def _site_assign_numpy(sites, site_ids, index, region=None):
+    """ru3d_site_assign on the host: int32 labels, site_ids[rank of index[p] among the sites in element order] where
+    `region` (None: everywhere) is set and index[p] >= 0, 0 elsewhere."""
+    sites = np.asarray(sites, dtype=bool)
+    site_ids = np.asarray(site_ids, dtype=np.int32)
+    if site_ids.shape != (int(sites.sum()),):
+        raise ValueError("site_assign: %s ids for %d sites" % (site_ids.shape, int(sites.sum())))
+    rank = np.cumsum(sites.reshape(-1)) - 1
+    take = index >= 0 if region is None else (index >= 0) & np.asarray(region, dtype=bool)
+    if not sites.reshape(-1)[index[take]].all():
+        raise ValueError("site_assign: an index that is not a site")
+    labels = np.zeros(sites.shape, dtype=np.int32)
+    labels[take] = site_ids[rank[index[take]]]
+    return labels
+
+
+def _territory_tally_numpy(labels, K, other=None, num_other=0, region=None):
+    """ru3d_territory_tally on the host: int64 [K + 1, num_other + 1], the voxels of `region` (None: all) per label and
+    per min(other, num_other)."""
+    cols = int(num_other) + 1
+    if other is None and num_other:
+        raise ValueError("territory_tally: num_other=%r without `other`" % (num_other,))
+    take = np.ones(labels.shape, dtype=bool) if region is None else np.asarray(region, dtype=bool)
+    l = labels[take].astype(np.int64)
+    if l.size and (l.min() < 0 or l.max() > K):
+        raise ValueError("territory_tally: a label outside 0 .. %d" % K)
+    o = np.minimum(other[take].astype(np.int64), num_other) if other is not None else 0
+    return np.bincount(l * cols + o, minlength=(int(K) + 1) * cols).astype(np.int64).reshape(int(K) + 1, cols)
+
+
+def nearest_feature(input, sampling=None):
+    """(index, squared distance) of the nearest non-zero voxel of `input` (1 to 3 axes) for every voxel: index is int32,
+    the linear index into the volume (-1 without any non-zero voxel), the squared distance float64 in `sampling` units
+    (inf then).  Among equally near voxels the choice is the one of include/ru3d.h, "nearest site / territories".
+    numpy in -> the numpy twin, numpy out; a HIP tensor in -> the kernels of csrc/territory.hip, HIP tensors out, equal
+    to the twin element for element."""
+    import distance
+    if torch.is_tensor(input):
+        import components
+        import morphology
+        import territory
+        return territory.nearest(morphology.pack(components.as_mask(input)), sampling)
+    volume = np.asarray(input)
+    if volume.ndim < 1 or volume.ndim > 3:
+        raise ValueError("nearest_feature: expected a volume of 1 to 3 axes, got shape %s" % (volume.shape,))
+    spacing = distance._spacing(sampling, volume.ndim)
+    index, sq = _nearest_site_numpy((volume != 0).reshape((1,) * (3 - volume.ndim) + volume.shape), spacing)
+    return index.reshape(volume.shape), sq.reshape(volume.shape)

@@ -801,6 +801,44 @@ int ru3d_skeleton_graph_measure(const uint64_t* skel, int X, int Y, int Z, const
 int ru3d_skeleton_graph_erase(uint64_t* skel, int X, int Y, int Z, const int32_t* ids, int64_t n, int64_t M, int64_t B,
                               const uint8_t* flags_branch, const uint8_t* flags_node, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ nearest site / territories */
+/* Which set voxel of a packed mask (a SITE: a centreline voxel of a vessel tree) is nearest to every voxel, the labels
+ * of a region by nearest site (a Voronoi partition: the territory of every branch) and their integer tally against a
+ * second label volume.  Masks are the packed masks of the morphology section, X*Y*Z < 2^31, a linear index is
+ * (x Y + y) Z + z, element order is the order of the linear index.
+ *
+ * ru3d_nearest_site: the exact Euclidean feature transform.  `spacing` is a HOST array of three finite values > 0 whose
+ * squared steps neither overflow nor underflow.  index (int32 [X, Y, Z]) receives the linear index of the nearest set
+ * voxel of `bits`, sq (float64 [X, Y, Z], or NULL) the squared distance to it, with exactly the bits ru3d_edt_squared
+ * gives for the same mask and spacing.  The site is chosen separably and BY VALUE, fl = round to nearest in float64:
+ *   Z pass   among the set voxels (x, y, z') of the voxel's own column the one with the least C = fl(fl(sz (z - z'))^2),
+ *            the smaller z' on equal C;  C_best(x, y, z) is that value, +inf for a column without a set voxel;
+ *   Y pass   over y' the least fl(B + C_best(x, y', z)), B = fl(fl(sy (y - y'))^2), the smaller y' on equal value;
+ *   X pass   over x' the least fl(A + (the Y pass's value at (x', y, z))), the smaller x' on equal value;
+ * and the site is the one the chosen (x', y', z') chain ends in.  Rounding is monotone, so the value equals the minimum
+ * over all sites of fl(A + fl(B + C)); with a spacing whose products are exact (unit, dyadic) the site is the one of
+ * least squared distance and, among those, of smallest linear index.  No set voxel at all: index -1 and sq +inf
+ * everywhere.  X and Y may not exceed RU3D_EDT_MAX_AXIS.  Workspace: ru3d_edt_workspace_bytes(X, Y, Z), and with
+ * sq == NULL 8 X Y Z bytes more (the values have to live somewhere between the passes). */
+int ru3d_nearest_site(const uint64_t* bits, int X, int Y, int Z, const double* spacing, int32_t* index, double* sq, void* ws,
+                      size_t ws_bytes, void* stream);
+/* labels (int32 [X, Y, Z]) = site_ids[rank(index[p])] where the bit of region_bits is set (everywhere with NULL) and
+ * index[p] >= 0, and 0 everywhere else.  rank(f) is the position of voxel f among the set bits of site_bits in element
+ * order - the order of ru3d_edt_gather and of the ids of ru3d_skeleton_graph_label - and site_ids is a device int32 [n].
+ * Checked on the device, nothing out of bounds read or written: n must be the number of set bits of site_bits (else
+ * every label is 0) and every index >= 0 inside the region a set voxel of site_bits (else that label is 0); either
+ * returns -2.  The call reads one word back: it returns after its kernels have run.  Workspace:
+ * 2 * ru3d_skeleton_workspace_bytes(X, Y, Z) - the error word, one int per 256 words of the mask and one int per word. */
+int ru3d_site_assign(const uint64_t* site_bits, const uint64_t* region_bits, const int32_t* index, const int32_t* site_ids,
+                     int64_t n, int X, int Y, int Z, int32_t* labels, void* ws, size_t ws_bytes, void* stream);
+/* table (int64 [K + 1, num_other + 1], overwritten) [labels[p]] [min(other[p], num_other)] += 1 over the voxels of
+ * region_bits (all voxels with NULL); `other` is a uint8 volume or NULL with num_other == 0 (one column).  Row 0 holds
+ * the region's voxels without a site.  A label outside 0 .. K is not counted and returns -2.  Integer counts only: the
+ * same table in every run and under every CU budget.  The call reads one word back, as ru3d_site_assign does.
+ * Workspace: 256 bytes. */
+int ru3d_territory_tally(const int32_t* labels, int K, const uint8_t* other, int num_other, const uint64_t* region_bits,
+                         int X, int Y, int Z, int64_t* table, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ soft skeletons, soft-clDice loss */
 /* The soft skeleton of Shit et al. (clDice, CVPR 2021) on float32 volumes x[A][B][Z] (Z fastest), `nvol` of them behind
  * one another; nothing outside a volume takes part and nothing crosses from one volume into the next.
