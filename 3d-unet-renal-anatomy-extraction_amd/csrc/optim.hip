@@ -1,38 +1,59 @@
 // The optimisers and what surrounds them: fused Adam (single tensor, multi-tensor, captured, and under the on-device fp16
 // loss scaler), the global L2 norm of the gradients with the clipping coefficient of torch.nn.utils.clip_grad_norm_, SGD
 // with (Nesterov) momentum and weight decay, AdamW, Adam with a clipped gradient, and the inf / nan check of loss scaling.
-// Every multi-tensor kernel walks the ru3d_adam_tensor table through the (tensor, chunk) block map of ru3d_adam_multi:
-// 256 threads, chunk_elems a multiple of 1024, an aligned f32x4 path and a scalar path for tails and for tensors that
-// do not sit on 16-byte boundaries, rows with a null `grad` skipped.
+// Every multi-tensor kernel takes its share of the ru3d_adam_tensor table from table_chunk(), the one place that reads
+// the (tensor, chunk) block map of ru3d_adam_multi, and walks it with one of two loops: multi_body (parameter, gradient
+// and state: every update rule) or grad_walk (the gradient alone: check, norm, scaling).  Both: 256 threads, chunk_elems
+// a multiple of 1024, an aligned f32x4 path and a scalar path for tails and for tensors that do not sit on 16-byte
+// boundaries, rows with a null `grad` skipped.
 //
 // Bits: each update rule is ONE per-element function compiled with floating-point contraction off, called from the
 // vector path and from the scalar path, by the kernel that takes its scalars as arguments and by the one that reads
-// them from the 8-float device row of a captured step - the four give identical bits (adam_multi_body's lesson,
-// below).  No floating-point atomics: the norm is a float64 sum of float64 squares, thread -> wave butterfly -> the
-// four waves of a block in order -> one workgroup over the per-block partials in order.
+// them from the 8-float device row of a captured step - the four give identical bits (AdamRule's lesson, below).  A
+// clipped and an unclipped step share a kernel: the coefficient is 1 without one, and x * 1.0f is x.  No
+// floating-point atomics: the norm is a float64 sum of float64 squares, thread -> wave butterfly -> the four waves of a
+// block in order -> one workgroup over the per-block partials in order.
 #include "common.h"
 #include <stddef.h>
 
 // --------------------------------------------------------------------------- the table walk
-// rule.first(): the rule keeps a first buffer in `exp_avg` (momentum / first moment); Rule::kSecond: it keeps `exp_avg_sq`
+// A block's share of the table: its row and the elements [begin, end) of that row's tensors.  A thread takes the 4-wide
+// slots at begin + 4 * threadIdx.x, + kSlotStride, ... in ascending order, and k = 0..3 inside a slot.
+struct TableChunk {
+    ru3d_adam_tensor t;
+    int64_t begin, end;
+};
+static constexpr int kSlotStride = 1024;        // 256 threads x 4 elements; chunk_elems is a multiple of it
+
+__device__ __forceinline__ TableChunk table_chunk(const ru3d_adam_tensor* __restrict__ tensors,
+                                                  const int32_t* __restrict__ block_map, int chunk_elems) {
+    TableChunk c;
+    c.t = tensors[block_map[2 * blockIdx.x]];
+    c.begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
+    c.end = c.begin + chunk_elems;
+    if (c.end > c.t.count) c.end = c.t.count;
+    return c;
+}
+
+// The update walk.  rule.first(): the rule keeps a first buffer in `exp_avg` (momentum / first moment); Rule::kSecond: it
+// keeps `exp_avg_sq`.  coef: the device-side clipping coefficient, null for an unclipped step.
 template <class Rule>
 __device__ __forceinline__ void multi_body(const ru3d_adam_tensor* __restrict__ tensors,
                                            const int32_t* __restrict__ block_map, int chunk_elems, const Rule rule,
                                            const float* __restrict__ coef) {
-    const ru3d_adam_tensor t = tensors[block_map[2 * blockIdx.x]];
+    const TableChunk ch = table_chunk(tensors, block_map, chunk_elems);
+    const ru3d_adam_tensor& t = ch.t;
     if (!t.grad) return;
     const bool first = rule.first();
     if ((first && !t.exp_avg) || (Rule::kSecond && !t.exp_avg_sq)) return;      // a row without its state is left alone
-    const int64_t begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
-    int64_t end = begin + chunk_elems;
-    if (end > t.count) end = t.count;
+    const int64_t end = ch.end;
     const float c = coef ? *coef : 1.f;          // x * 1.0f is x: the unclipped step needs no second body
     uintptr_t bits = ((uintptr_t)t.param) | ((uintptr_t)t.grad);
     if (first) bits |= (uintptr_t)t.exp_avg;
     if (Rule::kSecond) bits |= (uintptr_t)t.exp_avg_sq;
-    int64_t i = begin + (int64_t)threadIdx.x * 4;
+    int64_t i = ch.begin + (int64_t)threadIdx.x * 4;
     if ((bits & 15) == 0) {
-        for (; i + 3 < end; i += 1024) {
+        for (; i + 3 < end; i += kSlotStride) {
             f32x4 p = *reinterpret_cast<const f32x4*>(t.param + i);
             const f32x4 g = *reinterpret_cast<const f32x4*>(t.grad + i);
             f32x4 m = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
@@ -50,13 +71,35 @@ __device__ __forceinline__ void multi_body(const ru3d_adam_tensor* __restrict__ 
         }
     }
     // scalar tail (or unaligned tensors): this thread's remaining elements of its 4-wide slots
-    for (; i < end; i += 1024)
+    for (; i < end; i += kSlotStride)
         for (int k = 0; k < 4 && i + k < end; k++) {
             float pk = t.param[i + k], mk = first ? t.exp_avg[i + k] : 0.f, vk = Rule::kSecond ? t.exp_avg_sq[i + k] : 0.f;
             rule.elem(pk, t.grad[i + k], c, mk, vk);
             t.param[i + k] = pk;
             if (first) t.exp_avg[i + k] = mk;
             if (Rule::kSecond) t.exp_avg_sq[i + k] = vk;
+        }
+}
+
+// The gradient-only walk: every element g[j] of the chunk is loaded, handed to op, and - when `write` - replaced by
+// what op returned.  Nothing else is loaded or stored.  The caller has checked that the row has a gradient.
+template <class Op>
+__device__ __forceinline__ void grad_walk(const TableChunk& ch, bool write, Op op) {
+    float* g = const_cast<float*>(ch.t.grad);
+    const int64_t end = ch.end;
+    int64_t i = ch.begin + (int64_t)threadIdx.x * 4;
+    if ((((uintptr_t)g) & 15) == 0) {
+        for (; i + 3 < end; i += kSlotStride) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = op(v[k]);
+            if (write) *reinterpret_cast<f32x4*>(g + i) = v;
+        }
+    }
+    for (; i < end; i += kSlotStride)
+        for (int k = 0; k < 4 && i + k < end; k++) {
+            const float v = op(g[i + k]);
+            if (write) g[i + k] = v;
         }
 }
 
@@ -104,8 +147,12 @@ __global__ __launch_bounds__(256) void sgd_multi_dev_kernel(const ru3d_adam_tens
     multi_body(tensors, block_map, chunk_elems, sgd_rule(hyper[0], hyper[1], hyper[2], hyper[3], hyper[6]), coef);
 }
 
-// --------------------------------------------------------------------------- Adam (clipped) and AdamW
-// adam_multi_body's recurrence (below) on gh = g * gscale * coef; kDecay: torch.optim.AdamW's p *= 1 - lr * wd first.
+// --------------------------------------------------------------------------- Adam and AdamW
+// torch.optim.Adam on gh = g * gscale * coef:  m = b1 * m + (1 - b1) * gh;  v = b2 * v + (1 - b2) * gh * gh;
+// p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps).  kDecay: torch.optim.AdamW's p *= 1 - lr * wd first.
+// No fused multiply-adds here: the rule is compiled into several kernels (scalars as arguments / from device memory) and
+// into a vector and a scalar path - left to the compiler, the contraction of b2 * v + (1 - b2) * g * g differed
+// between them by one ulp, on the one parameter whose length is not a multiple of 4 (the head's bias).
 template <bool kDecay>
 struct AdamRule {
     float b1, b2, eps, step, bc2_sqrt, gscale, keep;
@@ -132,18 +179,20 @@ __device__ __forceinline__ AdamRule<kDecay> adam_rule(float lr, float b1, float 
     return r;
 }
 
-// Adam with a clipped gradient: the scalars of ru3d_adam_multi (sqrt(bias_corr2) taken on the host) / its hyper row
-__global__ __launch_bounds__(256) void adam_clip_kernel(const ru3d_adam_tensor* __restrict__ tensors,
-                                                        const int32_t* __restrict__ block_map, int chunk_elems, float lr,
-                                                        float b1, float b2, float eps, float bc1, float bc2_sqrt,
-                                                        float gscale, const float* __restrict__ coef) {
+// Adam, clipped or not: one launch for the whole model.  The scalars of ru3d_adam_multi (sqrt(bias_corr2) taken on the
+// host) ...
+__global__ __launch_bounds__(256) void adam_multi_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                         const int32_t* __restrict__ block_map, int chunk_elems,
+                                                         float lr, float b1, float b2, float eps, float bc1,
+                                                         float bc2_sqrt, float gscale, const float* __restrict__ coef) {
     multi_body(tensors, block_map, chunk_elems, adam_rule<false>(lr, b1, b2, eps, bc1, bc2_sqrt, gscale, 0.f), coef);
 }
 
-__global__ __launch_bounds__(256) void adam_clip_dev_kernel(const ru3d_adam_tensor* __restrict__ tensors,
-                                                            const int32_t* __restrict__ block_map, int chunk_elems,
-                                                            const float* __restrict__ hyper,
-                                                            const float* __restrict__ coef) {
+// ... or the same scalars from its hyper row in device memory (a captured launch: see ru3d.h)
+__global__ __launch_bounds__(256) void adam_multi_dev_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                             const int32_t* __restrict__ block_map, int chunk_elems,
+                                                             const float* __restrict__ hyper,
+                                                             const float* __restrict__ coef) {
     multi_body(tensors, block_map, chunk_elems,
                adam_rule<false>(hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[7], hyper[6], 0.f), coef);
 }
@@ -166,7 +215,56 @@ __global__ __launch_bounds__(256) void adamw_multi_dev_kernel(const ru3d_adam_te
                coef);
 }
 
-// --------------------------------------------------------------------------- Adam: single tensor, unclipped multi-tensor
+// ---- fp16 training inside a captured step: the loss scaler lives on the device (ru3d_amp_state, see ru3d.h).  The update
+// kernel skips itself when the gradient check found an overflow, takes 1 / scale and the number of steps really taken
+// from the state block (bias corrections from that count), and a one-thread kernel then moves the scaler: halve + reset
+// on overflow, count a clean step and double after `growth_interval` of them otherwise - apex's schedule
+// (reference trainer.py:492-493, 538-542), without the per-step read-back that kept the fp16 step out of a hipGraph.
+__global__ __launch_bounds__(256) void adam_multi_amp_kernel(const ru3d_adam_tensor* __restrict__ tensors,
+                                                             const int32_t* __restrict__ block_map, int chunk_elems,
+                                                             const float* __restrict__ hyper,
+                                                             const ru3d_amp_state* __restrict__ amp) {
+    if (amp->found_inf != 0.f) return;                                   // overflow: the step is skipped
+    const int t = __float_as_int(hyper[5]) + amp->steps + 1;             // Adam step number of this update
+    // the betas in double (float value + residual in the slots the captured amp launch does not use otherwise): the bias
+    // corrections then equal the host's `1 - beta ** t` to the last bit or two
+    const double b1d = (double)hyper[1] + (double)hyper[4], b2d = (double)hyper[2] + (double)hyper[7];
+    const double bc1 = 1.0 - pow(b1d, (double)t), bc2 = 1.0 - pow(b2d, (double)t);
+    multi_body(tensors, block_map, chunk_elems,
+               adam_rule<false>(hyper[0], hyper[1], hyper[2], hyper[3], (float)bc1, sqrtf((float)bc2), amp->inv_scale, 0.f),
+               nullptr);
+}
+
+__global__ void amp_update_kernel(ru3d_amp_state* amp, float growth, float backoff, int interval, float min_scale,
+                                  float max_scale) {
+    if (threadIdx.x || blockIdx.x) return;
+    if (amp->found_inf != 0.f) {
+        amp->scale = fmaxf(amp->scale * backoff, min_scale);
+        amp->tracker = 0;
+        amp->skipped += 1;
+    } else {
+        amp->steps += 1;
+        amp->tracker += 1;
+        if (amp->tracker >= interval) {
+            amp->scale = fminf(amp->scale * growth, max_scale);
+            amp->tracker = 0;
+        }
+    }
+    amp->inv_scale = 1.f / amp->scale;
+    amp->found_inf = 0.f;
+}
+
+extern "C" int ru3d_amp_update(ru3d_amp_state* amp, float growth_factor, float backoff_factor, int growth_interval,
+                               float min_scale, float max_scale, void* stream) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(amp && growth_factor >= 1.f && backoff_factor > 0.f && backoff_factor <= 1.f && growth_interval > 0 &&
+                     min_scale > 0.f && max_scale >= min_scale, "amp_update: bad argument");
+    hipLaunchKernelGGL(amp_update_kernel, dim3(1), dim3(64), 0, as_stream(stream), amp, growth_factor, backoff_factor,
+                       growth_interval, min_scale, max_scale);
+    return ru3d_check_launch("amp_update");
+}
+
+// --------------------------------------------------------------------------- Adam: single tensor
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t count,
                                                    float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
@@ -195,146 +293,6 @@ extern "C" int ru3d_adam_step(float* param, const float* grad, float* exp_avg, f
     return ru3d_check_launch("adam_step");
 }
 
-// multi-tensor form: one launch for the whole model (device-side tensor table + block map)
-__device__ __forceinline__ void adam_multi_body(const ru3d_adam_tensor* __restrict__ tensors,
-                                                const int32_t* __restrict__ block_map, int chunk_elems, float lr,
-                                                float b1, float b2, float eps, float bc1, float bc2_sqrt, float gscale) {
-    // no fused multiply-adds here: this body is compiled into two kernels (scalars as arguments / from device memory) and
-    // into a vector and a scalar path - left to the compiler, the contraction of b2 * v + (1 - b2) * g * g differed
-    // between them by one ulp, on the one parameter whose length is not a multiple of 4 (the head's bias)
-#pragma clang fp contract(off)
-    const ru3d_adam_tensor t = tensors[block_map[2 * blockIdx.x]];
-    if (!t.grad) return;
-    const int64_t begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
-    int64_t end = begin + chunk_elems;
-    if (end > t.count) end = t.count;
-    const float step = lr / bc1;
-    const bool vec = ((((uintptr_t)t.param) | ((uintptr_t)t.grad) | ((uintptr_t)t.exp_avg) | ((uintptr_t)t.exp_avg_sq)) & 15) == 0;
-    int64_t i = begin + (int64_t)threadIdx.x * 4;
-    if (vec) {
-        for (; i + 3 < end; i += 1024) {
-            f32x4 p = *reinterpret_cast<const f32x4*>(t.param + i);
-            const f32x4 g = *reinterpret_cast<const f32x4*>(t.grad + i);
-            f32x4 m = *reinterpret_cast<const f32x4*>(t.exp_avg + i);
-            f32x4 v = *reinterpret_cast<const f32x4*>(t.exp_avg_sq + i);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float gi = g[k] * gscale;
-                m[k] = b1 * m[k] + (1.f - b1) * gi;
-                v[k] = b2 * v[k] + (1.f - b2) * gi * gi;
-                p[k] -= step * (m[k] / (sqrtf(v[k]) / bc2_sqrt + eps));
-            }
-            *reinterpret_cast<f32x4*>(t.param + i) = p;
-            *reinterpret_cast<f32x4*>(t.exp_avg + i) = m;
-            *reinterpret_cast<f32x4*>(t.exp_avg_sq + i) = v;
-        }
-    }
-    // scalar tail (or unaligned tensors): this thread's remaining elements of its 4-wide slots
-    for (; i < end; i += 1024)
-        for (int k = 0; k < 4 && i + k < end; k++) {
-            const float gi = t.grad[i + k] * gscale;
-            const float mi = b1 * t.exp_avg[i + k] + (1.f - b1) * gi;
-            const float vi = b2 * t.exp_avg_sq[i + k] + (1.f - b2) * gi * gi;
-            t.exp_avg[i + k] = mi;
-            t.exp_avg_sq[i + k] = vi;
-            t.param[i + k] -= step * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-        }
-}
-
-
-__global__ __launch_bounds__(256) void adam_multi_kernel(const ru3d_adam_tensor* __restrict__ tensors,
-                                                         const int32_t* __restrict__ block_map, int chunk_elems,
-                                                         float lr, float b1, float b2, float eps, float bc1,
-                                                         float bc2_sqrt, float gscale) {
-    adam_multi_body(tensors, block_map, chunk_elems, lr, b1, b2, eps, bc1, bc2_sqrt, gscale);
-}
-
-// the per-step scalars from device memory (a captured launch: see ru3d.h)
-__global__ __launch_bounds__(256) void adam_multi_dev_kernel(const ru3d_adam_tensor* __restrict__ tensors,
-                                                             const int32_t* __restrict__ block_map, int chunk_elems,
-                                                             const float* __restrict__ hyper) {
-    adam_multi_body(tensors, block_map, chunk_elems, hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[7], hyper[6]);
-}
-
-extern "C" int ru3d_adam_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
-                               float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2,
-                               float grad_scale, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(tensors && block_map && nblocks > 0 && chunk_elems >= 1024 && (chunk_elems % 1024) == 0,
-                 "adam_multi: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
-                       chunk_elems, lr, beta1, beta2, eps, bias_corr1, sqrtf(bias_corr2), grad_scale);
-    return ru3d_check_launch("adam_multi");
-}
-
-extern "C" int ru3d_adam_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
-                                   int chunk_elems, const float* hyper, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(tensors && block_map && hyper && nblocks > 0 && chunk_elems >= 1024 && (chunk_elems % 1024) == 0,
-                 "adam_multi_dev: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(adam_multi_dev_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
-                       block_map, chunk_elems, hyper);
-    return ru3d_check_launch("adam_multi_dev");
-}
-
-// ---- fp16 training inside a captured step: the loss scaler lives on the device (ru3d_amp_state, see ru3d.h).  The update
-// kernel skips itself when the gradient check found an overflow, takes 1 / scale and the number of steps really taken
-// from the state block (bias corrections from that count), and a one-thread kernel then moves the scaler: halve + reset
-// on overflow, count a clean step and double after `growth_interval` of them otherwise - apex's schedule
-// (reference trainer.py:492-493, 538-542), without the per-step read-back that kept the fp16 step out of a hipGraph.
-__global__ __launch_bounds__(256) void adam_multi_amp_kernel(const ru3d_adam_tensor* __restrict__ tensors,
-                                                             const int32_t* __restrict__ block_map, int chunk_elems,
-                                                             const float* __restrict__ hyper,
-                                                             const ru3d_amp_state* __restrict__ amp) {
-    if (amp->found_inf != 0.f) return;                                   // overflow: the step is skipped
-    const int t = __float_as_int(hyper[5]) + amp->steps + 1;             // Adam step number of this update
-    // the betas in double (float value + residual in the slots the captured amp launch does not use otherwise): the bias
-    // corrections then equal the host's `1 - beta ** t` to the last bit or two
-    const double b1d = (double)hyper[1] + (double)hyper[4], b2d = (double)hyper[2] + (double)hyper[7];
-    const double bc1 = 1.0 - pow(b1d, (double)t), bc2 = 1.0 - pow(b2d, (double)t);
-    adam_multi_body(tensors, block_map, chunk_elems, hyper[0], hyper[1], hyper[2], hyper[3], (float)bc1, sqrtf((float)bc2),
-                    amp->inv_scale);
-}
-
-__global__ void amp_update_kernel(ru3d_amp_state* amp, float growth, float backoff, int interval, float min_scale,
-                                  float max_scale) {
-    if (threadIdx.x || blockIdx.x) return;
-    if (amp->found_inf != 0.f) {
-        amp->scale = fmaxf(amp->scale * backoff, min_scale);
-        amp->tracker = 0;
-        amp->skipped += 1;
-    } else {
-        amp->steps += 1;
-        amp->tracker += 1;
-        if (amp->tracker >= interval) {
-            amp->scale = fminf(amp->scale * growth, max_scale);
-            amp->tracker = 0;
-        }
-    }
-    amp->inv_scale = 1.f / amp->scale;
-    amp->found_inf = 0.f;
-}
-
-extern "C" int ru3d_adam_multi_amp(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
-                                   const float* hyper, const ru3d_amp_state* amp, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(tensors && block_map && hyper && amp && nblocks > 0 && chunk_elems >= 1024 && (chunk_elems % 1024) == 0,
-                 "adam_multi_amp: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(adam_multi_amp_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
-                       chunk_elems, hyper, amp);
-    return ru3d_check_launch("adam_multi_amp");
-}
-
-extern "C" int ru3d_amp_update(ru3d_amp_state* amp, float growth_factor, float backoff_factor, int growth_interval,
-                               float min_scale, float max_scale, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(amp && growth_factor >= 1.f && backoff_factor > 0.f && backoff_factor <= 1.f && growth_interval > 0 &&
-                     min_scale > 0.f && max_scale >= min_scale, "amp_update: bad argument");
-    hipLaunchKernelGGL(amp_update_kernel, dim3(1), dim3(64), 0, as_stream(stream), amp, growth_factor, backoff_factor,
-                       growth_interval, min_scale, max_scale);
-    return ru3d_check_launch("amp_update");
-}
-
 // --------------------------------------------------------------------------- loss scaling (fp16 storage)
 // Dynamic loss scaling of the reference's mixed-precision mode (apex O1, trainer.py:492-493, 538-542): gradients are
 // computed on `scale * loss`; before the optimizer step every gradient is checked for inf / nan (an overflow skips the
@@ -343,43 +301,14 @@ extern "C" int ru3d_amp_update(ru3d_amp_state* amp, float growth_factor, float b
 __global__ __launch_bounds__(256) void grad_scale_check_kernel(const ru3d_adam_tensor* __restrict__ tensors,
                                                                const int32_t* __restrict__ block_map, int chunk_elems,
                                                                float scale, float* __restrict__ found_inf) {
-    const ru3d_adam_tensor t = tensors[block_map[2 * blockIdx.x]];
-    if (!t.grad) return;
-    float* g = const_cast<float*>(t.grad);
-    const int64_t begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
-    int64_t end = begin + chunk_elems;
-    if (end > t.count) end = t.count;
-    const bool write = scale != 1.f;
+    const TableChunk ch = table_chunk(tensors, block_map, chunk_elems);
+    if (!ch.t.grad) return;
     bool bad = false;
-    int64_t i = begin + (int64_t)threadIdx.x * 4;
-    if ((((uintptr_t)g) & 15) == 0) {
-        for (; i + 3 < end; i += 1024) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                bad = bad || !(fabsf(v[k]) <= 3.402823466e38f);   // false for inf and nan
-                v[k] *= scale;
-            }
-            if (write) *reinterpret_cast<f32x4*>(g + i) = v;
-        }
-    }
-    for (; i < end; i += 1024)
-        for (int k = 0; k < 4 && i + k < end; k++) {
-            const float v = g[i + k];
-            bad = bad || !(fabsf(v) <= 3.402823466e38f);
-            if (write) g[i + k] = v * scale;
-        }
+    grad_walk(ch, scale != 1.f, [&](float v) {
+        bad = bad || !(fabsf(v) <= 3.402823466e38f);   // false for inf and nan
+        return v * scale;
+    });
     if (__any(bad) && (threadIdx.x & 63) == 0) *found_inf = 1.f;   // every writer stores the same value
-}
-
-extern "C" int ru3d_grad_scale_check(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
-                                     int chunk_elems, float scale, float* found_inf, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(tensors && block_map && found_inf && nblocks > 0 && chunk_elems >= 1024 && (chunk_elems % 1024) == 0,
-                 "grad_scale_check: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(grad_scale_check_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
-                       block_map, chunk_elems, scale, found_inf);
-    return ru3d_check_launch("grad_scale_check");
 }
 
 // --------------------------------------------------------------------------- gradient norm
@@ -398,24 +327,13 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const ru3d_adam_tensor*
                                                          const int32_t* __restrict__ block_map, int chunk_elems,
                                                          double* __restrict__ partials) {
     __shared__ double lds[4];
-    const ru3d_adam_tensor t = tensors[block_map[2 * blockIdx.x]];
+    const TableChunk ch = table_chunk(tensors, block_map, chunk_elems);
     double acc = 0.0;
-    if (t.grad) {
-        const float* g = t.grad;
-        const int64_t begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
-        int64_t end = begin + chunk_elems;
-        if (end > t.count) end = t.count;
-        int64_t i = begin + (int64_t)threadIdx.x * 4;
-        if ((((uintptr_t)g) & 15) == 0) {
-            for (; i + 3 < end; i += 1024) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
-#pragma unroll
-                for (int k = 0; k < 4; k++) acc += (double)v[k] * (double)v[k];
-            }
-        }
-        for (; i < end; i += 1024)
-            for (int k = 0; k < 4 && i + k < end; k++) acc += (double)g[i + k] * (double)g[i + k];
-    }
+    if (ch.t.grad)
+        grad_walk(ch, false, [&](float v) {
+            acc += (double)v * (double)v;
+            return v;
+        });
     const double s = block_sum_d(acc, lds);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
@@ -442,39 +360,124 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
 __global__ __launch_bounds__(256) void grad_scale_dev_kernel(const ru3d_adam_tensor* __restrict__ tensors,
                                                              const int32_t* __restrict__ block_map, int chunk_elems,
                                                              const float* __restrict__ coef) {
-    const ru3d_adam_tensor t = tensors[block_map[2 * blockIdx.x]];
-    if (!t.grad) return;
+    const TableChunk ch = table_chunk(tensors, block_map, chunk_elems);
+    if (!ch.t.grad) return;
     const float c = *coef;
     if (c == 1.f) return;
-    float* g = const_cast<float*>(t.grad);
-    const int64_t begin = (int64_t)block_map[2 * blockIdx.x + 1] * chunk_elems;
-    int64_t end = begin + chunk_elems;
-    if (end > t.count) end = t.count;
-    int64_t i = begin + (int64_t)threadIdx.x * 4;
-    if ((((uintptr_t)g) & 15) == 0) {
-        for (; i + 3 < end; i += 1024) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
-#pragma unroll
-            for (int k = 0; k < 4; k++) v[k] *= c;
-            *reinterpret_cast<f32x4*>(g + i) = v;
-        }
-    }
-    for (; i < end; i += 1024)
-        for (int k = 0; k < 4 && i + k < end; k++) g[i + k] *= c;
+    grad_walk(ch, true, [&](float v) { return v * c; });
 }
 
 // --------------------------------------------------------------------------- entry points
 #define RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) \
     ((tensors) && (block_map) && (nblocks) > 0 && (chunk_elems) >= 1024 && ((chunk_elems) % 1024) == 0)
 
+// What every table entry point does: device guard, the table check and the entry's own conditions (`ok`) with the entry's
+// own error text (`bad`), one workgroup per block-map pair, launch check under the entry's name (`what`).
+template <class... Params, class... Args>
+static int launch_table(void (*kernel)(const ru3d_adam_tensor*, const int32_t*, int, Params...), const char* what,
+                        const char* bad, bool ok, const ru3d_adam_tensor* tensors, const int32_t* block_map,
+                        int nblocks, int chunk_elems, void* stream, Args... args) {
+    Ru3dDeviceGuard dev_guard(stream);
+    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && ok, "%s", bad);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map, chunk_elems,
+                       args...);
+    return ru3d_check_launch(what);
+}
+
+// ru3d_adam_multi and ru3d_adam_multi_clip share a kernel (and so do their _dev forms): no coefficient is a null one
+extern "C" int ru3d_adam_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                               float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2,
+                               float grad_scale, void* stream) {
+    return launch_table(adam_multi_kernel, "adam_multi",
+                        "adam_multi: bad argument (chunk_elems must be a positive multiple of 1024)", true, tensors,
+                        block_map, nblocks, chunk_elems, stream, lr, beta1, beta2, eps, bias_corr1, sqrtf(bias_corr2),
+                        grad_scale, (const float*)nullptr);
+}
+
+extern "C" int ru3d_adam_multi_clip(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                    int chunk_elems, float lr, float beta1, float beta2, float eps, float bias_corr1,
+                                    float bias_corr2, float grad_scale, const float* coef, void* stream) {
+    return launch_table(adam_multi_kernel, "adam_multi_clip",
+                        "adam_multi_clip: bad argument (chunk_elems must be a positive multiple of 1024)",
+                        bias_corr1 > 0.f && bias_corr2 > 0.f, tensors, block_map, nblocks, chunk_elems, stream, lr, beta1,
+                        beta2, eps, bias_corr1, sqrtf(bias_corr2), grad_scale, coef);
+}
+
+extern "C" int ru3d_adam_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                   int chunk_elems, const float* hyper, void* stream) {
+    return launch_table(adam_multi_dev_kernel, "adam_multi_dev",
+                        "adam_multi_dev: bad argument (chunk_elems must be a positive multiple of 1024)", hyper != nullptr,
+                        tensors, block_map, nblocks, chunk_elems, stream, hyper, (const float*)nullptr);
+}
+
+extern "C" int ru3d_adam_multi_clip_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                        int chunk_elems, const float* hyper, const float* coef, void* stream) {
+    return launch_table(adam_multi_dev_kernel, "adam_multi_clip_dev",
+                        "adam_multi_clip_dev: bad argument (chunk_elems must be a positive multiple of 1024)",
+                        hyper != nullptr, tensors, block_map, nblocks, chunk_elems, stream, hyper, coef);
+}
+
+extern "C" int ru3d_adam_multi_amp(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                                   const float* hyper, const ru3d_amp_state* amp, void* stream) {
+    return launch_table(adam_multi_amp_kernel, "adam_multi_amp",
+                        "adam_multi_amp: bad argument (chunk_elems must be a positive multiple of 1024)", hyper && amp,
+                        tensors, block_map, nblocks, chunk_elems, stream, hyper, amp);
+}
+
+extern "C" int ru3d_adamw_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                                float lr, float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
+                                float bias_corr2, float grad_scale, const float* coef, void* stream) {
+    return launch_table(adamw_multi_kernel, "adamw_multi",
+                        "adamw_multi: bad argument (chunk_elems must be a positive multiple of 1024)",
+                        lr >= 0.f && eps >= 0.f && weight_decay >= 0.f && bias_corr1 > 0.f && bias_corr2 > 0.f, tensors,
+                        block_map, nblocks, chunk_elems, stream, lr, beta1, beta2, eps, weight_decay, bias_corr1,
+                        bias_corr2, grad_scale, coef);
+}
+
+extern "C" int ru3d_adamw_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                    int chunk_elems, const float* hyper, const float* coef, void* stream) {
+    return launch_table(adamw_multi_dev_kernel, "adamw_multi_dev",
+                        "adamw_multi_dev: bad argument (chunk_elems must be a positive multiple of 1024)", hyper != nullptr,
+                        tensors, block_map, nblocks, chunk_elems, stream, hyper, coef);
+}
+
+extern "C" int ru3d_sgd_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
+                              float lr, float momentum, float weight_decay, int nesterov, float grad_scale,
+                              const float* coef, void* stream) {
+    return launch_table(sgd_multi_kernel, "sgd_multi",
+                        "sgd_multi: bad argument (chunk_elems must be a positive multiple of 1024; nesterov needs momentum)",
+                        lr >= 0.f && momentum >= 0.f && weight_decay >= 0.f &&
+                            (nesterov == 0 || (nesterov == 1 && momentum > 0.f)),
+                        tensors, block_map, nblocks, chunk_elems, stream, lr, momentum, weight_decay,
+                        nesterov ? 1.f : 0.f, grad_scale, coef);
+}
+
+extern "C" int ru3d_sgd_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                  int chunk_elems, const float* hyper, const float* coef, void* stream) {
+    return launch_table(sgd_multi_dev_kernel, "sgd_multi_dev",
+                        "sgd_multi_dev: bad argument (chunk_elems must be a positive multiple of 1024)", hyper != nullptr,
+                        tensors, block_map, nblocks, chunk_elems, stream, hyper, coef);
+}
+
+extern "C" int ru3d_grad_scale_check(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                     int chunk_elems, float scale, float* found_inf, void* stream) {
+    return launch_table(grad_scale_check_kernel, "grad_scale_check",
+                        "grad_scale_check: bad argument (chunk_elems must be a positive multiple of 1024)",
+                        found_inf != nullptr, tensors, block_map, nblocks, chunk_elems, stream, scale, found_inf);
+}
+
 extern "C" int ru3d_grad_sumsq(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
                                double* partials, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && partials,
-                 "grad_sumsq: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
-                       chunk_elems, partials);
-    return ru3d_check_launch("grad_sumsq");
+    return launch_table(grad_sumsq_kernel, "grad_sumsq",
+                        "grad_sumsq: bad argument (chunk_elems must be a positive multiple of 1024)", partials != nullptr,
+                        tensors, block_map, nblocks, chunk_elems, stream, partials);
+}
+
+extern "C" int ru3d_grad_scale_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
+                                   int chunk_elems, const float* coef, void* stream) {
+    return launch_table(grad_scale_dev_kernel, "grad_scale_dev",
+                        "grad_scale_dev: bad argument (chunk_elems must be a positive multiple of 1024)", coef != nullptr,
+                        tensors, block_map, nblocks, chunk_elems, stream, coef);
 }
 
 extern "C" int ru3d_grad_norm_finish(const double* partials, int npartials, float grad_scale, const float* hyper,
@@ -493,79 +496,4 @@ extern "C" int ru3d_grad_norm(const ru3d_adam_tensor* tensors, const int32_t* bl
     const int rc = ru3d_grad_sumsq(tensors, block_map, nblocks, chunk_elems, partials, stream);
     if (rc) return rc;
     return ru3d_grad_norm_finish(partials, nblocks, grad_scale, nullptr, max_norm, out, stream);
-}
-
-extern "C" int ru3d_grad_scale_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
-                                   int chunk_elems, const float* coef, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && coef,
-                 "grad_scale_dev: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(grad_scale_dev_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
-                       block_map, chunk_elems, coef);
-    return ru3d_check_launch("grad_scale_dev");
-}
-
-extern "C" int ru3d_sgd_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
-                              float lr, float momentum, float weight_decay, int nesterov, float grad_scale,
-                              const float* coef, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && lr >= 0.f && momentum >= 0.f &&
-                     weight_decay >= 0.f && (nesterov == 0 || (nesterov == 1 && momentum > 0.f)),
-                 "sgd_multi: bad argument (chunk_elems must be a positive multiple of 1024; nesterov needs momentum)");
-    hipLaunchKernelGGL(sgd_multi_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
-                       chunk_elems, lr, momentum, weight_decay, nesterov ? 1.f : 0.f, grad_scale, coef);
-    return ru3d_check_launch("sgd_multi");
-}
-
-extern "C" int ru3d_sgd_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
-                                  int chunk_elems, const float* hyper, const float* coef, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && hyper,
-                 "sgd_multi_dev: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(sgd_multi_dev_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
-                       block_map, chunk_elems, hyper, coef);
-    return ru3d_check_launch("sgd_multi_dev");
-}
-
-extern "C" int ru3d_adamw_multi(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks, int chunk_elems,
-                                float lr, float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
-                                float bias_corr2, float grad_scale, const float* coef, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && lr >= 0.f && eps >= 0.f &&
-                     weight_decay >= 0.f && bias_corr1 > 0.f && bias_corr2 > 0.f,
-                 "adamw_multi: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
-                       chunk_elems, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale, coef);
-    return ru3d_check_launch("adamw_multi");
-}
-
-extern "C" int ru3d_adamw_multi_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
-                                    int chunk_elems, const float* hyper, const float* coef, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && hyper,
-                 "adamw_multi_dev: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(adamw_multi_dev_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
-                       block_map, chunk_elems, hyper, coef);
-    return ru3d_check_launch("adamw_multi_dev");
-}
-
-extern "C" int ru3d_adam_multi_clip(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
-                                    int chunk_elems, float lr, float beta1, float beta2, float eps, float bias_corr1,
-                                    float bias_corr2, float grad_scale, const float* coef, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && bias_corr1 > 0.f && bias_corr2 > 0.f,
-                 "adam_multi_clip: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors, block_map,
-                       chunk_elems, lr, beta1, beta2, eps, bias_corr1, sqrtf(bias_corr2), grad_scale, coef);
-    return ru3d_check_launch("adam_multi_clip");
-}
-
-extern "C" int ru3d_adam_multi_clip_dev(const ru3d_adam_tensor* tensors, const int32_t* block_map, int nblocks,
-                                        int chunk_elems, const float* hyper, const float* coef, void* stream) {
-    Ru3dDeviceGuard dev_guard(stream);
-    RU3D_REQUIRE(RU3D_TABLE_OK(tensors, block_map, nblocks, chunk_elems) && hyper,
-                 "adam_multi_clip_dev: bad argument (chunk_elems must be a positive multiple of 1024)");
-    hipLaunchKernelGGL(adam_clip_dev_kernel, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), tensors,
-                       block_map, chunk_elems, hyper, coef);
-    return ru3d_check_launch("adam_multi_clip_dev");
 }

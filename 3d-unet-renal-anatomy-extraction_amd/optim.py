@@ -33,6 +33,55 @@ class _AdamTensor(ctypes.Structure):
                 ("exp_avg_sq", ctypes.c_void_p), ("count", ctypes.c_int64)]
 
 
+def _block_map(numels):
+    """The flat [tensor, chunk] pairs of the kernels' block map: one workgroup per _CHUNK elements of every tensor."""
+    blocks = []
+    for ti, n in enumerate(numels):
+        for c in range((n + _CHUNK - 1) // _CHUNK):
+            blocks += [ti, c]
+    return blocks
+
+
+class _Table:
+    """A ru3d_adam_tensor table as the multi-tensor kernels take it: the pinned host block the rows are written into, its
+    device copy `table`, the `block_map` with `nblocks` pairs, and the event of the last host-to-device copy."""
+
+    def __init__(self):
+        self.numels = None
+        self.host = self.table = self.block_map = None
+        self.nblocks = 0
+        self.copied = None
+
+    def prepare(self, numels, device):
+        """The allocations, for tensors of these sizes: nothing to do while sizes and device stay as they are.  They are
+        not allowed while a stream is capturing, so a captured step calls this beforehand."""
+        numels = tuple(numels)
+        if self.numels == numels and self.table.device == device:
+            return
+        self.host = torch.empty(len(numels) * ctypes.sizeof(_AdamTensor), dtype=torch.uint8).pin_memory()
+        self.table = torch.empty(self.host.numel(), dtype=torch.uint8, device=device)
+        blocks = _block_map(numels)
+        self.block_map = torch.tensor(blocks, dtype=torch.int32).to(device)
+        self.nblocks = len(blocks) // 2
+        self.numels = numels
+
+    def fill(self, rows, capturing):
+        """rows: one (param, grad, exp_avg, exp_avg_sq, count) of addresses (None: null) per tensor."""
+        if self.copied is not None:
+            self.copied.synchronize()        # the previous async H2D of the table has left the host buffer
+        arr = (_AdamTensor * len(rows)).from_buffer(self.host.numpy())
+        for i, row in enumerate(rows):
+            arr[i] = _AdamTensor(*row)
+        self.table.copy_(self.host, non_blocking=True)
+        if capturing:
+            # the copy is a node of the graph (the gradients live at fixed addresses of the graph's memory pool): its
+            # memcpy node re-reads the pinned block at every replay, and the block stays as it is
+            self.copied = None
+        else:
+            self.copied = torch.cuda.Event()
+            self.copied.record()
+
+
 def _check_max_grad_norm(max_grad_norm):
     if max_grad_norm is None:
         return None
@@ -85,25 +134,18 @@ class _Fused(torch.optim.Optimizer):
         return False
 
     def _plan(self, gi, group, captured=False):
-        """Static part of the launch: block map + pinned host table (built once per param group; a captured step keeps
-        its own table - its memcpy node re-reads the pinned block at every replay)."""
+        """Static part of the launch: the _Table of a param group (built once per group and set of parameter sizes; a
+        captured step keeps its own table - its memcpy node re-reads the pinned block at every replay)."""
+        params = group["params"]
+        numels = tuple(p.numel() for p in params)
         plan = self._plans.get((gi, captured))
-        params = [p for p in group["params"]]
-        if plan is not None and plan["n"] == len(params):
-            return plan
-        dev = params[0].device
-        blocks = []
-        for ti, p in enumerate(params):
-            N.require_device(p, "parameter")
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise N.Ru3dError("optim.%s: parameters must be contiguous float32" % self._NAME)
-            for c in range((p.numel() + _CHUNK - 1) // _CHUNK):
-                blocks += [ti, c]
-        bm = torch.tensor(blocks, dtype=torch.int32).to(dev)
-        host = torch.empty(len(params) * ctypes.sizeof(_AdamTensor), dtype=torch.uint8).pin_memory()
-        table = torch.empty(host.numel(), dtype=torch.uint8, device=dev)
-        plan = {"n": len(params), "block_map": bm, "nblocks": len(blocks) // 2, "host": host, "table": table}
-        self._plans[(gi, captured)] = plan
+        if plan is None or plan.numels != numels:
+            for p in params:
+                N.require_device(p, "parameter")
+                if p.dtype != torch.float32 or not p.is_contiguous():
+                    raise N.Ru3dError("optim.%s: parameters must be contiguous float32" % self._NAME)
+            plan = self._plans[(gi, captured)] = _Table()
+            plan.prepare(numels, params[0].device)
         return plan
 
     def _clip_buffers(self, captured=False):
@@ -111,8 +153,8 @@ class _Fused(torch.optim.Optimizer):
         eager and captured steps share (last_grad_norm is a view of it, whichever kind of step ran last).  Sized from the
         plans of all groups as they are NOW: add_param_group or a group that grew gives new partials."""
         plans = [self._plan(gi, group, captured) for gi, group in enumerate(self.param_groups) if group["params"]]
-        nblocks = sum(pl["nblocks"] for pl in plans)
-        dev = plans[0]["table"].device
+        nblocks = sum(pl.nblocks for pl in plans)
+        dev = plans[0].table.device
         if self._norm is None or self._norm.device != dev:
             self._norm = torch.zeros(2, dtype=torch.float32, device=dev)
         bufs = self._clip.get(captured)
@@ -143,14 +185,12 @@ class _Fused(torch.optim.Optimizer):
             self._check_group(group)
             plan = self._plan(gi, group, capturing)
             N.note_device(params[0].device)
-            if plan.get("copied") is not None and not capturing:
-                plan["copied"].synchronize()     # previous step's async H2D of the table has left the host buffer
-            arr = (_AdamTensor * len(params)).from_buffer(plan["host"].numpy())
+            rows = []
             step_no = None
             any_grad = False
-            for i, p in enumerate(params):
+            for p in params:
                 if p.grad is None:
-                    arr[i] = _AdamTensor(p.data_ptr(), None, None, None, p.numel())
+                    rows.append((p.data_ptr(), None, None, None, p.numel()))
                     continue
                 g = p.grad
                 if g.dtype != torch.float32 or not g.is_contiguous():
@@ -163,24 +203,17 @@ class _Fused(torch.optim.Optimizer):
                     step_no = float(st["step"]) if step_no is None else step_no
                     if float(st["step"]) != step_no:
                         raise N.Ru3dError("optim.%s: parameters of one group must share the step count" % self._NAME)
-                arr[i] = _AdamTensor(p.data_ptr(), g.data_ptr(), None if first is None else first.data_ptr(),
-                                     None if second is None else second.data_ptr(), p.numel())
+                rows.append((p.data_ptr(), g.data_ptr(), None if first is None else first.data_ptr(),
+                             None if second is None else second.data_ptr(), p.numel()))
                 any_grad = True
             if not any_grad:
                 continue
             step_no = 0.0 if step_no is None else step_no
-            plan["table"].copy_(plan["host"], non_blocking=True)
-            if capturing:
-                # the table copy is part of the graph (the gradients live at fixed addresses of the graph's memory pool)
-                plan["copied"] = None
-            else:
-                ev = torch.cuda.Event()
-                ev.record()
-                plan["copied"] = ev
+            plan.fill(rows, capturing)
             if clip:
-                check(N.lib.ru3d_grad_sumsq(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                check(N.lib.ru3d_grad_sumsq(ptr(plan.table), ptr(plan.block_map), plan.nblocks, _CHUNK,
                                             ptr(bufs["partials"][npartials:]), stream()), "grad_sumsq")
-                npartials += plan["nblocks"]
+                npartials += plan.nblocks
             ready.append((gi, group, plan, step_no))
         coef = None
         if clip and ready:
@@ -192,7 +225,7 @@ class _Fused(torch.optim.Optimizer):
             coef = bufs["norm"][1:]
             self.last_grad_norm = bufs["norm"][0]
         for gi, group, plan, step_no in ready:
-            N.note_device(plan["table"].device)
+            N.note_device(plan.table.device)
             if capturing:
                 # the captured launch reads lr / bias corrections / grad_scale from the device block that
                 # replay_scalars() refreshes in front of every replay
@@ -201,7 +234,7 @@ class _Fused(torch.optim.Optimizer):
                 if amp is not None:
                     # fp16: the device-side loss scaler decides (skip on overflow, 1 / scale, the true step number)
                     self._captured["amp_base"][gi] = step_no - 1.0
-                    check(N.lib.ru3d_adam_multi_amp(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+                    check(N.lib.ru3d_adam_multi_amp(ptr(plan.table), ptr(plan.block_map), plan.nblocks, _CHUNK,
                                                     ptr(self._captured["hyper"][gi]), ptr(amp), stream()), "adam_multi_amp")
                 else:
                     self._launch_dev(plan, self._captured["hyper"][gi], coef)
@@ -309,24 +342,15 @@ class Adam(_AdamFamily):
 
     def _launch(self, plan, group, step_no, grad_scale, coef):
         b1, b2 = group["betas"]
-        bc1 = 1.0 - b1 ** step_no
-        bc2 = 1.0 - b2 ** step_no
-        if coef is None:
-            check(N.lib.ru3d_adam_multi(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
-                                        float(group["lr"]), float(b1), float(b2), float(group["eps"]), bc1, bc2,
-                                        float(grad_scale), stream()), "adam_multi")
-        else:
-            check(N.lib.ru3d_adam_multi_clip(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
-                                             float(group["lr"]), float(b1), float(b2), float(group["eps"]), bc1, bc2,
-                                             float(grad_scale), ptr(coef), stream()), "adam_multi_clip")
+        # a null coefficient is the unclipped step: ru3d_adam_multi's kernel and bits
+        check(N.lib.ru3d_adam_multi_clip(ptr(plan.table), ptr(plan.block_map), plan.nblocks, _CHUNK,
+                                         float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                         1.0 - b1 ** step_no, 1.0 - b2 ** step_no, float(grad_scale), ptr(coef), stream()),
+              "adam_multi_clip")
 
     def _launch_dev(self, plan, hyper_row, coef):
-        if coef is None:
-            check(N.lib.ru3d_adam_multi_dev(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
-                                            ptr(hyper_row), stream()), "adam_multi_dev")
-        else:
-            check(N.lib.ru3d_adam_multi_clip_dev(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
-                                                 ptr(hyper_row), ptr(coef), stream()), "adam_multi_clip_dev")
+        check(N.lib.ru3d_adam_multi_clip_dev(ptr(plan.table), ptr(plan.block_map), plan.nblocks, _CHUNK,
+                                             ptr(hyper_row), ptr(coef), stream()), "adam_multi_clip_dev")
 
     def _row(self, row, group, step_no, grad_scale):
         """lr, beta1, beta2, eps, bias_corr1, bias_corr2, grad_scale, sqrt(bias_corr2)"""
@@ -366,13 +390,13 @@ class AdamW(_AdamFamily):
 
     def _launch(self, plan, group, step_no, grad_scale, coef):
         b1, b2 = group["betas"]
-        check(N.lib.ru3d_adamw_multi(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+        check(N.lib.ru3d_adamw_multi(ptr(plan.table), ptr(plan.block_map), plan.nblocks, _CHUNK,
                                      float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                      float(group["weight_decay"]), 1.0 - b1 ** step_no, 1.0 - b2 ** step_no,
                                      float(grad_scale), ptr(coef), stream()), "adamw_multi")
 
     def _launch_dev(self, plan, hyper_row, coef):
-        check(N.lib.ru3d_adamw_multi_dev(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+        check(N.lib.ru3d_adamw_multi_dev(ptr(plan.table), ptr(plan.block_map), plan.nblocks, _CHUNK,
                                          ptr(hyper_row), ptr(coef), stream()), "adamw_multi_dev")
 
     def _row(self, row, group, step_no, grad_scale):
@@ -422,12 +446,12 @@ class SGD(_Fused):
         return st["momentum_buffer"], None
 
     def _launch(self, plan, group, step_no, grad_scale, coef):
-        check(N.lib.ru3d_sgd_multi(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+        check(N.lib.ru3d_sgd_multi(ptr(plan.table), ptr(plan.block_map), plan.nblocks, _CHUNK,
                                    float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]),
                                    int(bool(group["nesterov"])), float(grad_scale), ptr(coef), stream()), "sgd_multi")
 
     def _launch_dev(self, plan, hyper_row, coef):
-        check(N.lib.ru3d_sgd_multi_dev(ptr(plan["table"]), ptr(plan["block_map"]), plan["nblocks"], _CHUNK,
+        check(N.lib.ru3d_sgd_multi_dev(ptr(plan.table), ptr(plan.block_map), plan.nblocks, _CHUNK,
                                        ptr(hyper_row), ptr(coef), stream()), "sgd_multi_dev")
 
     def _row(self, row, group, step_no, grad_scale):
@@ -476,58 +500,28 @@ def clip_grad_norm_(parameters, max_norm):
     return out[0]
 
 
-class _GradTable:
-    """Device table of (grad pointer, count) per parameter in ru3d_adam_tensor layout + block map, rebuilt when the
-    gradient tensors move (GradSync re-aliases them into its buckets; autograd allocates fresh ones otherwise)."""
+class _GradTable(_Table):
+    """A _Table of (grad pointer, count) rows, one per parameter, refilled when the gradient tensors move (GradSync
+    re-aliases them into its buckets; autograd allocates fresh ones otherwise)."""
 
     def __init__(self, who="LossScaler"):
+        super().__init__()
         self.who = who
-        self.key = None
-        self.table = self.block_map = None
-        self.nblocks = 0
-        self.host = None
-        self.numels = None
-        self.copied = None
+        self.key = None         # what the device table was last filled from: the device, (grad pointer, count) per row
 
-    def prepare(self, params, dev):
-        """The allocations (pinned host block, device table, block map): not allowed while a stream is capturing, so a
-        captured step calls this beforehand (LossScaler.begin_capture)."""
-        n = len(params)
-        numels = tuple(p.numel() for p in params)
-        if self.host is not None and self.numels == numels and self.table.device == dev:
-            return
-        self.numels = numels
-        self.host = torch.empty(n * ctypes.sizeof(_AdamTensor), dtype=torch.uint8).pin_memory()
-        self.table = torch.empty(self.host.numel(), dtype=torch.uint8, device=dev)
-        blocks = []
-        for ti, p in enumerate(params):
-            for c in range((p.numel() + _CHUNK - 1) // _CHUNK):
-                blocks += [ti, c]
-        self.block_map = torch.tensor(blocks, dtype=torch.int32).to(dev)
-        self.nblocks = len(blocks) // 2
-        self.key = None
-
-    def update(self, params, capturing=False):
+    def update(self, params, capturing=False, refill=False):
+        """refill: fill and copy even when nothing moved (a captured step: the copy has to be a node of ITS graph)."""
         grads = [p.grad for p in params]
         dev = next(g.device for g in grads if g is not None)
-        key = tuple((0 if g is None else g.data_ptr(), p.numel()) for p, g in zip(params, grads))
-        if key == self.key:
+        key = (dev,) + tuple((0 if g is None else g.data_ptr(), p.numel()) for p, g in zip(params, grads))
+        if key == self.key and not refill:
             return
-        if self.copied is not None:
-            self.copied.synchronize()
-        n = len(params)
-        self.prepare(params, dev)
-        arr = (_AdamTensor * n).from_buffer(self.host.numpy())
-        for i, (p, g) in enumerate(zip(params, grads)):
+        for g in grads:
             if g is not None and (g.dtype != torch.float32 or not g.is_contiguous()):
                 raise N.Ru3dError("%s: gradients must be contiguous float32" % self.who)
-            arr[i] = _AdamTensor(None, None if g is None else g.data_ptr(), None, None, p.numel())
-        self.table.copy_(self.host, non_blocking=True)
-        if capturing:
-            self.copied = None          # the copy is a node of the graph; the pinned block stays as it is
-        else:
-            self.copied = torch.cuda.Event()
-            self.copied.record()
+        self.prepare([p.numel() for p in params], dev)
+        self.fill([(None, None if g is None else g.data_ptr(), None, None, p.numel()) for p, g in zip(params, grads)],
+                  capturing)
         self.key = key
 
 
@@ -570,7 +564,8 @@ class LossScaler:
         self._upload()
         for gi, group in enumerate(optimizer.param_groups):
             if group["params"]:
-                self._tables.setdefault((id(optimizer), gi, "cap"), _GradTable()).prepare(list(group["params"]), device)
+                self._tables.setdefault((id(optimizer), gi, "cap"), _GradTable()).prepare(
+                    [p.numel() for p in group["params"]], device)
         self._scale_t = self._dev[0:4].view(torch.float32).view(())
         self._found = self._dev[8:12].view(torch.float32)
         optimizer._captured["amp"] = self._dev
@@ -644,8 +639,7 @@ class LossScaler:
                 if not any(p.grad is not None for p in params):
                     continue
                 tab = self._tables.setdefault((id(optimizer), gi, "cap"), _GradTable())
-                tab.key = None
-                tab.update(params, capturing=True)
+                tab.update(params, capturing=True, refill=True)
                 N.note_device(tab.table.device)
                 check(N.lib.ru3d_grad_scale_check(ptr(tab.table), ptr(tab.block_map), tab.nblocks, _CHUNK, 1.0,
                                                   ptr(self._found), stream()), "grad_scale_check")

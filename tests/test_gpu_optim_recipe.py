@@ -2,9 +2,9 @@
 AdamW, clipped Adam - against float64 references on a real MI355X, then optim.SGD / AdamW / Adam(max_grad_norm=) on a
 whole model against torch.optim, captured against eager, through Trainer.fit and through the eager fp16 step.
 
-Layout: as tests/test_gpu_optim_kernels.py - every tensor table lives inside ONE float32 allocation per role (param,
-grad, exp_avg, exp_avg_sq) with NaN guard words around and between the tensors and a row without a gradient in the
-middle; after every launch the guards and that row are bit-unchanged.
+Layout (tests/optim_cases.py, shared with tests/test_gpu_optim_kernels.py): every tensor table lives inside ONE float32
+allocation per role (param, grad, exp_avg, exp_avg_sq) with NaN guard words around and between the tensors and a row
+without a gradient in the middle; after every launch the guards and that row are bit-unchanged.
 
 One-step tolerances.  u = 2^-24 (one rounding to nearest moves a value by at most u of itself), ulp(x) = the spacing of
 float32 at x (u |x| <= ulp(x)).  The reference is the rule in float64 on the kernel's own float32 state and on the float32
@@ -53,141 +53,11 @@ import loss as L  # noqa: E402
 import network  # noqa: E402
 import optim  # noqa: E402
 from oracle import unet_oracle as O  # noqa: E402
+from optim_cases import (CHUNK, DEV, NULL_SIZE, ROLES, SIZES, SKEWS, Layout, f32,  # noqa: E402
+                         make_grads, ulp)
 
-DEV = torch.device("cuda:0")
-CHUNK = optim._CHUNK
-ROLES = ("param", "grad", "exp_avg", "exp_avg_sq")
-GUARD = 8
-PATTERN = 0x7FC0BEEF              # a NaN: a guard word that is read as a gradient poisons the norm
-NULL_SIZE = 2049
-SIZES = [1, 3, 4, 5, 1023, 1024, NULL_SIZE, 1025, 16383, 16384, 16385, 2 * 16384 + 7, 100003]
-NULL_ROW = SIZES.index(NULL_SIZE)
-SKEWS = {"aligned": (), "unaligned": ROLES, "grad_unaligned": ("grad",)}
 U = 2.0 ** -24
 TINY = 4 * 2.0 ** -149
-
-
-def f32(x):
-    return float(torch.tensor(x, dtype=torch.float32))
-
-
-def ulp(t):
-    a = t.abs().float()
-    return (torch.nextafter(a, torch.full_like(a, float("inf"))) - a).double()
-
-
-class Layout:
-    """All tensors of one role inside one allocation: [guard] t0 [guard] t1 ... [guard]."""
-
-    def __init__(self, skew=(), seed=0):
-        self.sizes, self.null_row = list(SIZES), NULL_ROW
-        self.live = [i for i in range(len(SIZES)) if i != NULL_ROW]
-        self.count = sum(self.sizes[i] for i in self.live)
-        self.off, self.buf = {}, {}
-        g = torch.Generator().manual_seed(seed)
-        for role in ROLES:
-            offs, cur = [], GUARD
-            for n in self.sizes:
-                start = (cur + 3) // 4 * 4 + (1 if role in skew else 0)
-                offs.append(start)
-                cur = start + n + GUARD
-            total = (cur + 3) // 4 * 4 + 4
-            host = torch.full((total,), PATTERN, dtype=torch.int32).view(torch.float32)
-            for o, n in zip(offs, self.sizes):
-                if role == "param":
-                    host[o:o + n] = torch.randn(n, generator=g)
-                elif role == "exp_avg":
-                    host[o:o + n] = 0.01 * torch.randn(n, generator=g)
-                elif role == "exp_avg_sq":
-                    host[o:o + n] = 1e-4 * torch.rand(n, generator=g)
-                else:
-                    host[o:o + n] = 0.1 * torch.randn(n, generator=g)
-            self.off[role] = offs
-            self.buf[role] = host.to(DEV)
-            assert self.buf[role].data_ptr() % 16 == 0
-        for role in ROLES:
-            for i in range(len(self.sizes)):
-                assert self.view(role, i).data_ptr() % 16 == (4 if role in skew else 0)
-        self._keep = []
-
-    def view(self, role, i):
-        o = self.off[role][i]
-        return self.buf[role][o:o + self.sizes[i]]
-
-    def packed(self, role):
-        return torch.cat([self.view(role, i) for i in self.live]).cpu()
-
-    def set_packed(self, role, values):
-        pos = 0
-        for i in self.live:
-            n = self.sizes[i]
-            self.view(role, i).copy_(values[pos:pos + n])
-            pos += n
-
-    def position(self, i, j):
-        return sum(self.sizes[k] for k in self.live if k < i) + j
-
-    def bits(self):
-        return {role: self.buf[role].view(torch.int32).cpu().clone() for role in ROLES}
-
-    def restore(self, bits):
-        for role in ROLES:
-            self.buf[role].view(torch.int32).copy_(bits[role])
-
-    def assert_outside_untouched(self, before, what):
-        after = self.bits()
-        for role in ROLES:
-            m = torch.ones(self.buf[role].numel(), dtype=torch.bool)
-            for i in self.live:
-                o = self.off[role][i]
-                m[o:o + self.sizes[i]] = False
-            assert torch.equal(after[role][m], before[role][m]), "%s: wrote outside the tensors of %s" % (what, role)
-        return after
-
-    def table(self, first=True, second=True):
-        """Device copies of the ru3d_adam_tensor table and the block map.  The row without a gradient keeps its state
-        pointers: the kernel must leave it alone because its `grad` is null."""
-        n = len(self.sizes)
-        arr = (optim._AdamTensor * n)()
-        blocks = []
-        for i in range(n):
-            arr[i] = optim._AdamTensor(self.view("param", i).data_ptr(),
-                                       None if i == self.null_row else self.view("grad", i).data_ptr(),
-                                       self.view("exp_avg", i).data_ptr() if first else None,
-                                       self.view("exp_avg_sq", i).data_ptr() if second else None, self.sizes[i])
-            for c in range((self.sizes[i] + CHUNK - 1) // CHUNK):
-                blocks += [i, c]
-        tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(DEV)
-        bm = torch.tensor(blocks, dtype=torch.int32).to(DEV)
-        self._keep += [tab, bm]
-        return tab, bm, len(blocks) // 2
-
-    def optimizer(self, cls, **hp):
-        """A fused optimizer over parameters, gradients and state that are views into the four allocations."""
-        params = [torch.nn.Parameter(self.view("param", i)) for i in range(len(self.sizes))]
-        opt = cls(params, **hp)
-        for i in self.live:
-            assert params[i].data_ptr() == self.view("param", i).data_ptr()
-            params[i].grad = self.view("grad", i)
-            if cls is optim.SGD:
-                if hp.get("momentum", 0) != 0:
-                    opt.state[params[i]] = {"momentum_buffer": self.view("exp_avg", i)}
-            else:
-                opt.state[params[i]] = {"step": torch.tensor(0.0), "exp_avg": self.view("exp_avg", i),
-                                        "exp_avg_sq": self.view("exp_avg_sq", i)}
-        return opt, params
-
-
-def make_grads(count, step, seed):
-    """Normal gradients of both signs with exact zeros, 1e-30 (its square underflows) and 1e18 (its square is 1e36)."""
-    g = torch.Generator().manual_seed(1000 * seed + step)
-    v = 0.1 * torch.randn(count, generator=g)
-    idx = torch.arange(count)
-    sign = torch.where(v < 0, -1.0, 1.0)
-    v[idx % 7 == 0] = 0.0
-    v[idx % 11 == 0] = (1e-30 * sign)[idx % 11 == 0]
-    v[idx % 13 == 0] = (1e18 * sign)[idx % 13 == 0]
-    return v
 
 
 def _worst(err, tol):
@@ -746,8 +616,8 @@ def test_whole_model_first_step_matches_torch(three_steps, name):
         ulp).  Nesterov at the first step: u = (1 + mu) d, no cancellation.
       AdamW: |U - decay| <= lr at the first step (|m^ / (sqrt(v^) + eps)| <= 1); about ten roundings on each side:
         2^-19 lr; the decayed parameter differs by keep's last bit (float32 here, a double in torch) and its rounding:
-        3 ulp of the parameter in all.  And one difference that is not a rounding of the arithmetic: the kernel (like
-        adam_multi_body, whose recurrence it is) forms 1 - beta from the FLOAT32 beta, torch from the double.  A beta
+        3 ulp of the parameter in all.  And one difference that is not a rounding of the arithmetic: the kernel (AdamRule,
+        the one recurrence of Adam and AdamW) forms 1 - beta from the FLOAT32 beta, torch from the double.  A beta
         in [0.5, 1) is rounded by up to 2^-25, which is 2^-25 / (1 - beta) of 1 - beta: v^ is off by that share
         (3.0e-5 at beta2 = 0.999), its root by half of it, m^ by 2^-25 / (1 - beta1) (3.0e-7), while the bias
         corrections come from the double on both sides: lr * (2^-26 / (1 - beta2) + 2^-25 / (1 - beta1)) more."""

@@ -115,6 +115,13 @@ def test_adamw_state_dict_interchanges_with_torch():
     assert back.param_groups[0]["weight_decay"] == 0.05
 
 
+# ------------------------------------------------------------------------------------------------ the block map
+def test_block_map_has_one_pair_per_chunk_of_every_tensor():
+    c = optim._CHUNK
+    assert optim._block_map([1, c, c + 1]) == [0, 0, 1, 0, 2, 0, 2, 1]
+    assert optim._block_map([]) == []
+
+
 # ------------------------------------------------------------------------------------------------ captured rows
 def _f32(x):
     return float(torch.tensor(x, dtype=torch.float32))

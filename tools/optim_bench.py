@@ -79,9 +79,9 @@ def kernels_of(opt):
         N.note_device(dev)
         coef = None
         if bufs is not None:
-            N.check(N.lib.ru3d_grad_sumsq(N.ptr(plan["table"]), N.ptr(plan["block_map"]), plan["nblocks"], optim._CHUNK,
+            N.check(N.lib.ru3d_grad_sumsq(N.ptr(plan.table), N.ptr(plan.block_map), plan.nblocks, optim._CHUNK,
                                           N.ptr(bufs["partials"]), N.stream()), "grad_sumsq")
-            N.check(N.lib.ru3d_grad_norm_finish(N.ptr(bufs["partials"]), plan["nblocks"], 1.0, None, opt.max_grad_norm,
+            N.check(N.lib.ru3d_grad_norm_finish(N.ptr(bufs["partials"]), plan.nblocks, 1.0, None, opt.max_grad_norm,
                                                 N.ptr(bufs["norm"]), N.stream()), "grad_norm_finish")
             coef = bufs["norm"][1:]
         opt._launch(plan, group, 2.0, 1.0, coef)
