@@ -97,6 +97,11 @@ MORPH_ERODE, MORPH_DILATE = 0, 1
 MORPH_MAX_EXTENT, MORPH_MAX_ROWS = 15, 225
 KEEP_LARGEST_MAX = 8
 PROPAGATE_MAX_ROUNDS = 64
+GEODESIC_MAX_ROUNDS = 64        # rounds of one ru3d_geodesic_rounds call
+GEODESIC_MAX_TRIPS = 32         # RU3D_GEODESIC_MAX_TRIPS: relaxation trips of a tile inside one round
+GEODESIC_TILE = (8, 8, 32)      # voxels of a tile of csrc/geodesic.hip
+GEODESIC_MAX_WEIGHT = 1 << 20   # a step length in quanta
+GEODESIC_UNLIMITED = 0xFFFFFFFE  # the limit that stands for "no bound"
 CONFUSION_MAX_CLASSES = 32
 ORDER_STATS_MAX_RANKS = 8
 EDT_MAX_AXIS = 4096             # RU3D_EDT_MAX_AXIS: x and y extents of the distance transform
@@ -267,6 +272,11 @@ SIGNATURES = {
     "ru3d_nearest_site": (_i, [_vp, _i, _i, _i, ctypes.POINTER(_dbl), _vp, _vp, _vp, _sz, _vp]),
     "ru3d_site_assign": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ru3d_territory_tally": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ru3d_geodesic_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_geodesic_init": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ru3d_geodesic_rounds": (_i, [_vp, _i, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, _i, _i, _i,
+                                  _vp, _vp, _vp, _sz, _vp]),
+    "ru3d_geodesic_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "ru3d_cldice_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ru3d_cldice_state_bytes": (_sz, []),
     "ru3d_soft_skeleton_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -115,14 +115,45 @@ def branch_sites(g):
     return np.where(ids > 0, ids, B - ids).astype(np.int32), B + int(g['nodes'])
 
 
-def partition(skel, g, region, sampling=None, other=None, num_other=0):
+METRICS = ('euclidean', 'geodesic')
+# the steps of the geodesic metric: all 26, so that a path may cut a corner as a straight line does
+GEODESIC_STRUCTURE = np.ones((3, 3, 3), dtype=bool)
+
+
+def check_metric(metric, what):
+    if metric not in METRICS:
+        raise ValueError("%s: metric=%r (one of %s)" % (what, metric, ', '.join(repr(m) for m in METRICS)))
+    return metric
+
+
+def partition(skel, g, region, sampling=None, other=None, num_other=0, metric='euclidean', vessel=None):
     """(table, labels): the voxels of the PackedMask `region` by nearest voxel of the skeleton `skel` whose graph is `g`
     (skeleton.graph(skel, ...)).  labels is the int32 HIP volume of territories (branch b -> b, node m -> B + m, 0
     outside the region), table the host int64 [B + M + 1, num_other + 1] tally of them against `other`.  Only the table
-    is downloaded."""
+    is downloaded.  metric='euclidean': nearest in a straight line (`nearest`).  metric='geodesic': nearest along a
+    path of 26-neighbour steps that stays inside the region united with the PackedMask `vessel` (the lumen the skeleton
+    lies in; required) - geodesic.grow from the skeleton voxels as seeds, each carrying its id; a region voxel that no
+    such path reaches has label 0 and counts in row 0."""
+    check_metric(metric, "partition")
     site_ids, K = branch_sites(g)
-    index, _ = nearest(skel, sampling, return_sq=False)
-    labels = assign(skel, site_ids, index, region)
+    if metric == 'geodesic':
+        import geodesic
+        import morphology
+        _packed(skel, "partition")
+        _packed(region, "partition")
+        if vessel is None:
+            raise ValueError("partition: metric='geodesic' needs the vessel mask the skeleton lies in (vessel=)")
+        _packed(vessel, "partition")
+        _same_shape(skel, region, "partition")
+        _same_shape(skel, vessel, "partition")
+        seeds = torch.zeros(skel.shape, dtype=torch.int32, device=skel.device)
+        seeds[morphology.unpack(skel) != 0] = site_ids                      # element order: the order of the ids
+        allowed = morphology.PackedMask(region.bits | vessel.bits, region.shape)
+        _, reached = geodesic.grow(seeds, allowed, sampling, GEODESIC_STRUCTURE[(1,) * (3 - len(skel.shape))])
+        labels = torch.where(morphology.unpack(region) != 0, reached, torch.zeros_like(reached))
+    else:
+        index, _ = nearest(skel, sampling, return_sq=False)
+        labels = assign(skel, site_ids, index, region)
     return tally(labels, K, other, num_other, region).cpu().numpy(), labels
 
 

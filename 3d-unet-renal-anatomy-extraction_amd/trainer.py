@@ -1736,14 +1736,18 @@ def _label_values(entry, what):
 
 
 def vessel_territories_case(case, vessel, organ, other=None, key='pred', min_branch_mm=0.0, root=None,
-                            return_labels=False):
+                            return_labels=False, metric='euclidean'):
     """Which part of an organ every branch of a vessel tree feeds: the structure `vessel` of the label volume
     `case[key]` is thinned, pruned and read as a graph exactly as vessel_graph_case does, and the voxels of `organ` -
     together with those of `other` (a tumour is part of the organ it grows in, though it has a label of its own) - are
     partitioned by their nearest centreline voxel under the affine's spacing (territory.nearest: the exact Euclidean
     feature transform, ties by the rule of include/ru3d.h).  vessel, organ, other: a label value or a tuple of values.
     With organ == vessel every vessel voxel gets its branch: the vessel mask coloured by branch, and the territories are
-    the branches' vessel volumes.  Returns the dict of vessel_graph_case for the vessel, with, per segment,
+    the branches' vessel volumes.  metric='geodesic' measures along a path instead of a straight line: the centreline
+    voxels, each carrying its branch's or node's id, are grown through the region united with the vessel mask over the
+    26 neighbour steps (geodesic.grow, include/ru3d.h "geodesic distance"), so parenchyma across the renal sinus, a cyst
+    or a gap falls to the branch that reaches it through tissue, a lumen voxel to a branch of its own vessel, and a
+    region voxel that no path reaches is unassigned.  Returns the dict of vessel_graph_case for the vessel, with, per segment,
       territory_voxels, territory_ml   the voxels nearest to the branch's own path voxels, and their volume,
       downstream_voxels, downstream_ml   the same for the branch, the node it leads to and everything beyond it in the
                       tree rooted at `root` (territory.rooted: None picks the end node whose branch is thickest, the
@@ -1768,6 +1772,7 @@ def vessel_territories_case(case, vessel, organ, other=None, key='pred', min_bra
     region_values = tuple(sorted(set(organ_values) | set(other_values)))
     affine = np.asarray(case['affine'], dtype=np.float64) if case.get('affine') is not None else np.eye(4)
     spacing = get_spacing(affine)
+    territory.check_metric(metric, "vessel_territories_case")
     rounds = 0
     if hip:
         import morphology
@@ -1779,7 +1784,7 @@ def vessel_territories_case(case, vessel, organ, other=None, key='pred', min_bra
         g = skeleton.graph(skel, mask, spacing[3 - ndim:])
         tumour = morphology.unpack(_packed_union(volume, other_values)) if other_values else None
         table, labels = territory.partition(skel, g, _packed_union(volume, region_values), spacing[3 - ndim:], tumour,
-                                            1 if other_values else 0)
+                                            1 if other_values else 0, metric, mask)
     else:
         mask = np.isin(volume, vessel_values)
         skel = transform._skeleton_numpy(mask)[0]
@@ -1789,8 +1794,16 @@ def vessel_territories_case(case, vessel, organ, other=None, key='pred', min_bra
         region = np.isin(volume, region_values)
         tumour = np.isin(volume, other_values).astype(np.uint8) if other_values else None
         site_ids, K = territory.branch_sites(g)
-        index, _ = transform._nearest_site_numpy(skel, spacing)
-        labels = transform._site_assign_numpy(skel, site_ids, index, region)
+        if metric == 'geodesic':
+            import geodesic
+            seeds = np.zeros(skel.shape, dtype=np.int32)
+            seeds[skel] = site_ids
+            weights = geodesic.step_weights(spacing[3 - ndim:], ndim, 3)
+            labels = np.where(region, transform._geodesic_numpy(seeds, region | mask, weights, geodesic.UNLIMITED)[1], 0)
+            labels = labels.astype(np.int32)
+        else:
+            index, _ = transform._nearest_site_numpy(skel, spacing)
+            labels = transform._site_assign_numpy(skel, site_ids, index, region)
         table = transform._territory_tally_numpy(labels, K, tumour, 1 if other_values else 0, region)
         labels = labels.reshape(tuple(case[key].shape))
     B = g['branches']
@@ -1817,12 +1830,13 @@ def vessel_territories_case(case, vessel, organ, other=None, key='pred', min_bra
 
 
 def extract_vessel_territories(pred_file, save_dir=None, device=None, vessel=None, organ=None, other=None,
-                               min_branch_mm=0.0, root=None):
+                               min_branch_mm=0.0, root=None, metric='euclidean'):
     """vessel_territories_case of a NIfTI label volume with the file's affine (vessel and organ are required; organ ==
     vessel colours the vessel mask by branch).  save_dir: the dict is written as `<case_id>.label_<n>.territories.json`
     (n names the vessel; utils.json_save) and the int32 volume of territories as `<case_id>.label_<n>.territories.nii.gz`
-    with the file's affine; the dict gains 'file' and 'labels_file'.  device: a HIP device uploads the volume (as bytes)
-    and works there; the label volume is the one download beside the tables.  Prints one line; returns the dict."""
+    with the file's affine; the dict gains 'file' and 'labels_file'.  metric: 'euclidean' or 'geodesic', as there.
+    device: a HIP device uploads the volume (as bytes) and works there; the label volume is the one download beside the
+    tables.  Prints one line; returns the dict."""
     import nifti
     from pathlib import Path
     from utils import json_save
@@ -1836,7 +1850,7 @@ def extract_vessel_territories(pred_file, save_dir=None, device=None, vessel=Non
     pred, affine, _ = nifti.load(pred_file)
     pred = np.ascontiguousarray(np.clip(pred, 0, 255).astype(np.uint8))
     case = {'case_id': case_id, 'affine': affine, 'pred': pred if device is None else torch.from_numpy(pred).to(device)}
-    r = vessel_territories_case(case, vessel, organ, other, 'pred', min_branch_mm, root, return_labels=True)
+    r = vessel_territories_case(case, vessel, organ, other, 'pred', min_branch_mm, root, return_labels=True, metric=metric)
     labels = r.pop('labels')
     fed = [s['downstream_ml'] for s in r['segments'] if s['reachable'] and not s['chord'] and s['parent'] == 0]
     print("%s label_%s: %d branches from node %d, %d organ voxels in territories (%d unassigned), %.1f ml below the root"

@@ -1279,3 +1279,88 @@ def nearest_feature(input, sampling=None):
     spacing = distance._spacing(sampling, volume.ndim)
     index, sq = _nearest_site_numpy((volume != 0).reshape((1,) * (3 - volume.ndim) + volume.shape), spacing)
     return index.reshape(volume.shape), sq.reshape(volume.shape)
+
+
+# ------------------------------------------------------------------ geodesic distance (contract: include/ru3d.h)
+def _geodesic_numpy(seeds, allowed, weights, limit):
+    """The definition ru3d_geodesic_rounds is held to (include/ru3d.h, "geodesic distance"): (dist uint32, labels int32) of
+    an integer volume [X, Y, Z] of seeds (0: none, > 0: a label) grown through the bool volume `allowed` (None:
+    everywhere) - a heap Dijkstra on (dist, label) over the steps of geodesic.OFFSETS with the integer lengths `weights`
+    (0: no such step), a step taken only when it ends at a distance <= limit.  Not reached: 0xFFFFFFFF and 0.  With the
+    limit that stands for none (0xFFFFFFFE) an allowed voxel left unreached beside a reached one raises OverflowError."""
+    import heapq
+    from geodesic import OFFSETS, UNLIMITED, UNREACHED
+    seeds = np.asarray(seeds)
+    if seeds.ndim != 3:
+        raise ValueError("geodesic: a volume of shape %s (three axes here)" % (seeds.shape,))
+    if (seeds < 0).any():
+        raise ValueError("geodesic: a negative value among the seeds (0: no seed, > 0: a label)")
+    X, Y, Z = seeds.shape
+    open_ = np.zeros((X + 2, Y + 2, Z + 2), dtype=bool)                      # a closed rim instead of bounds checks
+    open_[1:-1, 1:-1, 1:-1] = True if allowed is None else np.asarray(allowed, dtype=bool)
+    sy, sx = Z + 2, (Y + 2) * (Z + 2)
+    # weight k is the step INTO a voxel from its neighbour at offset k, so it leads from p to p - offset
+    steps = [(-(dx * sx + dy * sy + dz), int(w)) for (dx, dy, dz), w in zip(OFFSETS, weights) if int(w)]
+    is_open = open_.reshape(-1).tolist()
+    dist, label = [UNREACHED] * open_.size, [0] * open_.size
+    heap = []
+    for x, y, z in np.argwhere(seeds > 0):
+        p = (x + 1) * sx + (y + 1) * sy + z + 1
+        dist[p], label[p] = 0, int(seeds[x, y, z])
+        heap.append((0, label[p], p))
+    heapq.heapify(heap)
+    limit = int(limit)
+    while heap:
+        d, l, p = heapq.heappop(heap)
+        if d != dist[p] or l != label[p]:
+            continue
+        for o, w in steps:
+            q = p + o
+            if is_open[q] and d + w <= limit and (d + w < dist[q] or (d + w == dist[q] and l < label[q])):
+                dist[q], label[q] = d + w, l
+                heapq.heappush(heap, (d + w, l, q))
+    dist = np.array(dist, dtype=np.int64).reshape(open_.shape)
+    label = np.array(label, dtype=np.int64).reshape(open_.shape)
+    if limit == UNLIMITED:
+        reached, stuck = dist != UNREACHED, open_ & (dist == UNREACHED)
+        for (dx, dy, dz), w in zip(OFFSETS, weights):
+            if int(w) and (stuck & np.roll(reached, (-dx, -dy, -dz), axis=(0, 1, 2))).any():  # the rim is never reached
+                raise OverflowError("geodesic: a distance beyond %d quanta - choose a larger quantum, or a max_distance"
+                                    % UNLIMITED)
+    return dist[1:-1, 1:-1, 1:-1].astype(np.uint32), label[1:-1, 1:-1, 1:-1].astype(np.int32)
+
+
+def geodesic_distance(seeds, mask=None, sampling=None, structure=None, quantum=2.0 ** -10, max_distance=None):
+    """(distance, labels): for every voxel the length of the shortest path to a seed that stays inside `mask` (None:
+    everywhere) and the label of that seed.  seeds: an integer volume of 1 to 3 axes, 0 = no seed, > 0 = the seed's
+    label; a seed outside the mask stays and spreads into its neighbours inside.  The path runs over the face steps
+    (structure None) or all 26 (the full cube) and every step counts its Euclidean length under `sampling`, rounded to a
+    multiple of `quantum`, so the sums are integers and the answer is unique: the smallest distance and, among equally
+    near seeds, the smallest label (include/ru3d.h, "geodesic distance").  distance is float64 in sampling units, inf
+    where no path arrives (or none within max_distance); labels int32, 0 there.  numpy in -> the numpy twin, numpy out;
+    HIP tensors in -> csrc/geodesic.hip, HIP tensors out, equal to the twin element for element."""
+    import geodesic
+    if torch.is_tensor(seeds):
+        import components
+        import morphology
+        if mask is not None and (not torch.is_tensor(mask) or tuple(mask.shape) != tuple(seeds.shape)):
+            raise ValueError("geodesic_distance: mask must be a HIP tensor of the seeds' shape %s" % (tuple(seeds.shape),))
+        if seeds.dtype in (torch.uint8, torch.bool, torch.int8, torch.int16, torch.int64):
+            seeds = seeds.to(torch.int32)
+        allowed = morphology.pack(components.as_mask(mask)) if mask is not None else None
+        dist, labels = geodesic.grow(seeds, allowed, sampling, structure, quantum, max_distance)
+        return geodesic.millimetres(dist, quantum), labels
+    volume = np.asarray(seeds)
+    if volume.ndim < 1 or volume.ndim > 3:
+        raise ValueError("geodesic_distance: expected a volume of 1 to 3 axes, got shape %s" % (volume.shape,))
+    if mask is not None and np.shape(mask) != volume.shape:
+        raise ValueError("geodesic_distance: mask of shape %s for seeds of shape %s" % (np.shape(mask), volume.shape))
+    import morphology
+    weights = geodesic.step_weights(sampling, volume.ndim, morphology._connectivity(structure, volume.ndim, "geodesic_distance"),
+                                    quantum)
+    shape3 = (1,) * (3 - volume.ndim) + volume.shape
+    dist, labels = _geodesic_numpy(volume.reshape(shape3), None if mask is None else (np.asarray(mask) != 0).reshape(shape3),
+                                   weights, geodesic.distance_limit(max_distance, quantum))
+    out = dist.astype(np.float64) * float(quantum)
+    out[dist == geodesic.UNREACHED] = np.inf
+    return out.reshape(volume.shape), labels.reshape(volume.shape)

@@ -839,6 +839,54 @@ int ru3d_site_assign(const uint64_t* site_bits, const uint64_t* region_bits, con
 int ru3d_territory_tally(const int32_t* labels, int K, const uint8_t* other, int num_other, const uint64_t* region_bits,
                          int X, int Y, int Z, int64_t* table, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ geodesic distance */
+/* What is nearest along a path that stays inside a mask, and how long that path is (csrc/geodesic.hip): a multi-source
+ * shortest-path transform on the 6- or 26-neighbour voxel graph of a packed mask, the weighted version of
+ * ru3d_binary_propagate.  Volumes are [X, Y, Z] with X*Y*Z < 2^31, masks the packed masks of the morphology section.
+ *
+ * Operands.  seeds (int32 volume): 0 = no seed, > 0 = the seed's label, < 0 raises flags_dev[0].  allowed: a packed mask
+ * (its complement inside the volume with invert_allowed = 1), NULL = every voxel; it is only read and may carry set
+ * bits at z >= Z.
+ * Step lengths are integers.  weights is a HOST array of 26 uint32, one per offset d in {-1, 0, 1}^3 without the centre
+ * in ascending (dx, dy, dz); 0 = no such step, else 1 .. 2^20.  The caller forms them, for a spacing s and a quantum q,
+ * as w(d) = rint(sqrt(sum (d_i s_i)^2) / q) in float64, half to even (geodesic.step_weights).  Only face steps non-zero
+ * is connectivity 1, all 26 connectivity 3; any other pattern runs as given.
+ * State is one 64-bit key per voxel: key = dist << 32 | label, all ones = not reached.  ru3d_geodesic_init writes
+ * key = label (distance 0) at a seed, whether or not it lies in `allowed` - as in ru3d_binary_propagate a seed outside
+ * `allowed` stays and spreads into its allowed neighbours - and all ones elsewhere.
+ * Relaxation rule.  For a voxel v of `allowed` and its neighbour u = v + d with a reached key, w the weight of d:
+ *   key[v] = min(key[v], key[u] + (w << 32)),   admitted only when dist(u) + w <= limit.
+ * limit is the caller's bound in quanta, at most 0xFFFFFFFE; 0xFFFFFFFE itself stands for "no bound".
+ * The result is the least fixpoint of the rule.  Integer addition makes (dist, label) strictly monotone under a step,
+ * so it equals a lexicographic Dijkstra: per voxel the smallest distance and, among the seeds at that distance, the
+ * smallest label.  It is unique: the same bytes in every run, whatever the order of updates and however stale a read.
+ * Overflow.  With limit == 0xFFFFFFFE a round raises flags_dev[1] when it leaves an allowed voxel unreached although
+ * a reached neighbour's step to it was turned down.  While the rounds run that can be a passing state; at the fixpoint
+ * it says that a distance does not fit 32 bits (use a larger quantum).  So the caller confirms a raised flag: clear it,
+ * run one round on the converged keys with first = 1 (every tile looks) and read it again.  A limit below 0xFFFFFFFE
+ * never raises it.
+ *
+ * ru3d_geodesic_init clears flags_dev[0 .. 2) (device int32) and the workspace's activity maps and writes the keys.
+ * ru3d_geodesic_rounds clears changed_dev[0 .. rounds) (device int32, 1 <= rounds <= 64) and runs `rounds` rounds as
+ * `rounds` launches on tiles of 8 x 8 x 32 voxels; changed_dev[r] = the tiles that stored a key in round r.  A tile
+ * relaxes its voxels from LDS until nothing falls or RU3D_GEODESIC_MAX_TRIPS trips are done and stores the keys that
+ * fell.  A round that counts 0 is the fixpoint and later rounds only read.  Convergence is the caller's loop, as for
+ * ru3d_binary_propagate.  The workspace holds two byte maps of tile activity: with skip_idle = 1 a tile whose own and
+ * 26 neighbouring tiles stored nothing in the round before exits at once - that round may be the last one of the call
+ * before on the same keys and workspace; first = 1 says there is none and makes every tile of round 0 run.
+ * skip_idle = 0 runs every tile in every round; the keys are the same bytes either way.
+ * ru3d_geodesic_split: dist (uint32) = the key's high half, 0xFFFFFFFF where not reached; labels (int32) = its low
+ * half, 0 where not reached.  Distances in the spacing's unit are dist * q.
+ * Workspace (init and rounds, the same buffer): ru3d_geodesic_workspace_bytes(X, Y, Z). */
+#define RU3D_GEODESIC_MAX_TRIPS 32 /* relaxation trips of a tile inside one round */
+size_t ru3d_geodesic_workspace_bytes(int X, int Y, int Z);
+int ru3d_geodesic_init(const int32_t* seeds, uint64_t* keys, int X, int Y, int Z, int32_t* flags_dev, void* ws,
+                       size_t ws_bytes, void* stream);
+int ru3d_geodesic_rounds(const uint64_t* allowed, int invert_allowed, uint64_t* keys, int X, int Y, int Z,
+                         const uint32_t* weights, uint32_t limit, int rounds, int first, int skip_idle, int32_t* changed_dev,
+                         int32_t* flags_dev, void* ws, size_t ws_bytes, void* stream);
+int ru3d_geodesic_split(const uint64_t* keys, uint32_t* dist, int32_t* labels, int X, int Y, int Z, void* stream);
+
 /* ------------------------------------------------------------------ soft skeletons, soft-clDice loss */
 /* The soft skeleton of Shit et al. (clDice, CVPR 2021) on float32 volumes x[A][B][Z] (Z fastest), `nvol` of them behind
  * one another; nothing outside a volume takes part and nothing crosses from one volume into the next.
