@@ -9,7 +9,9 @@ modes
   sync_bn    a BatchNorm ResBlock with the pooled sums all-reduced over two ranks (SyncBN).
   rccl_w1    the RCCL wrapper of the C ABI with a world of one rank: communicator from a unique id, fp32 / bf16
              all-reduce on a side stream, GradSync(transport="rccl") around the HIP model.
-"""
+
+RcclComm is ru3d_comm_unique_id, ru3d_comm_init, ru3d_comm_allreduce, ru3d_comm_reduce_scatter, ru3d_comm_all_gather and
+ru3d_comm_destroy; ops.dropout_scale outside a captured step is ru3d_dropout3d_scale."""
 import os
 import sys
 

@@ -1,7 +1,8 @@
 """bench.py --dump-outputs on a real MI355X: the files of two runs with the same arguments are equal bit for bit (same
 seeded inputs, deterministic bf16 kernels), and the eager loop writes what the hipGraph replay writes for the same
 number of training steps.  A plain run prints the headline line alone; --full runs the other legs behind the same timed
-steps.  Small model (2 levels, 32 features, 32^3 patches); run with `-m gpu`."""
+steps.  Small model (2 levels, 32 features, 32^3 patches); run with `-m gpu`.  The roofline leg of --full counts launches
+with ops.Probe, which is ru3d_probe_begin / ru3d_probe_end."""
 import json
 import os
 import subprocess

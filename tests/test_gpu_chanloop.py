@@ -11,7 +11,7 @@ take the whole-instance kernels of norm_small.hip (tests/test_gpu_small_norm.py 
 References are float64 restatements of the reference formulas on the STORED tensors (network.py:384-386, 411-416, the
 comments above bn_pool_kernel and pointwise_kernel), so only the kernels' own fp32 arithmetic and output rounding differ.
 Operands live in wide NDHWC buffers filled with a NaN bit pattern: a lane read outside the channel slice poisons the
-result, a lane written outside it changes the pattern, an output voxel left unwritten stays NaN.  Run with `-m gpu`."""
+result, a lane written outside it changes the pattern, an output voxel left unwritten stays NaN.  Run with `-m gpu`.  ops.bn_train_stats ends in ru3d_batchnorm_stats_finalize."""
 import ctypes
 
 import pytest

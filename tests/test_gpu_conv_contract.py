@@ -21,7 +21,10 @@ weight non-zero), the weight-gradient operands are drawn here.
 The wrappers of _ops are the callers: they hand the C entry points what N.workspace() / N.new_act() and _ops' own
 torch.empty() return, so the tests swap those (the last through a stand-in for the name `torch` inside _ops, nowhere
 else) for hostile ones around the one call under test and nothing else.
-Run with `-m gpu`."""
+Run with `-m gpu`.  Entry points the wrappers under test go through without the file naming them elsewhere: ops.convt_fwd_in is
+ru3d_convtranspose3d_k3s2p1_fwd_in; ops.head_bwd asks ru3d_head_bwd_supported and ru3d_head_bwd_workspace_bytes,
+ops.head_in_bwd ru3d_head_in_bwd_supported and ru3d_head_in_bwd_workspace_bytes, ops.skip1x1_in_lrelu_fwd
+ru3d_skip1x1_in_lrelu_fwd_supported."""
 import contextlib
 import functools
 import itertools

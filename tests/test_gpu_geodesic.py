@@ -6,9 +6,8 @@ max_distance, the overflow flag and that a bound does not raise it; idle-tile sk
 the memory contract (inputs, guard regions, short workspaces, bad arguments); transform.geodesic_distance and the
 trainer's territory drivers with metric='geodesic' on HIP operands against the host route.
 
-The wrapper is also entered into the case table of tests/test_gpu_scratch_contract.py (at the end of this file), which
-wants a case for every *_workspace_bytes query of the bindings: that module's checks run on geodesic.grow too.  Run with
-`-m gpu`, the whole suite: the scratch-contract module finds the case only when this one was collected with it."""
+The wrapper's cases in the table of tests/test_gpu_scratch_contract.py (geodesic.grow, geodesic.grow_cube_limit) hold it to
+that module's six checks.  Run with `-m gpu`."""
 import numpy as np
 import pytest
 import torch
@@ -28,7 +27,6 @@ import transform  # noqa: E402
 from test_gpu_territory import SPACINGS, guarded, on, organ_case, packed  # noqa: E402
 from test_host_geodesic import wall_case  # noqa: E402
 from test_host_skeleton_graph import same  # noqa: E402
-import test_gpu_scratch_contract as SC  # noqa: E402
 
 Q = 2.0 ** -10
 NONE = 0xFFFFFFFF
@@ -347,29 +345,3 @@ def test_territory_drivers_with_the_geodesic_metric_on_hip_operands(dev, tmp_pat
     assert host['file'].read_bytes() == device['file'].read_bytes()
     assert (nifti.load(host['labels_file'])[0] == nifti.load(device['labels_file'])[0]).all()
     assert same(json_load(device['file']), {k: v for k, v in device.items() if k not in ('file', 'labels_file')})
-
-
-# ------------------------------------------------------------------------------------------------ the scratch contract
-# tests/test_gpu_scratch_contract.py holds every wrapper with a *_workspace_bytes query to its six checks and fails when a
-# query of the bindings has no case; the case of geodesic.grow is entered here, in that module's own form.
-def _contract_case():
-    rng = np.random.RandomState(67)
-    allowed_np = SC._volumes()["mask"]
-    seeds_np = np.zeros(SC.VOL, dtype=np.int32)
-    seeds_np.reshape(-1)[rng.choice(seeds_np.size, 4, replace=False)] = (5, 1, 3, 3)
-    seeds, allowed = SC._up(seeds_np), SC._pack(allowed_np)
-
-    def call():
-        dist, labels = geodesic.grow(seeds, allowed, SPACINGS[1], CUBE)
-        return dict(dist=dist.view(torch.int32), labels=labels)
-
-    def reference(out):
-        want = twin(seeds_np, allowed_np, SPACINGS[1], 3)
-        assert np.array_equal(out["dist"].cpu().numpy().view(np.uint32), want[0])
-        assert np.array_equal(out["labels"].cpu().numpy(), want[1])
-    return call, reference
-
-
-if "geodesic.grow" not in SC.CASES:
-    SC.case("geodesic.grow", ["ru3d_geodesic_workspace_bytes"])(_contract_case)
-    SC.NAMES.append("geodesic.grow")

@@ -1,6 +1,7 @@
 """graph.GraphedTrainStep: a training step captured in a hipGraph and replayed is the SAME training run as the eager
 steps - same losses, same parameters, same Dropout3d masks, same Adam step counts / learning-rate schedule - bit for
-bit.  Needs a real MI355X: run with `-m gpu`."""
+bit.  Needs a real MI355X: run with `-m gpu`.  Inside a captured step the Dropout3d draws are
+ru3d_dropout3d_scale_dev."""
 import pytest
 import torch
 

@@ -10,7 +10,7 @@ same run with the head in the block or behind it.  The float64 CPU reference bui
     err_fused <= 1.5 * err_unfused + 1 ulp of the storage type (of the reference's largest magnitude),
 stays as the check that both are right.  The two means m1 / m2 themselves stay in the library's workspace; they are
 checked through gpre_sum (V * sum_n m1) and dy2 (scale * (g' - m1 - xhat * m2)), which read them element by element.
-Run with `-m gpu`."""
+Run with `-m gpu`.  ops.skip1x1_in_lrelu_head_fwd asks ru3d_skip1x1_in_lrelu_head_fwd_supported first."""
 import functools
 import os
 

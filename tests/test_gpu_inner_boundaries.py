@@ -22,7 +22,8 @@ Two comparisons:
                  for case A, equally exact under the same premise, which the test asserts).  A dropped position or a
                  misplaced reduce tile, which a tolerance of a fraction of the tensor's maximum can hide, cannot pass.
 
-Run with `-m gpu`."""
+Run with `-m gpu`.  The transposed conv's wrappers ops.convt_fwd, convt_dgrad and convt_wgrad are the entry points
+ru3d_convtranspose3d_k3s2p1_fwd, ru3d_convtranspose3d_k3s2p1_dgrad and ru3d_convtranspose3d_k3s2p1_wgrad."""
 import functools
 
 import pytest

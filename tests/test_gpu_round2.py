@@ -2,7 +2,8 @@
   * channel padding: F = 30 widths (the reference's default num_features, network.py:107; BASELINE config 4) on the
     MFMA kernels - padded weight packs, un-padded weight gradients, whole-net parity against the oracle's 16-bit
     storage model and against the un-padded generic-kernel run of the same model;
-  * activation checkpointing (BASELINE config 5): gradients bit-equal to the plain run, less memory."""
+  * activation checkpointing (BASELINE config 5): gradients bit-equal to the plain run, less memory.
+ops.unpad_wgrad is the entry point ru3d_unpad_weight_grad."""
 import os
 
 import numpy as np

@@ -27,11 +27,18 @@ Checks per case, in this order:
                    allocation of the wrapper has a guard of its own behind it, checked after every run; where only a
                    counted prefix of a capacity buffer is valid the case returns that prefix and says so
 
-The coverage test at the end holds the case table against _native.SIGNATURES.
+The post-processing cases (morphometry, floods, keep-largest, the vessel graph, territories, geodesic growth) take their
+host volumes from tests/contract_inputs.py; tests/test_host_contract_inputs.py holds those volumes, without a device, to
+what each case is there to exercise (a second batch of rounds, a tie, an empty id, ..).
+
+Two coverage tests at the end hold the case table against _native.SIGNATURES: every *_workspace_bytes / *_state_bytes
+query is named by a case, and every entry point is called by the clean run of a case or listed, with the test file that
+holds it, in HELD_ELSEWHERE.
 Run with `-m gpu`."""
 import contextlib
 import functools
 import math
+import os
 
 import numpy as np
 import pytest
@@ -49,16 +56,21 @@ import augment  # noqa: E402
 import components  # noqa: E402
 import degrade  # noqa: E402
 import distance  # noqa: E402
+import geodesic  # noqa: E402
 import loss as L  # noqa: E402
 import mesh  # noqa: E402
 import morphology  # noqa: E402
+import morphometry  # noqa: E402
 import prepare  # noqa: E402
 import skeleton  # noqa: E402
+import territory  # noqa: E402
 import trainer  # noqa: E402
 import transform as T  # noqa: E402
 import visualize as V  # noqa: E402
+import contract_inputs as CI  # noqa: E402
 import test_gpu_loss_contract as LC  # noqa: E402
 import test_gpu_topk as TK  # noqa: E402
+from test_host_skeleton_graph import same  # noqa: E402
 
 DEV = torch.device("cuda:0")
 LEFTOVERS = (0x00, 0xFF, 0x7F)
@@ -1026,20 +1038,414 @@ def _t_select():
     return call, reference
 
 
+# ---- propagation and hole filling (reference: scipy, tests/test_gpu_postprocess.py, equality).  No scratch: the flood's
+# counters are a torch.empty vector, which the stand-in fills.  last_rounds is an output: a leftover byte must not move it
+@case("morphology.propagate")
+def _m_propagate():
+    """(20, 10, 67), two tiles of the flood along x: the corridor of contract_inputs.flood_zigzag takes more rounds
+    than the first batch has"""
+    seed, allowed, _, _ = CI.flood_zigzag()
+    s, a = _pack(seed), _pack(allowed)
+    before = s.bits.clone(), a.bits.clone()
+
+    def call():
+        reach = morphology.propagate(s, a, None, 0)
+        assert torch.equal(s.bits, before[0]) and torch.equal(a.bits, before[1])
+        return dict(reach=reach, rounds=morphology.last_rounds)
+
+    def reference(out):
+        assert int(out["rounds"]) > CI.FLOOD_FIRST_BATCH, "one batch of rounds: %d" % int(out["rounds"])
+        assert np.array_equal(_bools(out["reach"], CI.FLOOD_SHAPE), ndi.binary_propagation(seed, mask=allowed))
+    return call, reference
+
+
+@case("morphology.propagate_cube_border")
+def _m_propagate_border():
+    """allowed=None: the complement of an empty mask, inverted on load; the full cube, the outside set"""
+    seed = CI.flood_cube_seed()
+    s = _pack(seed)
+
+    def call():
+        return dict(reach=morphology.propagate(s, None, CI.CUBE, 1), rounds=morphology.last_rounds)
+
+    def reference(out):
+        want = ndi.binary_propagation(seed, structure=CI.CUBE, border_value=1)
+        assert want.all() and np.array_equal(_bools(out["reach"]), want)
+    return call, reference
+
+
+@case("morphology.fill_holes")
+def _m_fill_holes():
+    solid, tunnel = CI.solid_with_cavities()
+    p = _pack(solid)
+
+    def call():
+        return dict(filled=morphology.fill_holes(p), rounds=morphology.last_rounds)
+
+    def reference(out):
+        got = _bools(out["filled"])
+        assert np.array_equal(got, ndi.binary_fill_holes(solid))
+        assert (got & ~solid).sum() > 0 and not got[tunnel].any()          # cavities filled, the tunnel not
+    return call, reference
+
+
+# ---- components.keep_largest (reference: the numpy twin of tests/postprocess_cases.py, equality)
+def _keep(relabel):
+    host, lab, k, sizes = CI.keep_volume()
+    d, dsizes, dmask = _up(lab), _up(sizes.astype(np.int32)), _up(host.astype(np.uint8))
+
+    def call():
+        m = dmask.clone()
+        out, kept = components.keep_largest(d, k, dsizes, k=2, mask=m, relabel=relabel)
+        return dict(mask=m, kept=kept, **(dict(labels=out) if relabel else {}))
+
+    def reference(out):
+        want_mask, want_labels = CI.keep_largest_numpy(host, 2)
+        assert int(out["kept"]) == 2 and np.array_equal(out["mask"].cpu().numpy().astype(bool), want_mask)
+        if relabel:
+            assert np.array_equal(out["labels"].cpu().numpy(), want_labels.astype(np.int32))
+    return call, reference
+
+
+case("components.keep_largest", ["ru3d_filter_components_workspace_bytes"])(lambda: _keep(False))
+case("components.keep_largest_relabel", ["ru3d_filter_components_workspace_bytes"])(lambda: _keep(True))
+
+
+# ---- morphometry.py (reference: its numpy route, tests/test_gpu_morphometry.py: equality; extents to the rounding of a
+# four-term sum).  No scratch: every table is a torch.empty of the wrapper.  Plain names: the int32 components of the
+# speckle mask (id_bytes 4); _u8: a uint8 class volume (id_bytes 1)
+def _mm(id_bytes):
+    ids, count, other, num_other = CI.morphometry_ids(id_bytes)
+    return ids, count, other, num_other, _up(ids), (None if other is None else _up(other))
+
+
+def _mm_moments(id_bytes):
+    ids, count, _, _, d, _ = _mm(id_bytes)
+
+    def reference(out):
+        assert np.array_equal(out["moments"].cpu().numpy(), morphometry.moments(ids, count))
+    return (lambda: dict(moments=morphometry.moments(d, count))), reference
+
+
+def _mm_faces(id_bytes):
+    """int32 ids against `other`; the uint8 volume in class mode"""
+    ids, count, other, num_other, d, o = _mm(id_bytes)
+
+    def reference(out):
+        assert np.array_equal(out["faces"].cpu().numpy(), morphometry.faces(ids, count, other, num_other))
+    return (lambda: dict(faces=morphometry.faces(d, count, o, num_other))), reference
+
+
+def _mm_extents(id_bytes):
+    ids, count, _, _, d, _ = _mm(id_bytes)
+    frames = CI.morphometry_frames(count)
+
+    def reference(out):
+        got, want = out["extents"].cpu().numpy(), morphometry.extents(ids, count, frames)
+        # extent_tolerance of tests/test_gpu_morphometry.py: 4 u (|ax x| + |ay y| + |az z| + |b|), the largest of an id
+        tol = np.zeros((count, 3))
+        lin, k = morphometry._valid(ids, count)
+        x, y, z = (c.astype(np.float64)[:, None] for c in morphometry._xyz(lin, ids.shape))
+        fk = np.abs(frames)[k - 1]
+        np.maximum.at(tol, k - 1, fk[:, :, 0] * x + fk[:, :, 1] * y + fk[:, :, 2] * z + fk[:, :, 3])
+        tol *= 4 * 2.0 ** -53
+        finite = np.isfinite(want)
+        assert not finite.all() and np.array_equal(np.isfinite(got), finite) and np.array_equal(got[~finite], want[~finite])
+        err = np.abs(np.where(finite, got, 0.0) - np.where(finite, want, 0.0))
+        print("extents id_bytes=%d: worst error / bound %.3g" % (id_bytes, (err / np.maximum(tol[:, :, None], 1e-300)).max()))
+        assert np.all(err <= tol[:, :, None]) and np.array_equal(got[:, 0], want[:, 0])
+    return (lambda: dict(extents=morphometry.extents(d, count, frames))), reference
+
+
+def _sorted_groups(cand, starts, counts):
+    groups = [np.sort(cand[s:s + c]) for s, c in zip(starts.tolist(), counts.tolist())]
+    return np.concatenate(groups) if groups else cand
+
+
+def _mm_candidates(id_bytes):
+    """the device leaves the order inside a group undefined: the case returns every group sorted (sorted_groups of
+    tests/test_gpu_morphometry.py)"""
+    ids, count, _, _, d, _ = _mm(id_bytes)
+
+    def call():
+        cand, starts, counts = morphometry.candidates(d, count)
+        return dict(cand=_sorted_groups(cand.cpu().numpy(), starts.cpu(), counts.cpu()), starts=starts, counts=counts)
+
+    def reference(out):
+        cand, starts, counts = morphometry.candidates(ids, count)
+        assert np.array_equal(out["counts"].cpu().numpy(), counts) and np.array_equal(out["starts"].cpu().numpy(), starts)
+        assert np.array_equal(out["cand"].numpy(), _sorted_groups(cand, starts, counts))
+    return call, reference
+
+
+def _mm_feret(id_bytes):
+    """voxel units: every term of d^2 is a small integer, so the float64 sums are exact and d^2 is held with ==; the
+    pair as tests/test_gpu_morphometry.py holds it: two voxels of the id that give d^2 back"""
+    ids, count, _, _, d, _ = _mm(id_bytes)
+
+    def call():
+        d2, pair = morphometry.feret(d, count)
+        return dict(d2=d2, pair=pair)
+
+    def reference(out):
+        d2, pair = out["d2"].cpu().numpy(), out["pair"].cpu().numpy()
+        want, _ = morphometry.feret(ids, count)
+        assert np.array_equal(d2, want)
+        n = morphometry.moments(ids, count)[:, 0]
+        assert np.array_equal(d2 < 0, n == 0) and np.all(d2[n == 1] == 0.0)
+        for k in range(count):
+            if n[k] == 0:
+                assert pair[k].tolist() == [-1] * 6
+            else:
+                assert ids[tuple(pair[k, :3])] == k + 1 and ids[tuple(pair[k, 3:])] == k + 1
+                assert float(((pair[k, :3] - pair[k, 3:]).astype(np.int64) ** 2).sum()) == d2[k]
+    return call, reference
+
+
+for _name, _fn in (("moments", _mm_moments), ("faces", _mm_faces), ("extents", _mm_extents),
+                   ("candidates", _mm_candidates), ("feret", _mm_feret)):
+    case("morphometry." + _name)(functools.partial(_fn, 4))
+    case("morphometry.%s_u8" % _name)(functools.partial(_fn, 1))
+
+
+# ---- skeleton.graph and prune (reference: the numpy twins of transform.py, tests/test_gpu_skeleton_graph.py, equality
+# with nan equal to nan).  The host tables come back as numpy
+GRAPH_TABLES = ('n', 'nodes', 'branches', 'node_table', 'branch_table', 'length', 'chord', 'tortuosity')
+GRAPH_RADII = ('radius_min', 'radius_mean', 'radius_max')
+
+
+def _graph(with_mask, regrow=False):
+    skel = CI.wire_tree()
+    p = _pack(skel)
+    m = _pack(CI.wire_lumen()) if with_mask else None
+    sampling = CI.SAMPLING if with_mask else None
+
+    def call():
+        if not regrow:
+            return dict(skeleton.graph(p, m, sampling))
+        saved = dict(skeleton._ids_capacity)
+        skeleton._ids_capacity[p.device] = CI.FORCED_IDS_CAPACITY          # below n: the ids buffer grows, a second labelling
+        try:
+            return dict(skeleton.graph(p, m, sampling), capacity=skeleton._ids_capacity[p.device])
+        finally:
+            skeleton._ids_capacity.clear()
+            skeleton._ids_capacity.update(saved)
+
+    def reference(out):
+        sq = trainer._radii_squared_numpy(skel, CI.wire_lumen(), CI.SAMPLING) if with_mask else None
+        want = T._skeleton_graph_numpy(skel, sq, CI.SAMPLING if with_mask else (1.0, 1.0, 1.0))
+        keys = GRAPH_TABLES + (GRAPH_RADII if with_mask else ())
+        assert set(out) == set(want) | ({"capacity"} if regrow else set())
+        assert out["ids"].dtype == torch.int32 and np.array_equal(out["ids"].cpu().numpy(), want["ids"])
+        for k in keys:
+            got = out[k].numpy()
+            assert same(got if got.ndim else got.item(), want[k]), k
+        if regrow:
+            assert CI.FORCED_IDS_CAPACITY < want["n"] <= int(out["capacity"]) == 1 << (want["n"] - 1).bit_length()
+    return call, reference
+
+
+case("skeleton.graph", ["ru3d_skeleton_workspace_bytes"])(lambda: _graph(False))
+case("skeleton.graph_radii", ["ru3d_skeleton_workspace_bytes", "ru3d_edt_workspace_bytes"])(lambda: _graph(True))
+case("skeleton.graph_regrow", ["ru3d_skeleton_workspace_bytes"])(lambda: _graph(False, regrow=True))
+
+
+@case("skeleton.prune", ["ru3d_skeleton_workspace_bytes"])
+def _s_prune():
+    skel = CI.wire_tree()
+    p = _pack(skel)
+    before = p.bits.clone()
+
+    def call():
+        pruned, rounds = skeleton.prune(p, CI.PRUNE_MIN_LENGTH)
+        assert torch.equal(p.bits, before)
+        return dict(pruned=pruned, rounds=rounds)
+
+    def reference(out):
+        want, rounds = T._skeleton_prune_numpy(skel, CI.PRUNE_MIN_LENGTH)
+        assert int(out["rounds"]) == rounds >= 3 and np.array_equal(_bools(out["pruned"]), want)
+    return call, reference
+
+
+# ---- territory.py (reference: the numpy twins of transform.py, tests/test_gpu_territory.py, equality)
+def _t_nearest(return_sq):
+    """return_sq=False asks for 8 X Y Z bytes more: the values then live in the scratch"""
+    host = CI.sites()[0]
+    s = _pack(host)
+
+    def call():
+        index, sq = territory.nearest(s, CI.SAMPLING, return_sq=return_sq)
+        assert return_sq or sq is None
+        return dict(index=index, **(dict(sq=sq) if return_sq else {}))
+
+    def reference(out):
+        index, sq = T._nearest_site_numpy(host, CI.SAMPLING)
+        assert np.array_equal(out["index"].cpu().numpy(), index)
+        assert not return_sq or np.array_equal(out["sq"].cpu().numpy(), sq)
+    return call, reference
+
+
+case("territory.nearest", ["ru3d_edt_workspace_bytes"])(lambda: _t_nearest(True))
+case("territory.nearest_index_only", ["ru3d_edt_workspace_bytes"])(lambda: _t_nearest(False))
+
+
+def _t_assign(with_region):
+    host, site_ids, _, region, _ = CI.sites()
+    index, want = CI.site_labels(with_region)
+    s, ids, idx = _pack(host), _up(site_ids), _up(index)
+    r = _pack(region) if with_region else None
+
+    def reference(out):
+        assert np.array_equal(out["labels"].cpu().numpy(), want)
+    return (lambda: dict(labels=territory.assign(s, ids, idx, r))), reference
+
+
+case("territory.assign", ["ru3d_skeleton_workspace_bytes"])(lambda: _t_assign(False))
+case("territory.assign_region", ["ru3d_skeleton_workspace_bytes"])(lambda: _t_assign(True))
+
+
+def _t_tally(K):
+    """ru3d_territory_tally has no query: its scratch is the 256 bytes of the error word (TR_TALLY_WORKSPACE).  K = 6:
+    the counters of a workgroup in LDS; K = 4000: (K + 1) * 3 cells are beyond LDS, 64-bit atomics on the table"""
+    _, _, _, region, other = CI.sites()
+    labels = CI.site_labels(True)[1]
+    d, o, r = _up(labels), _up(other), _pack(region)
+
+    def reference(out):
+        assert np.array_equal(out["table"].cpu().numpy(), T._territory_tally_numpy(labels, K, other, 2, region))
+    return (lambda: dict(table=territory.tally(d, K, o, 2, r))), reference
+
+
+case("territory.tally")(lambda: _t_tally(CI.sites()[2]))
+case("territory.tally_beyond_lds")(lambda: _t_tally(CI.TALLY_BEYOND_LDS))
+
+
+def _t_partition(metric):
+    """the composed driver on the wire tree inside its organ: nearest + assign + tally, or unpack + grow + tally"""
+    skel, g, region, vessel, other = CI.organ()
+    p, r, v, o = _pack(skel), _pack(region), _pack(vessel), _up(other)
+    dg = dict(ids=_up(g["ids"]), branches=g["branches"], nodes=g["nodes"])
+
+    def call():
+        table, labels = territory.partition(p, dg, r, CI.SAMPLING, o, 1, metric=metric, vessel=v)
+        return dict(table=table, labels=labels)
+
+    def reference(out):
+        site_ids, K = territory.branch_sites(g)
+        if metric == "euclidean":
+            index, _ = T._nearest_site_numpy(skel, CI.SAMPLING)
+            labels = T._site_assign_numpy(skel, site_ids, index, region)
+        else:
+            seeds = np.zeros(VOL, dtype=np.int32)
+            seeds[skel] = site_ids
+            labels = np.where(region, CI.grow_twin(seeds, region | vessel, 3)[1], 0).astype(np.int32)
+        assert (labels[region] > 0).any()
+        assert np.array_equal(out["labels"].cpu().numpy(), labels)
+        assert np.array_equal(out["table"].numpy(), T._territory_tally_numpy(labels, K, other, 1, region))
+    return call, reference
+
+
+case("territory.partition", ["ru3d_edt_workspace_bytes", "ru3d_skeleton_workspace_bytes"])(lambda: _t_partition("euclidean"))
+case("territory.partition_geodesic", ["ru3d_geodesic_workspace_bytes"])(lambda: _t_partition("geodesic"))
+
+
+# ---- geodesic.py (reference: transform._geodesic_numpy, tests/test_gpu_geodesic.py, equality on dist and labels)
+@case("geodesic.grow", ["ru3d_geodesic_workspace_bytes"])
+def _g_grow():
+    """masked, the face steps, anisotropic: the serpentine inside the first tile takes more rounds than the first batch
+    has; the seeds 5 and 4 tie at (8, 9, 48); one seed of label 2 is not allowed"""
+    seeds, allowed, _, _ = CI.grow_masked()
+    s, a = _up(seeds), _pack(allowed)
+    before = s.clone(), a.bits.clone()
+
+    def call():
+        dist, labels = geodesic.grow(s, a, CI.SAMPLING, None, CI.QUANTUM)
+        assert torch.equal(s, before[0]) and torch.equal(a.bits, before[1])
+        return dict(dist=dist.view(torch.int32), labels=labels, rounds=geodesic.last_rounds)
+
+    def reference(out):
+        want = CI.grow_twin(seeds, allowed, 1)
+        assert int(out["rounds"]) > CI.FLOOD_FIRST_BATCH, "one batch of rounds: %d" % int(out["rounds"])
+        assert np.array_equal(out["dist"].cpu().numpy().view(np.uint32), want[0])
+        assert np.array_equal(out["labels"].cpu().numpy(), want[1])
+    return call, reference
+
+
+@case("geodesic.grow_cube", ["ru3d_geodesic_workspace_bytes"])
+def _g_grow_cube():
+    """masked, all 26 steps: four seeds dropped on the speckle mask wherever they fall, one label twice"""
+    allowed = _volumes()["mask"]
+    seeds = np.zeros(VOL, dtype=np.int32)
+    seeds.reshape(-1)[np.random.RandomState(67).choice(seeds.size, 4, replace=False)] = (5, 1, 3, 3)
+    s, a = _up(seeds), _pack(allowed)
+
+    def call():
+        dist, labels = geodesic.grow(s, a, CI.SAMPLING, CI.CUBE)
+        return dict(dist=dist.view(torch.int32), labels=labels, rounds=geodesic.last_rounds)
+
+    def reference(out):
+        want = CI.grow_twin(seeds, allowed, 3)
+        assert np.array_equal(out["dist"].cpu().numpy().view(np.uint32), want[0])
+        assert np.array_equal(out["labels"].cpu().numpy(), want[1])
+    return call, reference
+
+
+@case("geodesic.grow_cube_limit", ["ru3d_geodesic_workspace_bytes"])
+def _g_grow_limit():
+    """allowed=None (every voxel is allowed, so no seed can lie outside: geodesic.grow has that seed), all 26 steps, a
+    max_distance that cuts, every tile in every round"""
+    seeds, max_distance = CI.grow_cube()
+    s = _up(seeds)
+
+    def call():
+        dist, labels = geodesic.grow(s, None, CI.SAMPLING, CI.CUBE, CI.QUANTUM, max_distance, skip_idle=False)
+        return dict(dist=dist.view(torch.int32), labels=labels, rounds=geodesic.last_rounds)
+
+    def reference(out):
+        want = CI.grow_twin(seeds, None, 3, max_distance)
+        dist = out["dist"].cpu().numpy().view(np.uint32)
+        assert (dist == geodesic.UNREACHED).any() and np.array_equal(dist, want[0])
+        assert np.array_equal(out["labels"].cpu().numpy(), want[1])
+    return call, reference
+
+
 NAMES = list(CASES)
 # wrappers that launch an entry point without scratch ahead of their first ask: the sampler its presence kernel (the label
-# rule of the patch kernel reads its mask), transform.extract_mesh the pack of the volume
+# rule of the patch kernel reads its mask), transform.extract_mesh the pack of the volume, the geodesic partition the
+# unpack of the skeleton (the seeds of the growth are the skeleton's voxels, and unpacking needs no scratch)
 AHEAD = {"augment.sample": ["augment_label_presence"], "augment.sample_rotation_elastic": ["augment_label_presence"],
-         "mesh.extract_measure": ["mask_pack"]}
+         "mesh.extract_measure": ["mask_pack"], "territory.partition_geodesic": ["mask_unpack"]}
 
 
 # ------------------------------------------------------------------------------------------------ the checks
+CALLED = {}             # case -> the entry points of _native.SIGNATURES its first clean run called
+
+
+@contextlib.contextmanager
+def _recorded(into):
+    """every entry point of _native.SIGNATURES on N.lib, wrapped as _spied wraps the queries: the names called go `into`"""
+    saved = {}
+    for n in N.SIGNATURES:
+        saved[n] = fn = getattr(N.lib, n)
+
+        def spy(*a, _fn=fn, _n=n):
+            into.add(_n)
+            return _fn(*a)
+        setattr(N.lib, n, spy)
+    try:
+        yield
+    finally:
+        for n, fn in saved.items():
+            setattr(N.lib, n, fn)
+
+
 @functools.lru_cache(maxsize=None)
 def _clean(name):
     """checks 1 and 2: the clean run, held to the case's reference, then made again: the same launches, the same bits
     (DESIGN's fixed-order reductions - every later comparison stands on it)"""
     call, reference = _built(name)
-    names, out, err = _run(call, name)
+    with _recorded(CALLED.setdefault(name, set())):        # for the second coverage test; checks 3 to 5 run without it
+        names, out, err = _run(call, name)
     assert err is None, err
     print("CLEAN %s %s" % (name, names))
     reference(out)
@@ -1196,3 +1602,148 @@ def test_every_query_of_the_signature_table_has_a_case():
     named = {q for _, queries, _ in CASES.values() for q in queries}
     assert named <= wanted, "cases name %s, no query of the table" % sorted(named - wanted)
     assert wanted <= named, "no case for %s" % sorted(wanted - named)
+
+
+# entry points no case of this table calls, and the file under tests/ that holds each (its text names the entry point): the
+# conv, norm and pool families, the optimizers and loss scaling, comm / probe / cu_budget, the predict, cascade and
+# render-tile entry points that neither carve nor allocate, the *_supported and layout queries.  The two of TOOL_ONLY
+# are called by tools/topk_loss_bench.py alone and named by no test, so no file can stand for them here
+HELD_ELSEWHERE = {
+    **dict.fromkeys((
+        "ru3d_comm_all_gather", "ru3d_comm_allreduce", "ru3d_comm_available", "ru3d_comm_destroy", "ru3d_comm_init",
+        "ru3d_comm_reduce_scatter", "ru3d_comm_unique_id", "ru3d_dropout3d_scale", "ru3d_flat_cast",
+    ), "tests/dist_child.py"),
+    **dict.fromkeys((
+        "ru3d_probe_begin", "ru3d_probe_end",
+    ), "tests/test_gpu_bench.py"),
+    **dict.fromkeys((
+        "ru3d_get_cu_budget", "ru3d_set_cu_budget",
+    ), "tests/test_gpu_boundary.py"),
+    **dict.fromkeys((
+        "ru3d_add", "ru3d_affine_lrelu_fwd", "ru3d_batchnorm_bwd_apply", "ru3d_batchnorm_bwd_pool",
+        "ru3d_batchnorm_stats_finalize", "ru3d_batchnorm_stats_pool", "ru3d_cast_f32", "ru3d_channel_sum",
+        "ru3d_conv3d_dgrad_in_bwd", "ru3d_copy_channels", "ru3d_head_in_bwd", "ru3d_in_lrelu_bwd",
+        "ru3d_in_lrelu_bwd_apply", "ru3d_in_lrelu_fwd", "ru3d_instnorm_stats", "ru3d_last_error",
+        "ru3d_ncdhw_to_ndhwc", "ru3d_ndhwc_to_ncdhw", "ru3d_pointwise", "ru3d_reduce_workspace_bytes",
+    ), "tests/test_gpu_chanloop.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_fwd", "ru3d_convtranspose3d_k3s2p1_fwd_in", "ru3d_head_bwd_supported",
+        "ru3d_head_bwd_workspace_bytes", "ru3d_head_in_bwd_supported", "ru3d_head_in_bwd_workspace_bytes",
+        "ru3d_skip1x1_in_lrelu_fwd_supported",
+    ), "tests/test_gpu_conv_contract.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_fwd_in_workspace_bytes", "ru3d_conv3d_s2_pair_fwd_in",
+        "ru3d_conv3d_s2_pair_fwd_in_workspace_bytes", "ru3d_conv3d_wgrad_pair", "ru3d_conv3d_wgrad_pair_supported",
+        "ru3d_conv3d_wgrad_pair_workspace_bytes", "ru3d_conv3d_wgrad_workspace_bytes",
+        "ru3d_convtranspose3d_k3s2p1_wgrad_workspace_bytes", "ru3d_set_cu_budget_device",
+    ), "tests/test_gpu_cu_budget.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_plan_names",
+    ), "tests/test_gpu_direct_plan.py"),
+    **dict.fromkeys((
+        "ru3d_dropout3d_scale_dev",
+    ), "tests/test_gpu_graph.py"),
+    **dict.fromkeys((
+        "ru3d_loss_state_bad_labels_offset", "ru3d_predict_accumulate", "ru3d_predict_accumulate_groups",
+        "ru3d_predict_merge", "ru3d_predict_merge_groups",
+    ), "tests/test_gpu_groups.py"),
+    **dict.fromkeys((
+        "ru3d_head_bwd", "ru3d_skip1x1_in_lrelu_fwd", "ru3d_skip1x1_in_lrelu_head_fwd",
+        "ru3d_skip1x1_in_lrelu_head_fwd_supported",
+    ), "tests/test_gpu_head_tail.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_wgrad_bias",
+    ), "tests/test_gpu_headstem.py"),
+    **dict.fromkeys((
+        "ru3d_ds_loss_ignore_bwd", "ru3d_ds_loss_ignore_fwd", "ru3d_loss_ignore_bwd", "ru3d_loss_ignore_fwd",
+        "ru3d_topk_loss_ignore_bwd", "ru3d_topk_loss_ignore_fwd",
+    ), "tests/test_gpu_ignore_label.py"),
+    **dict.fromkeys((
+        "ru3d_convtranspose3d_k3s2p1_dgrad", "ru3d_convtranspose3d_k3s2p1_fwd", "ru3d_convtranspose3d_k3s2p1_wgrad",
+    ), "tests/test_gpu_inner_boundaries.py"),
+    **dict.fromkeys((
+        "ru3d_mask_bytes",
+    ), "tests/test_gpu_morphology.py"),
+    **dict.fromkeys((
+        "ru3d_adam_multi", "ru3d_adam_multi_amp", "ru3d_adam_multi_dev", "ru3d_adam_step", "ru3d_amp_update",
+        "ru3d_grad_scale_check",
+    ), "tests/test_gpu_optim_kernels.py"),
+    **dict.fromkeys((
+        "ru3d_adam_multi_clip", "ru3d_adam_multi_clip_dev", "ru3d_adamw_multi", "ru3d_adamw_multi_dev",
+        "ru3d_grad_norm", "ru3d_grad_norm_finish", "ru3d_grad_scale_dev", "ru3d_grad_sumsq", "ru3d_sgd_multi",
+        "ru3d_sgd_multi_dev",
+    ), "tests/test_gpu_optim_recipe.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_s1_dgrad_pair", "ru3d_conv3d_s2_dgrad_pair",
+    ), "tests/test_gpu_pairs.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_fwd_in", "ru3d_version",
+    ), "tests/test_gpu_parity.py"),
+    **dict.fromkeys((
+        "ru3d_maxpool3d_bwd", "ru3d_maxpool3d_fwd",
+    ), "tests/test_gpu_plain_unet.py"),
+    **dict.fromkeys((
+        "ru3d_predict_accumulate_weighted", "ru3d_predict_gather",
+    ), "tests/test_gpu_predict_tta.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_wgrad",
+    ), "tests/test_gpu_reduce_tails.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_dgrad", "ru3d_pack_weight", "ru3d_pack_weights", "ru3d_packed_weight_bytes",
+        "ru3d_unpad_weight_grad",
+    ), "tests/test_gpu_round2.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_workspace_bytes",
+    ), "tests/test_gpu_s1_routing.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_fwd_in_lrelu", "ru3d_conv3d_fwd_in_lrelu_workspace_bytes",
+    ), "tests/test_gpu_small_norm.py"),
+    **dict.fromkeys((
+        "ru3d_topk_select_trip_elements",
+    ), "tests/test_gpu_topk.py"),
+    **dict.fromkeys((
+        "ru3d_render_tiles",
+    ), "tests/test_gpu_visualize.py"),
+    **dict.fromkeys((
+        "ru3d_augment_intensity",
+    ), "tests/test_host_augment_degrade.py"),
+    **dict.fromkeys((
+        "ru3d_cascade_merge", "ru3d_region_accumulate",
+    ), "tests/test_host_components.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_dgrad_in_bwd_workspace_bytes", "ru3d_conv3d_s1_dgrad_pair_supported",
+        "ru3d_planar_concat_supported",
+    ), "tests/test_host_conv_plan.py"),
+    **dict.fromkeys((
+        "ru3d_ds_block_bytes", "ru3d_ds_state_bad_labels_offset",
+    ), "tests/test_host_deepsup.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_s2_dgrad_pair_supported", "ru3d_conv3d_s2_pair_fwd_in_supported",
+        "ru3d_convtranspose3d_k3s2p1_fwd_in_workspace_bytes",
+    ), "tests/test_host_direct_plan.py"),
+    **dict.fromkeys((
+        "ru3d_mesh_smooth",
+    ), "tests/test_host_mesh.py"),
+    **dict.fromkeys((
+        "ru3d_conv3d_wgrad_bias_workspace_bytes",
+    ), "tests/test_host_wgrad_plan.py"),
+}
+
+
+def test_every_entry_point_of_the_signature_table_is_called_by_a_case_or_held_elsewhere():
+    called = set()
+    for name in NAMES:
+        _clean(name)
+        called |= CALLED[name]
+    assert called <= set(N.SIGNATURES)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for entry, path in HELD_ELSEWHERE.items():
+        assert entry in N.SIGNATURES, "HELD_ELSEWHERE names %s, no entry point of the table" % entry
+        assert path.startswith("tests/") and os.path.isfile(os.path.join(root, path)), "%s: no file %s" % (entry, path)
+        with open(os.path.join(root, path)) as f:
+            assert entry in f.read(), "%s does not name %s" % (path, entry)
+    both = sorted(called & set(HELD_ELSEWHERE))
+    assert not both, "HELD_ELSEWHERE lists %s, which a case of this table calls" % both
+    assert not TOOL_ONLY & (called | set(HELD_ELSEWHERE))
+    missing = sorted(set(N.SIGNATURES) - called - set(HELD_ELSEWHERE) - TOOL_ONLY)
+    assert not missing, "neither called by a case nor held elsewhere: %s" % missing

@@ -3,7 +3,7 @@
 straight from the split-K slices of the deepest convs.  Checked against float64 restatements of the reference formulas on
 the STORED 16-bit tensors (so the only differences are the kernels' own fp32 arithmetic and the output rounding), and
 bit for bit against the three-launch path of norm.hip where the contract demands it (a checkpointed block recomputes its
-activation with ru3d_in_lrelu_fwd).  Run with `-m gpu`."""
+activation with ru3d_in_lrelu_fwd).  Run with `-m gpu`.  ops.conv_fwd_in_act is ru3d_conv3d_fwd_in_lrelu on a scratch of ru3d_conv3d_fwd_in_lrelu_workspace_bytes."""
 import pytest
 import torch
 
