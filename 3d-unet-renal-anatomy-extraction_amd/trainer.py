@@ -1876,6 +1876,139 @@ def batch_extract_vessel_territories(pred_dir, save_dir, data_range=None, device
             for i in (data_range if data_range is not None else range(len(pred_files)))]
 
 
+# ------------------------------------------------------------------ local thickness: calibre and parenchyma thickness
+THICKNESS_Q = (5.0, 50.0, 95.0)
+
+
+def _thickness_stats_numpy(t2_values, q=THICKNESS_Q):
+    """thickness.summary on the host: the same dict from the float64 vector of T2 over a structure's voxels."""
+    n = int(t2_values.size)
+    if n == 0:
+        return {'n': 0}
+    ordered = np.sort(t2_values)
+    thick = 2.0 * np.sqrt(ordered)
+    return {'n': n, 't2_max': float(ordered[-1]), 't2_min': float(ordered[0]),
+            'order': {float(v): tuple(float(ordered[r]) for r in _percentile_ranks(n, float(v))) for v in q},
+            'mean': float(thick.mean()), 'std': float(thick.std())}
+
+
+def _thickness_metrics(stats):
+    """voxels, min, mean, std, max and the percentiles p05 .. of the thickness from the dict of thickness.summary (or its
+    host twin).  The square roots are taken here, on a handful of numbers; a percentile is np.percentile's linear
+    interpolation between the roots of its two order statistics, written out as in _surface_metrics."""
+    n = stats['n']
+    if n == 0:
+        return {'voxels': 0}
+    out = {'voxels': n, 'min': 2.0 * math.sqrt(stats['t2_min']), 'mean': stats['mean'], 'std': stats['std'],
+           'max': 2.0 * math.sqrt(stats['t2_max'])}
+    for v, (lo, hi) in stats['order'].items():
+        lo, hi = 2.0 * math.sqrt(lo), 2.0 * math.sqrt(hi)
+        gamma = v / 100.0 * (n - 1) - _percentile_ranks(n, v)[0]
+        if lo == hi:
+            value = lo                                  # also the full mask, where both are inf
+        else:
+            value = hi - (hi - lo) * (1 - gamma) if gamma >= 0.5 else lo + (hi - lo) * gamma
+        out['p%02d' % int(round(v))] = value
+    return out
+
+
+def thickness_case(case, labels=None, key='pred', return_device=False, return_map=False):
+    """The local thickness of every structure of the label volume `case[key]` (include/ru3d.h, "local thickness"): per
+    voxel the diameter of the largest ball that fits inside the structure and contains the voxel - the calibre of a
+    vessel at every lumen voxel, the thickness of the parenchyma.  A list of dicts of plain numbers, ready for json:
+      label     the value (or the tuple of values whose union was measured),
+      voxels    the structure's voxels (an empty structure has this entry alone),
+      min, mean, std, max, p05, p50, p95   of the thickness over those voxels, in millimetres (std: population).
+    The voxel spacing is that of the affine (`case['affine']`; 1 without one); distances run between voxel centres.
+    return_map=True returns (list, map): the float32 volume of the thickness in millimetres, every voxel carrying the
+    thickness of its own label's structure (the later entry where entries overlap), 0 in the background - a HIP tensor
+    with return_device on the device route, else numpy.  A numpy volume takes the numpy route
+    (transform._local_thickness_numpy, quadratic in a structure's voxels); a HIP volume is packed and measured on the
+    device (csrc/thickness.hip) and one vector of numbers per structure comes down.  Both routes give the same numbers:
+    the order statistics exactly, mean and std to summation order.  A structure that fills its volume has no clear voxel to
+    measure against: every figure is inf and std is nan (json writes Infinity and NaN)."""
+    from data import get_spacing
+    import transform
+    (volume,), ndim, hip = _centerline_operands(case, (key,), "thickness_case")
+    affine = np.asarray(case['affine'], dtype=np.float64) if case.get('affine') is not None else np.eye(4)
+    spacing = tuple(float(v) for v in get_spacing(affine))
+    top = 0
+    if labels is None:
+        top = (int(volume.max().item()) if volume.numel() else 0) if hip else (int(volume.max()) if volume.size else 0)
+    shape = tuple(case[key].shape)
+    results, tmap = [], None
+    if return_map:
+        tmap = torch.zeros(shape, dtype=torch.float32, device=volume.device) if hip else np.zeros(shape, dtype=np.float32)
+    for name, values in _mesh_labels(labels, top):
+        if hip:
+            import thickness
+            mask = _packed_union(volume, values)
+            t2 = thickness.local_squared(mask, spacing[3 - ndim:])
+            stats = thickness.summary(t2, mask, THICKNESS_Q)
+            if return_map and stats['n']:
+                tmap = torch.where(t2 > 0, thickness.diameter(t2).to(torch.float32), tmap)
+        else:
+            mask = np.isin(volume, values)
+            t2 = transform._local_thickness_numpy(mask, spacing)
+            stats = _thickness_stats_numpy(t2[mask], THICKNESS_Q)
+            if return_map and stats['n']:
+                tmap = np.where(mask, (2.0 * np.sqrt(t2)).astype(np.float32), tmap.reshape(mask.shape)).reshape(shape)
+        results.append(dict(label=name, **_thickness_metrics(stats)))
+    if not return_map:
+        return results
+    if hip and not return_device:
+        tmap = tmap.cpu().numpy()
+    return results, tmap
+
+
+def measure_thickness(pred_file, save_dir=None, device=None, labels=None, save_map=True):
+    """thickness_case of a NIfTI label volume with the file's affine.  save_dir: every structure's numbers are written as
+    `<case_id>.label_<n>.thickness.json` (utils.json_save; the dict gains 'file') and, with save_map, the float32 map of
+    the thickness in millimetres as `<case_id>.thickness.nii.gz` with the file's affine.  device: a HIP device uploads the
+    volume (as bytes) and works there; the map is the one large download.  Prints one line per structure; returns the
+    list of dicts."""
+    import nifti
+    from pathlib import Path
+    from utils import json_save
+    pred_file = Path(pred_file)
+    case_id = pred_file.name
+    for suffix in ('.gz', '.nii', '.pred'):
+        if case_id.endswith(suffix):
+            case_id = case_id[:-len(suffix)]
+    pred, affine, _ = nifti.load(pred_file)
+    pred = np.ascontiguousarray(np.clip(pred, 0, 255).astype(np.uint8))
+    case = {'case_id': case_id, 'affine': affine, 'pred': pred if device is None else torch.from_numpy(pred).to(device)}
+    want_map = bool(save_map) and save_dir is not None
+    results = thickness_case(case, labels, 'pred', return_map=want_map)
+    tmap = None
+    if want_map:
+        results, tmap = results
+    if save_dir is not None:
+        save_dir = Path(save_dir)
+        save_dir.mkdir(parents=True, exist_ok=True)
+    for r in results:
+        if r['voxels']:
+            print("%s label_%s: %d voxels, thickness %.2f mm (median %.2f, p05 %.2f, p95 %.2f, max %.2f)"
+                  % (case_id, _label_name(r['label']), r['voxels'], r['mean'], r['p50'], r['p05'], r['p95'], r['max']))
+        else:
+            print("%s label_%s: empty" % (case_id, _label_name(r['label'])))
+        if save_dir is not None:
+            path = save_dir / ('%s.label_%s.thickness.json' % (case_id, _label_name(r['label'])))
+            json_save(path, r)
+            r['file'] = path
+    if tmap is not None:
+        nifti.save(tmap, affine, save_dir / ('%s.thickness.nii.gz' % case_id))
+    return results
+
+
+def batch_measure_thickness(pred_dir, save_dir, data_range=None, device=None, **options):
+    """measure_thickness over the sorted *.nii.gz files of `pred_dir`; returns the per-file lists."""
+    from pathlib import Path
+    pred_files = sorted(Path(pred_dir).glob('*.nii.gz'))
+    return [measure_thickness(pred_files[i], save_dir, device, **options)
+            for i in (data_range if data_range is not None else range(len(pred_files)))]
+
+
 def preview_case(case, key='pred', axes=(0, 1, 2), num_slices=8, views=((30, 20), (120, 20), (210, -20)), size=256,
                  alpha=None, labels=None, colours=None, window=None, pixel_mm=None):
     """One picture of a case to leaf through, uint8 [H, W, 3]: `visualize.case_sheet` (slices of the image under the

@@ -887,6 +887,47 @@ int ru3d_geodesic_rounds(const uint64_t* allowed, int invert_allowed, uint64_t* 
                          int32_t* flags_dev, void* ws, size_t ws_bytes, void* stream);
 int ru3d_geodesic_split(const uint64_t* keys, uint32_t* dist, int32_t* labels, int X, int Y, int Z, void* stream);
 
+/* ------------------------------------------------------------------ local thickness */
+/* How thick a structure is at each of its voxels (csrc/thickness.hip): the squared radius of the largest inscribed ball
+ * that contains the voxel (Hildebrand and Rueegsegger 1997) - vessel calibre at every lumen voxel, parenchymal and wall
+ * thickness.  Volumes are [X, Y, Z] with X*Y*Z < 2^31, a linear index is (x Y + y) Z + z, masks are the packed masks of
+ * the morphology section.  M is the set of set bits of the mask, s the spacing (a HOST array of three finite values
+ * > 0).  All arithmetic is float64, fl = round to nearest, no contraction:
+ *     d2(x, p) = fl(A + fl(B + C)),  A = fl(fl(sx (xx - px))^2),  B and C alike for y and z
+ *                (the expression of ru3d_edt_squared),
+ *     R2(p)    = min over the CLEAR voxels b inside the volume of d2(p, b), for p in M: the bits ru3d_edt_squared gives
+ *                for the complement of the mask.  The volume's faces are not background (scipy's convention, the EDT's),
+ *     T2(x)    = max { R2(p) : p in M, d2(x, p) < R2(p) } for x in M, with strict <;  T2(x) = 0 for x outside M.
+ * No clear voxel in the volume: T2 = +inf on every voxel.  Empty mask: T2 = 0 everywhere.  The thickness is
+ * 2 sqrt(T2) in the unit of the spacing.  This is a formula, not an algorithm: results compare with ==, and a maximum
+ * does not depend on the order of its operands, so the bytes are the same in every run.
+ * Consequences:
+ *   - p = x always qualifies (d2 = 0 < R2), so T2 >= R2 on M;
+ *   - every value of T2 on M is a value of R2;
+ *   - with strict < a ball never contains a clear voxel b (d2(b, p) = d2(p, b) >= R2(p)), so painting the balls needs
+ *     no test of the mask;
+ *   - distances run between voxel CENTRES: a slab of k voxels reads k voxels thick for even k and k + 1 for odd k
+ *     (its middle voxel is (k + 1) / 2 steps from the nearest clear voxel on both sides).  This is the definition on
+ *     a grid and is not corrected for.
+ *
+ * ru3d_thickness_candidates: index[r] (int32) = the linear index of the r-th set bit of `bits` in element order (the
+ * order of ru3d_edt_gather); count (device int64) receives the number of set bits whatever the capacity; nothing is
+ * written at or beyond index[capacity].  index == NULL counts only.  `bits` is only read and may carry set bits at
+ * z >= Z.  Workspace: ru3d_thickness_workspace_bytes(X, Y, Z) - one int per 256 words of the mask -, aligned to 8 bytes;
+ * a short or misaligned one is refused before any launch.
+ * ru3d_thickness_paint: out (float64 [X, Y, Z], overwritten, not r2) = T2 from the n candidates index[0 .. n) (device
+ * int32) and the float64 volume r2 of their squared radii, R2(p) = r2[index[i]]: out is cleared, and every candidate
+ * paints R2(p) by maximum into the voxels x of its bounding box with d2(x, p) < R2(p).  A candidate with
+ * R2 == +inf stores +inf at its own voxel alone (with no clear voxel every voxel is a candidate); one with R2 <= 0
+ * or an index outside the volume paints nothing.  The order of the list changes the work, never the bytes: painting the
+ * large balls first lets most later tests end at a plain load.  work_dev: NULL, or a device int64 [2] that receives the
+ * voxels tested against the contract's expression and the atomic updates issued.
+ *
+ * The three prototypes stand in ru3d_since.h, included here: the prototypes of this file are held one to one against
+ * _native.SIGNATURES, and entry points added since the tests' case table was last brought up to date are bound from
+ * _native.SIGNATURES_SINCE; the two are folded back together. */
+#include "ru3d_since.h"
+
 /* ------------------------------------------------------------------ soft skeletons, soft-clDice loss */
 /* The soft skeleton of Shit et al. (clDice, CVPR 2021) on float32 volumes x[A][B][Z] (Z fastest), `nvol` of them behind
  * one another; nothing outside a volume takes part and nothing crosses from one volume into the next.
